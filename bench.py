@@ -8,16 +8,26 @@ device-resident before the timed region.  Workload = BASELINE.json configs[1] (c
 REMI vocabulary V=337 (336 + pad), 6 layers, d_model=512 (8 heads x 64), L = max_seq = 2048, bf16
 kernels with fp32 master weights / statistics / accumulation, per-GPU batch 128 (weak scaling; the
 reference's own default is 6, config.py:35 -- larger batches only help both sides; 32 until round 3, 64 in rounds
-3-5: the same tree reads 2.5 % higher at 128 than at 64 on one box, profiles/README.md round 6; the line carries
-`batch64` and `batch8` blocks beside the main figure).
+3-5: the same tree reads 2.5 % higher at 128 than at 64 on one box, profiles/README.md round 6; with --full the line
+carries `batch64` and `batch8` blocks beside the main figure).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
            --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (see the driver contract): value, roofline (dominant kernel, timed
-live with HIP events on the launch stream) and cpu_baseline (the oracle's eager fp32 CPU restatement
-of the same step on a bounded sample, rank 0 at N=1 only).
+Prints ONE JSON line on rank 0 (see the driver contract).  A plain run does only what the headline figure needs: set up,
+warm up, time --steps steps, print value / ms_per_step.  --full adds everything else the line used to carry: roofline
+(dominant kernel, timed live with HIP events on the launch stream), the cfg4 / batch8 / batch64 side blocks, the cfg5
+decode block and cpu_baseline (the oracle's eager fp32 CPU restatement of the same step on a bounded sample, rank 0 at
+N=1 only); each of them can still be left out with its --no-* flag.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+--dump-outputs DIR writes what the last timed step computed as float32 .npy files (dump_outputs below), so that two builds
+can be compared output for output.  It implies --deterministic: the step then runs in the library's deterministic-reduction
+mode (ops.set_deterministic), and a run with the same arguments -- hence the same inputs, weights and dropout seeds --
+computes the same values bit for bit every time.  A plain run times the product's default step (float atomics in the
+cross-workgroup sums), whose outputs differ from run to run.
 """
 from __future__ import annotations
 
@@ -59,12 +69,19 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also run the measurements beside the headline figure: per-kernel "
+                    "timing and roofline, the cfg4 / batch8 / batch64 blocks, the cfg5 decode block and the CPU baseline "
+                    "(each still subject to its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed "
+                    "(loss, accuracy, per-row argmax, a fixed sample of the logits, of the updated fp32 weights and of both Adam "
+                    "moments) as float32 DIR/<name>.npy; implies --deterministic, so that a second run writes the same files")
     ap.add_argument("--workload", choices=("cfg2", "cfg4"), default="cfg2", help="cfg2 (default): BASELINE configs[1], the metric's "
                     "workload.  cfg4: BASELINE configs[3] at its single-GPU share (MuMIDI V=486, 12 layers, d=768, L=4096, batch 4) as "
-                    "the main line -- for profiling; the default run already reports it in its `cfg4` block")
+                    "the main line -- for profiling; a --full run already reports it in its `cfg4` block")
     ap.add_argument("--no-cfg4", action="store_true", help="skip the cfg4 block (N=1 only)")
     ap.add_argument("--deterministic", action="store_true", help="run with mgx_set_deterministic (order-independent integer "
-                    "atomics for the cross-workgroup sums; also MGX_DETERMINISTIC=1): reported in config.deterministic")
+                    "atomics for the cross-workgroup sums; also MGX_DETERMINISTIC=1; implied by --dump-outputs): reported in "
+                    "config.deterministic")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (weak scaling; default 128 for cfg2); rounds 1-3 were quoted at "
                     "32 and rounds 3-5 at 64, which read about 4.5 %% and 2.5 %% lower on the same box (profiles/README.md)")
     ap.add_argument("--seq-len", type=int, default=None)
@@ -99,6 +116,8 @@ def parse():
     ap.add_argument("--buckets", type=int, default=0, help="N > 1: merge the per-layer gradient buckets into this many contiguous "
                     "groups (2: one all-reduce mid-backward, one at its end; mitigation 3 of DESIGN.md 4).  0 = one bucket per layer")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     base = CFG4 if a.workload == "cfg4" else CFG2
     for k, dflt in (("batch", base["batch"]), ("seq_len", base["seq_len"]), ("d_model", base["d_model"]),
                     ("layers", base["layers"]), ("vocab", base["vocab"])):
@@ -361,6 +380,48 @@ def pmc_traffic(kernel, B, L, d):
             "traffic_over_algorithmic": tr / algo, "traffic_over_algorithmic_plus_design": tr / (algo + design)}
 
 
+DUMP_SAMPLE = 1 << 20          # elements per sampled array of --dump-outputs (4 MB as float32)
+
+
+def dump_outputs(out_dir, m, logits, opt):
+    """--dump-outputs: what the last timed step handed back, as float32 .npy files (at most 40 MB):
+    loss and accuracy (1 element each), argmax (the per-row argmax of the logits, the `bucket` metric), logits_sample
+    (a fixed sample of the [B, L, V] logits), and param_sample / adam_exp_avg_sample / adam_exp_avg_sq_sample (one fixed
+    sample of the flat fp32 master weights and of both Adam moments after that step's update).  A tensor of at most
+    2 * DUMP_SAMPLE elements is written whole; the sample indices depend only on the tensor's size, so two runs with the
+    same arguments sample the same elements.  --dump-outputs implies deterministic-reduction mode (main), so two runs of one
+    build write identical files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def index(n, seed):
+        if n <= 2 * DUMP_SAMPLE:
+            return None
+        g = torch.Generator().manual_seed(seed)
+        return torch.randint(0, n, (DUMP_SAMPLE,), generator=g).sort().values
+
+    def save(name, t):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy().astype(np.float32))
+
+    save("loss", m["loss"].reshape(1))
+    save("accuracy", m["accuracy"].reshape(1))
+    am = m["bucket"].reshape(-1)
+    i = index(am.numel(), 1)
+    save("argmax", am if i is None else am[i.to(am.device)])
+    B, L, V = logits.shape
+    i = index(B * L * V, 2)
+    if i is None:
+        save("logits_sample", logits.reshape(-1))
+    else:
+        i = i.to(logits.device)
+        save("logits_sample", logits[i // (L * V), (i // V) % L, i % V])
+    flat = opt.store.param
+    i = index(flat.numel(), 3)
+    i = None if i is None else i.to(flat.device)
+    for name, t in (("param_sample", flat), ("adam_exp_avg_sample", opt.m), ("adam_exp_avg_sq_sample", opt.v)):
+        save(name, t if i is None else t[i])
+
+
 def _free_port():
     import socket
     s = socket.socket()
@@ -395,7 +456,7 @@ def self_launch(args):
         # the HIP runtime); when sysfs says nothing, let the child ranks fail on their own set_device
         n_dev = _kfd_gpu_count()
         if n_dev is not None and n_dev < args.gpus:
-            print(f"bench.py: --gpus {args.gpus} but only {n_dev} GPU(s) in /sys/class/kfd/kfd/topology", file=sys.stderr)
+            print(f"bench.py: --gpus {args.gpus} but the kernel driver's topology lists only {n_dev} HIP device(s)", file=sys.stderr)
             return 2
     # build libmgx.so ONCE here (hipcc only, no GPU call): N ranks importing a stale tree would otherwise all compile it
     from musicgeneration_amd import _build
@@ -436,6 +497,9 @@ def main():
         raise SystemExit("bench.py needs a HIP device (no CPU fallback for the product path)")
     if args.one_device:
         local_rank = 0
+    if local_rank >= torch.cuda.device_count():
+        # the driver may list more GPUs than this process may use: refuse by name instead of failing inside set_device
+        raise SystemExit(f"bench.py: rank {rank} needs HIP device {local_rank}, {torch.cuda.device_count()} visible")
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     if world > 1:
@@ -458,7 +522,11 @@ def main():
 
     V, d, nl, L, B = args.vocab, args.d_model, args.layers, args.seq_len, args.batch
     from musicgeneration_amd import ops as _ops
-    if args.deterministic:
+    # a plain run times the product's step (float atomics in the cross-workgroup sums).  A dump is only worth comparing if the run
+    # repeats: with float atomics the order-dependent last bits of a few gradients flip the sign of Adam's first updates
+    # (lr * sign(g)) and two runs' weights, logits and moments drift apart; so --dump-outputs implies deterministic-reduction mode
+    # (order-independent fixed-point sums, bit-reproducible), and config.deterministic says which step was timed
+    if args.deterministic or args.dump_outputs:
         _ops.set_deterministic(True, dev)
     torch.manual_seed(0)
     mt = MusicTransformer(embedding_dim=d, vocab_size=V, num_layer=nl, max_seq=L, dropout=args.dropout).to(dev)
@@ -482,9 +550,15 @@ def main():
         xf = torch.randint(0, V - 1, (B, L + 1), generator=gen)
         ring.append((xf[:, :-1].to(torch.int32).contiguous().to(dev), xf[:, 1:].to(torch.int32).contiguous().to(dev)))
 
+    kept = {}
+
     def step(i):
         x, y = ring[i % len(ring)]
-        m = ms(mt(x), y)
+        logits = mt(x)
+        m = ms(logits, y)
+        if args.dump_outputs and i == args.warmup + args.steps - 1:
+            kept["logits"] = logits                        # the last timed step's logits, for --dump-outputs
+        del logits
         loss = m["loss"]
         if world > 1:
             loss = loss * dp.loss_weight(ms.last_nonpad)      # the 4-byte non-pad-count all-reduce of the real train loop
@@ -514,6 +588,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     mt.check_no_leading_pads()      # device-side no-leading-pads record of every forward above (read after the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, kept.pop("logits"), opt)
+    kept.clear()
     streams_cfg = ({"side_cus": plan.side.cus if plan.side else 0, "main_cus": plan.main.cus if plan.main else "all",
                     "reserved_for_rccl": plan.reserved} if plan is not None else "one stream, whole chip")
     if plan is not None:
@@ -551,7 +628,7 @@ def main():
                                      "stream that depends on the collective; host clock with gloo).  Large while `exposed` is small: the "
                                      "collectives queue behind backward's kernels (co-residency, DESIGN 4) but still finish in time; "
                                      "large AND exposed large: RCCL itself is slow; compare with a --no-overlap run")
-    if rank == 0 and not args.no_kernel_timing:
+    if rank == 0 and args.full and not args.no_kernel_timing:
         kt = time_kernels(B, L, d, L)
         # credited (algorithmic) and executed product-units per kernel; 1 unit = B*L^2*d FLOPs
         # backward: dP, dV, dK (the dK/dV kernel, which also forms the dS everybody else reads), dq = dS K + dS_rel Er (dq_lite),
@@ -607,16 +684,16 @@ def main():
             "ms_per_layer": sum(kt.values()),
             "achieved_tflops": attn_flops_per_launch(B, L, d, 9.0) / (sum(kt.values()) * 1e-3) / 1e12,
             "executed_tflops": attn_flops_per_launch(B, L, d, sum(executed.values())) / (sum(kt.values()) * 1e-3) / 1e12}
-    if rank == 0 and world == 1 and not args.no_cfg4 and args.workload == "cfg2":
+    if rank == 0 and world == 1 and args.full and not args.no_cfg4 and args.workload == "cfg2":
         del mt, opt, sch, ring, last
         torch.cuda.empty_cache()
         out["cfg4"] = cfg4_block(args)
         out["batch8"] = batch8_block(args)
         if B != 64:
             out["batch64"] = batch64_block(args)
-    if rank == 0 and world == 1 and not args.no_decode:
+    if rank == 0 and world == 1 and args.full and not args.no_decode:
         out["decode"] = decode_bench(args)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
         out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
     if rank == 0:

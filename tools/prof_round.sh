@@ -11,7 +11,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof
 export TMPD=/tmp/mgx_prof_$$; mkdir -p $TMPD
 mkdir -p $OUT
-echo "== bench line"; timeout -k 10 900 python3 bench.py --batch $B --steps 20 --warmup 5 2> $OUT/${TAG}_bench.err > $OUT/${TAG}_bench_line.json || { tail -5 $OUT/${TAG}_bench.err; exit 1; }
+echo "== bench line"; timeout -k 10 900 python3 bench.py --batch $B --steps 20 --warmup 5 --full 2> $OUT/${TAG}_bench.err > $OUT/${TAG}_bench_line.json || { tail -5 $OUT/${TAG}_bench.err; exit 1; }
 cut -c1-400 $OUT/${TAG}_bench_line.json
 echo "== kernel trace of the step"
 rm -rf $TMPD/kt && (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPD/kt -- python3 $ROOT/bench.py --batch $B --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-timing --no-decode --no-cfg4 > $TMPD/kt.log 2>&1) || { tail -5 $TMPD/kt.log; exit 1; }
