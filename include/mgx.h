@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id */
-#define MGX_ABI_VERSION 18
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged */
+#define MGX_ABI_VERSION 19
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -303,6 +303,31 @@ int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float temperatur
 int mgx_sample_topk_topp_rows(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
                               uint64_t seed, int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld,
                               float* probs_out, int B, int row0, int advance, const uint32_t* allow_table, void* stream);
+
+/* ---- Ragged decode (ABI 19): one position per batch row, so one batch continues prompts of different lengths.
+ * Each *_ragged call is its namesake with `pos_dev` replaced by pos_rows, device int32[B] (B = the call's rows; M rows for
+ * the fused embedding), and row b computes exactly what the namesake computes with pos_dev[0] = pos_rows[b]:
+ *   - the embedding adds pe[pos_rows[b]];
+ *   - the attention appends row b's k/v at cache row t = pos_rows[b] and attends over row b's keys 0..t; the key splits are
+ *     the ones the namesake would use at that t, so a short row may leave whole splits empty (the merge skips them);
+ *   - the sampler draws with (seed, pos_rows[b], row0 + b), writes out_tokens[b, pos_rows[b] + 1], and with advance != 0
+ *     adds 1 to every pos_rows[b].
+ * Contract (not checked: the positions live on the device): 0 <= pos_rows[b] < Lmax <= M for the attention, pos_rows[b] < the
+ * rows of pe for the embedding, pos_rows[b] + 1 < out_ld when out_tokens is given.                                        */
+int mgx_decode_embed_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
+                            uint16_t* out, int B, int d, int V, void* stream);
+int mgx_decode_embed_linear_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
+                                   const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V,
+                                   void* stream);
+int mgx_decode_embed_linear_frag_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
+                                        const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K,
+                                        int V, void* stream);
+int mgx_rel_attn_decode_ragged(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
+                               const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes,
+                               int B, int Lmax, int d, int M, void* stream);
+int mgx_sample_topk_topp_ragged(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
+                                uint64_t seed, int32_t* pos_rows, int32_t* next_tok, int32_t* out_tokens, int out_ld,
+                                float* probs_out, int B, int row0, int advance, const uint32_t* allow_table, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

@@ -11,12 +11,17 @@
 //   mgx_sample_topk_topp  temperature -> softmax -> top-k -> top-p -> categorical draw, one wave per row;
 //                         top_k = 0 and top_p = 1 reproduce the reference's full-softmax categorical
 //                         (network.py:73-74).  Thresholds are exact (bisection on the float bit pattern).
+//
+// Every kernel that reads the position has a PER_ROW instantiation (the *_ragged entry points, ABI 19): pos_dev then holds
+// one position per batch row, so a batch can continue prompts of different lengths in lockstep.  Nothing else in a step
+// depends on the position (the relative term E[M-1-(t-j)] only on the row's own t); PER_ROW = false is the shared counter.
 #include "mgx_common.hpp"
 
 namespace {
 constexpr float LOG2E = 1.4426950408889634f;
 }
 
+template <bool PER_ROW>
 __global__ __launch_bounds__(256) void decode_embed_kernel(const int32_t* __restrict__ tok, const float* __restrict__ table,
                                                            const float* __restrict__ pe, const int32_t* __restrict__ pos_dev,
                                                            uint16_t* __restrict__ out, int B, int d, int V, float scale) {
@@ -26,7 +31,7 @@ __global__ __launch_bounds__(256) void decode_embed_kernel(const int32_t* __rest
     const int r = g / gpr, c = (g % gpr) * 8;
     int t = tok[r];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    const int pos = pos_dev[0];
+    const int pos = pos_dev[PER_ROW ? r : 0];
     const f32x4* tp = (const f32x4*)(table + (size_t)t * d + c);
     const f32x4* pp = (const f32x4*)(pe + (size_t)pos * d + c);
     const f32x4 a0 = tp[0], a1 = tp[1], p0 = pp[0], p1 = pp[1];
@@ -48,6 +53,7 @@ constexpr int DEC_PART = 68;                                   // floats per par
 #ifndef MGX_DEC_NT
 #define MGX_DEC_NT 1
 #endif
+template <bool PER_ROW>
 __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
     const uint16_t* __restrict__ qkv_new, uint16_t* __restrict__ kcache, uint16_t* __restrict__ vcache,
     const uint16_t* __restrict__ E, const int32_t* __restrict__ pos_dev, uint16_t* __restrict__ ctx,
@@ -57,7 +63,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
     const int nsplit = gridDim.y, sp = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int ks = lane >> 3, dg = lane & 7;
-    const int t = pos_dev[0];                                   // current position; keys 0..t
+    const int t = pos_dev[PER_ROW ? b : 0];                     // current position; keys 0..t (per row: a short row may leave
+                                                                // whole splits empty, which write m = -inf, l = 0)
     const uint16_t* qrow = qkv_new + (size_t)b * 3 * d + hd * 64;
     // caches are head-major [B, h, Lmax, 64]: a workgroup streams one contiguous run of 128-byte rows
     uint16_t* kc = kcache + ((size_t)b * heads + hd) * Lmax * 64;
@@ -172,6 +179,7 @@ MGX_DEV float u01(uint64_t seed, uint32_t step, uint32_t row) {
     return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
 }
 
+template <bool PER_ROW>
 __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__ logits, int V, int ld, float inv_temp,
                                                     int top_k, float top_p, uint64_t seed, int32_t* __restrict__ pos_dev,
                                                     int32_t* __restrict__ next_tok, int32_t* __restrict__ out_tokens,
@@ -261,7 +269,7 @@ __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__
 #pragma unroll
     for (int i = 0; i < SMP_PER_LANE; ++i) { if (!(p[i] >= tau)) p[i] = 0.f; kept += p[i]; }
     const float total = wave_sum(kept);
-    const int step = pos_dev[0];
+    const int step = pos_dev[PER_ROW ? row : 0];
     const float target = u01(seed, (uint32_t)step, (uint32_t)(row0 + row)) * total;
     int choice = -1;
     float base = 0.f;
@@ -293,16 +301,31 @@ __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__
     }
 }
 __global__ void advance_pos_kernel(int32_t* pos_dev) { pos_dev[0] += 1; }
+__global__ __launch_bounds__(256) void advance_pos_rows_kernel(int32_t* __restrict__ pos_rows, int B) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < B) pos_rows[i] += 1;
+}
+
+template <bool PER_ROW>
+static int decode_embed(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, uint16_t* out, int B,
+                        int d, int V, void* stream, const char* name) {
+    MGX_REQUIRE(tok && table && pe && pos_dev && out, MGX_ERR_NULL, "%s: NULL pointer", name);
+    MGX_REQUIRE(B > 0 && d > 0 && d % 8 == 0 && V > 0, MGX_ERR_SHAPE, "%s: need d%%8==0 (B=%d d=%d)", name, B, d);
+    const int total = B * (d / 8);
+    hipLaunchKernelGGL(decode_embed_kernel<PER_ROW>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
+                       pos_dev, out, B, d, V, sqrtf((float)d));
+    MGX_CHECK_LAUNCH(name);
+    return MGX_OK;
+}
 
 extern "C" int mgx_decode_embed(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
                                 uint16_t* out, int B, int d, int V, void* stream) {
-    MGX_REQUIRE(tok && table && pe && pos_dev && out, MGX_ERR_NULL, "mgx_decode_embed: NULL pointer");
-    MGX_REQUIRE(B > 0 && d > 0 && d % 8 == 0 && V > 0, MGX_ERR_SHAPE, "mgx_decode_embed: need d%%8==0 (B=%d d=%d)", B, d);
-    const int total = B * (d / 8);
-    hipLaunchKernelGGL(decode_embed_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
-                       pos_dev, out, B, d, V, sqrtf((float)d));
-    MGX_CHECK_LAUNCH("mgx_decode_embed");
-    return MGX_OK;
+    return decode_embed<false>(tok, table, pe, pos_dev, out, B, d, V, stream, "mgx_decode_embed");
+}
+
+extern "C" int mgx_decode_embed_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
+                                       uint16_t* out, int B, int d, int V, void* stream) {
+    return decode_embed<true>(tok, table, pe, pos_rows, out, B, d, V, stream, "mgx_decode_embed_ragged");
 }
 
 // key splits per (b,h): enough workgroups to keep ~4 per CU (32 waves) streaming once the cache is long; short caches
@@ -325,23 +348,38 @@ extern "C" size_t mgx_rel_attn_decode_workspace(int B, int Lmax, int d) {
     return s == 1 ? 0 : (size_t)B * (d / 64) * s * DEC_PART * sizeof(float);
 }
 
-extern "C" int mgx_rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
-                                   const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax,
-                                   int d, int M, void* stream) {
-    MGX_REQUIRE(qkv_new && kcache && vcache && E && pos_dev && ctx, MGX_ERR_NULL, "mgx_rel_attn_decode: NULL pointer");
+template <bool PER_ROW>
+static int rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E, const int32_t* pos_dev,
+                           uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M, void* stream,
+                           const char* name) {
+    MGX_REQUIRE(qkv_new && kcache && vcache && E && pos_dev && ctx, MGX_ERR_NULL, "%s: NULL pointer", name);
     MGX_REQUIRE(B > 0 && d > 0 && d % 64 == 0 && Lmax > 0 && M >= Lmax, MGX_ERR_SHAPE,
-                "mgx_rel_attn_decode: need d%%64==0 and M>=Lmax (B=%d Lmax=%d d=%d M=%d)", B, Lmax, d, M);
+                "%s: need d%%64==0 and M>=Lmax (B=%d Lmax=%d d=%d M=%d)", name, B, Lmax, d, M);
     const int ns = decode_splits(B, Lmax, d);
     MGX_REQUIRE(ns == 1 || (workspace && ws_bytes >= mgx_rel_attn_decode_workspace(B, Lmax, d)), MGX_ERR_SHAPE,
-                "mgx_rel_attn_decode: workspace must hold mgx_rel_attn_decode_workspace() = %zu bytes (got %zu)",
+                "%s: workspace must hold mgx_rel_attn_decode_workspace() = %zu bytes (got %zu)", name,
                 mgx_rel_attn_decode_workspace(B, Lmax, d), ws_bytes);
-    hipLaunchKernelGGL(rel_attn_decode_kernel, dim3(B * (d / 64), ns), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream, qkv_new,
-                       kcache, vcache, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
+    hipLaunchKernelGGL(rel_attn_decode_kernel<PER_ROW>, dim3(B * (d / 64), ns), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream,
+                       qkv_new, kcache, vcache, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
     if (ns > 1)
         hipLaunchKernelGGL(rel_attn_decode_merge_kernel, dim3(B * (d / 64)), dim3(64), 0, (hipStream_t)stream,
                            (const float*)workspace, ctx, ns, d);
-    MGX_CHECK_LAUNCH("mgx_rel_attn_decode");
+    MGX_CHECK_LAUNCH(name);
     return MGX_OK;
+}
+
+extern "C" int mgx_rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
+                                   const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax,
+                                   int d, int M, void* stream) {
+    return rel_attn_decode<false>(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax, d, M, stream,
+                                  "mgx_rel_attn_decode");
+}
+
+extern "C" int mgx_rel_attn_decode_ragged(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
+                                          const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes, int B,
+                                          int Lmax, int d, int M, void* stream) {
+    return rel_attn_decode<true>(qkv_new, kcache, vcache, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d, M, stream,
+                                 "mgx_rel_attn_decode_ragged");
 }
 
 extern "C" int mgx_sample_topk_topp_rows(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
@@ -351,10 +389,26 @@ extern "C" int mgx_sample_topk_topp_rows(const uint16_t* logits, int V, int ld, 
     MGX_REQUIRE(logits && pos_dev && next_tok, MGX_ERR_NULL, "mgx_sample_topk_topp: NULL pointer");
     MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && top_p > 0.f && row0 >= 0, MGX_ERR_SHAPE,
                 "mgx_sample_topk_topp: need 0<V<=%d, ld>=V, temperature>0, top_p>0, row0>=0 (V=%d ld=%d)", 64 * SMP_PER_LANE, V, ld);
-    hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
+    hipLaunchKernelGGL(sample_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
                        top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, row0, allow_table);
     if (advance) hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos_dev);
     MGX_CHECK_LAUNCH("mgx_sample_topk_topp");
+    return MGX_OK;
+}
+
+extern "C" int mgx_sample_topk_topp_ragged(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
+                                           uint64_t seed, int32_t* pos_rows, int32_t* next_tok, int32_t* out_tokens, int out_ld,
+                                           float* probs_out, int B, int row0, int advance, const uint32_t* allow_table,
+                                           void* stream) {
+    MGX_REQUIRE(logits && pos_rows && next_tok, MGX_ERR_NULL, "mgx_sample_topk_topp_ragged: NULL pointer");
+    MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && top_p > 0.f && row0 >= 0, MGX_ERR_SHAPE,
+                "mgx_sample_topk_topp_ragged: need 0<V<=%d, ld>=V, temperature>0, top_p>0, row0>=0 (V=%d ld=%d)", 64 * SMP_PER_LANE,
+                V, ld);
+    hipLaunchKernelGGL(sample_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
+                       top_p, seed, pos_rows, next_tok, out_tokens, out_ld, probs_out, row0, allow_table);
+    if (advance)
+        hipLaunchKernelGGL(advance_pos_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_rows, B);
+    MGX_CHECK_LAUNCH("mgx_sample_topk_topp_ragged");
     return MGX_OK;
 }
 

@@ -1764,7 +1764,8 @@ __global__ __launch_bounds__(256) void linear_skinny_ln_kernel(const uint16_t* _
 // workgroup (47 us against 9.4 + 5.2: 16 workgroups each stream all of W1 behind a 32-row operand with ~8 KB in flight per
 // wave -- the chain is bound by dependent L2 round trips, and recomputation multiplies them).
 // =================================================================================================
-template <bool FRAG>
+// PER_ROW (ABI 19, *_ragged): pos_dev holds one position per row instead of one shared counter.
+template <bool FRAG, bool PER_ROW>
 __global__ __launch_bounds__(256) void linear_skinny_embed_kernel(const int32_t* __restrict__ tok, const float* __restrict__ table,
                                                                   const float* __restrict__ pe, const int32_t* __restrict__ pos_dev,
                                                                   const uint16_t* __restrict__ W, const float* __restrict__ bias,
@@ -1780,7 +1781,7 @@ __global__ __launch_bounds__(256) void linear_skinny_embed_kernel(const int32_t*
     const bool nv = FRAG || nrow < N, mv = mrow < M;
     int t = tok[mv ? mrow : 0];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    const int pos = pos_dev[0];
+    const int pos = pos_dev[PER_ROW ? (mv ? mrow : 0) : 0];
     const float* tp = table + (size_t)t * K + w * kq + hh * 8;
     const float* pp = pe + (size_t)pos * K + w * kq + hh * 8;
     const uint16_t* wp = FRAG ? W + (((size_t)blockIdx.x * (K >> 4) + (size_t)(w * kq >> 4)) * 64 + lane) * 8
@@ -2167,7 +2168,7 @@ extern "C" int mgx_decode_embed_linear(const int32_t* tok, const float* table, c
     MGX_REQUIRE(tok && table && pe && pos_dev && W && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear: NULL pointer");
     MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
                 "mgx_decode_embed_linear: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
-    hipLaunchKernelGGL(linear_skinny_embed_kernel<false>, dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe, pos_dev,
+    hipLaunchKernelGGL((linear_skinny_embed_kernel<false, false>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe, pos_dev,
                        W, bias, C, H, M, N, K, V, sqrtf((float)K));
     MGX_CHECK_LAUNCH("mgx_decode_embed_linear");
     return MGX_OK;
@@ -2179,8 +2180,32 @@ extern "C" int mgx_decode_embed_linear_frag(const int32_t* tok, const float* tab
     MGX_REQUIRE(tok && table && pe && pos_dev && Wf && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear_frag: NULL pointer");
     MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
                 "mgx_decode_embed_linear_frag: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
-    hipLaunchKernelGGL(linear_skinny_embed_kernel<true>, dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
+    hipLaunchKernelGGL((linear_skinny_embed_kernel<true, false>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
                        pos_dev, Wf, bias, C, H, M, N, K, V, sqrtf((float)K));
     MGX_CHECK_LAUNCH("mgx_decode_embed_linear_frag");
+    return MGX_OK;
+}
+
+extern "C" int mgx_decode_embed_linear_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
+                                              const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K,
+                                              int V, void* stream) {
+    MGX_REQUIRE(tok && table && pe && pos_rows && W && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear_ragged: NULL pointer");
+    MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
+                "mgx_decode_embed_linear_ragged: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
+    hipLaunchKernelGGL((linear_skinny_embed_kernel<false, true>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
+                       pos_rows, W, bias, C, H, M, N, K, V, sqrtf((float)K));
+    MGX_CHECK_LAUNCH("mgx_decode_embed_linear_ragged");
+    return MGX_OK;
+}
+
+extern "C" int mgx_decode_embed_linear_frag_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
+                                                   const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N,
+                                                   int K, int V, void* stream) {
+    MGX_REQUIRE(tok && table && pe && pos_rows && Wf && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear_frag_ragged: NULL pointer");
+    MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
+                "mgx_decode_embed_linear_frag_ragged: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
+    hipLaunchKernelGGL((linear_skinny_embed_kernel<true, true>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
+                       pos_rows, Wf, bias, C, H, M, N, K, V, sqrtf((float)K));
+    MGX_CHECK_LAUNCH("mgx_decode_embed_linear_frag_ragged");
     return MGX_OK;
 }

@@ -40,11 +40,43 @@ def get_options(argv=None):
     parser.add_option('-c', '--condition-file', dest='condition_file', type='string', default=getattr(config, 'condition_file', None),
                       help='MIDI file to continue (the reference reads config.condition_file, generate.py:101-105): its '
                            'first 500 MIDI-like events become the prior of every sample')
+    parser.add_option('--condition-files', dest='condition_files', type='string', default=None,
+                      help='comma-separated MIDI files to continue in one batch: each file is one sample (-b is ignored), '
+                           'its first 500 MIDI-like events that sample\'s prompt (KV-cache decode over prompts of different '
+                           'lengths)')
     return parser.parse_args(argv)[0]
+
+
+def _ragged_priors(o):
+    """--condition-files: one MIDI-like prompt per file, right-padded into [B, Pmax]; returns (prior, lengths)"""
+    if o.condition_file is not None or o.grammar or o.reference_mask:
+        raise SystemExit('--condition-files cannot be combined with -c, --grammar or --reference-mask')
+    if o.repr != 'midi_like':
+        raise SystemExit('--condition-files continues MIDI-like (EventSeq) prompts: use --repr midi_like')
+    from .sequence import EventSeq, NoteSeq
+    files = [f for f in o.condition_files.split(',') if f]
+    if not files:
+        raise SystemExit('--condition-files: no file given')
+    ids = []
+    for f in files:
+        a = EventSeq.from_note_seq(NoteSeq.from_midi_file(f)).to_array()[:500]
+        if len(a) == 0:
+            raise SystemExit(f'{f}: no notes in the MIDI-like pitch range')
+        ids.append(a)
+        print('Prompt: {} events from {}'.format(len(a), f))
+    lens = [len(a) for a in ids]
+    if max(lens) + o.max_len > o.max_seq:
+        raise SystemExit(f'--condition-files: the longest prompt ({max(lens)} events) + -l {o.max_len} exceeds -M {o.max_seq}')
+    pad = vocab_of(o.repr) - 1
+    prior = np.full((len(ids), max(lens)), pad, dtype=np.int64)
+    for i, a in enumerate(ids):
+        prior[i, :len(a)] = a
+    return torch.from_numpy(prior), lens
 
 
 def main(argv=None):
     o = get_options(argv)
+    ragged = _ragged_priors(o) if o.condition_files is not None else None     # checked before any model or device work
     device = torch.device('cuda:0')
     vocab = vocab_of(o.repr)
     mt = MusicTransformer(embedding_dim=o.d_model, vocab_size=vocab, num_layer=o.num_layers, max_seq=o.max_seq,
@@ -63,6 +95,13 @@ def main(argv=None):
                 m = ms(pred, torch.from_numpy(y).to(device, dtype=torch.int))
             print('Test >>>> Loss: {:6.6}, Accuracy: {}'.format(m['loss'], m['accuracy']))
     mt.test()
+    if ragged is not None:
+        prior, lens = ragged
+        res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
+                                 prior_lengths=lens).cpu().numpy()
+        res = [row[:n + o.max_len] for row, n in zip(res, lens)]             # without the pad tail
+        _write(o, res)
+        return
     prior = torch.tensor([[24, 28, 31]] * o.batch_size, dtype=torch.long, device=device)
     if o.condition_file is not None:
         # generate.py:101-105: MIDI -> notes -> MIDI-like events -> the first 500 indices, repeated for the batch
@@ -88,6 +127,10 @@ def main(argv=None):
     else:
         res = mt.generate(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                           reference_mask=o.reference_mask).cpu().numpy()
+    _write(o, res)
+
+
+def _write(o, res):
     os.makedirs(o.output_dir, exist_ok=True)
     for i, seq in enumerate(res):
         name = os.path.join(o.output_dir, f'gen-{i:03d}')

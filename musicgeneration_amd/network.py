@@ -323,7 +323,7 @@ class MusicTransformer(torch.nn.Module):
     def generate_cached(self, prior: torch.Tensor, length: int, temperature: float = 1.0, top_k: int = 0,
                         top_p: float = 1.0, seed: int = 0, use_graph: bool = True, return_probs: bool = False,
                         grammar=None, prefill: str = "auto", return_cache: bool = False, groups: Optional[int] = None,
-                        masked_groups: bool = False):
+                        masked_groups: bool = False, prior_lengths=None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq; no sliding window).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -337,7 +337,27 @@ class MusicTransformer(torch.nn.Module):
         to a multiple of 32 rows would exceed max_seq).  The two prefill paths fill the caches through different GEMM kernels
         (same values to bf16 rounding, not bitwise), so with a fixed seed the SAMPLED continuation may differ between a
         33-token and a 32-token prompt's path: pass ``prefill`` explicitly where run-to-run identical samples matter.
-        ``return_cache`` adds the per-layer (K, V) caches to the result (parity tests)."""
+        ``return_cache`` adds the per-layer (K, V) caches to the result (parity tests).
+
+        ``prior_lengths`` (length-B ints): prompts of different lengths P_b, right-padded into ``prior`` [B, Pmax] (entries at or
+        beyond P_b are ignored).  One batched causal prefill covers prior[:, :Pmax-1] (a row's cache rows past P_b-2 are
+        overwritten by its own decode steps before they are read), then every row decodes ``length`` tokens in lockstep from
+        its own position P_b-1 (per-row positions on the device, *_ragged kernels; graph capture, ``groups`` and ``grammar``
+        as above).  Returns int32 [B, Pmax+length]: row b holds its prompt, its ``length`` sampled tokens, then ``pad_token``.
+        Unequal lengths need the batched prefill ("token" is refused; "auto" means "batched").  With ``return_probs`` row b
+        carries the distributions after positions P_b-1 .. P_b+length-2 and zeros elsewhere -- unlike the uniform case, which
+        prefills token by token to report every position.  With ``return_cache`` row b's cache rows from P_b+length-1 on
+        are zero, as the uniform case leaves its rows from P+length-1 on.  All lengths equal: exactly the call without
+        ``prior_lengths`` on prior[:, :P] (bitwise), its outputs padded to Pmax+length as above."""
+        lens = None
+        if prior_lengths is not None:
+            lens = self._check_prior_lengths(prior, prior_lengths, length, prefill)
+            if min(lens) == max(lens):
+                P, Pmax = lens[0], prior.shape[1]
+                res = self.generate_cached(prior[:, :P], length, temperature, top_k, top_p, seed, use_graph, return_probs,
+                                           grammar, prefill, return_cache, groups, masked_groups)
+                return self._pad_uniform_result(res, Pmax - P, return_probs, return_cache)
+        ragged = lens is not None
         st = self.store()
         st.sync_shadow()
         was_training = self.training
@@ -360,10 +380,16 @@ class MusicTransformer(torch.nn.Module):
         # SLOWER than one does (0.75 ms/token at 2 groups, 0.48 at 3-4, 0.72 at 6, against 0.50-0.51 at 1), so it stays off.
         G = max(1, min(int(groups or 1), B))
         cuts = [B * g // G for g in range(G + 1)]
-        pos_all = torch.zeros(G, dtype=torch.int32, device=dev)
+        pos_all = torch.zeros(B if ragged else G, dtype=torch.int32, device=dev)     # ragged: one position per row
         tok = prior[:, 0].to(torch.int32).contiguous().to(dev)
         prior_i = prior.to(torch.int32).to(dev)
         out_tokens = torch.zeros(B, total, dtype=torch.int32, device=dev)
+        if ragged:
+            lens_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
+            rows = torch.arange(B, device=dev)
+            # the right padding becomes pad_token (a valid id for the prefill; the result's tail past each row's samples)
+            prior_i = torch.where(torch.arange(P, device=dev)[None, :] < lens_dev[:, None], prior_i, self.pad_token)
+            out_tokens.fill_(self.pad_token)
         out_tokens[:, :P] = prior_i
         probs_all = torch.zeros(B, total, V, dtype=torch.float32, device=dev) if return_probs else None
         probs_step = torch.zeros(B, V, dtype=torch.float32, device=dev) if return_probs else None
@@ -376,7 +402,7 @@ class MusicTransformer(torch.nn.Module):
         for g in range(G):
             r = _Rows()
             r.b0, b1 = cuts[g], cuts[g + 1]
-            r.pos = pos_all[g:g + 1]
+            r.pos = pos_all[r.b0:b1] if ragged else pos_all[g:g + 1]
             r.tok, r.out, r.h, r.ctx = tok[r.b0:b1], out_tokens[r.b0:b1], hbuf[r.b0:b1], ctxbuf[r.b0:b1]
             r.probs = probs_step[r.b0:b1] if return_probs else None
             r.kc, r.vc = [k[r.b0:b1] for k in kc], [v[r.b0:b1] for v in vc]
@@ -424,12 +450,12 @@ class MusicTransformer(torch.nn.Module):
         def step_rows(r, sample_into_out: bool):
             if fuse_ln:
                 qkv, h = ops.decode_embed_linear(r.tok, Pm["Decoder.embedding.weight"].data, pe, r.pos, layers[0]["wqkv_f"],
-                                                 layers[0]["bqkv"], r.h)
+                                                 layers[0]["bqkv"], r.h, ragged=ragged)
             else:
-                h = ops.decode_embed(r.tok, Pm["Decoder.embedding.weight"].data, pe, r.pos, r.h)
+                h = ops.decode_embed(r.tok, Pm["Decoder.embedding.weight"].data, pe, r.pos, r.h, ragged=ragged)
                 qkv = ops.linear_fwd(h, layers[0]["wqkv"], layers[0]["bqkv"], 0)
             for i, ly in enumerate(layers):
-                ops.rel_attn_decode(qkv, r.kc[i], r.vc[i], ly["E"], r.pos, r.ctx, r.ws)
+                ops.rel_attn_decode(qkv, r.kc[i], r.vc[i], ly["E"], r.pos, r.ctx, r.ws, ragged=ragged)
                 nxt = layers[i + 1] if i + 1 < nl else None
                 if fuse_ln:
                     a = ops.linear_fwd(r.ctx, ly["wfc_f"], ly["bfc"], 0)
@@ -450,7 +476,7 @@ class MusicTransformer(torch.nn.Module):
                     else:
                         logits = ops.linear_fwd(h, wv, bv, 0)
             ops.sample_topk_topp(logits, V, r.pos, r.tok, r.out if sample_into_out else None, r.probs, temperature,
-                                 top_k, top_p, seed, advance=True, allow_table=allow, row0=r.b0)
+                                 top_k, top_p, seed, advance=True, allow_table=allow, row0=r.b0, ragged=ragged)
 
         def step(sample_into_out: bool):                  # eager: the sub-batches one after the other on the current stream
             for r in subs:
@@ -458,7 +484,7 @@ class MusicTransformer(torch.nn.Module):
 
         if prefill not in ("auto", "token", "batched"):
             raise ValueError("prefill must be 'auto', 'token' or 'batched'")
-        if prefill == "batched" and return_probs:
+        if prefill == "batched" and return_probs and not ragged:
             raise ValueError("return_probs needs prefill='token' (it reports the distribution after every prior token)")
         first = 0
         # the batched pass pads the prompt to a multiple of 32 rows; when that exceeds max_seq (max_seq not a multiple of 32)
@@ -466,7 +492,7 @@ class MusicTransformer(torch.nn.Module):
         fits = (P - 1 + 31) // 32 * 32 <= self.max_seq
         if prefill == "batched" and not fits:
             raise ValueError(f"prefill='batched' pads the {P - 1}-token prompt to {(P - 1 + 31) // 32 * 32} rows > max_seq={self.max_seq}")
-        if prefill == "batched" or (prefill == "auto" and not return_probs and P > 32 and fits):
+        if ragged or prefill == "batched" or (prefill == "auto" and not return_probs and P > 32 and fits):
             # batched prefill: positions 0..P-2 through the full-sequence kernels (causal, so the zero-padded tail up to a
             # multiple of 32 cannot reach them); token P-1 then takes the ordinary decode step below
             n = P - 1
@@ -489,11 +515,20 @@ class MusicTransformer(torch.nn.Module):
                 pos_all.fill_(n)
                 tok.copy_(prior_i[:, n])
                 first = n
+            if ragged:                                    # every row resumes at its own last prompt token
+                pos_all.copy_(lens_dev - 1)
+                tok.copy_(prior_i[rows, lens_dev.long() - 1])
+
+        def put_probs(p):                                 # the distribution after position p (per row: after P_b - 1 + p - first)
+            if ragged:
+                probs_all[rows, lens_dev.long() - 1 + (p - first)] = probs_step
+            else:
+                probs_all[:, p] = probs_step
         # the (rest of the) prior is teacher-forced token by token (it also warms every kernel up before capture)
         for p in range(first, P):
             step(sample_into_out=(p == P - 1) and length > 0)
             if return_probs:
-                probs_all[:, p] = probs_step
+                put_probs(p)
             if p + 1 < P:
                 tok.copy_(prior_i[:, p + 1])
         remaining = length - 1 if length > 0 else 0
@@ -522,12 +557,51 @@ class MusicTransformer(torch.nn.Module):
                 for p in range(remaining):
                     step(True)
                     if return_probs:
-                        probs_all[:, P + p] = probs_step
+                        put_probs(P + p)
         self.train(was_training)
         res = (out_tokens, probs_all) if return_probs else out_tokens
         if return_cache:
+            if ragged:                                    # prefill rows a short row's decode never reached
+                stale = (torch.arange(total, device=dev)[None, :] >= (lens_dev[:, None] + length - 1)).view(B, 1, total, 1)
+                for c in kc + vc:
+                    c.masked_fill_(stale, 0)
             return (res, kc, vc)
         return res
+
+    def _check_prior_lengths(self, prior: torch.Tensor, prior_lengths, length: int, prefill: str) -> list:
+        """validates generate_cached's ``prior_lengths`` (ValueError) and returns them as a list of ints"""
+        B, Pmax = prior.shape
+        lens = [int(v) for v in torch.as_tensor(prior_lengths).reshape(-1).tolist()]
+        if len(lens) != B:
+            raise ValueError(f"prior_lengths has {len(lens)} entries for a batch of {B} prompts")
+        if any(not 1 <= v <= Pmax for v in lens):
+            raise ValueError(f"prior_lengths must lie in 1 .. {Pmax} (the width of prior), got {lens}")
+        if Pmax + length > self.max_seq:
+            raise ValueError(f"the longest prompt ({Pmax}) + length ({length}) must be <= max_seq ({self.max_seq})")
+        if prefill not in ("auto", "token", "batched"):
+            raise ValueError("prefill must be 'auto', 'token' or 'batched'")
+        if min(lens) != max(lens):
+            if prefill == "token":
+                raise ValueError("prompts of different lengths need prefill='batched' or 'auto' (token-by-token prefill in "
+                                 "lockstep would need a per-row teacher-forced prefix)")
+            if (Pmax - 1 + 31) // 32 * 32 > self.max_seq:
+                raise ValueError(f"prompts of different lengths are prefilled in one batched pass, which pads the {Pmax - 1}-token "
+                                 f"prompt to {(Pmax - 1 + 31) // 32 * 32} rows > max_seq={self.max_seq}")
+        return lens
+
+    def _pad_uniform_result(self, res, extra: int, return_probs: bool, return_cache: bool):
+        """generate_cached's result for equal prior_lengths P < Pmax: tokens padded with pad_token, probabilities and caches
+        with zeros, to Pmax + length positions"""
+        if extra == 0:
+            return res
+        if return_cache:
+            res, kc, vc = res
+            kc = [torch.nn.functional.pad(c, (0, 0, 0, extra)) for c in kc]
+            vc = [torch.nn.functional.pad(c, (0, 0, 0, extra)) for c in vc]
+        toks, probs = res if return_probs else (res, None)
+        toks = torch.nn.functional.pad(toks, (0, extra), value=self.pad_token)
+        res = (toks, torch.nn.functional.pad(probs, (0, 0, 0, extra))) if return_probs else toks
+        return (res, kc, vc) if return_cache else res
 
     def test(self):
         self.eval()

@@ -560,27 +560,39 @@ def linear_dw_grouped(problems):
 
 
 # ---- decode path (no autograd) ----------------------------------------------------------------------
-def decode_embed(tok, table, pe, pos_dev, out):
+def _check_pos_rows(pos_dev, B, ragged):
+    """``ragged=True`` (ABI 19): pos_dev is int32 [B], one position per row, instead of the shared counter pos_dev[0]"""
+    if ragged and (pos_dev.dtype != torch.int32 or pos_dev.numel() != B or not pos_dev.is_contiguous()):
+        raise ValueError(f"ragged decode: the positions must be a contiguous int32 tensor of {B} entries "
+                         f"(got {pos_dev.dtype}, {pos_dev.numel()} entries)")
+    return "_ragged" if ragged else ""
+
+
+def decode_embed(tok, table, pe, pos_dev, out, *, ragged=False):
     _need_cuda(tok, table, pe, pos_dev, out)
     V, d = table.shape
-    check(_lib.load().mgx_decode_embed(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(out), tok.numel(), d, V,
-                                       stream_ptr()), "mgx_decode_embed")
+    name = "mgx_decode_embed" + _check_pos_rows(pos_dev, tok.numel(), ragged)
+    check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(out), tok.numel(), d, V, stream_ptr()), name)
     return out
 
 
-def decode_embed_linear(tok, table, pe, pos_dev, w, bias, hout):
-    """h = table[tok]*sqrt(d) + pe[t] (written to ``hout`` bf16 [B,d]) and c bf16 [B,N] = h w^T + bias in one launch"""
+def decode_embed_linear(tok, table, pe, pos_dev, w, bias, hout, *, ragged=False):
+    """h = table[tok]*sqrt(d) + pe[t] (written to ``hout`` bf16 [B,d]) and c bf16 [B,N] = h w^T + bias in one launch;
+    ``ragged``: t = pos_dev[b] per row"""
     V, d = table.shape
     N = w.shape[0]
     c = torch.empty(tok.numel(), N, dtype=torch.bfloat16, device=hout.device)
+    sfx = _check_pos_rows(pos_dev, tok.numel(), ragged)
     if isinstance(w, FragWeight):
         _need_cuda(tok, table, pe, pos_dev, w.data, bias, hout)
-        check(_lib.load().mgx_decode_embed_linear_frag(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(w.data), ptr(bias), ptr(c),
-                                                       ptr(hout), tok.numel(), N, d, V, stream_ptr()), "mgx_decode_embed_linear_frag")
+        name = "mgx_decode_embed_linear_frag" + sfx
+        check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(w.data), ptr(bias), ptr(c), ptr(hout),
+                                         tok.numel(), N, d, V, stream_ptr()), name)
         return c, hout
     _need_cuda(tok, table, pe, pos_dev, w, bias, hout)
-    check(_lib.load().mgx_decode_embed_linear(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(w), ptr(bias), ptr(c), ptr(hout),
-                                              tok.numel(), N, d, V, stream_ptr()), "mgx_decode_embed_linear")
+    name = "mgx_decode_embed_linear" + sfx
+    check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(w), ptr(bias), ptr(c), ptr(hout),
+                                     tok.numel(), N, d, V, stream_ptr()), name)
     return c, hout
 
 
@@ -595,34 +607,38 @@ def rel_attn_decode_workspace(B, Lmax, d, device):
     return torch.empty(n, dtype=torch.uint8, device=device) if n else None
 
 
-def rel_attn_decode(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace=None):
-    """kcache / vcache bf16 [B, h, Lmax, 64] (head-major: workgroup (b, h) streams one contiguous run of rows)"""
+def rel_attn_decode(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace=None, *, ragged=False):
+    """kcache / vcache bf16 [B, h, Lmax, 64] (head-major: workgroup (b, h) streams one contiguous run of rows);
+    ``ragged``: row b's position is pos_dev[b] (each < Lmax: not checked, the positions live on the device)"""
     _need_cuda(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace)
     B, heads, Lmax, dh = kcache.shape
     if dh != 64 or vcache.shape != kcache.shape:
         raise ValueError("rel_attn_decode: caches must be bf16 [B, h, Lmax, 64]")
     d = heads * 64
-    check(_lib.load().mgx_rel_attn_decode(ptr(qkv_new), ptr(kcache), ptr(vcache), ptr(E), ptr(pos_dev), ptr(ctx), ptr(workspace),
-                                          0 if workspace is None else workspace.numel(), B, Lmax, d, E.shape[0], stream_ptr()),
-          "mgx_rel_attn_decode")
+    name = "mgx_rel_attn_decode" + _check_pos_rows(pos_dev, B, ragged)
+    check(getattr(_lib.load(), name)(ptr(qkv_new), ptr(kcache), ptr(vcache), ptr(E), ptr(pos_dev), ptr(ctx), ptr(workspace),
+                                     0 if workspace is None else workspace.numel(), B, Lmax, d, E.shape[0], stream_ptr()), name)
     return ctx
 
 
 def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=None, temperature=1.0, top_k=0, top_p=1.0,
-                     seed=0, advance=True, allow_table=None, row0=0):
+                     seed=0, advance=True, allow_table=None, row0=0, *, ragged=False):
     """allow_table: optional int32/uint32 [V, ceil(V/32)] grammar mask on the device (bit v of row t: v may follow t);
-    row0: index of the first row in the whole batch when the tensors are a sub-batch's rows (the draw is by global row)"""
+    row0: index of the first row in the whole batch when the tensors are a sub-batch's rows (the draw is by global row);
+    ragged: row b's position is pos_dev[b] (draw, out_tokens column pos_dev[b] + 1, and every entry advanced)"""
     _need_cuda(logits, pos_dev, next_tok, out_tokens, probs_out, allow_table)
     ld = logits.shape[-1]
     B = logits.numel() // ld
+    sfx = _check_pos_rows(pos_dev, B, ragged)
+    name = "mgx_sample_topk_topp" + (sfx or "_rows")
     if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
                                     or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4
                                     or not allow_table.is_contiguous()):
         raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
-    check(_lib.load().mgx_sample_topk_topp_rows(ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed),
-                                                ptr(pos_dev), ptr(next_tok), ptr(out_tokens),
-                                                0 if out_tokens is None else out_tokens.shape[-1], ptr(probs_out), B, int(row0),
-                                                1 if advance else 0, ptr(allow_table), stream_ptr()), "mgx_sample_topk_topp")
+    check(getattr(_lib.load(), name)(ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed),
+                                     ptr(pos_dev), ptr(next_tok), ptr(out_tokens),
+                                     0 if out_tokens is None else out_tokens.shape[-1], ptr(probs_out), B, int(row0),
+                                     1 if advance else 0, ptr(allow_table), stream_ptr()), "mgx_sample_topk_topp" + sfx)
     return next_tok
 
 
