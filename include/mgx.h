@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged */
-#define MGX_ABI_VERSION 19
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged */
+#define MGX_ABI_VERSION 20
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -328,6 +328,28 @@ int mgx_rel_attn_decode_ragged(const uint16_t* qkv_new, uint16_t* kcache, uint16
 int mgx_sample_topk_topp_ragged(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
                                 uint64_t seed, int32_t* pos_rows, int32_t* next_tok, int32_t* out_tokens, int out_ld,
                                 float* probs_out, int B, int row0, int advance, const uint32_t* allow_table, void* stream);
+
+/* ---- 8-bit K/V cache (ABI 20): the decode attention over caches that hold OCP fp8 e4m3fn codes (not the fnuz variant).
+ * kcache, vcache: uint8 [B,h,Lmax,64] codes; kscale, vscale: float [B,h,Lmax], one scale per (b,h,row).  An element is
+ * float(code) * scale.  A row x of 64 bf16 values is quantized with all arithmetic in f32:
+ *   amax = max |x_i|;
+ *   amax == 0:  scale = 0, every code 0;
+ *   otherwise:  inv = 448.0f / amax (IEEE division), code_i = e4m3fn(x_i * inv) rounded to nearest even, scale = amax / 448.0f
+ *               (x_i * inv never rounds above 448, so no code is NaN).
+ * mgx_kv_store_fp8: rows 0..n-1 of the K and V columns (d..2d-1, 2d..3d-1) of qkv bf16 [B,Lrows,3d] are quantized into cache
+ *   rows 0..n-1 (n <= Lrows, n <= Lmax; n = 0 does nothing); the other rows are not touched.                              */
+int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* kcache, uint8_t* vcache,
+                     float* kscale, float* vscale, int B, int Lmax, int d, void* stream);
+/* mgx_rel_attn_decode over the 8-bit cache: k_t, v_t of qkv_new are quantized as above and appended at row t, and row t enters
+ * this call already quantized, so ctx is exactly softmax_j((q.k~_j + q.E[M-1-(t-j)])/8) v~_j over the dequantized rows
+ * k~_j, v~_j, j = 0..t.  q, E and ctx stay bf16.  The key splits, workspace and partials are those of mgx_rel_attn_decode
+ * (mgx_rel_attn_decode_workspace / _splits cover both).  The _ragged form reads pos_rows int32[B] as the ragged calls above. */
+int mgx_rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
+                            const uint16_t* E, const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes,
+                            int B, int Lmax, int d, int M, void* stream);
+int mgx_rel_attn_decode_fp8_ragged(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
+                                   const uint16_t* E, const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes,
+                                   int B, int Lmax, int d, int M, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

@@ -170,6 +170,180 @@ __global__ __launch_bounds__(64) void rel_attn_decode_merge_kernel(const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// 8-bit K/V cache (ABI 20): codes uint8 [B, h, Lmax, 64] in OCP e4m3fn, one f32 scale per (b, h, row); element = code * scale.
+// A row x of 64 values is quantized in f32:  amax = max |x_i|;  amax == 0: scale 0, codes 0;  else inv = 448 / amax,
+// code_i = e4m3fn_rne(x_i * inv), scale = amax / 448  (x_i * inv never rounds above 448: no code is NaN).
+// Four consecutive lanes hold one row, 16 values each: a lane's 16 codes are one 16-byte word.
+// ---------------------------------------------------------------------------------------------------
+MGX_DEV u32x4 fp8_quant16(const float* x, float& scale) {
+    float a = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) a = fmaxf(a, fabsf(x[k]));
+    a = fmaxf(a, __shfl_xor(a, 1, 64));
+    a = fmaxf(a, __shfl_xor(a, 2, 64));
+    scale = a / 448.0f;
+    const float inv = 448.0f / a;
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        int v = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * k] * inv, x[4 * k + 1] * inv, 0, false);
+        v = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * k + 2] * inv, x[4 * k + 3] * inv, v, true);
+        c[k] = a == 0.f ? 0u : (uint32_t)v;
+    }
+    return u32x4{c[0], c[1], c[2], c[3]};
+}
+MGX_DEV void fp8_unpack16(const u32x4& w, float* f) {
+    const uint32_t c[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[k], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[k], true);
+        f[4 * k] = lo.x; f[4 * k + 1] = lo.y; f[4 * k + 2] = hi.x; f[4 * k + 3] = hi.y;
+    }
+}
+MGX_DEV void unpack16(const uint16_t* p, float* f) {            // 16 bf16 -> f32 (two 16-byte loads)
+    unpack8(*(const u32x4*)p, f);
+    unpack8(*(const u32x4*)(p + 8), f + 8);
+}
+
+// The attention of rel_attn_decode_kernel over the 8-bit cache: the same split-K scheme, partial layout and merge kernel.
+// lane = (key slot ks = lane>>2, dim group dg = lane&3): a wave handles 16 keys per iteration, each lane 16 of the 64 dims
+// (a 16-byte load of codes; a key costs 64 + 64 bytes of codes and 4 + 4 of scales instead of 256).
+// s_j = scale_k[j] (q.code_k[j]) + q.E_row, and p_j scale_v[j] weights the V codes.  Row t enters its own step already
+// quantized: the key slot that covers j == t quantizes k_t / v_t from qkv_new in registers with the appender's arithmetic, so
+// the call is exactly attention over the dequantized rows 0..t.
+template <bool PER_ROW>
+__global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_fp8_kernel(
+    const uint16_t* __restrict__ qkv_new, uint8_t* __restrict__ kcache, uint8_t* __restrict__ vcache, float* __restrict__ kscale,
+    float* __restrict__ vscale, const uint16_t* __restrict__ E, const int32_t* __restrict__ pos_dev, uint16_t* __restrict__ ctx,
+    float* __restrict__ partial, int Lmax, int d, int M) {
+    const int heads = d >> 6;
+    const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
+    const int nsplit = gridDim.y, sp = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int ks = lane >> 2, dg = lane & 3;
+    const int t = pos_dev[PER_ROW ? b : 0];
+    const uint16_t* qrow = qkv_new + (size_t)b * 3 * d + hd * 64;
+    const size_t row0 = ((size_t)b * heads + hd) * Lmax;
+    uint8_t* kc = kcache + row0 * 64;
+    uint8_t* vc = vcache + row0 * 64;
+    float* ksc = kscale + row0;
+    float* vsc = vscale + row0;
+    // append row t (split 0): lanes 0-3 quantize k_t, lanes 4-7 v_t
+    if (sp == 0 && tid < 8) {
+        const int kv = tid >> 2;
+        float x[16], sc;
+        unpack16(qrow + (1 + kv) * d + dg * 16, x);
+        const u32x4 c = fp8_quant16(x, sc);
+        *(u32x4*)((kv ? vc : kc) + (size_t)t * 64 + dg * 16) = c;
+        if (dg == 0) (kv ? vsc : ksc)[t] = sc;
+    }
+    float q[16];
+    unpack16(qrow + dg * 16, q);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) q[k] *= 0.125f * LOG2E;
+    const int share = ((t + nsplit) / nsplit + 63) & ~63;
+    const int lo = sp * share, hi = min(t + 1, lo + share);
+
+    float m = -INFINITY, l = 0.f, acc[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc[k] = 0.f;
+    const uint16_t* Eb = E + (size_t)(M - 1 - t) * 64;
+    for (int j0 = lo + (w * 16); j0 < hi; j0 += DEC_WAVES * 16) {
+        const int j = j0 + ks;
+        const bool valid = j < hi;
+        const int jc = valid ? j : hi - 1;
+        u32x4 kw = __builtin_nontemporal_load((const u32x4*)(kc + (size_t)jc * 64 + dg * 16));
+        u32x4 vw = __builtin_nontemporal_load((const u32x4*)(vc + (size_t)jc * 64 + dg * 16));
+        float sk = __builtin_nontemporal_load(ksc + jc), sv = __builtin_nontemporal_load(vsc + jc);
+        if (jc == t) {                                          // row t: from qkv_new, quantized here (the append races)
+            float x[16];
+            unpack16(qrow + d + dg * 16, x);
+            kw = fp8_quant16(x, sk);
+            unpack16(qrow + 2 * d + dg * 16, x);
+            vw = fp8_quant16(x, sv);
+        }
+        float kf[16], ef[16], vf[16];
+        fp8_unpack16(kw, kf);
+        unpack16(Eb + (size_t)jc * 64 + dg * 16, ef);
+        fp8_unpack16(vw, vf);
+        float sq = 0.f, se = 0.f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) { sq += q[k] * kf[k]; se += q[k] * ef[k]; }
+        float s = sk * sq + se;
+        s += __shfl_xor(s, 1, 64);
+        s += __shfl_xor(s, 2, 64);
+        if (!valid) s = -INFINITY;
+        const float mn = fmaxf(m, s);
+        const float alpha = (mn == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f(m - mn);
+        const float p = (mn == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(s - mn);
+        l = l * alpha + p;
+        const float pv = p * sv;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[k] = acc[k] * alpha + pv * vf[k];
+        m = mn;
+    }
+    // merge the 16 key slots of the wave (lanes with equal dg), then the 8 waves through LDS
+#pragma unroll
+    for (int o = 4; o < 64; o <<= 1) {
+        const float mo = __shfl_xor(m, o, 64), lo2 = __shfl_xor(l, o, 64);
+        const float mn = fmaxf(m, mo);
+        const float a0 = (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m - mn);
+        const float a1 = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
+        l = l * a0 + lo2 * a1;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) acc[k] = acc[k] * a0 + __shfl_xor(acc[k], o, 64) * a1;
+        m = mn;
+    }
+    __shared__ float sm[DEC_WAVES], sl[DEC_WAVES], sacc[DEC_WAVES][64];
+    if (ks == 0) {
+        if (dg == 0) { sm[w] = m; sl[w] = l; }
+#pragma unroll
+        for (int k = 0; k < 16; ++k) sacc[w][dg * 16 + k] = acc[k];
+    }
+    __syncthreads();
+    if (tid < 64) {
+        float mm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < DEC_WAVES; ++i) mm = fmaxf(mm, sm[i]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < DEC_WAVES; ++i) {
+            const float a = (sm[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(sm[i] - mm);
+            ll += sl[i] * a;
+            o += sacc[i][tid] * a;
+        }
+        if (nsplit == 1) {
+            ctx[(size_t)b * d + hd * 64 + tid] = f32_to_bf16(o / ll);
+        } else {
+            float* pp = partial + ((size_t)blockIdx.x * nsplit + sp) * DEC_PART;
+            if (tid == 0) { pp[64] = mm; pp[65] = ll; }
+            pp[tid] = o;
+        }
+    }
+}
+
+// rows 0..n-1 of the K and V columns of qkv bf16 [B, Lrows, 3d] -> the 8-bit caches: one 4-lane group per (b, row, K|V, head)
+// (groups of one row side by side: each reads a 128-byte run of the qkv row, writes a 64-byte run of codes)
+__global__ __launch_bounds__(256) void kv_store_fp8_kernel(const uint16_t* __restrict__ qkv, int Lrows, int n,
+                                                           uint8_t* __restrict__ kcache, uint8_t* __restrict__ vcache,
+                                                           float* __restrict__ kscale, float* __restrict__ vscale, int B, int Lmax,
+                                                           int d) {
+    const int heads = d >> 6;
+    const size_t g = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 2;
+    const int dg = threadIdx.x & 3;
+    if (g >= (size_t)B * n * 2 * heads) return;                  // whole 4-lane groups leave together
+    const int hd = (int)(g % heads), kv = (int)((g / heads) & 1);
+    const size_t br = g / heads / 2;                             // b * n + row
+    const int row = (int)(br % n), b = (int)(br / n);
+    float x[16], sc;
+    unpack16(qkv + ((size_t)b * Lrows + row) * 3 * d + (1 + kv) * d + hd * 64 + dg * 16, x);
+    const u32x4 c = fp8_quant16(x, sc);
+    const size_t r = ((size_t)b * heads + hd) * Lmax + row;
+    *(u32x4*)((kv ? vcache : kcache) + r * 64 + dg * 16) = c;
+    if (dg == 0) (kv ? vscale : kscale)[r] = sc;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // sampling: one wave per row, V <= 64 * 16
 // ---------------------------------------------------------------------------------------------------
 constexpr int SMP_PER_LANE = 16;
@@ -380,6 +554,55 @@ extern "C" int mgx_rel_attn_decode_ragged(const uint16_t* qkv_new, uint16_t* kca
                                           int Lmax, int d, int M, void* stream) {
     return rel_attn_decode<true>(qkv_new, kcache, vcache, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d, M, stream,
                                  "mgx_rel_attn_decode_ragged");
+}
+
+// the 8-bit cache takes the bf16 cache's key splits, so mgx_rel_attn_decode_workspace / _splits cover both
+template <bool PER_ROW>
+static int rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
+                               const uint16_t* E, const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B,
+                               int Lmax, int d, int M, void* stream, const char* name) {
+    MGX_REQUIRE(qkv_new && kcache && vcache && kscale && vscale && E && pos_dev && ctx, MGX_ERR_NULL, "%s: NULL pointer", name);
+    MGX_REQUIRE(B > 0 && d > 0 && d % 64 == 0 && Lmax > 0 && M >= Lmax, MGX_ERR_SHAPE,
+                "%s: need d%%64==0 and M>=Lmax (B=%d Lmax=%d d=%d M=%d)", name, B, Lmax, d, M);
+    const int ns = decode_splits(B, Lmax, d);
+    MGX_REQUIRE(ns == 1 || (workspace && ws_bytes >= mgx_rel_attn_decode_workspace(B, Lmax, d)), MGX_ERR_SHAPE,
+                "%s: workspace must hold mgx_rel_attn_decode_workspace() = %zu bytes (got %zu)", name,
+                mgx_rel_attn_decode_workspace(B, Lmax, d), ws_bytes);
+    hipLaunchKernelGGL(rel_attn_decode_fp8_kernel<PER_ROW>, dim3(B * (d / 64), ns), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream,
+                       qkv_new, kcache, vcache, kscale, vscale, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
+    if (ns > 1)
+        hipLaunchKernelGGL(rel_attn_decode_merge_kernel, dim3(B * (d / 64)), dim3(64), 0, (hipStream_t)stream,
+                           (const float*)workspace, ctx, ns, d);
+    MGX_CHECK_LAUNCH(name);
+    return MGX_OK;
+}
+
+extern "C" int mgx_rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
+                                       const uint16_t* E, const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes,
+                                       int B, int Lmax, int d, int M, void* stream) {
+    return rel_attn_decode_fp8<false>(qkv_new, kcache, vcache, kscale, vscale, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax, d, M,
+                                      stream, "mgx_rel_attn_decode_fp8");
+}
+
+extern "C" int mgx_rel_attn_decode_fp8_ragged(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale,
+                                              float* vscale, const uint16_t* E, const int32_t* pos_rows, uint16_t* ctx,
+                                              void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M, void* stream) {
+    return rel_attn_decode_fp8<true>(qkv_new, kcache, vcache, kscale, vscale, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d, M,
+                                     stream, "mgx_rel_attn_decode_fp8_ragged");
+}
+
+extern "C" int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* kcache, uint8_t* vcache, float* kscale,
+                                float* vscale, int B, int Lmax, int d, void* stream) {
+    MGX_REQUIRE(qkv && kcache && vcache && kscale && vscale, MGX_ERR_NULL, "mgx_kv_store_fp8: NULL pointer");
+    MGX_REQUIRE(B > 0 && d > 0 && d % 64 == 0 && n >= 0 && n <= Lrows && n <= Lmax, MGX_ERR_SHAPE,
+                "mgx_kv_store_fp8: need d%%64==0 and 0<=n<=min(Lrows,Lmax) (B=%d Lrows=%d n=%d Lmax=%d d=%d)", B, Lrows, n, Lmax, d);
+    if (n == 0) return MGX_OK;
+    const size_t threads = (size_t)B * n * 2 * (d / 64) * 4;
+    MGX_REQUIRE((threads + 255) / 256 <= 0x7fffffff, MGX_ERR_SHAPE, "mgx_kv_store_fp8: too many rows (B=%d n=%d d=%d)", B, n, d);
+    hipLaunchKernelGGL(kv_store_fp8_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, qkv, Lrows, n,
+                       kcache, vcache, kscale, vscale, B, Lmax, d);
+    MGX_CHECK_LAUNCH("mgx_kv_store_fp8");
+    return MGX_OK;
 }
 
 extern "C" int mgx_sample_topk_topp_rows(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,

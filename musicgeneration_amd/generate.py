@@ -44,6 +44,9 @@ def get_options(argv=None):
                       help='comma-separated MIDI files to continue in one batch: each file is one sample (-b is ignored), '
                            'its first 500 MIDI-like events that sample\'s prompt (KV-cache decode over prompts of different '
                            'lengths)')
+    parser.add_option('--kv-cache', dest='kv_cache', type='choice', choices=['bf16', 'fp8'], default='bf16',
+                      help='K/V cache of the KV-cache decode (--grammar, --condition-files): bf16 (default) or fp8, '
+                           'e4m3fn codes with one scale per row -- half the bytes per key, samples differ from bf16')
     return parser.parse_args(argv)[0]
 
 
@@ -76,6 +79,9 @@ def _ragged_priors(o):
 
 def main(argv=None):
     o = get_options(argv)
+    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None):
+        raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
+                         '(the default sampler recomputes the window and keeps no cache)')
     ragged = _ragged_priors(o) if o.condition_files is not None else None     # checked before any model or device work
     device = torch.device('cuda:0')
     vocab = vocab_of(o.repr)
@@ -98,7 +104,7 @@ def main(argv=None):
     if ragged is not None:
         prior, lens = ragged
         res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                 prior_lengths=lens).cpu().numpy()
+                                 prior_lengths=lens, kv_cache=o.kv_cache).cpu().numpy()
         res = [row[:n + o.max_len] for row, n in zip(res, lens)]             # without the pad tail
         _write(o, res)
         return
@@ -123,7 +129,7 @@ def main(argv=None):
         bar = Codec.feat_ranges()['bar'][0]
         prior = torch.full((o.batch_size, 1), bar, dtype=torch.long, device=device)
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                 grammar=Codec.next_token_table()).cpu().numpy()
+                                 grammar=Codec.next_token_table(), kv_cache=o.kv_cache).cpu().numpy()
     else:
         res = mt.generate(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                           reference_mask=o.reference_mask).cpu().numpy()

@@ -323,7 +323,7 @@ class MusicTransformer(torch.nn.Module):
     def generate_cached(self, prior: torch.Tensor, length: int, temperature: float = 1.0, top_k: int = 0,
                         top_p: float = 1.0, seed: int = 0, use_graph: bool = True, return_probs: bool = False,
                         grammar=None, prefill: str = "auto", return_cache: bool = False, groups: Optional[int] = None,
-                        masked_groups: bool = False, prior_lengths=None):
+                        masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16"):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq; no sliding window).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -348,14 +348,24 @@ class MusicTransformer(torch.nn.Module):
         carries the distributions after positions P_b-1 .. P_b+length-2 and zeros elsewhere -- unlike the uniform case, which
         prefills token by token to report every position.  With ``return_cache`` row b's cache rows from P_b+length-1 on
         are zero, as the uniform case leaves its rows from P+length-1 on.  All lengths equal: exactly the call without
-        ``prior_lengths`` on prior[:, :P] (bitwise), its outputs padded to Pmax+length as above."""
+        ``prior_lengths`` on prior[:, :P] (bitwise), its outputs padded to Pmax+length as above.
+
+        ``kv_cache``: "bf16" (default) or "fp8", an opt-in 8-bit cache -- OCP e4m3fn codes with one f32 scale per (b, h, row)
+        (format: include/mgx.h, ABI 20) -- that streams 136 instead of 256 bytes per key and (b, h) and holds a batch in 53 % of
+        the memory.  Every K / V row is quantized as it enters the cache (the batched prefill through ops.kv_store_fp8), so the
+        distributions and samples differ from the bf16 run.  Works with every option above; with
+        ``return_cache`` the result is (res, K codes, V codes, K scales, V scales) per layer, the codes as float8_e4m3fn
+        [B, h, L, 64] and the scales f32 [B, h, L]."""
+        if kv_cache not in ("bf16", "fp8"):
+            raise ValueError(f"kv_cache must be 'bf16' or 'fp8', got {kv_cache!r}")
+        fp8 = kv_cache == "fp8"
         lens = None
         if prior_lengths is not None:
             lens = self._check_prior_lengths(prior, prior_lengths, length, prefill)
             if min(lens) == max(lens):
                 P, Pmax = lens[0], prior.shape[1]
                 res = self.generate_cached(prior[:, :P], length, temperature, top_k, top_p, seed, use_graph, return_probs,
-                                           grammar, prefill, return_cache, groups, masked_groups)
+                                           grammar, prefill, return_cache, groups, masked_groups, kv_cache=kv_cache)
                 return self._pad_uniform_result(res, Pmax - P, return_probs, return_cache)
         ragged = lens is not None
         st = self.store()
@@ -370,8 +380,12 @@ class MusicTransformer(torch.nn.Module):
         d, V, Vp, nl = self.embedding_dim, self.vocab_size, self.vocab_padded, self.num_layer
         bf = torch.bfloat16
         # caches are head-major [B, h, total, 64]: the decode kernel's workgroup (b, h) streams one contiguous run
-        kc = [torch.zeros(B, d // 64, total, 64, dtype=bf, device=dev) for _ in range(nl)]
-        vc = [torch.zeros(B, d // 64, total, 64, dtype=bf, device=dev) for _ in range(nl)]
+        cdt = torch.uint8 if fp8 else bf
+        kc = [torch.zeros(B, d // 64, total, 64, dtype=cdt, device=dev) for _ in range(nl)]
+        vc = [torch.zeros(B, d // 64, total, 64, dtype=cdt, device=dev) for _ in range(nl)]
+        # the 8-bit cache's scales, one per (b, h, row); None per layer for the bf16 cache
+        ksc = [torch.zeros(B, d // 64, total, dtype=torch.float32, device=dev) if fp8 else None for _ in range(nl)]
+        vsc = [torch.zeros(B, d // 64, total, dtype=torch.float32, device=dev) if fp8 else None for _ in range(nl)]
         # ``groups`` (default 1): the batch rows as that many independent sub-batches, each with its own
         # captured step graph replayed on its own stream.  Rows never interact and the sampler draws by (seed, step, GLOBAL
         # row), so the tokens do not depend on the grouping (tests/test_gpu_decode.py).  The point would be to let one
@@ -406,6 +420,7 @@ class MusicTransformer(torch.nn.Module):
             r.tok, r.out, r.h, r.ctx = tok[r.b0:b1], out_tokens[r.b0:b1], hbuf[r.b0:b1], ctxbuf[r.b0:b1]
             r.probs = probs_step[r.b0:b1] if return_probs else None
             r.kc, r.vc = [k[r.b0:b1] for k in kc], [v[r.b0:b1] for v in vc]
+            r.ks, r.vs = [None if s_ is None else s_[r.b0:b1] for s_ in ksc], [None if s_ is None else s_[r.b0:b1] for s_ in vsc]
             r.ws = ops.rel_attn_decode_workspace(b1 - r.b0, total, d, dev)       # split-K partials (long caches only)
             # masked_groups (round 6 experiment): each sub-batch's stream restricted to its own 1/G of the CUs (ops.masked_stream)
             if masked_groups and G > 1:
@@ -455,7 +470,7 @@ class MusicTransformer(torch.nn.Module):
                 h = ops.decode_embed(r.tok, Pm["Decoder.embedding.weight"].data, pe, r.pos, r.h, ragged=ragged)
                 qkv = ops.linear_fwd(h, layers[0]["wqkv"], layers[0]["bqkv"], 0)
             for i, ly in enumerate(layers):
-                ops.rel_attn_decode(qkv, r.kc[i], r.vc[i], ly["E"], r.pos, r.ctx, r.ws, ragged=ragged)
+                ops.rel_attn_decode(qkv, r.kc[i], r.vc[i], ly["E"], r.pos, r.ctx, r.ws, ragged=ragged, kscale=r.ks[i], vscale=r.vs[i])
                 nxt = layers[i + 1] if i + 1 < nl else None
                 if fuse_ln:
                     a = ops.linear_fwd(r.ctx, ly["wfc_f"], ly["bfc"], 0)
@@ -503,8 +518,11 @@ class MusicTransformer(torch.nn.Module):
                 hh = ops.embed_pe_fwd(seq, Pm["Decoder.embedding.weight"].data, pe)
                 for i, ly in enumerate(layers):
                     qkv_p = ops.linear_fwd(hh, ly["wqkv"], ly["bqkv"], 0)
-                    kc[i][:, :, :n] = qkv_p[:, :n, d:2 * d].view(B, n, d // 64, 64).permute(0, 2, 1, 3)
-                    vc[i][:, :, :n] = qkv_p[:, :n, 2 * d:].view(B, n, d // 64, 64).permute(0, 2, 1, 3)
+                    if fp8:
+                        ops.kv_store_fp8(qkv_p, n, kc[i], vc[i], ksc[i], vsc[i])
+                    else:
+                        kc[i][:, :, :n] = qkv_p[:, :n, d:2 * d].view(B, n, d // 64, 64).permute(0, 2, 1, 3)
+                        vc[i][:, :, :n] = qkv_p[:, :n, 2 * d:].view(B, n, d // 64, 64).permute(0, 2, 1, 3)
                     if i + 1 == nl:
                         break                             # the last layer's output rows are not needed: token P-1 follows
                     att, _ = ops.rel_attn_fwd(qkv_p, ly["E"], None)
@@ -565,6 +583,10 @@ class MusicTransformer(torch.nn.Module):
                 stale = (torch.arange(total, device=dev)[None, :] >= (lens_dev[:, None] + length - 1)).view(B, 1, total, 1)
                 for c in kc + vc:
                     c.masked_fill_(stale, 0)
+                for c in ksc + vsc if fp8 else ():
+                    c.masked_fill_(stale.view(B, 1, total), 0)
+            if fp8:
+                return (res, [c.view(torch.float8_e4m3fn) for c in kc], [c.view(torch.float8_e4m3fn) for c in vc], ksc, vsc)
             return (res, kc, vc)
         return res
 
@@ -594,14 +616,20 @@ class MusicTransformer(torch.nn.Module):
         with zeros, to Pmax + length positions"""
         if extra == 0:
             return res
-        if return_cache:
-            res, kc, vc = res
-            kc = [torch.nn.functional.pad(c, (0, 0, 0, extra)) for c in kc]
-            vc = [torch.nn.functional.pad(c, (0, 0, 0, extra)) for c in vc]
+        caches = ()
+        if return_cache:                                  # (K, V) caches, and with kv_cache="fp8" the two scale lists
+            res, *caches = res
+
+            def grow(c):                                  # rows [B, h, L, 64] / scales [B, h, L]; float8 codes padded as bytes
+                pad = (0, 0, 0, extra) if c.dim() == 4 else (0, extra)
+                if c.dtype == torch.float8_e4m3fn:
+                    return torch.nn.functional.pad(c.view(torch.uint8), pad).view(torch.float8_e4m3fn)
+                return torch.nn.functional.pad(c, pad)
+            caches = tuple([grow(c) for c in layer] for layer in caches)
         toks, probs = res if return_probs else (res, None)
         toks = torch.nn.functional.pad(toks, (0, extra), value=self.pad_token)
         res = (toks, torch.nn.functional.pad(probs, (0, 0, 0, extra))) if return_probs else toks
-        return (res, kc, vc) if return_cache else res
+        return (res, *caches) if return_cache else res
 
     def test(self):
         self.eval()
