@@ -50,9 +50,56 @@ __global__ __launch_bounds__(256) void decode_embed_kernel(const int32_t* __rest
 // whichever split covers it (another workgroup appends it to the cache in the same launch).
 constexpr int DEC_WAVES = 8;
 constexpr int DEC_PART = 68;                                   // floats per partial: acc[64], m, l, 2 pad (16-byte aligned rows)
-#ifndef MGX_DEC_NT
-#define MGX_DEC_NT 1
-#endif
+// What the bf16 and the 8-bit kernel share.  DPL = dims per lane (8: bf16, 16: 8-bit codes), so 64 / DPL lanes per key.
+// this split's keys: [lo, hi), shares of ceil((t+1)/nsplit) keys rounded up to the workgroup's 64-key stride
+MGX_DEV void dec_key_range(int t, int nsplit, int sp, int& lo, int& hi) {
+    const int share = ((t + nsplit) / nsplit + 63) & ~63;
+    lo = sp * share, hi = min(t + 1, lo + share);
+}
+// merge the key slots of the wave (lanes with equal dg), then the 8 waves through LDS; 64 threads write ctx (one split) or
+// this split's unnormalised partial
+template <int DPL>
+MGX_DEV void dec_finish(float m, float l, float* acc, uint16_t* __restrict__ ctx, float* __restrict__ partial, int b, int hd, int d,
+                        int nsplit, int sp, int tid, int w, int ks, int dg) {
+#pragma unroll
+    for (int o = 64 / DPL; o < 64; o <<= 1) {
+        const float mo = __shfl_xor(m, o, 64), lo2 = __shfl_xor(l, o, 64);
+        const float mn = fmaxf(m, mo);
+        const float a0 = (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m - mn);
+        const float a1 = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
+        l = l * a0 + lo2 * a1;
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) acc[k] = acc[k] * a0 + __shfl_xor(acc[k], o, 64) * a1;
+        m = mn;
+    }
+    __shared__ float sm[DEC_WAVES], sl[DEC_WAVES], sacc[DEC_WAVES][64];
+    if (ks == 0) {
+        if (dg == 0) { sm[w] = m; sl[w] = l; }
+#pragma unroll
+        for (int k = 0; k < DPL; ++k) sacc[w][dg * DPL + k] = acc[k];
+    }
+    __syncthreads();
+    if (tid < 64) {
+        float mm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < DEC_WAVES; ++i) mm = fmaxf(mm, sm[i]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int i = 0; i < DEC_WAVES; ++i) {
+            const float a = (sm[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(sm[i] - mm);
+            ll += sl[i] * a;
+            o += sacc[i][tid] * a;
+        }
+        if (nsplit == 1) {
+            ctx[(size_t)b * d + hd * 64 + tid] = f32_to_bf16(o / ll);
+        } else {                                                // an empty split leaves (m = -inf, l = 0, acc = 0)
+            float* pp = partial + ((size_t)blockIdx.x * nsplit + sp) * DEC_PART;
+            if (tid == 0) { pp[64] = mm; pp[65] = ll; }
+            pp[tid] = o;
+        }
+    }
+}
+
 template <bool PER_ROW>
 __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
     const uint16_t* __restrict__ qkv_new, uint16_t* __restrict__ kcache, uint16_t* __restrict__ vcache,
@@ -79,9 +126,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
     unpack8(*(const u32x4*)(qrow + dg * 8), q);
 #pragma unroll
     for (int k = 0; k < 8; ++k) q[k] *= 0.125f * LOG2E;         // logits in log2 units
-    // this split's keys: [lo, hi), shares of ceil((t+1)/nsplit) keys rounded up to the workgroup's 64-key stride
-    const int share = ((t + nsplit) / nsplit + 63) & ~63;
-    const int lo = sp * share, hi = min(t + 1, lo + share);
+    int lo, hi;
+    dec_key_range(t, nsplit, sp, lo, hi);
 
     float m = -INFINITY, l = 0.f, acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const uint16_t* Eb = E + (size_t)(M - 1 - t) * 64;           // E row of key j is Eb + j*64
@@ -93,9 +139,9 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
         const uint16_t* vp = (jc == t) ? qrow + 2 * d : vc + (size_t)jc * 64;
         float kf[8], ef[8], vf[8];
         // the K / V caches are streamed once per token (3.2 GB per step at cfg5's end): nontemporal; E rows are shared by every (b, h): cached
-        unpack8(MGX_DEC_NT ? __builtin_nontemporal_load((const u32x4*)(kp + dg * 8)) : *(const u32x4*)(kp + dg * 8), kf);
+        unpack8(__builtin_nontemporal_load((const u32x4*)(kp + dg * 8)), kf);
         unpack8(*(const u32x4*)(Eb + (size_t)jc * 64 + dg * 8), ef);
-        unpack8(MGX_DEC_NT ? __builtin_nontemporal_load((const u32x4*)(vp + dg * 8)) : *(const u32x4*)(vp + dg * 8), vf);
+        unpack8(__builtin_nontemporal_load((const u32x4*)(vp + dg * 8)), vf);
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) s += q[k] * (kf[k] + ef[k]);
@@ -111,44 +157,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
         for (int k = 0; k < 8; ++k) acc[k] = acc[k] * alpha + p * vf[k];
         m = mn;
     }
-    // merge the 8 key slots of the wave (lanes with equal dg), then the 8 waves through LDS
-#pragma unroll
-    for (int o = 8; o < 64; o <<= 1) {
-        const float mo = __shfl_xor(m, o, 64), lo2 = __shfl_xor(l, o, 64);
-        const float mn = fmaxf(m, mo);
-        const float a0 = (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m - mn);
-        const float a1 = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
-        l = l * a0 + lo2 * a1;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = acc[k] * a0 + __shfl_xor(acc[k], o, 64) * a1;
-        m = mn;
-    }
-    __shared__ float sm[DEC_WAVES], sl[DEC_WAVES], sacc[DEC_WAVES][64];
-    if (ks == 0) {
-        if (dg == 0) { sm[w] = m; sl[w] = l; }
-#pragma unroll
-        for (int k = 0; k < 8; ++k) sacc[w][dg * 8 + k] = acc[k];
-    }
-    __syncthreads();
-    if (tid < 64) {
-        float mm = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < DEC_WAVES; ++i) mm = fmaxf(mm, sm[i]);
-        float ll = 0.f, o = 0.f;
-#pragma unroll
-        for (int i = 0; i < DEC_WAVES; ++i) {
-            const float a = (sm[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(sm[i] - mm);
-            ll += sl[i] * a;
-            o += sacc[i][tid] * a;
-        }
-        if (nsplit == 1) {
-            ctx[(size_t)b * d + hd * 64 + tid] = f32_to_bf16(o / ll);
-        } else {                                                // an empty split leaves (m = -inf, l = 0, acc = 0)
-            float* pp = partial + ((size_t)blockIdx.x * nsplit + sp) * DEC_PART;
-            if (tid == 0) { pp[64] = mm; pp[65] = ll; }
-            pp[tid] = o;
-        }
-    }
+    dec_finish<8>(m, l, acc, ctx, partial, b, hd, d, nsplit, sp, tid, w, ks, dg);
 }
 
 // ctx[b, hd*64 + c] = sum_s acc_s[c] 2^(m_s - m) / sum_s l_s 2^(m_s - m): one wave per (b,h)
@@ -241,8 +250,8 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_fp8_kernel(
     unpack16(qrow + dg * 16, q);
 #pragma unroll
     for (int k = 0; k < 16; ++k) q[k] *= 0.125f * LOG2E;
-    const int share = ((t + nsplit) / nsplit + 63) & ~63;
-    const int lo = sp * share, hi = min(t + 1, lo + share);
+    int lo, hi;
+    dec_key_range(t, nsplit, sp, lo, hi);
 
     float m = -INFINITY, l = 0.f, acc[16];
 #pragma unroll
@@ -282,44 +291,7 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_fp8_kernel(
         for (int k = 0; k < 16; ++k) acc[k] = acc[k] * alpha + pv * vf[k];
         m = mn;
     }
-    // merge the 16 key slots of the wave (lanes with equal dg), then the 8 waves through LDS
-#pragma unroll
-    for (int o = 4; o < 64; o <<= 1) {
-        const float mo = __shfl_xor(m, o, 64), lo2 = __shfl_xor(l, o, 64);
-        const float mn = fmaxf(m, mo);
-        const float a0 = (m == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m - mn);
-        const float a1 = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
-        l = l * a0 + lo2 * a1;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acc[k] = acc[k] * a0 + __shfl_xor(acc[k], o, 64) * a1;
-        m = mn;
-    }
-    __shared__ float sm[DEC_WAVES], sl[DEC_WAVES], sacc[DEC_WAVES][64];
-    if (ks == 0) {
-        if (dg == 0) { sm[w] = m; sl[w] = l; }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) sacc[w][dg * 16 + k] = acc[k];
-    }
-    __syncthreads();
-    if (tid < 64) {
-        float mm = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < DEC_WAVES; ++i) mm = fmaxf(mm, sm[i]);
-        float ll = 0.f, o = 0.f;
-#pragma unroll
-        for (int i = 0; i < DEC_WAVES; ++i) {
-            const float a = (sm[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(sm[i] - mm);
-            ll += sl[i] * a;
-            o += sacc[i][tid] * a;
-        }
-        if (nsplit == 1) {
-            ctx[(size_t)b * d + hd * 64 + tid] = f32_to_bf16(o / ll);
-        } else {
-            float* pp = partial + ((size_t)blockIdx.x * nsplit + sp) * DEC_PART;
-            if (tid == 0) { pp[64] = mm; pp[65] = ll; }
-            pp[tid] = o;
-        }
-    }
+    dec_finish<16>(m, l, acc, ctx, partial, b, hd, d, nsplit, sp, tid, w, ks, dg);
 }
 
 // rows 0..n-1 of the K and V columns of qkv bf16 [B, Lrows, 3d] -> the 8-bit caches: one 4-lane group per (b, row, K|V, head)
@@ -522,19 +494,27 @@ extern "C" size_t mgx_rel_attn_decode_workspace(int B, int Lmax, int d) {
     return s == 1 ? 0 : (size_t)B * (d / 64) * s * DEC_PART * sizeof(float);
 }
 
-template <bool PER_ROW>
-static int rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E, const int32_t* pos_dev,
-                           uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M, void* stream,
-                           const char* name) {
-    MGX_REQUIRE(qkv_new && kcache && vcache && E && pos_dev && ctx, MGX_ERR_NULL, "%s: NULL pointer", name);
+// the four attention entry points.  FP8: the caches are e4m3fn codes with their two scale arrays; it takes the bf16 cache's key
+// splits, so mgx_rel_attn_decode_workspace / _splits cover both
+template <bool FP8, bool PER_ROW>
+static int rel_attn_decode(const uint16_t* qkv_new, void* kcache, void* vcache, float* kscale, float* vscale, const uint16_t* E,
+                           const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M,
+                           void* stream, const char* name) {
+    MGX_REQUIRE(qkv_new && kcache && vcache && (!FP8 || (kscale && vscale)) && E && pos_dev && ctx, MGX_ERR_NULL, "%s: NULL pointer",
+                name);
     MGX_REQUIRE(B > 0 && d > 0 && d % 64 == 0 && Lmax > 0 && M >= Lmax, MGX_ERR_SHAPE,
                 "%s: need d%%64==0 and M>=Lmax (B=%d Lmax=%d d=%d M=%d)", name, B, Lmax, d, M);
     const int ns = decode_splits(B, Lmax, d);
     MGX_REQUIRE(ns == 1 || (workspace && ws_bytes >= mgx_rel_attn_decode_workspace(B, Lmax, d)), MGX_ERR_SHAPE,
                 "%s: workspace must hold mgx_rel_attn_decode_workspace() = %zu bytes (got %zu)", name,
                 mgx_rel_attn_decode_workspace(B, Lmax, d), ws_bytes);
-    hipLaunchKernelGGL(rel_attn_decode_kernel<PER_ROW>, dim3(B * (d / 64), ns), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream,
-                       qkv_new, kcache, vcache, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
+    const dim3 grid(B * (d / 64), ns), block(64 * DEC_WAVES);
+    if constexpr (FP8)
+        hipLaunchKernelGGL(rel_attn_decode_fp8_kernel<PER_ROW>, grid, block, 0, (hipStream_t)stream, qkv_new, (uint8_t*)kcache,
+                           (uint8_t*)vcache, kscale, vscale, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
+    else
+        hipLaunchKernelGGL(rel_attn_decode_kernel<PER_ROW>, grid, block, 0, (hipStream_t)stream, qkv_new, (uint16_t*)kcache,
+                           (uint16_t*)vcache, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
     if (ns > 1)
         hipLaunchKernelGGL(rel_attn_decode_merge_kernel, dim3(B * (d / 64)), dim3(64), 0, (hipStream_t)stream,
                            (const float*)workspace, ctx, ns, d);
@@ -543,52 +523,31 @@ static int rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* 
 }
 
 extern "C" int mgx_rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
-                                   const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax,
-                                   int d, int M, void* stream) {
-    return rel_attn_decode<false>(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax, d, M, stream,
-                                  "mgx_rel_attn_decode");
+                                   const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax, int d,
+                                   int M, void* stream) {
+    return rel_attn_decode<false, false>(qkv_new, kcache, vcache, nullptr, nullptr, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax,
+                                         d, M, stream, "mgx_rel_attn_decode");
 }
 
 extern "C" int mgx_rel_attn_decode_ragged(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
-                                          const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes, int B,
-                                          int Lmax, int d, int M, void* stream) {
-    return rel_attn_decode<true>(qkv_new, kcache, vcache, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d, M, stream,
-                                 "mgx_rel_attn_decode_ragged");
-}
-
-// the 8-bit cache takes the bf16 cache's key splits, so mgx_rel_attn_decode_workspace / _splits cover both
-template <bool PER_ROW>
-static int rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
-                               const uint16_t* E, const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B,
-                               int Lmax, int d, int M, void* stream, const char* name) {
-    MGX_REQUIRE(qkv_new && kcache && vcache && kscale && vscale && E && pos_dev && ctx, MGX_ERR_NULL, "%s: NULL pointer", name);
-    MGX_REQUIRE(B > 0 && d > 0 && d % 64 == 0 && Lmax > 0 && M >= Lmax, MGX_ERR_SHAPE,
-                "%s: need d%%64==0 and M>=Lmax (B=%d Lmax=%d d=%d M=%d)", name, B, Lmax, d, M);
-    const int ns = decode_splits(B, Lmax, d);
-    MGX_REQUIRE(ns == 1 || (workspace && ws_bytes >= mgx_rel_attn_decode_workspace(B, Lmax, d)), MGX_ERR_SHAPE,
-                "%s: workspace must hold mgx_rel_attn_decode_workspace() = %zu bytes (got %zu)", name,
-                mgx_rel_attn_decode_workspace(B, Lmax, d), ws_bytes);
-    hipLaunchKernelGGL(rel_attn_decode_fp8_kernel<PER_ROW>, dim3(B * (d / 64), ns), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream,
-                       qkv_new, kcache, vcache, kscale, vscale, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
-    if (ns > 1)
-        hipLaunchKernelGGL(rel_attn_decode_merge_kernel, dim3(B * (d / 64)), dim3(64), 0, (hipStream_t)stream,
-                           (const float*)workspace, ctx, ns, d);
-    MGX_CHECK_LAUNCH(name);
-    return MGX_OK;
+                                          const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax,
+                                          int d, int M, void* stream) {
+    return rel_attn_decode<false, true>(qkv_new, kcache, vcache, nullptr, nullptr, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax,
+                                        d, M, stream, "mgx_rel_attn_decode_ragged");
 }
 
 extern "C" int mgx_rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
                                        const uint16_t* E, const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes,
                                        int B, int Lmax, int d, int M, void* stream) {
-    return rel_attn_decode_fp8<false>(qkv_new, kcache, vcache, kscale, vscale, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax, d, M,
-                                      stream, "mgx_rel_attn_decode_fp8");
+    return rel_attn_decode<true, false>(qkv_new, kcache, vcache, kscale, vscale, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax, d,
+                                        M, stream, "mgx_rel_attn_decode_fp8");
 }
 
 extern "C" int mgx_rel_attn_decode_fp8_ragged(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale,
                                               float* vscale, const uint16_t* E, const int32_t* pos_rows, uint16_t* ctx,
                                               void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M, void* stream) {
-    return rel_attn_decode_fp8<true>(qkv_new, kcache, vcache, kscale, vscale, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d, M,
-                                     stream, "mgx_rel_attn_decode_fp8_ragged");
+    return rel_attn_decode<true, true>(qkv_new, kcache, vcache, kscale, vscale, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d,
+                                       M, stream, "mgx_rel_attn_decode_fp8_ragged");
 }
 
 extern "C" int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* kcache, uint8_t* vcache, float* kscale,
@@ -605,41 +564,45 @@ extern "C" int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* 
     return MGX_OK;
 }
 
+// the three sampler entry points; advance: one more launch moves the position(s) on
+template <bool PER_ROW>
+static int sample(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p, uint64_t seed, int32_t* pos_dev,
+                  int32_t* next_tok, int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
+                  const uint32_t* allow_table, void* stream, const char* name) {
+    MGX_REQUIRE(logits && pos_dev && next_tok, MGX_ERR_NULL, "%s: NULL pointer", name);
+    MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && top_p > 0.f && row0 >= 0, MGX_ERR_SHAPE,
+                "%s: need 0<V<=%d, ld>=V, temperature>0, top_p>0, row0>=0 (V=%d ld=%d)", name, 64 * SMP_PER_LANE, V, ld);
+    hipLaunchKernelGGL(sample_kernel<PER_ROW>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
+                       top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, row0, allow_table);
+    if (advance && PER_ROW)
+        hipLaunchKernelGGL(advance_pos_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_dev, B);
+    else if (advance)
+        hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos_dev);
+    MGX_CHECK_LAUNCH(name);
+    return MGX_OK;
+}
+
 extern "C" int mgx_sample_topk_topp_rows(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
                                          uint64_t seed, int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld,
                                          float* probs_out, int B, int row0, int advance, const uint32_t* allow_table,
                                          void* stream) {
-    MGX_REQUIRE(logits && pos_dev && next_tok, MGX_ERR_NULL, "mgx_sample_topk_topp: NULL pointer");
-    MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && top_p > 0.f && row0 >= 0, MGX_ERR_SHAPE,
-                "mgx_sample_topk_topp: need 0<V<=%d, ld>=V, temperature>0, top_p>0, row0>=0 (V=%d ld=%d)", 64 * SMP_PER_LANE, V, ld);
-    hipLaunchKernelGGL(sample_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
-                       top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, row0, allow_table);
-    if (advance) hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos_dev);
-    MGX_CHECK_LAUNCH("mgx_sample_topk_topp");
-    return MGX_OK;
+    return sample<false>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B, row0,
+                         advance, allow_table, stream, "mgx_sample_topk_topp_rows");
 }
 
 extern "C" int mgx_sample_topk_topp_ragged(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
                                            uint64_t seed, int32_t* pos_rows, int32_t* next_tok, int32_t* out_tokens, int out_ld,
                                            float* probs_out, int B, int row0, int advance, const uint32_t* allow_table,
                                            void* stream) {
-    MGX_REQUIRE(logits && pos_rows && next_tok, MGX_ERR_NULL, "mgx_sample_topk_topp_ragged: NULL pointer");
-    MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && top_p > 0.f && row0 >= 0, MGX_ERR_SHAPE,
-                "mgx_sample_topk_topp_ragged: need 0<V<=%d, ld>=V, temperature>0, top_p>0, row0>=0 (V=%d ld=%d)", 64 * SMP_PER_LANE,
-                V, ld);
-    hipLaunchKernelGGL(sample_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
-                       top_p, seed, pos_rows, next_tok, out_tokens, out_ld, probs_out, row0, allow_table);
-    if (advance)
-        hipLaunchKernelGGL(advance_pos_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_rows, B);
-    MGX_CHECK_LAUNCH("mgx_sample_topk_topp_ragged");
-    return MGX_OK;
+    return sample<true>(logits, V, ld, temperature, top_k, top_p, seed, pos_rows, next_tok, out_tokens, out_ld, probs_out, B, row0,
+                        advance, allow_table, stream, "mgx_sample_topk_topp_ragged");
 }
 
-extern "C" int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                                    uint64_t seed, int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld,
-                                    float* probs_out, int B, int advance, const uint32_t* allow_table, void* stream) {
-    return mgx_sample_topk_topp_rows(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld,
-                                     probs_out, B, 0, advance, allow_table, stream);
+extern "C" int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p, uint64_t seed,
+                                    int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld, float* probs_out, int B,
+                                    int advance, const uint32_t* allow_table, void* stream) {
+    return sample<false>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B, 0,
+                         advance, allow_table, stream, "mgx_sample_topk_topp");
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -2162,50 +2162,43 @@ extern "C" int mgx_linear_ln_fwd_frag(const uint16_t* X, const uint16_t* RES, co
 }
 
 
-extern "C" int mgx_decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
-                                       const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K,
-                                       int V, void* stream) {
-    MGX_REQUIRE(tok && table && pe && pos_dev && W && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear: NULL pointer");
+// the four fused-embedding entry points: W row-major or (FRAG) in MFMA fragment order, one position or (PER_ROW) one per row
+template <bool FRAG, bool PER_ROW>
+static int decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, const uint16_t* W,
+                               const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V, void* stream,
+                               const char* name) {
+    MGX_REQUIRE(tok && table && pe && pos_dev && W && C && H, MGX_ERR_NULL, "%s: NULL pointer", name);
     MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
-                "mgx_decode_embed_linear: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
-    hipLaunchKernelGGL((linear_skinny_embed_kernel<false, false>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe, pos_dev,
-                       W, bias, C, H, M, N, K, V, sqrtf((float)K));
-    MGX_CHECK_LAUNCH("mgx_decode_embed_linear");
+                "%s: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", name, M, N, K);
+    hipLaunchKernelGGL((linear_skinny_embed_kernel<FRAG, PER_ROW>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table,
+                       pe, pos_dev, W, bias, C, H, M, N, K, V, sqrtf((float)K));
+    MGX_CHECK_LAUNCH(name);
     return MGX_OK;
+}
+
+extern "C" int mgx_decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
+                                       const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V,
+                                       void* stream) {
+    return decode_embed_linear<false, false>(tok, table, pe, pos_dev, W, bias, C, H, M, N, K, V, stream, "mgx_decode_embed_linear");
 }
 
 extern "C" int mgx_decode_embed_linear_frag(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
                                             const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K,
                                             int V, void* stream) {
-    MGX_REQUIRE(tok && table && pe && pos_dev && Wf && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear_frag: NULL pointer");
-    MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
-                "mgx_decode_embed_linear_frag: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
-    hipLaunchKernelGGL((linear_skinny_embed_kernel<true, false>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
-                       pos_dev, Wf, bias, C, H, M, N, K, V, sqrtf((float)K));
-    MGX_CHECK_LAUNCH("mgx_decode_embed_linear_frag");
-    return MGX_OK;
+    return decode_embed_linear<true, false>(tok, table, pe, pos_dev, Wf, bias, C, H, M, N, K, V, stream,
+                                            "mgx_decode_embed_linear_frag");
 }
 
 extern "C" int mgx_decode_embed_linear_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
                                               const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K,
                                               int V, void* stream) {
-    MGX_REQUIRE(tok && table && pe && pos_rows && W && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear_ragged: NULL pointer");
-    MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
-                "mgx_decode_embed_linear_ragged: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
-    hipLaunchKernelGGL((linear_skinny_embed_kernel<false, true>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
-                       pos_rows, W, bias, C, H, M, N, K, V, sqrtf((float)K));
-    MGX_CHECK_LAUNCH("mgx_decode_embed_linear_ragged");
-    return MGX_OK;
+    return decode_embed_linear<false, true>(tok, table, pe, pos_rows, W, bias, C, H, M, N, K, V, stream,
+                                            "mgx_decode_embed_linear_ragged");
 }
 
 extern "C" int mgx_decode_embed_linear_frag_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
                                                    const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N,
                                                    int K, int V, void* stream) {
-    MGX_REQUIRE(tok && table && pe && pos_rows && Wf && C && H, MGX_ERR_NULL, "mgx_decode_embed_linear_frag_ragged: NULL pointer");
-    MGX_REQUIRE(M > 0 && M <= 32 && N > 0 && K > 0 && K % 64 == 0 && V > 0, MGX_ERR_SHAPE,
-                "mgx_decode_embed_linear_frag_ragged: need 0<M<=32, K%%64==0 (got M=%d N=%d K=%d)", M, N, K);
-    hipLaunchKernelGGL((linear_skinny_embed_kernel<true, true>), dim3((N + 31) / 32), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
-                       pos_rows, Wf, bias, C, H, M, N, K, V, sqrtf((float)K));
-    MGX_CHECK_LAUNCH("mgx_decode_embed_linear_frag_ragged");
-    return MGX_OK;
+    return decode_embed_linear<true, true>(tok, table, pe, pos_rows, Wf, bias, C, H, M, N, K, V, stream,
+                                           "mgx_decode_embed_linear_frag_ragged");
 }

@@ -11,10 +11,9 @@ import os
 
 from typing import Optional
 
-import numpy as np
 import torch
 
-from . import config, ops
+from . import config, decode, ops
 from .layers import Encoder, EncoderLayer, FlatStore
 
 
@@ -316,9 +315,7 @@ class MusicTransformer(torch.nn.Module):
             result_array = torch.cat((result_array, nxt), dim=-1)
         return result_array
 
-    # ------------------------------------------------------------------------------------------
-    # KV-cache decode (cfg5): O(t) per token instead of the reference's O(W^2) recompute
-    # ------------------------------------------------------------------------------------------
+    # KV-cache decode (cfg5): O(t) per token instead of the reference's O(W^2) recompute; the driver is decode.py
     @torch.no_grad()
     def generate_cached(self, prior: torch.Tensor, length: int, temperature: float = 1.0, top_k: int = 0,
                         top_p: float = 1.0, seed: int = 0, use_graph: bool = True, return_probs: bool = False,
@@ -356,280 +353,8 @@ class MusicTransformer(torch.nn.Module):
         distributions and samples differ from the bf16 run.  Works with every option above; with
         ``return_cache`` the result is (res, K codes, V codes, K scales, V scales) per layer, the codes as float8_e4m3fn
         [B, h, L, 64] and the scales f32 [B, h, L]."""
-        if kv_cache not in ("bf16", "fp8"):
-            raise ValueError(f"kv_cache must be 'bf16' or 'fp8', got {kv_cache!r}")
-        fp8 = kv_cache == "fp8"
-        lens = None
-        if prior_lengths is not None:
-            lens = self._check_prior_lengths(prior, prior_lengths, length, prefill)
-            if min(lens) == max(lens):
-                P, Pmax = lens[0], prior.shape[1]
-                res = self.generate_cached(prior[:, :P], length, temperature, top_k, top_p, seed, use_graph, return_probs,
-                                           grammar, prefill, return_cache, groups, masked_groups, kv_cache=kv_cache)
-                return self._pad_uniform_result(res, Pmax - P, return_probs, return_cache)
-        ragged = lens is not None
-        st = self.store()
-        st.sync_shadow()
-        was_training = self.training
-        self.eval()
-        B, P = prior.shape
-        total = P + length
-        if total > self.max_seq or P < 1:
-            raise ValueError(f"prior ({P}) + length ({length}) must be <= max_seq ({self.max_seq}) and prior non-empty")
-        dev = st.param.device
-        d, V, Vp, nl = self.embedding_dim, self.vocab_size, self.vocab_padded, self.num_layer
-        bf = torch.bfloat16
-        # caches are head-major [B, h, total, 64]: the decode kernel's workgroup (b, h) streams one contiguous run
-        cdt = torch.uint8 if fp8 else bf
-        kc = [torch.zeros(B, d // 64, total, 64, dtype=cdt, device=dev) for _ in range(nl)]
-        vc = [torch.zeros(B, d // 64, total, 64, dtype=cdt, device=dev) for _ in range(nl)]
-        # the 8-bit cache's scales, one per (b, h, row); None per layer for the bf16 cache
-        ksc = [torch.zeros(B, d // 64, total, dtype=torch.float32, device=dev) if fp8 else None for _ in range(nl)]
-        vsc = [torch.zeros(B, d // 64, total, dtype=torch.float32, device=dev) if fp8 else None for _ in range(nl)]
-        # ``groups`` (default 1): the batch rows as that many independent sub-batches, each with its own
-        # captured step graph replayed on its own stream.  Rows never interact and the sampler draws by (seed, step, GLOBAL
-        # row), so the tokens do not depend on the grouping (tests/test_gpu_decode.py).  The point would be to let one
-        # sub-batch's bandwidth-bound attention stream its caches while another's chain of ~40 small projections waits out
-        # its launch latencies; measured at cfg5 (profiles/README.md, round 3) two hardware queues dispatch those chains
-        # SLOWER than one does (0.75 ms/token at 2 groups, 0.48 at 3-4, 0.72 at 6, against 0.50-0.51 at 1), so it stays off.
-        G = max(1, min(int(groups or 1), B))
-        cuts = [B * g // G for g in range(G + 1)]
-        pos_all = torch.zeros(B if ragged else G, dtype=torch.int32, device=dev)     # ragged: one position per row
-        tok = prior[:, 0].to(torch.int32).contiguous().to(dev)
-        prior_i = prior.to(torch.int32).to(dev)
-        out_tokens = torch.zeros(B, total, dtype=torch.int32, device=dev)
-        if ragged:
-            lens_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
-            rows = torch.arange(B, device=dev)
-            # the right padding becomes pad_token (a valid id for the prefill; the result's tail past each row's samples)
-            prior_i = torch.where(torch.arange(P, device=dev)[None, :] < lens_dev[:, None], prior_i, self.pad_token)
-            out_tokens.fill_(self.pad_token)
-        out_tokens[:, :P] = prior_i
-        probs_all = torch.zeros(B, total, V, dtype=torch.float32, device=dev) if return_probs else None
-        probs_step = torch.zeros(B, V, dtype=torch.float32, device=dev) if return_probs else None
-        hbuf = torch.empty(B, d, dtype=bf, device=dev)
-        ctxbuf = torch.empty(B, d, dtype=bf, device=dev)
-
-        class _Rows:                                        # one sub-batch: views of rows [b0, b1) of every per-row buffer
-            pass
-        subs = []
-        for g in range(G):
-            r = _Rows()
-            r.b0, b1 = cuts[g], cuts[g + 1]
-            r.pos = pos_all[r.b0:b1] if ragged else pos_all[g:g + 1]
-            r.tok, r.out, r.h, r.ctx = tok[r.b0:b1], out_tokens[r.b0:b1], hbuf[r.b0:b1], ctxbuf[r.b0:b1]
-            r.probs = probs_step[r.b0:b1] if return_probs else None
-            r.kc, r.vc = [k[r.b0:b1] for k in kc], [v[r.b0:b1] for v in vc]
-            r.ks, r.vs = [None if s_ is None else s_[r.b0:b1] for s_ in ksc], [None if s_ is None else s_[r.b0:b1] for s_ in vsc]
-            r.ws = ops.rel_attn_decode_workspace(b1 - r.b0, total, d, dev)       # split-K partials (long caches only)
-            # masked_groups (round 6 experiment): each sub-batch's stream restricted to its own 1/G of the CUs (ops.masked_stream)
-            if masked_groups and G > 1:
-                per = torch.cuda.get_device_properties(dev).multi_processor_count // G // 8 * 8
-                r.stream = ops.masked_stream(per, g * per, dev).stream
-            else:
-                r.stream = torch.cuda.Stream()
-            subs.append(r)
-        pe = self.Decoder.pos_encoding.table()
-        Pm = st.params
-        layers = []
-        for i in range(nl):
-            pre = f"Decoder.enc_layers.{i}."
-            layers.append(dict(
-                wqkv=st.fused(pre + "rga.Wq.weight", pre + "rga.Wv.weight", 3 * d, d),
-                bqkv=st.fused(pre + "rga.Wq.bias", pre + "rga.Wv.bias", 1, 3 * d, "param").view(3 * d),
-                E=st.w(pre + "rga.E"), wfc=st.w(pre + "rga.fc.weight"), bfc=Pm[pre + "rga.fc.bias"].data,
-                g1=Pm[pre + "layernorm1.weight"].data, b1=Pm[pre + "layernorm1.bias"].data,
-                w1=self._layer_params()[i].wpre, bb1=self._layer_params()[i].bpre,
-                w2=self._layer_params()[i].wsuf, bb2=Pm[pre + "FFN_suf.bias"].data,
-                g2=Pm[pre + "layernorm2.weight"].data, b2=Pm[pre + "layernorm2.bias"].data))
-        wv, bv = st.padded_view("fc.weight", Vp, d), st.padded_view("fc.bias", Vp, None, "param")
-        # grammar: [V, ceil(V/32)] bit table "token v may follow token t" (e.g. REMI_EventSeq.next_token_table()); applied
-        # inside the sampling kernel, so the constrained step stays graph-captured
-        allow = None
-        if grammar is not None:
-            allow = torch.as_tensor(np.ascontiguousarray(grammar).view(np.int32) if isinstance(grammar, np.ndarray) else grammar)
-            allow = allow.to(device=dev, dtype=torch.int32).contiguous()
-
-        # decode-size batches: every LayerNorm rides in the projection that consumes it (mgx_linear_ln_fwd) and the embedding in
-        # the first QKV projection (mgx_decode_embed_linear): 39 launches per token instead of 46
-        fuse_ln = B <= 32 and d <= 1024
-        if fuse_ln:
-            # ... and every projection weight is re-laid out once per call in MFMA fragment order (ops.FragWeight): a wave load of
-            # weights is then 1 KB contiguous instead of 32 B of 32 different rows
-            # (the batched prefill below keeps using the row-major matrices)
-            for ly in layers:
-                for k in ("wqkv", "wfc", "w1", "w2"):
-                    ly[k + "_f"] = ops.FragWeight(ly[k])
-            wv_f = ops.FragWeight(wv)
-
-        def step_rows(r, sample_into_out: bool):
-            if fuse_ln:
-                qkv, h = ops.decode_embed_linear(r.tok, Pm["Decoder.embedding.weight"].data, pe, r.pos, layers[0]["wqkv_f"],
-                                                 layers[0]["bqkv"], r.h, ragged=ragged)
-            else:
-                h = ops.decode_embed(r.tok, Pm["Decoder.embedding.weight"].data, pe, r.pos, r.h, ragged=ragged)
-                qkv = ops.linear_fwd(h, layers[0]["wqkv"], layers[0]["bqkv"], 0)
-            for i, ly in enumerate(layers):
-                ops.rel_attn_decode(qkv, r.kc[i], r.vc[i], ly["E"], r.pos, r.ctx, r.ws, ragged=ragged, kscale=r.ks[i], vscale=r.vs[i])
-                nxt = layers[i + 1] if i + 1 < nl else None
-                if fuse_ln:
-                    a = ops.linear_fwd(r.ctx, ly["wfc_f"], ly["bfc"], 0)
-                    f, o1 = ops.linear_ln_fwd(a, h, ly["g1"], ly["b1"], ly["w1_f"], ly["bb1"], 1)
-                    f = ops.linear_fwd(f, ly["w2_f"], ly["bb2"], 0)
-                    if nxt is not None:
-                        qkv, h = ops.linear_ln_fwd(f, o1, ly["g2"], ly["b2"], nxt["wqkv_f"], nxt["bqkv"], 0)
-                    else:
-                        logits, h = ops.linear_ln_fwd(f, o1, ly["g2"], ly["b2"], wv_f, bv, 0)
-                else:
-                    a = ops.linear_fwd(r.ctx, ly["wfc"], ly["bfc"], 0)
-                    o1 = ops.add_ln_fwd(a, h, ly["g1"], ly["b1"], 1e-6)[0]
-                    f = ops.linear_fwd(o1, ly["w1"], ly["bb1"], 1)
-                    f = ops.linear_fwd(f, ly["w2"], ly["bb2"], 0)
-                    h = ops.add_ln_fwd(f, o1, ly["g2"], ly["b2"], 1e-6)[0]
-                    if nxt is not None:
-                        qkv = ops.linear_fwd(h, nxt["wqkv"], nxt["bqkv"], 0)
-                    else:
-                        logits = ops.linear_fwd(h, wv, bv, 0)
-            ops.sample_topk_topp(logits, V, r.pos, r.tok, r.out if sample_into_out else None, r.probs, temperature,
-                                 top_k, top_p, seed, advance=True, allow_table=allow, row0=r.b0, ragged=ragged)
-
-        def step(sample_into_out: bool):                  # eager: the sub-batches one after the other on the current stream
-            for r in subs:
-                step_rows(r, sample_into_out)
-
-        if prefill not in ("auto", "token", "batched"):
-            raise ValueError("prefill must be 'auto', 'token' or 'batched'")
-        if prefill == "batched" and return_probs and not ragged:
-            raise ValueError("return_probs needs prefill='token' (it reports the distribution after every prior token)")
-        first = 0
-        # the batched pass pads the prompt to a multiple of 32 rows; when that exceeds max_seq (max_seq not a multiple of 32)
-        # the full-sequence kernels cannot take it: 'auto' falls back to token-by-token prefill, 'batched' says why
-        fits = (P - 1 + 31) // 32 * 32 <= self.max_seq
-        if prefill == "batched" and not fits:
-            raise ValueError(f"prefill='batched' pads the {P - 1}-token prompt to {(P - 1 + 31) // 32 * 32} rows > max_seq={self.max_seq}")
-        if ragged or prefill == "batched" or (prefill == "auto" and not return_probs and P > 32 and fits):
-            # batched prefill: positions 0..P-2 through the full-sequence kernels (causal, so the zero-padded tail up to a
-            # multiple of 32 cannot reach them); token P-1 then takes the ordinary decode step below
-            n = P - 1
-            if n > 0:
-                Lp = (n + 31) // 32 * 32
-                seq = torch.zeros(B, Lp, dtype=torch.int32, device=dev)
-                seq[:, :n] = prior_i[:, :n]
-                hh = ops.embed_pe_fwd(seq, Pm["Decoder.embedding.weight"].data, pe)
-                for i, ly in enumerate(layers):
-                    qkv_p = ops.linear_fwd(hh, ly["wqkv"], ly["bqkv"], 0)
-                    if fp8:
-                        ops.kv_store_fp8(qkv_p, n, kc[i], vc[i], ksc[i], vsc[i])
-                    else:
-                        kc[i][:, :, :n] = qkv_p[:, :n, d:2 * d].view(B, n, d // 64, 64).permute(0, 2, 1, 3)
-                        vc[i][:, :, :n] = qkv_p[:, :n, 2 * d:].view(B, n, d // 64, 64).permute(0, 2, 1, 3)
-                    if i + 1 == nl:
-                        break                             # the last layer's output rows are not needed: token P-1 follows
-                    att, _ = ops.rel_attn_fwd(qkv_p, ly["E"], None)
-                    a_p = ops.linear_fwd(att, ly["wfc"], ly["bfc"], 0)
-                    o1_p = ops.add_ln_fwd(a_p, hh, ly["g1"], ly["b1"], 1e-6)[0]
-                    f_p = ops.linear_fwd(ops.linear_fwd(o1_p, ly["w1"], ly["bb1"], 1), ly["w2"], ly["bb2"], 0)
-                    hh = ops.add_ln_fwd(f_p, o1_p, ly["g2"], ly["b2"], 1e-6)[0]
-                pos_all.fill_(n)
-                tok.copy_(prior_i[:, n])
-                first = n
-            if ragged:                                    # every row resumes at its own last prompt token
-                pos_all.copy_(lens_dev - 1)
-                tok.copy_(prior_i[rows, lens_dev.long() - 1])
-
-        def put_probs(p):                                 # the distribution after position p (per row: after P_b - 1 + p - first)
-            if ragged:
-                probs_all[rows, lens_dev.long() - 1 + (p - first)] = probs_step
-            else:
-                probs_all[:, p] = probs_step
-        # the (rest of the) prior is teacher-forced token by token (it also warms every kernel up before capture)
-        for p in range(first, P):
-            step(sample_into_out=(p == P - 1) and length > 0)
-            if return_probs:
-                put_probs(p)
-            if p + 1 < P:
-                tok.copy_(prior_i[:, p + 1])
-        remaining = length - 1 if length > 0 else 0
-        if remaining > 0:
-            if use_graph and not return_probs and remaining > 2:
-                # one graph per sub-batch, each replayed on its own stream: the sub-batches never meet until the end, so their
-                # chains of launches overlap freely (parallel branches INSIDE one graph were measured to run one after the other)
-                cur = torch.cuda.current_stream()
-                torch.cuda.synchronize()
-                for r in subs:
-                    r.stream.wait_stream(cur)
-                    with torch.cuda.stream(r.stream):
-                        r.graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(r.graph, stream=r.stream):
-                            step_rows(r, True)              # the capture itself does not execute
-                for p in range(remaining):
-                    for r in subs:
-                        with torch.cuda.stream(r.stream):
-                            r.graph.replay()
-                for r in subs:
-                    cur.wait_stream(r.stream)
-                # the graphs, their private pools and the side streams are locals: they must outlive the replays still in flight
-                for r in subs:
-                    r.stream.synchronize()
-            else:
-                for p in range(remaining):
-                    step(True)
-                    if return_probs:
-                        put_probs(P + p)
-        self.train(was_training)
-        res = (out_tokens, probs_all) if return_probs else out_tokens
-        if return_cache:
-            if ragged:                                    # prefill rows a short row's decode never reached
-                stale = (torch.arange(total, device=dev)[None, :] >= (lens_dev[:, None] + length - 1)).view(B, 1, total, 1)
-                for c in kc + vc:
-                    c.masked_fill_(stale, 0)
-                for c in ksc + vsc if fp8 else ():
-                    c.masked_fill_(stale.view(B, 1, total), 0)
-            if fp8:
-                return (res, [c.view(torch.float8_e4m3fn) for c in kc], [c.view(torch.float8_e4m3fn) for c in vc], ksc, vsc)
-            return (res, kc, vc)
-        return res
-
-    def _check_prior_lengths(self, prior: torch.Tensor, prior_lengths, length: int, prefill: str) -> list:
-        """validates generate_cached's ``prior_lengths`` (ValueError) and returns them as a list of ints"""
-        B, Pmax = prior.shape
-        lens = [int(v) for v in torch.as_tensor(prior_lengths).reshape(-1).tolist()]
-        if len(lens) != B:
-            raise ValueError(f"prior_lengths has {len(lens)} entries for a batch of {B} prompts")
-        if any(not 1 <= v <= Pmax for v in lens):
-            raise ValueError(f"prior_lengths must lie in 1 .. {Pmax} (the width of prior), got {lens}")
-        if Pmax + length > self.max_seq:
-            raise ValueError(f"the longest prompt ({Pmax}) + length ({length}) must be <= max_seq ({self.max_seq})")
-        if prefill not in ("auto", "token", "batched"):
-            raise ValueError("prefill must be 'auto', 'token' or 'batched'")
-        if min(lens) != max(lens):
-            if prefill == "token":
-                raise ValueError("prompts of different lengths need prefill='batched' or 'auto' (token-by-token prefill in "
-                                 "lockstep would need a per-row teacher-forced prefix)")
-            if (Pmax - 1 + 31) // 32 * 32 > self.max_seq:
-                raise ValueError(f"prompts of different lengths are prefilled in one batched pass, which pads the {Pmax - 1}-token "
-                                 f"prompt to {(Pmax - 1 + 31) // 32 * 32} rows > max_seq={self.max_seq}")
-        return lens
-
-    def _pad_uniform_result(self, res, extra: int, return_probs: bool, return_cache: bool):
-        """generate_cached's result for equal prior_lengths P < Pmax: tokens padded with pad_token, probabilities and caches
-        with zeros, to Pmax + length positions"""
-        if extra == 0:
-            return res
-        caches = ()
-        if return_cache:                                  # (K, V) caches, and with kv_cache="fp8" the two scale lists
-            res, *caches = res
-
-            def grow(c):                                  # rows [B, h, L, 64] / scales [B, h, L]; float8 codes padded as bytes
-                pad = (0, 0, 0, extra) if c.dim() == 4 else (0, extra)
-                if c.dtype == torch.float8_e4m3fn:
-                    return torch.nn.functional.pad(c.view(torch.uint8), pad).view(torch.float8_e4m3fn)
-                return torch.nn.functional.pad(c, pad)
-            caches = tuple([grow(c) for c in layer] for layer in caches)
-        toks, probs = res if return_probs else (res, None)
-        toks = torch.nn.functional.pad(toks, (0, extra), value=self.pad_token)
-        res = (toks, torch.nn.functional.pad(probs, (0, 0, 0, extra))) if return_probs else toks
-        return (res, *caches) if return_cache else res
+        return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
+                                      prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache)
 
     def test(self):
         self.eval()

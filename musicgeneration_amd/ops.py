@@ -582,16 +582,11 @@ def decode_embed_linear(tok, table, pe, pos_dev, w, bias, hout, *, ragged=False)
     V, d = table.shape
     N = w.shape[0]
     c = torch.empty(tok.numel(), N, dtype=torch.bfloat16, device=hout.device)
-    sfx = _check_pos_rows(pos_dev, tok.numel(), ragged)
-    if isinstance(w, FragWeight):
-        _need_cuda(tok, table, pe, pos_dev, w.data, bias, hout)
-        name = "mgx_decode_embed_linear_frag" + sfx
-        check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(w.data), ptr(bias), ptr(c), ptr(hout),
-                                         tok.numel(), N, d, V, stream_ptr()), name)
-        return c, hout
-    _need_cuda(tok, table, pe, pos_dev, w, bias, hout)
-    name = "mgx_decode_embed_linear" + sfx
-    check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(w), ptr(bias), ptr(c), ptr(hout),
+    frag = isinstance(w, FragWeight)                    # the weight in MFMA fragment order
+    name = "mgx_decode_embed_linear" + ("_frag" if frag else "") + _check_pos_rows(pos_dev, tok.numel(), ragged)
+    wd = w.data if frag else w
+    _need_cuda(tok, table, pe, pos_dev, wd, bias, hout)
+    check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(wd), ptr(bias), ptr(c), ptr(hout),
                                      tok.numel(), N, d, V, stream_ptr()), name)
     return c, hout
 
@@ -610,23 +605,33 @@ def rel_attn_decode_workspace(B, Lmax, d, device):
 _FP8_CACHE = (torch.uint8, torch.float8_e4m3fn)
 
 
-def _check_fp8_cache(kcache, vcache, kscale, vscale, what):
-    """the 8-bit cache (ABI 20): codes uint8 / float8_e4m3fn [B, h, Lmax, 64], scales f32 [B, h, Lmax]"""
-    if kcache.dim() != 4 or kcache.shape[-1] != 64 or vcache.shape != kcache.shape or vcache.dtype not in _FP8_CACHE \
-            or kcache.dtype not in _FP8_CACHE:
-        raise ValueError(f"{what}: the 8-bit caches must be uint8 or float8_e4m3fn [B, h, Lmax, 64] of one shape")
+def _check_kv_cache(kcache, vcache, kscale, vscale, what) -> bool:
+    """validates a K/V cache pair, shape first, then dtype: bf16 [B, h, Lmax, 64], or the 8-bit cache (ABI 20) -- codes uint8 /
+    float8_e4m3fn [B, h, Lmax, 64] with scales f32 [B, h, Lmax].  Returns whether it is the 8-bit cache."""
+    if kcache.dim() != 4 or kcache.shape[-1] != 64 or vcache.shape != kcache.shape:
+        raise ValueError(f"{what}: kcache / vcache must be [B, h, Lmax, 64] of one shape, got {tuple(kcache.shape)} / {tuple(vcache.shape)}")
+    if kcache.dtype not in _FP8_CACHE:
+        if kcache.dtype != torch.bfloat16 or vcache.dtype != torch.bfloat16:
+            raise ValueError(f"{what}: caches must be bf16, uint8 or float8_e4m3fn, got {kcache.dtype} / {vcache.dtype}")
+        if kscale is not None or vscale is not None:
+            raise ValueError(f"{what}: kscale / vscale belong to the 8-bit cache (uint8 or float8_e4m3fn), the caches are bf16")
+        return False
+    if vcache.dtype not in _FP8_CACHE:
+        raise ValueError(f"{what}: the 8-bit caches must both be uint8 or float8_e4m3fn, got {kcache.dtype} / {vcache.dtype}")
     for s in (kscale, vscale):
         if s is None or s.dtype != torch.float32 or tuple(s.shape) != tuple(kcache.shape[:3]):
             raise ValueError(f"{what}: kscale / vscale must be float32 [B, h, Lmax] = {tuple(kcache.shape[:3])} beside the 8-bit caches")
     for t in (kcache, vcache, kscale, vscale):
         if not t.is_contiguous():
             raise ValueError(f"{what}: the 8-bit caches and their scales must be contiguous")
+    return True
 
 
 def kv_store_fp8(qkv, n, kcache, vcache, kscale, vscale):
     """quantize rows 0..n-1 of the K and V columns of qkv bf16 [B, Lrows, 3d] into the 8-bit caches (format: include/mgx.h,
     ABI 20); the other cache rows are left as they are"""
-    _check_fp8_cache(kcache, vcache, kscale, vscale, "kv_store_fp8")
+    if not _check_kv_cache(kcache, vcache, kscale, vscale, "kv_store_fp8"):
+        raise ValueError("kv_store_fp8: the caches must be the 8-bit cache (uint8 or float8_e4m3fn), got bf16")
     B, heads, Lmax, _ = kcache.shape
     d = heads * 64
     if qkv.dtype != torch.bfloat16 or qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[2] != 3 * d or not qkv.is_contiguous():
@@ -640,28 +645,14 @@ def rel_attn_decode(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace=None, *,
     """kcache / vcache bf16 [B, h, Lmax, 64] (head-major: workgroup (b, h) streams one contiguous run of rows);
     ``ragged``: row b's position is pos_dev[b] (each < Lmax: not checked, the positions live on the device).
     uint8 / float8_e4m3fn caches are the 8-bit cache (ABI 20) and need ``kscale`` / ``vscale`` f32 [B, h, Lmax]."""
-    fp8 = kcache.dtype in _FP8_CACHE
-    if fp8:
-        _check_fp8_cache(kcache, vcache, kscale, vscale, "rel_attn_decode")
-    elif kscale is not None or vscale is not None:
-        raise ValueError("rel_attn_decode: kscale / vscale belong to the 8-bit cache (uint8 or float8_e4m3fn), "
-                         f"the caches are {kcache.dtype}")
+    fp8 = _check_kv_cache(kcache, vcache, kscale, vscale, "rel_attn_decode")
     _need_cuda(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace, kscale, vscale)
-    B, heads, Lmax, dh = kcache.shape
-    if dh != 64 or vcache.shape != kcache.shape:
-        raise ValueError("rel_attn_decode: caches must be bf16 [B, h, Lmax, 64]")
-    if not fp8 and (kcache.dtype != torch.bfloat16 or vcache.dtype != torch.bfloat16):
-        raise ValueError(f"rel_attn_decode: caches must be bf16, uint8 or float8_e4m3fn, got {kcache.dtype} / {vcache.dtype}")
-    d = heads * 64
-    sfx = _check_pos_rows(pos_dev, B, ragged)
-    ws = (ptr(workspace), 0 if workspace is None else workspace.numel(), B, Lmax, d, E.shape[0], stream_ptr())
-    if fp8:
-        name = "mgx_rel_attn_decode_fp8" + sfx
-        check(getattr(_lib.load(), name)(ptr(qkv_new), ptr(kcache), ptr(vcache), ptr(kscale), ptr(vscale), ptr(E), ptr(pos_dev),
-                                         ptr(ctx), *ws), name)
-        return ctx
-    name = "mgx_rel_attn_decode" + sfx
-    check(getattr(_lib.load(), name)(ptr(qkv_new), ptr(kcache), ptr(vcache), ptr(E), ptr(pos_dev), ptr(ctx), *ws), name)
+    B, heads, Lmax, _ = kcache.shape
+    name = "mgx_rel_attn_decode" + ("_fp8" if fp8 else "") + _check_pos_rows(pos_dev, B, ragged)
+    scales = (ptr(kscale), ptr(vscale)) if fp8 else ()
+    check(getattr(_lib.load(), name)(ptr(qkv_new), ptr(kcache), ptr(vcache), *scales, ptr(E), ptr(pos_dev), ptr(ctx), ptr(workspace),
+                                     0 if workspace is None else workspace.numel(), B, Lmax, heads * 64, E.shape[0],
+                                     stream_ptr()), name)
     return ctx
 
 
