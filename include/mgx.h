@@ -289,11 +289,16 @@ int mgx_rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vca
                         int B, int Lmax, int d, int M, void* stream);
 /* logits bf16 [B,ld] -> next_tok int32 [B] drawn from softmax(logits/temperature) restricted to the top_k
  * most likely ids (0 = all) and then to the smallest set whose mass reaches top_p (1 = all).
+ * Both cuts are thresholds on the probability -- top-k keeps {p >= tau} for the largest tau with count(p >= tau) >= top_k,
+ * top-p then the largest tau with mass(p >= tau) >= top_p * (the mass top-k kept) -- so ids whose probabilities are EQUAL
+ * are kept or dropped together: a tie across the k-th value keeps more than top_k ids.  The draw is the first kept id, in id
+ * order, whose inclusive CDF reaches u * (kept mass).
  * out_tokens int32 [B,out_ld] (or NULL): column t+1 receives the token; probs_out f32 [B,V] (or NULL)
  * receives the unfiltered softmax.  The draw is a pure function of (seed, t, row).
  * advance != 0: pos_dev[0] += 1 after sampling.  V <= 1024.
  * allow_table (optional, NULL = none): uint32 [V, ceil(V/32)] grammar mask -- bit v of row t set iff token v may follow
- * token t (t = the token next_tok holds on entry); disallowed logits are -inf before temperature/top-k/top-p.     */
+ * token t (t = the token next_tok holds on entry); disallowed logits are -inf before temperature/top-k/top-p.  A grammar row
+ * that leaves no finite logit (it allows nothing, or only ids whose logit is -inf) is ignored for that draw.     */
 int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
                          uint64_t seed, int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld,
                          float* probs_out, int B, int advance, const uint32_t* allow_table, void* stream);

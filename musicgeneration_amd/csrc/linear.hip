@@ -1688,7 +1688,7 @@ __global__ __launch_bounds__(256) void linear_skinny_ln_kernel(const uint16_t* _
     const bool nv = FRAG || nrow < N, mv = mrow < M;
     const size_t xoff = (size_t)(mv ? mrow : 0) * K + w * kq + hh * 8;
     float z[SKLN_MAXF][8];
-    float s1 = 0.f, s2 = 0.f;
+    float s1 = 0.f;
     // the weight fragments are requested first: their latency hides under the statistics
     const uint16_t* wp = FRAG ? W + (((size_t)blockIdx.x * (K >> 4) + (size_t)(w * kq >> 4)) * 64 + lane) * 8
                               : W + (size_t)(nv ? nrow : 0) * K + w * kq + hh * 8;
@@ -1707,18 +1707,28 @@ __global__ __launch_bounds__(256) void linear_skinny_ln_kernel(const uint16_t* _
             for (int k = 0; k < 8; ++k) {
                 z[f][k] = a[k] + r[k];
                 s1 += z[f][k];
-                s2 += z[f][k] * z[f][k];
             }
         }
     }
+    // the statistics in two passes over the registers, as the training kernel (rowwise_ops.hip) takes them: the variance is the
+    // mean of (z - mean)^2.  E[z^2] - mean^2 in one pass loses |mean| / std squared in relative accuracy (a row of mean 60 and
+    // std 0.25: rstd off by 6e-3); the second LDS exchange and barrier cost 0.7 % of a cfg5 decode step (profiles/README.md)
     s1 += __shfl_xor(s1, 32, 64);
-    s2 += __shfl_xor(s2, 32, 64);
-    if (hh == 0) { stat[0][w][l31] = s1; stat[1][w][l31] = s2; }
+    if (hh == 0) stat[0][w][l31] = s1;
     __syncthreads();
-    const float t1 = stat[0][0][l31] + stat[0][1][l31] + stat[0][2][l31] + stat[0][3][l31];
-    const float t2 = stat[1][0][l31] + stat[1][1][l31] + stat[1][2][l31] + stat[1][3][l31];
-    const float mean = t1 / (float)K;
-    const float rstd = rsqrtf(fmaxf(t2 / (float)K - mean * mean, 0.f) + eps);
+    const float mean = (stat[0][0][l31] + stat[0][1][l31] + stat[0][2][l31] + stat[0][3][l31]) / (float)K;
+    float s2 = 0.f;
+#pragma unroll
+    for (int f = 0; f < SKLN_MAXF; ++f) {
+        if (f < nf) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { const float c = z[f][k] - mean; s2 += c * c; }
+        }
+    }
+    s2 += __shfl_xor(s2, 32, 64);
+    if (hh == 0) stat[1][w][l31] = s2;
+    __syncthreads();
+    const float rstd = rsqrtf((stat[1][0][l31] + stat[1][1][l31] + stat[1][2][l31] + stat[1][3][l31]) / (float)K + eps);
     f32x16 acc = zero16();
 #pragma unroll
     for (int f = 0; f < SKLN_MAXF; ++f) {

@@ -9,27 +9,13 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from oracle.decode_ref import dequant, quant_twin
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 BF = torch.bfloat16
 SENTINEL = 0xA5
-
-
-def quant_twin(x):
-    """torch twin of the cache's quantizer (include/mgx.h): x [..., 64] -> (codes uint8 [..., 64], scales f32 [...]); inv is
-    an IEEE f32 division (``448.0 / t`` would be t.reciprocal() * 448)"""
-    xf = x.float()
-    amax = xf.abs().amax(-1)
-    zero = amax == 0
-    inv = torch.tensor(448.0, device=amax.device) / torch.where(zero, torch.ones_like(amax), amax)
-    codes = (xf * inv[..., None]).to(torch.float8_e4m3fn).view(torch.uint8).clone()
-    codes[zero] = 0
-    return codes, amax / 448.0
-
-
-def dequant(codes, scale):
-    return codes.view(torch.float8_e4m3fn).float() * scale[..., None].float()
 
 
 def _model(d=128, nl=2, L=96, V=337, seed=0):
