@@ -161,7 +161,9 @@ int mgx_rel_attn_bwd_parts(const uint16_t* qkv, const uint16_t* E, const uint32_
                            int B, int L, int d, int M, int parts, void* stream);
 
 /* ---- K6: out = LayerNorm(dropout(x) + res) * gamma + beta, eps    layers.py:154-155,159-160 --
- * x,res,out bf16 [rows,d]; gamma,beta f32 [d]; mean,rstd f32 [rows] saved for the backward.    */
+ * x,res,out bf16 [rows,d]; gamma,beta f32 [d]; mean,rstd f32 [rows] saved for the backward.
+ * mean is the fp32 sum divided by d (a correctly rounded division): a row whose elements are all equal has mean = that
+ * value, rstd = 1/sqrt(eps) and out = beta exactly.                                              */
 int mgx_add_ln_fwd(const uint16_t* x, const uint16_t* res, const float* gamma, const float* beta,
                    uint16_t* out, float* mean, float* rstd, int rows, int d, float eps,
                    float p_drop, uint64_t seed, void* stream);
@@ -185,7 +187,8 @@ int mgx_smooth_ce_fwd(const uint16_t* logits, const int32_t* target, float* stat
 /* dlogits bf16 [rows,ld] (columns >= V written as 0) = g/stats[1] * (softmax - q') for target!=pad rows, else 0, where
  * g = gscale * (gscale_dev ? *gscale_dev : 1): the upstream gradient of the scalar loss -- a host constant (1/accum) times,
  * optionally, a device-side f32 scalar (autograd's grad_output, the data-parallel loss weight): both are read on the device,
- * as stats is (no host sync, no extra elementwise pass over dlogits) (ABI 16).                    */
+ * as stats is (no host sync, no extra elementwise pass over dlogits) (ABI 16).  stats[1] is the count the call is GIVEN (it
+ * includes whatever the caller accumulated before); when it is 0 -- every target is pad -- dlogits is all zeros, never NaN. */
 int mgx_smooth_ce_bwd(const uint16_t* logits, const int32_t* target, const float* stats,
                       const float* row_lse, uint16_t* dlogits, int rows, int V, int ld,
                       float eps_ls, int pad, float gscale, const float* gscale_dev, void* stream);
@@ -195,7 +198,7 @@ int mgx_smooth_ce_bwd(const uint16_t* logits, const int32_t* target, const float
  * pass.  step >= 1 (bias correction as torch.optim.Adam), gscale multiplies g (e.g. 1/world).   */
 int mgx_adam_step(float* p, const float* g, float* m, float* v, uint16_t* shadow, size_t n,
                   float lr, float beta1, float beta2, float eps, int step, float gscale, void* stream);
-/* shadow bf16 [n] = round(p f32 [n]) */
+/* shadow bf16 [n] = round(p f32 [n]): nearest even, subnormals kept, +-inf kept, NaN -> a NaN (payload unspecified) */
 int mgx_cast_bf16(const float* p, uint16_t* shadow, size_t n, void* stream);
 
 /* ---- K2/K5/K7/K8: C = act(A @ W^T + bias)                         layers.py:71-84,108,157-158; network.py:39

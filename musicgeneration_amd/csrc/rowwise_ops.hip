@@ -265,7 +265,10 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(
                 for (int k = 0; k < 8; ++k) z[c][k] = 0.f;
             }
         }
-        const float mean = wave_sum(s) * inv_d;
+        // a true division: d * fl(1 / d) is not 1 for most d, and |mean| * rstd magnifies that error of the mean in every output
+        // (a constant row must give out = beta exactly; profiles/r11_rowwise_gru_kernel_tests.txt).  inv_d serves the variance only,
+        // where the error stays relative.
+        const float mean = wave_sum(s) / (float)d;
         float q = 0.f;
 #pragma unroll
         for (int c = 0; c < NC; ++c) {

@@ -1,0 +1,482 @@
+"""ORACLE -- test infrastructure only.  NOT part of the product path.
+
+fp64 references for the training kernels of ``csrc/rowwise_ops.hip`` (embedding + PE, residual + LayerNorm, smoothed cross
+entropy, Adam, bf16 cast, pad bitmap) and ``csrc/gru_train.hip`` (GRU cell, fused steps, bf16 dropout, row scatter), each a
+plain restatement of what ``include/mgx.h`` promises for the entry point it names and of the closed formula in the kernel's
+comment.  CPU only, numpy / torch only.  Inputs are the exact values the kernels read (bf16 / f32 tensors); every function
+widens them to fp64 first, so the only error left in a result is fp64's own.  Scalars a kernel receives as ``float`` (eps,
+betas, lr, p_drop) are taken at their fp32 value.
+
+Noise floors.  Every formula can also be evaluated in fp32 with its sums taken in reverse order (``fp32_reversed=True``):
+not a reference but a second, differently ordered fp32 evaluation.  Its distance from the fp64 value, plus one fp32 ulp of
+the result, is the floor F of a family.  Two refinements, so that F says what fp32 does to the formula and not what one
+lucky element did:
+  * the ulp is taken at the largest addend of the result's last sum (``scale``): where the addends cancel the result's own
+    ulp says nothing about the rounding the sum has already suffered;
+  * for the row-wise families (LayerNorm, CE, embedding, GRU cell) F is the maximum over the row, as
+    ``decode_ref.attn_noise_floor`` takes it over a head's 64 outputs: single elements of a second fp32 evaluation land on
+    the fp64 value by chance.
+  * the LayerNorm forward is checked in stages (``add_ln_out``): its output against the formula on the mean / rstd it saved.
+For sums over rows or tokens (dgamma, dbeta, dxsum, dtable, stats[0], scatter) the floor is 2^-24 * sum |terms| (+ that ulp).
+
+The dropout mask is a pure integer function of (seed, element index): ``make_drop`` / ``hash32`` / ``drop_mult8`` are its
+integer twin and return the exact multiplier (0 or the fp32 constant ``scale``) of every element.
+
+``tests/test_train_ref.py`` ties these to independent fp64 computations (torch's own layer_norm / GRUCell / Adam / autograd,
+``oracle.ref_cpu.smooth_ce``); ``tests/test_gpu_rowwise_kernels.py`` and ``tests/test_gpu_gru_kernels.py`` compare the
+kernels with them element by element.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+F64 = torch.float64
+F32 = torch.float32
+BF = torch.bfloat16
+EPS32 = 2.0 ** -24
+M32 = 0xFFFFFFFF
+
+
+def _d(t) -> torch.Tensor:
+    return torch.as_tensor(t).to(F64)
+
+
+def _f32(v) -> float:
+    """the value a C ``float`` parameter holds"""
+    return float(np.float32(v))
+
+
+def ulp32(x) -> torch.Tensor:
+    """one fp32 ulp at |x| (never zero: the smallest subnormal at 0), as fp64"""
+    a = torch.clamp(_d(x).abs(), max=1e38).to(F32)
+    return torch.nextafter(a, torch.full_like(a, float("inf"))).to(F64) - a.to(F64)
+
+
+def bf16_round(t) -> torch.Tensor:
+    """the bf16 value (RNE) of an fp32-representable quantity, as fp64"""
+    return torch.as_tensor(t).to(F32).to(BF).to(F64)
+
+
+def sum_floor(terms, dim, ref) -> torch.Tensor:
+    """floor of an fp32 sum over ``dim``: 2^-24 * sum |terms| + one ulp of the result"""
+    return EPS32 * _d(terms).abs().sum(dim) + ulp32(ref)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dropout: integer twin of make_drop / hash32 / drop_mult8 (csrc/mgx_common.hpp)
+# ---------------------------------------------------------------------------------------------------------------------
+def make_drop(p, seed):
+    """-> (thr16, mix, scale): drop iff a 16-bit random < thr16; scale = fp32(1 / (1 - thr16 / 65536))"""
+    p = _f32(p)
+    if p <= 0.0:
+        return 0, 0, np.float32(1.0)
+    thr = min(int(p * 65536.0 + 0.5), 65535)
+    scale = np.float32(1.0 / (1.0 - thr / 65536.0))
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    lo, hi = seed & M32, seed >> 32
+    mix = (lo * 0x9E3779B9 + (hi ^ 0x85EBCA6B) * 0xC2B2AE35 + 0x27D4EB2F) & M32
+    return thr, mix, scale
+
+
+def hash32(x) -> np.ndarray:
+    x = np.asarray(x, dtype=np.uint64) & M32
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & M32
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & M32
+    x = x ^ (x >> 16)
+    return x
+
+
+def drop_mult8(cfg, g) -> np.ndarray:
+    """multipliers of the 8 consecutive elements of every group in g (g = element index // 8, taken mod 2^32) -> f32 [len(g), 8]"""
+    thr, mix, scale = cfg
+    g = np.asarray(g, dtype=np.uint64).reshape(-1) & M32
+    out = np.empty((g.size, 8), dtype=np.float32)
+    for k in range(4):
+        r = hash32(((g * 4 + k) & M32) ^ mix)
+        out[:, 2 * k] = np.where((r & 0xFFFF) < thr, np.float32(0), scale)
+        out[:, 2 * k + 1] = np.where((r >> 16) < thr, np.float32(0), scale)
+    return out
+
+
+def drop_mult(p, seed, n, chunk=1 << 22) -> torch.Tensor:
+    """the multiplier of elements 0..n-1 (n % 8 == 0) of a buffer -> f32 tensor [n]"""
+    assert n % 8 == 0
+    cfg = make_drop(p, seed)
+    if cfg[0] == 0:
+        return torch.ones(n, dtype=F32)
+    out = np.empty(n, dtype=np.float32)
+    for g0 in range(0, n // 8, chunk):
+        g1 = min(n // 8, g0 + chunk)
+        out[8 * g0:8 * g1] = drop_mult8(cfg, np.arange(g0, g1, dtype=np.uint64)).reshape(-1)
+    return torch.from_numpy(out)
+
+
+def _mult(mult, like, dt):
+    return torch.ones((), dtype=dt) if mult is None else torch.as_tensor(mult).to(dt).reshape(like.shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# K6: residual + LayerNorm
+# ---------------------------------------------------------------------------------------------------------------------
+def add_ln_fwd(x, res, gamma, beta, eps, mult=None, *, fp32_reversed=False):
+    """mgx_add_ln_fwd: z = x * mult + res; mean, rstd = 1 / sqrt(biased var + eps) (centred two-pass form); out = (z - mean)
+    * rstd * gamma + beta -> (mean [rows], rstd [rows], out [rows, d])"""
+    dt = F32 if fp32_reversed else F64
+    x, res, gamma, beta = (torch.as_tensor(t).to(dt) for t in (x, res, gamma, beta))
+    m = _mult(mult, x, dt)
+    z = x * m + res
+    if fp32_reversed:
+        z, gamma, beta = z.flip(-1), gamma.flip(-1), beta.flip(-1)
+    d = z.shape[-1]
+    mean = z.sum(-1, keepdim=True) / d
+    c = z - mean
+    rstd = 1.0 / torch.sqrt((c * c).sum(-1, keepdim=True) / d + torch.tensor(_f32(eps), dtype=dt))
+    out = c * rstd * gamma + beta
+    if fp32_reversed:
+        out = out.flip(-1)
+    return mean[:, 0], rstd[:, 0], out
+
+
+def add_ln_out(x, res, gamma, beta, mean, rstd, mult=None, *, fp32=False):
+    """the last stage of mgx_add_ln_fwd on the mean / rstd the call SAVED: out = (x * mult + res - mean) * rstd * gamma + beta.
+    The saved mean is an fp32 value, up to an ulp from the true one, and on a row far from zero that ulp, times rstd * |gamma|,
+    is most of the distance between out and the fp64 LayerNorm; checked in stages -- mean and rstd against fp64, out against
+    this -- no bound has to carry it."""
+    dt = F32 if fp32 else F64
+    x, res, gamma, beta, mean, rstd = (torch.as_tensor(t).to(dt) for t in (x, res, gamma, beta, mean, rstd))
+    return (x * _mult(mult, x, dt) + res - mean[:, None]) * rstd[:, None] * gamma + beta
+
+
+def add_ln_fwd_floor(x, res, gamma, beta, eps, mult, ref):
+    """-> (F_mean, F_rstd), each [rows]"""
+    mean, rstd, _ = ref
+    m32, r32, _ = add_ln_fwd(x, res, gamma, beta, eps, mult, fp32_reversed=True)
+    z = _d(x) * _mult(mult, _d(x), F64) + _d(res)
+    return (m32.to(F64) - mean).abs() + ulp32(z.abs().mean(-1)), (r32.to(F64) - rstd).abs() + ulp32(rstd)
+
+
+def add_ln_out_floor(x, res, gamma, beta, mean, rstd, mult, ref):
+    """-> F [rows] of add_ln_out"""
+    o32 = add_ln_out(x, res, gamma, beta, mean, rstd, mult, fp32=True)
+    scale = ((ref - _d(beta)).abs() + _d(beta).abs()).amax(-1)
+    return (o32.to(F64) - ref).abs().amax(-1) + ulp32(scale)
+
+
+def add_ln_bwd(dout, x, res, gamma, mean, rstd, mult=None, *, fp32_reversed=False):
+    """mgx_add_ln_bwd, with the mean / rstd the call is GIVEN (they are inputs of the backward): xhat = (x * mult + res - mean)
+    * rstd, g = dout * gamma, dres = rstd * (g - mean(g) - xhat * mean(g * xhat)), dx = dres * mult; the column sums dgamma =
+    sum dout * xhat, dbeta = sum dout, dxsum = sum dx (of the unrounded dx: the kernel sums its bf16 dx, tests compare that with
+    the sum of the dx it wrote) -> (dres, dx, dgamma, dbeta, dxsum)"""
+    dt = F32 if fp32_reversed else F64
+    dout, x, res, gamma, mean, rstd = (torch.as_tensor(t).to(dt) for t in (dout, x, res, gamma, mean, rstd))
+    m = _mult(mult, x, dt)
+    xh = (x * m + res - mean[:, None]) * rstd[:, None]
+    g = dout * gamma
+    d = x.shape[-1]
+    if fp32_reversed:
+        c1, c2 = g.flip(-1).sum(-1, keepdim=True) / d, (g * xh).flip(-1).sum(-1, keepdim=True) / d
+    else:
+        c1, c2 = g.sum(-1, keepdim=True) / d, (g * xh).sum(-1, keepdim=True) / d
+    dres = rstd[:, None] * (g - c1 - xh * c2)
+    dx = dres * m
+    rows = (lambda t: t.flip(0)) if fp32_reversed else (lambda t: t)
+    return dres, dx, rows(dout * xh).sum(0), rows(dout).sum(0), rows(dx).sum(0)
+
+
+def add_ln_bwd_floor(dout, x, res, gamma, mean, rstd, mult, ref):
+    """-> (F_row [rows] for dres and dx, F_dgamma [d], F_dbeta [d])"""
+    dres, dx, dgamma, dbeta, _ = ref
+    r32 = add_ln_bwd(dout, x, res, gamma, mean, rstd, mult, fp32_reversed=True)
+    m = _mult(mult, _d(x), F64)
+    xh = (_d(x) * m + _d(res) - _d(mean)[:, None]) * _d(rstd)[:, None]
+    g = _d(dout) * _d(gamma)
+    d = xh.shape[-1]
+    scale = _d(rstd) * (g.abs().amax(-1) + g.sum(-1).abs() / d + (xh.abs() * ((g * xh).sum(-1, keepdim=True).abs() / d)).amax(-1))
+    scale = scale * m.abs().amax().clamp(min=1.0)
+    f_row = torch.maximum((r32[0].to(F64) - dres).abs().amax(-1), (r32[1].to(F64) - dx).abs().amax(-1)) + ulp32(scale)
+    return f_row, sum_floor(_d(dout) * xh, 0, dgamma), sum_floor(dout, 0, dbeta)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# K9 + K10: label-smoothed cross entropy, arg-max, accuracy
+# ---------------------------------------------------------------------------------------------------------------------
+def smooth_ce_fwd(logits, target, V, eps_ls, pad, *, fp32_reversed=False):
+    """mgx_smooth_ce_fwd on the V real columns: lse [rows]; arg-max [rows] (the FIRST index of the maximum); per-row loss =
+    lse - (1 - eps) x_t - (eps / V) sum_v x_v; stats [4] = (sum of loss over target != pad, #target != pad,
+    #(argmax == target) over ALL rows, rows) -> (lse, argmax int64, stats, loss)"""
+    dt = F32 if fp32_reversed else F64
+    x = torch.as_tensor(logits)[:, :V].to(dt)
+    t = torch.as_tensor(target).long()
+    rows = x.shape[0]
+    am = torch.from_numpy(np.argmax(x.to(F64).numpy(), axis=1))            # numpy: first occurrence
+    inside = (t >= 0) & (t < V)
+    xt = torch.where(inside, x[torch.arange(rows), t.clamp(0, V - 1)], torch.zeros((), dtype=dt))
+    if fp32_reversed:
+        x = x.flip(-1)
+    mx = x.amax(-1)
+    lse = mx + torch.log(torch.exp(x - mx[:, None]).sum(-1))
+    e = torch.tensor(_f32(eps_ls), dtype=dt)
+    loss = lse - (1.0 - e) * xt - (e / V) * x.sum(-1)
+    keep = t != pad
+    stats = torch.stack([(loss.flip(0) if fp32_reversed else loss)[keep.flip(0) if fp32_reversed else keep].sum().to(F64),
+                         keep.sum().to(F64), (am == t).sum().to(F64), torch.tensor(float(rows), dtype=F64)])
+    return lse, am, stats, loss
+
+
+def smooth_ce_fwd_floor(logits, target, V, eps_ls, pad, ref):
+    """-> (F_lse [rows], F_loss_sum scalar)"""
+    lse, _, stats, _ = ref
+    l32, _, _, _ = smooth_ce_fwd(logits, target, V, eps_ls, pad, fp32_reversed=True)
+    x = _d(torch.as_tensor(logits)[:, :V])
+    t = torch.as_tensor(target).long()
+    inside = (t >= 0) & (t < V)
+    xt = torch.where(inside, x[torch.arange(x.shape[0]), t.clamp(0, V - 1)], torch.zeros((), dtype=F64))
+    e = _f32(eps_ls)
+    terms = (lse.abs() + (1.0 - e) * xt.abs() + (e / V) * x.abs().sum(-1))[t != pad]
+    return (l32.to(F64) - lse).abs() + ulp32(torch.maximum(lse.abs(), x.abs().amax(-1))), EPS32 * terms.sum() + ulp32(stats[0])
+
+
+def smooth_ce_bwd(logits, target, cnt, row_lse, V, ld, eps_ls, pad, g, *, fp32=False):
+    """mgx_smooth_ce_bwd with the lse and the count the call is GIVEN: dlogits [rows, ld] = g / cnt * (exp(x - lse) - eps / V
+    - (1 - eps) [v == target]) on the V real columns of the rows with target != pad, 0 everywhere else (an all-pad batch, cnt =
+    0, is all zeros)"""
+    dt = F32 if fp32 else F64
+    x = torch.as_tensor(logits)[:, :V].to(dt)
+    t = torch.as_tensor(target).long()
+    rows = x.shape[0]
+    out = torch.zeros(rows, ld, dtype=dt)
+    keep = t != pad
+    if float(cnt) == 0.0 or not bool(keep.any()):
+        return out
+    e = torch.tensor(_f32(eps_ls), dtype=dt)
+    sc = torch.tensor(g, dtype=dt) / torch.tensor(float(cnt), dtype=dt)
+    onehot = (torch.arange(V)[None, :] == t[:, None]).to(dt)
+    grad = sc * (torch.exp(x - torch.as_tensor(row_lse).to(dt)[:, None]) - e / V - onehot * (1.0 - e))
+    out[:, :V] = torch.where(keep[:, None], grad, torch.zeros((), dtype=dt))
+    return out
+
+
+def smooth_ce_bwd_floor(logits, target, cnt, row_lse, V, ld, eps_ls, pad, g, ref):
+    """-> F [rows]"""
+    g32 = smooth_ce_bwd(logits, target, cnt, row_lse, V, ld, eps_ls, pad, g, fp32=True)
+    if float(cnt) == 0.0:
+        return ulp32(torch.zeros(ref.shape[0], dtype=F64))
+    x = _d(torch.as_tensor(logits)[:, :V])
+    scale = abs(g / float(cnt)) * (torch.exp(x - _d(row_lse)[:, None]).amax(-1) + 1.0)
+    return (g32.to(F64) - ref).abs().amax(-1) + ulp32(scale)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# K11: Adam
+# ---------------------------------------------------------------------------------------------------------------------
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, step, gscale=1.0, *, fp32=False):
+    """mgx_adam_step = torch.optim.Adam's update on g * gscale: m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2,
+    p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps) -> (p, m, v, upd) with upd the subtracted term"""
+    dt = F32 if fp32 else F64
+    p, g, m, v = (torch.as_tensor(t).to(dt) for t in (p, g, m, v))
+    S = (lambda a: torch.tensor(_f32(a), dtype=dt))
+    lr, b1, b2, eps, gs = S(lr), S(beta1), S(beta2), S(eps), S(gscale)
+    gk = g * gs
+    m = b1 * m + (1.0 - b1) * gk
+    v = b2 * v + (1.0 - b2) * gk * gk
+    bc1 = 1.0 - b1 ** step
+    bc2s = torch.sqrt(1.0 - b2 ** step)
+    upd = (lr / bc1) * m / (torch.sqrt(v) / bc2s + eps)
+    return p - upd, m, v, upd
+
+
+def adam_floor(p, g, m, v, lr, beta1, beta2, eps, step, gscale, ref):
+    """-> (F_p, F_m, F_v) per element"""
+    r32 = adam_step(p, g, m, v, lr, beta1, beta2, eps, step, gscale, fp32=True)
+    gk = _d(g) * _f32(gscale)
+    b1, b2 = _f32(beta1), _f32(beta2)
+    return ((r32[0].to(F64) - ref[0]).abs() + ulp32(torch.maximum(_d(p).abs(), ref[3].abs())),
+            (r32[1].to(F64) - ref[1]).abs() + ulp32(torch.maximum(b1 * _d(m).abs(), (1 - b1) * gk.abs())),
+            (r32[2].to(F64) - ref[2]).abs() + ulp32(torch.maximum(b2 * _d(v).abs(), (1 - b2) * gk * gk)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# K1: embedding * sqrt(d) + PE, and its backward; the row scatter
+# ---------------------------------------------------------------------------------------------------------------------
+def embed_pe_fwd(tok, table, pe, L, mult=None, *, fp32=False):
+    """mgx_embed_pe_fwd: out[r] = (table[tok[r]] * sqrt(d) + pe[r % L]) * mult[r] -> [rows, d]"""
+    dt = F32 if fp32 else F64
+    tok = torch.as_tensor(tok).long().reshape(-1)
+    d = table.shape[1]
+    s = torch.tensor(_f32(math.sqrt(d)) if fp32 else math.sqrt(d), dtype=dt)
+    out = torch.as_tensor(table).to(dt)[tok] * s + torch.as_tensor(pe).to(dt)[torch.arange(tok.numel()) % L]
+    return out * _mult(mult, out, dt)
+
+
+def embed_pe_fwd_floor(tok, table, pe, L, mult, ref):
+    """-> F [rows]"""
+    tok = torch.as_tensor(tok).long().reshape(-1)
+    d = table.shape[1]
+    o32 = embed_pe_fwd(tok, table, pe, L, mult, fp32=True)
+    scale = (_d(table)[tok].abs() * math.sqrt(d) + _d(pe)[torch.arange(tok.numel()) % L].abs()).amax(-1)
+    scale = scale * _mult(mult, ref, F64).abs().amax().clamp(min=1.0)
+    return (o32.to(F64) - ref).abs().amax(-1) + ulp32(scale)
+
+
+def scatter_add_rows(idx, src, V, cols):
+    """mgx_scatter_add_rows: update [V, cols] with row idx[r] += src[r, :cols]; indices outside [0, V) are ignored
+    -> (update, sum of |terms|)"""
+    idx = torch.as_tensor(idx).long().reshape(-1)
+    s = _d(src)[:, :cols]
+    ok = (idx >= 0) & (idx < V)
+    upd = torch.zeros(V, cols, dtype=F64).index_add_(0, idx[ok], s[ok])
+    return upd, torch.zeros(V, cols, dtype=F64).index_add_(0, idx[ok], s[ok].abs())
+
+
+def embed_bwd(tok, dout, V, mult=None):
+    """mgx_embed_bwd: update of dtable [V, d] = sqrt(d) * sum_{r: tok[r] == v} mult[r] * dout[r] -> (update, sum of |terms|)"""
+    dout = _d(dout).reshape(-1, dout.shape[-1])
+    d = dout.shape[1]
+    upd, S = scatter_add_rows(torch.as_tensor(tok).reshape(-1), dout * _mult(mult, dout, F64), V, d)
+    return upd * math.sqrt(d), S * math.sqrt(d)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# K13b: GRU cell (torch.nn.GRU, gate order r, z, n) and the projections of the fused steps
+# ---------------------------------------------------------------------------------------------------------------------
+def _gates(gi, gh, dt):
+    gi, gh = torch.as_tensor(gi).to(dt), torch.as_tensor(gh).to(dt)
+    H = gi.shape[-1] // 3
+    r = torch.sigmoid(gi[:, :H] + gh[:, :H])
+    z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
+    hn = gh[:, 2 * H:]
+    n = torch.tanh(gi[:, 2 * H:] + r * hn)
+    return r, z, n, hn
+
+
+def gru_cell_fwd(gi, gh, h_prev, *, fp32=False):
+    """mgx_gru_cell_fwd: r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r gh_n), h' = (1 - z) n + z h -> h' [B, H]"""
+    dt = F32 if fp32 else F64
+    r, z, n, _ = _gates(gi, gh, dt)
+    return (1.0 - z) * n + z * torch.as_tensor(h_prev).to(dt)
+
+
+def gru_cell_fwd_floor(gi, gh, h_prev, ref):
+    """-> F [B]"""
+    _, z, n, _ = _gates(gi, gh, F64)
+    scale = torch.maximum(((1 - z) * n).abs(), (z * _d(h_prev)).abs()).amax(-1)
+    return (gru_cell_fwd(gi, gh, h_prev, fp32=True).to(F64) - ref).abs().amax(-1) + ulp32(scale)
+
+
+def gru_cell_coef(gi, gh, h_prev):
+    """the coefficients of dh in the cell backward: dgi = dgh = dh * (c_r, c_z, c_n) except dgh_n = dh * c_n * r;
+    dh_prev_direct = dh * z -> dict of fp64 [B, H]"""
+    r, z, n, hn = _gates(gi, gh, F64)
+    c_n = (1 - z) * (1 - n * n)
+    return {"r": c_n * hn * r * (1 - r), "z": (_d(h_prev) - n) * z * (1 - z), "n": c_n, "nr": c_n * r, "h": z}
+
+
+def gru_cell_bwd(gi, gh, h_prev, dh, *, fp32=False):
+    """mgx_gru_cell_bwd for a given total dh (= dh_direct + d_rec + dy, each optional) -> (dgi [B, 3H], dgh [B, 3H],
+    dh_prev_direct [B, H])"""
+    dt = F32 if fp32 else F64
+    r, z, n, hn = _gates(gi, gh, dt)
+    dh = torch.as_tensor(dh).to(dt)
+    dn = dh * (1.0 - z) * (1.0 - n * n)
+    dz = dh * (torch.as_tensor(h_prev).to(dt) - n) * z * (1.0 - z)
+    dr = dn * hn * r * (1.0 - r)
+    return torch.cat([dr, dz, dn], 1), torch.cat([dr, dz, dn * r], 1), dh * z
+
+
+def gru_cell_bwd_floor(gi, gh, h_prev, dh, ref):
+    """-> F [B], one floor for the three outputs of a batch row"""
+    r32 = gru_cell_bwd(gi, gh, h_prev, dh, fp32=True)
+    f = torch.stack([(a.to(F64) - b).abs().amax(-1) for a, b in zip(r32, ref)]).amax(0)
+    return f + ulp32(torch.stack([b.abs().amax(-1) for b in ref]).amax(0))
+
+
+def proj(a, w, bias=None):
+    """a [M, K] @ w [N, K]^T + bias in fp64 -> (c [M, N], S = sum_k |a_k w_k| + |bias|): the recurrent and input projections of
+    the fused steps (gh = h_bf16 W_hh^T + b_hh, gi = x W_ih^T + b_ih) and, with w = W_hh^T, d_rec = dgh_next W_hh.  mgx.h rounds
+    each of them to bf16 before the cell reads it: ``bf16_round``."""
+    a, w = _d(a), _d(w)
+    c, S = a @ w.T, a.abs() @ w.abs().T
+    if bias is not None:
+        c, S = c + _d(bias), S + _d(bias).abs()
+    return c, S
+
+
+def proj_floor(a, w, bias, ref, S):
+    """fp32 product with the reduction reversed against fp64, + 2^-24 S (the classical unit of an fp32 accumulation)"""
+    a32, w32 = torch.as_tensor(a).to(F32).flip(-1), torch.as_tensor(w).to(F32).flip(-1)
+    c32 = a32 @ w32.T
+    if bias is not None:
+        c32 = c32 + torch.as_tensor(bias).to(F32)
+    return (c32.to(F64) - ref).abs() + EPS32 * S + ulp32(ref)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# inputs the GPU tests build (on the CPU, so that tests/test_train_ref.py can assert their preconditions without a GPU)
+# ---------------------------------------------------------------------------------------------------------------------
+LN_KINDS = ("zero-mean", "far", "const", "scales")
+
+
+def ln_case(kind, rows, d, seed=0):
+    """x, res bf16 [rows, d] of one LayerNorm case:
+      zero-mean  x, res ~ N(0, 1)
+      far        rows far from zero: x is a per-row offset of 16 .. 60 (an integer: exact in bf16), res a detail of std 0.25
+                 whose elements below 2^-10 are zero, so that x + res, and 2 x + res (dropout at p = 0.5), are exact in fp32
+                 (7 + 17 bits)
+      const      every row a constant (variance 0: rstd = 1 / sqrt(eps), out = beta)
+      scales     rows of very different scale in one call: row r is N(0, 1) * 2^(-12 + 3 (r % 9))"""
+    g = torch.Generator().manual_seed(1000 * seed + 7 * rows + d)
+    rn = lambda *s: torch.randn(*s, generator=g)                                                    # noqa: E731
+    if kind == "zero-mean":
+        x, res = rn(rows, d), rn(rows, d)
+    elif kind == "far":
+        off = torch.randint(16, 61, (rows, 1), generator=g).float() * torch.where(torch.arange(rows)[:, None] % 2 == 0, 1.0, -1.0)
+        x = off.expand(rows, d).clone()
+        res = (0.25 * rn(rows, d)).to(BF).float()
+        res = torch.where(res.abs() < 2.0 ** -10, torch.zeros(()), res)
+    elif kind == "const":
+        c = torch.randint(-40, 41, (rows, 1), generator=g).float() * 0.25
+        x, res = c.expand(rows, d).clone(), torch.zeros(rows, d)
+    elif kind == "scales":
+        s = 2.0 ** (-12.0 + 3.0 * (torch.arange(rows) % 9).float())[:, None]
+        x, res = rn(rows, d) * s, rn(rows, d) * s
+    else:
+        raise ValueError(kind)
+    return x.to(BF), res.to(BF)
+
+
+def ce_logits(kind, rows, V, ld, seed=0, fill=0.0):
+    """logits bf16 [rows, ld]; columns >= V hold ``fill`` (NaN / +inf in the padding tests):
+      gauss   N(0, 2)            pm80    every logit +80 or -80            equal   all-equal rows (arg-max 0)
+      last    N(0, 1) with the row maximum in column V - 1"""
+    g = torch.Generator().manual_seed(1000 * seed + 13 * rows + V)
+    if kind == "gauss":
+        x = 2.0 * torch.randn(rows, V, generator=g)
+    elif kind == "pm80":
+        x = torch.where(torch.rand(rows, V, generator=g) < 0.5, 80.0, -80.0)
+    elif kind == "equal":
+        x = torch.randint(-3, 4, (rows, 1), generator=g).float().expand(rows, V).clone()
+    elif kind == "last":
+        x = torch.randn(rows, V, generator=g)
+        x[:, V - 1] = 6.0
+    else:
+        raise ValueError(kind)
+    out = torch.full((rows, ld), float(fill))
+    out[:, :V] = x
+    return out.to(BF)
+
+
+def ce_targets(rows, V, pad, seed=0):
+    """random targets with the edge columns planted in the first rows: 0, V - 1, 511, 512 (where they exist) and ``pad``"""
+    g = torch.Generator().manual_seed(seed + rows + V)
+    t = torch.randint(0, V, (rows,), generator=g)
+    plant = [0, V - 1, pad] + [c for c in (511, 512) if c < V]
+    for i, c in enumerate(plant[:rows]):
+        t[i] = c
+    if rows > 8:
+        t[torch.rand(rows, generator=g) < 0.1] = pad
+    return t.to(torch.int32)

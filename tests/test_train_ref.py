@@ -1,0 +1,264 @@
+"""oracle/train_ref.py (the fp64 references of the row-wise and GRU training kernels) against independent fp64 computations:
+torch's own layer_norm / GRUCell / Adam / index_add_ and autograd, oracle.ref_cpu.smooth_ce, and hand-computed words of the
+dropout hash.  Also the preconditions of the inputs the GPU tests build.  No GPU."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import ref_cpu as R
+from oracle import train_ref as T
+
+F64 = torch.float64
+BF = torch.bfloat16
+
+
+def close(a, b, tol=1e-12):
+    a, b = torch.as_tensor(a).to(F64), torch.as_tensor(b).to(F64)
+    assert a.shape == b.shape
+    assert (a - b).abs().max().item() <= tol * max(1.0, b.abs().max().item()), (a - b).abs().max().item()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# LayerNorm
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["zero-mean", "far", "scales"])
+@pytest.mark.parametrize("rows,d", [(5, 8), (7, 520), (3, 2048)])
+def test_layernorm_forward_and_backward_are_torch_layer_norm_and_its_autograd(kind, rows, d):
+    x, res = T.ln_case(kind, rows, d)
+    g = torch.Generator().manual_seed(d)
+    gamma, beta = 1 + 0.5 * torch.randn(d, generator=g), torch.randn(d, generator=g)
+    dout = torch.randn(rows, d, generator=g).to(BF)
+    mult = T.drop_mult(0.5, 11, rows * d).reshape(rows, d)
+    eps = float(np.float32(1e-6))
+    xa, ra = x.double().requires_grad_(), res.double().requires_grad_()
+    ga, ba = gamma.double().requires_grad_(), beta.double().requires_grad_()
+    out = torch.nn.functional.layer_norm(xa * mult.double() + ra, (d,), ga, ba, eps)
+    out.backward(dout.double())
+    mean, rstd, ref = T.add_ln_fwd(x, res, gamma, beta, 1e-6, mult)
+    close(ref, out.detach())
+    z = x.double() * mult.double() + res.double()
+    close(mean, z.mean(-1))
+    close(rstd, 1 / torch.sqrt(z.var(-1, unbiased=False) + eps))
+    dres, dx, dgamma, dbeta, dxsum = T.add_ln_bwd(dout, x, res, gamma, mean, rstd, mult)
+    close(dres, ra.grad, 1e-10)
+    close(dx, xa.grad, 1e-10)
+    close(dgamma, ga.grad, 1e-10)
+    close(dbeta, ba.grad)
+    close(dxsum, xa.grad.sum(0), 1e-10)
+    # the floors: positive, and at fp32 distance
+    Fm, Fr = T.add_ln_fwd_floor(x, res, gamma, beta, 1e-6, mult, (mean, rstd, ref))
+    assert Fm.shape == (rows,) and Fm.min() > 0 and Fr.min() > 0
+    # the staged form: on the exact mean / rstd it is the LayerNorm; on fp32-rounded ones its own, nearby, value
+    close(T.add_ln_out(x, res, gamma, beta, mean, rstd, mult), ref)
+    staged = T.add_ln_out(x, res, gamma, beta, mean.float(), rstd.float(), mult)
+    Fo = T.add_ln_out_floor(x, res, gamma, beta, mean.float(), rstd.float(), mult, staged)
+    assert Fo.shape == (rows,) and Fo.min() > 0 and (Fo / (staged.abs().amax(-1) + 1)).max() < 2 ** -18
+    # half an ulp of the mean through rstd * |gamma|, half an ulp of rstd through |xhat gamma|
+    assert ((staged - ref).abs() <= (T.ulp32(mean) * rstd)[:, None] * gamma.double().abs() + 2 ** -23 * (ref - beta.double()).abs() + 1e-13).all()
+    Frow, Fg, Fb = T.add_ln_bwd_floor(dout, x, res, gamma, mean, rstd, mult, (dres, dx, dgamma, dbeta, dxsum))
+    assert Frow.shape == (rows,) and Fg.shape == (d,) and min(Frow.min(), Fg.min(), Fb.min()) > 0
+
+
+@pytest.mark.parametrize("rows,d", [(1, 8), (5, 504), (2049, 64), (33, 2048)])
+def test_layernorm_case_preconditions(rows, d):
+    x, res = T.ln_case("far", rows, d)
+    xf, rf = x.float(), res.float()
+    assert ((xf + rf).double() == xf.double() + rf.double()).all()           # x + res is exact in fp32
+    assert xf.abs().min() >= 16 and xf.abs().max() <= 60 and (xf == xf[:, :1]).all()
+    if rows * d >= 2048:
+        assert 0.2 < rf.std().item() < 0.3
+    m2 = T.drop_mult(0.5, 9, rows * d).reshape(rows, d)      # p = 0.5: scale 2, the dropped-out sum is exact too
+    assert ((xf * m2 + rf).double() == xf.double() * m2.double() + rf.double()).all() and set(m2.unique().tolist()) <= {0.0, 2.0}
+    x, res = T.ln_case("const", rows, d)
+    assert (x == x[:, :1]).all() and (res == 0).all()
+    assert (x.float() * 4 == (x.float() * 4).round()).all() and x.float().abs().max() <= 10     # d <= 2048 copies sum exactly in fp32
+    mean, rstd, out = T.add_ln_fwd(x, res, torch.ones(d), torch.full((d,), 0.5), 1e-6)
+    close(mean, x[:, 0].double())
+    close(rstd, torch.full((rows,), 1 / math.sqrt(float(np.float32(1e-6))), dtype=F64))
+    assert (out == 0.5).all()
+    x, res = T.ln_case("scales", 18, d)
+    amax = (x.float() + res.float()).abs().amax(-1)
+    assert amax.max() / amax.min() > 2 ** 20
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# cross entropy
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["gauss", "pm80", "equal", "last"])
+@pytest.mark.parametrize("V,ld", [(7, 8), (513, 640), (2049, 2049)])
+def test_cross_entropy_is_ref_cpu_smooth_ce_and_its_autograd(kind, V, ld):
+    rows, eps_ls, pad = 17, 0.1, V - 2
+    logits = T.ce_logits(kind, rows, V, ld, fill=float("nan"))
+    target = T.ce_targets(rows, V, pad)
+    lse, am, stats, loss = T.smooth_ce_fwd(logits, target, V, eps_ls, pad)
+    x = logits[:, :V].double().requires_grad_()
+    close(lse, torch.logsumexp(x, -1).detach())
+    e = float(np.float32(eps_ls))
+    q = torch.full((rows, V), e / V, dtype=F64)
+    q[torch.arange(rows), target.long()] += 1 - e
+    per = -(q * torch.log_softmax(x, -1)).sum(-1)                            # the definition, not the closed form
+    close(loss, per.detach(), 1e-9)
+    keep = target != pad
+    close(stats, torch.tensor([per[keep].sum().item(), keep.sum().item(), (x.argmax(-1) == target).sum().item(), rows], dtype=F64), 1e-9)
+    want = R.smooth_ce(logits[:, :V].float(), target, e, V, pad)              # fp32 inside
+    assert abs(stats[0].item() / stats[1].item() - want.item()) <= 1e-5 * max(1.0, abs(want.item()))
+    (per[keep].sum() / keep.sum() * 0.25).backward()
+    got = T.smooth_ce_bwd(logits, target, stats[1].item(), lse, V, ld, eps_ls, pad, 0.25)
+    close(got[:, :V], x.grad, 1e-9)
+    assert (got[:, V:] == 0).all() and (got[~keep] == 0).all() and torch.isfinite(got).all()
+    xr = logits[:, :V].float().requires_grad_()
+    (R.smooth_ce(xr, target, e, V, pad) * 0.25).backward()
+    assert (got[:, :V] - xr.grad.double()).abs().max() <= 1e-6
+    # first-index arg-max
+    if kind == "equal":
+        assert (am == 0).all()
+    if kind == "last":
+        assert (am == V - 1).all()
+    if kind == "pm80":
+        first = [int(np.nonzero(r == 80)[0][0]) if (r == 80).any() else 0 for r in logits[:, :V].float().numpy()]
+        assert am.tolist() == first
+    Fl, Fs = T.smooth_ce_fwd_floor(logits, target, V, eps_ls, pad, (lse, am, stats, loss))
+    assert Fl.min() > 0 and Fs > 0 and Fl.max() < 2 ** -14
+    Fb = T.smooth_ce_bwd_floor(logits, target, stats[1].item(), lse, V, ld, eps_ls, pad, 0.25, got)
+    assert Fb.shape == (rows,) and Fb.min() > 0
+
+
+def test_cross_entropy_all_pad_batch_and_target_preconditions():
+    V, pad = 600, 5
+    logits = T.ce_logits("gauss", 4, V, V)
+    target = torch.full((4,), pad, dtype=torch.int32)
+    lse, am, stats, _ = T.smooth_ce_fwd(logits, target, V, 0.1, pad)
+    assert stats[0] == 0 and stats[1] == 0 and stats[3] == 4
+    assert (T.smooth_ce_bwd(logits, target, 0.0, lse, V, V, 0.1, pad, 1.0) == 0).all()
+    t = T.ce_targets(17, V, pad)
+    assert {0, V - 1, pad, 511, 512} <= set(t.tolist())
+    t = T.ce_targets(8209, 9, 3)
+    assert {0, 8, 3} <= set(t.tolist()) and 0.05 < (t == 3).float().mean() < 0.3
+    for kind in ("gauss", "pm80", "equal", "last"):
+        x = T.ce_logits(kind, 5, 9, 16, fill=float("inf"))
+        assert torch.isfinite(x[:, :9]).all() and torch.isinf(x[:, 9:]).all()
+        assert (x.float().to(BF) == x).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Adam
+# ---------------------------------------------------------------------------------------------------------------------
+def test_adam_is_torch_optim_adam_on_float64_parameters():
+    g = torch.Generator().manual_seed(0)
+    n, lr, b1, b2, eps, gs = 37, 1e-3, 0.9, 0.98, 1e-9, 0.5
+    f = lambda a: float(np.float32(a))                                                              # noqa: E731
+    p0 = torch.randn(n, generator=g)
+    pt = p0.double().clone().requires_grad_()
+    opt = torch.optim.Adam([pt], lr=f(lr), betas=(f(b1), f(b2)), eps=f(eps))
+    p, m, v = p0.double(), torch.zeros(n, dtype=F64), torch.zeros(n, dtype=F64)
+    for step in range(1, 8):
+        grad = torch.randn(n, generator=g)
+        pt.grad = grad.double() * f(gs)
+        opt.step()
+        p, m, v, _ = T.adam_step(p, grad, m, v, lr, b1, b2, eps, step, gs)
+        close(p, pt.detach(), 1e-13)
+    st = opt.state[pt]
+    close(m, st["exp_avg"], 1e-13)
+    close(v, st["exp_avg_sq"], 1e-13)
+    Fp, Fm, Fv = T.adam_floor(p0, grad, m.float(), v.float(), lr, b1, b2, eps, 8, gs,
+                              T.adam_step(p0, grad, m.float(), v.float(), lr, b1, b2, eps, 8, gs))
+    assert min(Fp.min(), Fm.min(), Fv.min()) > 0 and (Fp / (p0.abs().double() + 1e-3)).max() < 2 ** -18
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# embedding, scatter
+# ---------------------------------------------------------------------------------------------------------------------
+def test_embedding_forward_backward_and_scatter_are_index_select_and_index_add():
+    g = torch.Generator().manual_seed(3)
+    B, L, d, V = 3, 32, 24, 11
+    tok = torch.randint(0, V - 1, (B, L), generator=g).to(torch.int32)       # token V - 1 never occurs
+    table = torch.randn(V, d, generator=g)
+    pe = R.sinusoid_table(L, d).float()
+    mult = T.drop_mult(0.1, 5, B * L * d).reshape(B * L, d)
+    ta = table.double().requires_grad_()
+    out = (ta[tok.long().reshape(-1)] * math.sqrt(d) + pe.double().repeat(B, 1)) * mult.double()
+    ref = T.embed_pe_fwd(tok, table, pe, L, mult)
+    close(ref, out.detach())
+    dout = torch.randn(B * L, d, generator=g).to(BF)
+    out.backward(dout.double())
+    upd, S = T.embed_bwd(tok, dout, V, mult)
+    close(upd, ta.grad)
+    assert (upd[V - 1] == 0).all() and (S >= upd.abs() - 1e-12).all()
+    assert T.embed_pe_fwd_floor(tok, table, pe, L, mult, ref).min() > 0
+    idx = torch.tensor([0, 3, 3, -1, V, 3, 10], dtype=torch.int32)
+    src = torch.randn(7, 16, generator=g).to(BF)
+    upd, S = T.scatter_add_rows(idx, src, V, 12)
+    want = torch.zeros(V, 12, dtype=F64).index_add_(0, torch.tensor([0, 3, 3, 3, 10]), src[[0, 1, 2, 5, 6], :12].double())
+    close(upd, want)
+    close(S[3], src[[1, 2, 5], :12].double().abs().sum(0))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GRU cell
+# ---------------------------------------------------------------------------------------------------------------------
+def test_gru_cell_is_torch_grucell_and_its_autograd():
+    g = torch.Generator().manual_seed(4)
+    B, H, K = 5, 24, 16
+    cell = torch.nn.GRUCell(K, H).double()
+    x, h = torch.randn(B, K, generator=g).double(), torch.randn(B, H, generator=g).double().requires_grad_()
+    gi = (x @ cell.weight_ih.T + cell.bias_ih).detach().requires_grad_()
+    gh = (h @ cell.weight_hh.T + cell.bias_hh).detach().requires_grad_()
+    want = cell(x, h)
+    ref = T.gru_cell_fwd(gi.detach(), gh.detach(), h.detach())
+    close(ref, want.detach())
+    dh = torch.randn(B, H, generator=g).double()
+    # autograd of the cell formula with gi, gh and h as leaves
+    r, z, n, _ = T._gates(gi, gh, F64)
+    hl = h.detach().requires_grad_()
+    ((1 - z) * n + z * hl).backward(dh)
+    dgi, dgh, dhp = T.gru_cell_bwd(gi.detach(), gh.detach(), h.detach(), dh)
+    close(dgi, gi.grad)
+    close(dgh, gh.grad)
+    close(dhp, hl.grad)
+    # and through torch's own cell: dh/dh_prev = direct + dgh @ W_hh
+    want.backward(dh)
+    close(dhp + dgh @ cell.weight_hh.detach(), h.grad)
+    c = T.gru_cell_coef(gi.detach(), gh.detach(), h.detach())
+    close(torch.cat([dh * c["r"], dh * c["z"], dh * c["n"]], 1), dgi)
+    close(torch.cat([dh * c["r"], dh * c["z"], dh * c["nr"]], 1), dgh)
+    close(dh * c["h"], dhp)
+    assert T.gru_cell_fwd_floor(gi.detach(), gh.detach(), h.detach(), ref).min() > 0
+    assert T.gru_cell_bwd_floor(gi.detach(), gh.detach(), h.detach(), dh, (dgi, dgh, dhp)).shape == (B,)
+    pr, S = T.proj(h.detach(), cell.weight_hh.detach(), cell.bias_hh.detach())
+    close(pr, gh.detach())
+    assert (S >= pr.abs() - 1e-12).all() and T.proj_floor(h.detach(), cell.weight_hh.detach(), cell.bias_hh.detach(), pr, S).min() > 0
+    assert (T.bf16_round(torch.tensor([1.0 + 2 ** -8, 1.0 + 3 * 2 ** -8])) == torch.tensor([1.0, 1.0 + 2 ** -6], dtype=F64)).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# dropout twin
+# ---------------------------------------------------------------------------------------------------------------------
+def test_dropout_twin_constants_hash_words_and_keep_rate():
+    assert T.make_drop(0.0, 99) == (0, 0, np.float32(1.0))
+    thr, mix, scale = T.make_drop(0.1, 0)
+    assert (thr, mix) == (6554, 0xF9A08D56) and scale == np.float32(65536.0 / 58982.0) and scale.dtype == np.float32
+    assert T.make_drop(0.5, 1) == (32768, 0x97D8070F, np.float32(2.0))
+    assert T.make_drop(0.99999, 1234) == (65535, 0xA1094B18, np.float32(65536.0))
+    assert T.make_drop(0.5, (1 << 32) + 5)[1] == 0x4E033FBE                   # a seed above 2^32: the high word enters
+    assert T.make_drop(0.5, 0x123456789ABCDEF0)[1] == 0x9DD7B08E
+    assert T.make_drop(0.5, 5)[1] != T.make_drop(0.5, (1 << 32) + 5)[1]
+    words = {0: 0, 1: 0x688990C0, 2: 0xD1132181, 0xFFFFFFFF: 0x6768824A, 0x12345678: 0xF5E71C96}
+    assert T.hash32(list(words)).tolist() == list(words.values())
+    # element e of group g: 16-bit half (e % 2) of hash32((4 g + e // 2) ^ mix)
+    cfg = T.make_drop(0.5, 7)
+    m8 = T.drop_mult8(cfg, [0, 5, 2 ** 32 + 5])
+    assert (m8[1] == m8[2]).all()                                             # the group index is taken mod 2^32
+    for k in range(8):
+        r = int(T.hash32([(4 * 5 + k // 2) ^ cfg[1]])[0])
+        half = (r >> 16) if k % 2 else (r & 0xFFFF)
+        assert m8[1, k] == (0.0 if half < cfg[0] else 2.0)
+    for p in (0.1, 0.5, 0.99999):
+        m = T.drop_mult(p, 42, 1 << 20)
+        thr, _, scale = T.make_drop(p, 42)
+        assert set(m.unique().tolist()) <= {0.0, float(scale)}
+        keep = (m != 0).float().mean().item()
+        assert abs(keep - (1 - thr / 65536)) < 4 * math.sqrt(0.25 / (1 << 20)) + 1e-6, (p, keep)
+    assert (T.drop_mult(0.0, 42, 64) == 1).all()
+    assert (T.drop_mult(0.5, 42, 1 << 12)[:64] == T.drop_mult(0.5, 42, 64)).all()
