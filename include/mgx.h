@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged */
-#define MGX_ABI_VERSION 20
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor */
+#define MGX_ABI_VERSION 21
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -358,6 +358,27 @@ int mgx_rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* v
 int mgx_rel_attn_decode_fp8_ragged(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
                                    const uint16_t* E, const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes,
                                    int B, int Lmax, int d, int M, void* stream);
+
+/* ---- Re-anchored decode window (ABI 21): the KV-cache decode past max_seq.  A row's cache holds a window of its sequence:
+ * window position t (the `pos` every decode call reads) is column base + t of out_tokens, and every `hop` tokens the window
+ * drops its oldest hop tokens, renumbers the rest from 0 and rebuilds their K/V in one full-sequence pass.  pos_dev and base_dev
+ * have one shape: int32[1] shared by the rows (per_row = 0) or int32[B] (per_row != 0).
+ * mgx_sample_topk_topp_window is mgx_sample_topk_topp_rows (per_row = 0) / _ragged (per_row != 0) with the absolute step
+ * base + t in place of t: the draw is a function of (seed, base + t, row0 + row), out_tokens column base + t + 1 receives the
+ * token, and advance != 0 adds 1 to pos_dev only.  base_dev == 0 gives the namesake's result bit for bit.
+ * Contract (not checked: both live on the device): base + t + 1 < out_ld when out_tokens is given.                     */
+int mgx_sample_topk_topp_window(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
+                                uint64_t seed, int32_t* pos_dev, const int32_t* base_dev, int32_t* next_tok,
+                                int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
+                                const uint32_t* allow_table, int per_row, void* stream);
+/* The re-anchor, in stream order: t' = pos_dev - hop and base' = base_dev + hop replace pos_dev and base_dev (every entry),
+ * then the prefill's token matrix seq int32 [B,n_pad] is filled from the moved window: seq[b,i] = out_tokens[b, base'_b + i]
+ * for i < t'_b and pad_token elsewhere (out_tokens int32 [B,out_ld]).  The counters move in a launch of their own before
+ * seq is filled, so no workgroup reads a position another has already moved.  hop >= 0 (0 only fills seq).
+ * Contract (not checked: the counters live on the device): t'_b >= 0 and base'_b + t'_b < out_ld; a column outside
+ * out_tokens is not read (seq gets pad_token there).                                                                    */
+int mgx_decode_reanchor(int32_t* pos_dev, int32_t* base_dev, const int32_t* out_tokens, int out_ld, int32_t* seq,
+                        int n_pad, int hop, int pad_token, int B, int per_row, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

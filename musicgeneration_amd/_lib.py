@@ -13,7 +13,7 @@ _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 
 # the ABI the SIGNATURES table below was written for (MGX_ABI_VERSION of include/mgx.h).  A left-over
 # libmgx.so of another ABI still exports the same names: calling it with this table would shift arguments.
-EXPECTED_ABI = 20
+EXPECTED_ABI = 21
 
 # name -> argtypes ; every symbol declared in include/mgx.h (restype int unless noted)
 SIGNATURES = {
@@ -60,6 +60,9 @@ SIGNATURES = {
     "mgx_kv_store_fp8": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
     "mgx_rel_attn_decode_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
     "mgx_rel_attn_decode_fp8_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
+    # ABI 21: the re-anchored decode window (base beside pos; shared or per row by a flag)
+    "mgx_sample_topk_topp_window": [_vp, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp],
+    "mgx_decode_reanchor": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
     "mgx_gather_rows": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "mgx_gru_gates": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "mgx_linear_dx": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],

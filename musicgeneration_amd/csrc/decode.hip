@@ -15,6 +15,9 @@
 // Every kernel that reads the position has a PER_ROW instantiation (the *_ragged entry points, ABI 19): pos_dev then holds
 // one position per batch row, so a batch can continue prompts of different lengths in lockstep.  Nothing else in a step
 // depends on the position (the relative term E[M-1-(t-j)] only on the row's own t); PER_ROW = false is the shared counter.
+// Past max_seq (ABI 21) the cache holds a window of the sequence: pos_dev is the position inside the window, a second counter
+// of the same shape, base_dev, the output column of window position 0.  Only the sampler reads it
+// (mgx_sample_topk_topp_window); mgx_decode_reanchor moves both when the host re-anchors the window.
 #include "mgx_common.hpp"
 
 namespace {
@@ -330,7 +333,8 @@ __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__
                                                     int top_k, float top_p, uint64_t seed, int32_t* __restrict__ pos_dev,
                                                     int32_t* __restrict__ next_tok, int32_t* __restrict__ out_tokens,
                                                     int out_ld, float* __restrict__ probs_out, int row0,
-                                                    const uint32_t* __restrict__ allow_table) {
+                                                    const uint32_t* __restrict__ allow_table,
+                                                    const int32_t* __restrict__ base_dev) {
     const int row = blockIdx.x, lane = threadIdx.x;
     const uint16_t* lp = logits + (size_t)row * ld;
     float p[SMP_PER_LANE];
@@ -415,7 +419,8 @@ __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__
 #pragma unroll
     for (int i = 0; i < SMP_PER_LANE; ++i) { if (!(p[i] >= tau)) p[i] = 0.f; kept += p[i]; }
     const float total = wave_sum(kept);
-    const int step = pos_dev[PER_ROW ? row : 0];
+    // the absolute step: the position itself, or (mgx_sample_topk_topp_window) the window position plus the window's base
+    const int step = pos_dev[PER_ROW ? row : 0] + (base_dev ? base_dev[PER_ROW ? row : 0] : 0);
     const float target = u01(seed, (uint32_t)step, (uint32_t)(row0 + row)) * total;
     int choice = -1;
     float base = 0.f;
@@ -450,6 +455,24 @@ __global__ void advance_pos_kernel(int32_t* pos_dev) { pos_dev[0] += 1; }
 __global__ __launch_bounds__(256) void advance_pos_rows_kernel(int32_t* __restrict__ pos_rows, int B) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < B) pos_rows[i] += 1;
+}
+// mgx_decode_reanchor, in two launches so that no workgroup reads a position another has already moved: the n counters first
+// (n = B per row, 1 shared), then the prefill's token matrix from the moved window
+__global__ __launch_bounds__(256) void reanchor_move_kernel(int32_t* __restrict__ pos_dev, int32_t* __restrict__ base_dev, int n,
+                                                            int hop) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) { pos_dev[i] -= hop; base_dev[i] += hop; }
+}
+template <bool PER_ROW>
+__global__ __launch_bounds__(256) void reanchor_fill_kernel(const int32_t* __restrict__ pos_dev, const int32_t* __restrict__ base_dev,
+                                                            const int32_t* __restrict__ out_tokens, int out_ld,
+                                                            int32_t* __restrict__ seq, int n_pad, int pad_token, int B) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= B * n_pad) return;
+    const int b = g / n_pad, i = g % n_pad;
+    const int t = pos_dev[PER_ROW ? b : 0], col = base_dev[PER_ROW ? b : 0] + i;
+    // the contract keeps col inside the row for i < t; a row that breaks it reads pad_token, never past out_tokens
+    seq[g] = (i < t && col >= 0 && col < out_ld) ? out_tokens[(size_t)b * out_ld + col] : pad_token;
 }
 
 template <bool PER_ROW>
@@ -564,16 +587,16 @@ extern "C" int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* 
     return MGX_OK;
 }
 
-// the three sampler entry points; advance: one more launch moves the position(s) on
+// the four sampler entry points; advance: one more launch moves the position(s) on.  base_dev: the window's base(s), or NULL
 template <bool PER_ROW>
 static int sample(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p, uint64_t seed, int32_t* pos_dev,
                   int32_t* next_tok, int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
-                  const uint32_t* allow_table, void* stream, const char* name) {
+                  const uint32_t* allow_table, void* stream, const char* name, const int32_t* base_dev = nullptr) {
     MGX_REQUIRE(logits && pos_dev && next_tok, MGX_ERR_NULL, "%s: NULL pointer", name);
     MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && top_p > 0.f && row0 >= 0, MGX_ERR_SHAPE,
                 "%s: need 0<V<=%d, ld>=V, temperature>0, top_p>0, row0>=0 (V=%d ld=%d)", name, 64 * SMP_PER_LANE, V, ld);
     hipLaunchKernelGGL(sample_kernel<PER_ROW>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
-                       top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, row0, allow_table);
+                       top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, row0, allow_table, base_dev);
     if (advance && PER_ROW)
         hipLaunchKernelGGL(advance_pos_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_dev, B);
     else if (advance)
@@ -603,6 +626,37 @@ extern "C" int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float
                                     int advance, const uint32_t* allow_table, void* stream) {
     return sample<false>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B, 0,
                          advance, allow_table, stream, "mgx_sample_topk_topp");
+}
+
+extern "C" int mgx_sample_topk_topp_window(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
+                                           uint64_t seed, int32_t* pos_dev, const int32_t* base_dev, int32_t* next_tok,
+                                           int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
+                                           const uint32_t* allow_table, int per_row, void* stream) {
+    const char* name = "mgx_sample_topk_topp_window";
+    MGX_REQUIRE(base_dev, MGX_ERR_NULL, "%s: NULL pointer", name);
+    return per_row ? sample<true>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B,
+                                  row0, advance, allow_table, stream, name, base_dev)
+                   : sample<false>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B,
+                                   row0, advance, allow_table, stream, name, base_dev);
+}
+
+extern "C" int mgx_decode_reanchor(int32_t* pos_dev, int32_t* base_dev, const int32_t* out_tokens, int out_ld, int32_t* seq,
+                                   int n_pad, int hop, int pad_token, int B, int per_row, void* stream) {
+    MGX_REQUIRE(pos_dev && base_dev && out_tokens && seq, MGX_ERR_NULL, "mgx_decode_reanchor: NULL pointer");
+    MGX_REQUIRE(B > 0 && n_pad > 0 && out_ld > 0 && hop >= 0 && (size_t)B * n_pad <= 0x7fffffff, MGX_ERR_SHAPE,
+                "mgx_decode_reanchor: need B>0, n_pad>0, out_ld>0, hop>=0, B*n_pad<2^31 (B=%d n_pad=%d out_ld=%d hop=%d)", B, n_pad,
+                out_ld, hop);
+    const int n = per_row ? B : 1;
+    hipLaunchKernelGGL(reanchor_move_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_dev, base_dev, n, hop);
+    const dim3 grid((B * n_pad + 255) / 256), block(256);
+    if (per_row)
+        hipLaunchKernelGGL(reanchor_fill_kernel<true>, grid, block, 0, (hipStream_t)stream, pos_dev, base_dev, out_tokens, out_ld, seq,
+                           n_pad, pad_token, B);
+    else
+        hipLaunchKernelGGL(reanchor_fill_kernel<false>, grid, block, 0, (hipStream_t)stream, pos_dev, base_dev, out_tokens, out_ld, seq,
+                           n_pad, pad_token, B);
+    MGX_CHECK_LAUNCH("mgx_decode_reanchor");
+    return MGX_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------

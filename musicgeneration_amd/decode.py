@@ -1,7 +1,8 @@
 """KV-cache decode of ``MusicTransformer`` (cfg5; options documented at ``MusicTransformer.generate_cached``).
 ``generate_cached`` below is the driver: ``check_args`` holds every refusal and runs before any device work, ``KVCache`` is
 the only place that knows the two cache formats, ``SubBatch`` is where ``groups`` cuts the batch and where a row's position
-lives (``pos``, on the device: one shared counter, or one per row when prompts differ in length)."""
+lives (``pos``, on the device: one shared counter, or one per row when prompts differ in length).  ``window_schedule`` is the
+host-side plan of the re-anchored window (``window=``), the one way to generate past max_seq with the cache."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -76,12 +77,51 @@ class KVCache:
         return (self.k, self.v)
 
 
-def check_args(model, prior, length: int, return_probs: bool, prefill: str, prior_lengths, kv_cache: str):
+def default_hop(window: int) -> int:
+    return max(1, window // 8)
+
+
+def window_start(lens, window: int):
+    """(base, t) per row before the first step: a prompt longer than the window starts from its last ``window`` tokens"""
+    return [max(0, p - window) for p in lens], [min(p, window) - 1 for p in lens]
+
+
+def window_schedule(lens, length: int, window: int, hop: Optional[int] = None):
+    """The re-anchored window of generate_cached(window=, hop=), on the host: for prompt lengths ``lens`` and ``length`` steps it
+    returns (base, t, anchors) -- base[s][b] the output column that holds row b's window position 0 at step s, t[s][b] the window
+    position of that step's input token (so base + t = P_b - 1 + s is the token's column and cache rows 0..t-1 are valid), and
+    anchors, the steps before which the window is re-anchored.  A re-anchor happens when the longest row has filled the window
+    (max_b t_b == window) and moves every row together: t -= hop, base += hop.  ``hop`` None: max(1, window // 8)."""
+    hop = default_hop(window) if hop is None else hop
+    base, t = window_start(lens, window)
+    bases, ts, anchors = [], [], []
+    for s in range(length):
+        if max(t) == window:
+            anchors.append(s)
+            base, t = [v + hop for v in base], [v - hop for v in t]
+        bases.append(base)
+        ts.append(t)
+        t = [v + 1 for v in t]
+    return bases, ts, anchors
+
+
+def check_args(model, prior, length: int, return_probs: bool, prefill: str, prior_lengths, kv_cache: str, window=None, hop=None,
+               groups=None, masked_groups: bool = False):
     """every refusal of generate_cached (ValueError), on the host.  Returns (P: the columns of ``prior`` to decode from, below its
-    width for equal prior_lengths; lens: the per-row prompt lengths if they differ, else None; batched: the prefill that runs)"""
+    width for equal prior_lengths; lens: the per-row prompt lengths if they differ, else None; batched: the prefill that runs;
+    hop: the window's hop, None without ``window``)"""
     if kv_cache not in KVCache.KINDS:
         raise ValueError(f"kv_cache must be 'bf16' or 'fp8', got {kv_cache!r}")
     max_seq = model.max_seq
+    if window is None and hop is not None:
+        raise ValueError(f"hop ({hop}) is the stride of the re-anchored window: it needs window")
+    if window is not None:
+        if not 2 <= window <= max_seq:
+            raise ValueError(f"window must lie in 2 .. max_seq ({max_seq}), got {window}")
+        if (groups or 1) > 1 or masked_groups:
+            raise ValueError("groups / masked_groups are not combined with window (the window decodes the batch as one group)")
+        if prefill == "token":
+            raise ValueError("prefill='token' is not combined with window: the window is always prefilled in one batched pass")
     B, Pmax = prior.shape
     P, lens = Pmax, None
     if prior_lengths is not None:
@@ -90,14 +130,27 @@ def check_args(model, prior, length: int, return_probs: bool, prefill: str, prio
             raise ValueError(f"prior_lengths has {len(lens)} entries for a batch of {B} prompts")
         if any(not 1 <= v <= Pmax for v in lens):
             raise ValueError(f"prior_lengths must lie in 1 .. {Pmax} (the width of prior), got {lens}")
-        if Pmax + length > max_seq:
+        if window is None and Pmax + length > max_seq:
             raise ValueError(f"the longest prompt ({Pmax}) + length ({length}) must be <= max_seq ({max_seq})")
         if min(lens) == max(lens):                        # all equal: exactly the uniform call on prior[:, :P]
             P, lens = lens[0], None
     if prefill not in ("auto", "token", "batched"):
         raise ValueError("prefill must be 'auto', 'token' or 'batched'")
-    if P + length > max_seq or P < 1:
+    if (window is None and P + length > max_seq) or P < 1:
         raise ValueError(f"prior ({P}) + length ({length}) must be <= max_seq ({max_seq}) and prior non-empty")
+    if window is not None:
+        # the window may run past max_seq; what has to fit are its two batched passes, each padded to a multiple of 32 rows
+        t0 = window_start(lens or [P], window)[1]
+        spread = max(t0) - min(t0)
+        hop = default_hop(window) if hop is None else int(hop)
+        if hop < 1 or hop + spread > window - 1:
+            raise ValueError(f"hop must lie in 1 .. window - 1 - spread = {window - 1 - spread} (window {window}; spread {spread}: how "
+                             f"far the prompts' start positions lie apart; every row keeps a cached token), got {hop}")
+        for what, n in (("first", max(t0)), ("re-anchor", window - hop)):
+            if (n + 31) // 32 * 32 > max_seq:
+                raise ValueError(f"the window's {what} prefill pads {n} tokens to {(n + 31) // 32 * 32} rows > max_seq={max_seq}: "
+                                 "choose a smaller window" + (" or a larger hop" if what == "re-anchor" else ""))
+        return P, lens, True, hop
     # the batched pass pads the prompt to a multiple of 32 rows; when that exceeds max_seq (max_seq not a multiple of 32)
     # the full-sequence kernels cannot take it: 'auto' falls back to token-by-token prefill, the rest say why
     padded = (P - 1 + 31) // 32 * 32
@@ -109,12 +162,12 @@ def check_args(model, prior, length: int, return_probs: bool, prefill: str, prio
         if not fits:
             raise ValueError(f"prompts of different lengths are prefilled in one batched pass, which pads the {P - 1}-token "
                              f"prompt to {padded} rows > max_seq={max_seq}")
-        return P, lens, True
+        return P, lens, True, None
     if prefill == "batched" and return_probs:
         raise ValueError("return_probs needs prefill='token' (it reports the distribution after every prior token)")
     if prefill == "batched" and not fits:
         raise ValueError(f"prefill='batched' pads the {P - 1}-token prompt to {padded} rows > max_seq={max_seq}")
-    return P, None, prefill == "batched" or (prefill == "auto" and not return_probs and P > 32 and fits)
+    return P, None, prefill == "batched" or (prefill == "auto" and not return_probs and P > 32 and fits), None
 
 
 class Weights:
@@ -157,14 +210,19 @@ class SubBatch:
     ws: Optional[torch.Tensor]    # split-K partials (long caches only)
     stream: torch.cuda.Stream
     graph: Optional[torch.cuda.CUDAGraph] = None
+    base: Optional[torch.Tensor] = None   # int32 of pos's shape with ``window``: the column of ``out`` that holds window position 0
 
 
-def prefill_batched(w: Weights, cache: KVCache, tokens: torch.Tensor) -> None:
+def prefill_batched(w: Weights, cache: KVCache, tokens: torch.Tensor, n: Optional[int] = None) -> None:
     """positions 0..n-1 (tokens int32 [B, n]) through the full-sequence kernels (causal, so the zero-padded tail up to a
-    multiple of 32 cannot reach them), every layer's K / V rows into the cache"""
-    B, n = tokens.shape
-    seq = torch.zeros(B, (n + 31) // 32 * 32, dtype=torch.int32, device=tokens.device)
-    seq[:, :n] = tokens
+    multiple of 32 cannot reach them), every layer's K / V rows into the cache.  With ``n`` given, ``tokens`` is already padded
+    to a multiple of 32 columns (any valid ids in the tail) and its first n columns are the positions"""
+    if n is None:
+        B, n = tokens.shape
+        seq = torch.zeros(B, (n + 31) // 32 * 32, dtype=torch.int32, device=tokens.device)
+        seq[:, :n] = tokens
+    else:
+        seq = tokens
     hh = ops.embed_pe_fwd(seq, w.emb, w.pe)
     for i, ly in enumerate(w.layers):
         qkv = ops.linear_fwd(hh, ly["wqkv"], ly["bqkv"], 0)
@@ -201,12 +259,13 @@ def decode_step(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_int
         wn, bn = (L[i + 1]["wqkv"], L[i + 1]["bqkv"]) if i + 1 < len(L) else (w.wv_step, w.bv)
         qkv, h = ln_linear(f, o1, ly["g2"], ly["b2"], wn, bn, 0)      # the next layer's qkv; after the last layer the logits
     ops.sample_topk_topp(qkv, w.V, r.pos, r.tok, r.out if sample_into_out else None, r.probs, advance=True, row0=r.b0,
-                         ragged=ragged, **sampler)
+                         ragged=ragged, base=r.base, **sampler)
 
 
-def replay_graphs(subs, steps: int, step_rows) -> None:
+def replay_graphs(subs, steps: int, step_rows, before=None) -> None:
     """one graph of ``step_rows(r)`` per sub-batch, each replayed ``steps`` times on its own stream: the sub-batches meet at the
-    end only, so their chains of launches overlap freely (parallel branches INSIDE one graph were measured to run in turn)"""
+    end only, so their chains of launches overlap freely (parallel branches INSIDE one graph were measured to run in turn).
+    ``before(i, r)``: eager work on r's stream ahead of its replay i (the window's re-anchor)"""
     cur = torch.cuda.current_stream()
     torch.cuda.synchronize()
     for r in subs:
@@ -215,9 +274,11 @@ def replay_graphs(subs, steps: int, step_rows) -> None:
             r.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(r.graph, stream=r.stream):
                 step_rows(r)                              # the capture itself does not execute
-    for _ in range(steps):
+    for i in range(steps):
         for r in subs:
             with torch.cuda.stream(r.stream):
+                if before is not None:
+                    before(i, r)
                 r.graph.replay()
     for r in subs:
         cur.wait_stream(r.stream)
@@ -226,10 +287,53 @@ def replay_graphs(subs, steps: int, step_rows) -> None:
         r.stream.synchronize()
 
 
+def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length: int, window: int, hop: int, ragged: bool,
+                  sampler: dict, use_graph: bool, probs_all, pad_token: int):
+    """the steps of generate_cached(window=): the cache holds window positions 0..window-1 only, and every time the longest
+    row has filled it the window is re-anchored -- ops.decode_reanchor drops the oldest ``hop`` tokens of every row (pos -= hop,
+    base += hop) and gathers the remaining ones, which one batched causal pass turns back into cache rows 0.. .  The schedule is
+    window_schedule's, known on the host, so nothing is read back; the step graph is captured once and replayed across the
+    re-anchors, which run eagerly on the graph's stream.  ``lens``: every row's prompt length; ``r``: the whole batch.  Returns
+    the window position of every row's last input token"""
+    dev, B = prior_i.device, prior_i.shape[0]
+    base0, t0 = window_start(lens, window)
+    _, ts, anchors = window_schedule(lens, length, window, hop)
+
+    def as_dev(v):
+        return torch.tensor(v, dtype=torch.int32, device=dev)
+    rows, base_rows, t_rows = torch.arange(B, device=dev), as_dev(base0).long(), as_dev(t0).long()
+    r.pos.copy_(as_dev(t0 if ragged else t0[:1]))
+    r.base.copy_(as_dev(base0 if ragged else base0[:1]))
+    n = max(t0)
+    if n > 0:                                             # window positions 0..n-1 of every row, the ragged start's one pass
+        prefill_batched(w, cache, prior_i.gather(1, base_rows[:, None] + torch.arange(n, device=dev)[None, :]))
+    r.tok.copy_(prior_i[rows, base_rows + t_rows])        # every row resumes at its own last prompt token
+    n = window - hop                                      # a re-anchor leaves the longest row this many tokens
+    seq = torch.empty(B, (n + 31) // 32 * 32, dtype=torch.int32, device=dev) if anchors else None
+    col0 = as_dev(lens).long() - 1
+
+    def reanchor():
+        ops.decode_reanchor(r.pos, r.base, r.out, seq, hop, pad_token, ragged=ragged)
+        prefill_batched(w, cache, seq, n)
+    steps = max(length, 1)                                # length 0 still runs the last prompt token (its distribution)
+    eager = 1 if use_graph and steps - 1 > 2 else steps   # the first step also warms every kernel up before capture
+    for s in range(eager):
+        if s in anchors:
+            reanchor()
+        decode_step(w, r, sampler, ragged, length > 0)
+        if probs_all is not None:                         # the distribution after column P_b - 1 + s
+            probs_all[rows, col0 + s] = r.probs
+    if eager < steps:
+        replay_graphs([r], steps - 1, lambda r_: decode_step(w, r_, sampler, ragged, True),
+                      before=lambda i, r_: reanchor() if i + 1 in anchors else None)
+    return ts[-1] if ts else t0
+
+
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
-                    return_cache, groups, masked_groups, prior_lengths, kv_cache):
+                    return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None):
     """MusicTransformer.generate_cached (documented there)"""
-    P, lens, batched = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache)
+    P, lens, batched, hop = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache, window, hop, groups,
+                                       masked_groups)
     extra, prior, ragged = prior.shape[1] - P, prior[:, :P], lens is not None      # extra > 0: equal prior_lengths below the width
     st = model.store()
     st.sync_shadow()
@@ -237,7 +341,8 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     model.eval()
     B, total, dev = prior.shape[0], P + length, st.param.device
     d, V = model.embedding_dim, model.vocab_size
-    cache = KVCache(kv_cache, B, d // 64, total, model.num_layer, dev)
+    cache_rows = total if window is None else min(window, total)     # a window never holds more than ``window`` positions
+    cache = KVCache(kv_cache, B, d // 64, cache_rows, model.num_layer, dev)
     # ``groups`` (default 1): the batch rows as that many independent sub-batches, each with its own
     # captured step graph replayed on its own stream.  Rows never interact and the sampler draws by (seed, step, GLOBAL
     # row), so the tokens do not depend on the grouping (tests/test_gpu_decode.py).  The point would be to let one
@@ -246,6 +351,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     # SLOWER than one does (0.75 ms/token at 2 groups, 0.48 at 3-4, 0.72 at 6, against 0.50-0.51 at 1), so it stays off.
     G = max(1, min(int(groups or 1), B))
     pos_all = torch.zeros(B if ragged else G, dtype=torch.int32, device=dev)     # ragged: one position per row
+    base_all = torch.zeros_like(pos_all) if window is not None else None
     tok = prior[:, 0].to(torch.int32).contiguous().to(dev)
     prior_i = prior.to(torch.int32).to(dev)
     out_tokens = torch.zeros(B, total, dtype=torch.int32, device=dev)
@@ -270,7 +376,8 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
             stream = torch.cuda.Stream()
         subs.append(SubBatch(b0, pos_all[b0:b1] if ragged else pos_all[g:g + 1], tok[b0:b1], out_tokens[b0:b1], hbuf[b0:b1],
                              ctxbuf[b0:b1], probs_step[b0:b1] if return_probs else None, cache.rows(b0, b1),
-                             ops.rel_attn_decode_workspace(b1 - b0, total, d, dev), stream))
+                             ops.rel_attn_decode_workspace(b1 - b0, cache_rows, d, dev), stream,
+                             base=None if window is None else base_all[b0:b1] if ragged else base_all[g:g + 1]))
     # grammar: [V, ceil(V/32)] bit table "token v may follow token t" (e.g. REMI_EventSeq.next_token_table()); applied
     # inside the sampling kernel, so the constrained step stays graph-captured
     allow = None
@@ -284,43 +391,51 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
         for r in subs:
             decode_step(w, r, sampler, ragged, sample_into_out)
 
-    first = 0
-    if batched:
-        # positions 0..P-2 in one pass; token P-1 then takes the ordinary decode step below
-        n = P - 1
-        if n > 0:
-            prefill_batched(w, cache, prior_i[:, :n])
-            pos_all.fill_(n)
-            tok.copy_(prior_i[:, n])
-            first = n
-        if ragged:                                        # every row resumes at its own last prompt token
-            pos_all.copy_(lens_dev - 1)
-            tok.copy_(prior_i[rows, lens_dev.long() - 1])
-
-    def put_probs(p):                                     # the distribution after position p (per row: after P_b - 1 + p - first)
-        if ragged:
-            probs_all[rows, lens_dev.long() - 1 + (p - first)] = probs_step
-        else:
-            probs_all[:, p] = probs_step
-    # the (rest of the) prior is teacher-forced token by token (it also warms every kernel up before capture)
-    for p in range(first, P):
-        step(sample_into_out=(p == P - 1) and length > 0)
-        if return_probs:
-            put_probs(p)
-        if p + 1 < P:
-            tok.copy_(prior_i[:, p + 1])
-    remaining = length - 1 if length > 0 else 0
-    if use_graph and not return_probs and remaining > 2:
-        replay_graphs(subs, remaining, lambda r: decode_step(w, r, sampler, ragged, True))
+    if window is not None:
+        final_t = decode_window(w, subs[0], cache, prior_i, lens or [P] * B, length, window, hop, ragged, sampler,
+                                use_graph and not return_probs, probs_all, model.pad_token)
     else:
-        for p in range(remaining):
-            step(True)
+        first = 0
+        if batched:
+            # positions 0..P-2 in one pass; token P-1 then takes the ordinary decode step below
+            n = P - 1
+            if n > 0:
+                prefill_batched(w, cache, prior_i[:, :n])
+                pos_all.fill_(n)
+                tok.copy_(prior_i[:, n])
+                first = n
+            if ragged:                                        # every row resumes at its own last prompt token
+                pos_all.copy_(lens_dev - 1)
+                tok.copy_(prior_i[rows, lens_dev.long() - 1])
+
+        def put_probs(p):                                     # the distribution after position p (per row: after P_b - 1 + p - first)
+            if ragged:
+                probs_all[rows, lens_dev.long() - 1 + (p - first)] = probs_step
+            else:
+                probs_all[:, p] = probs_step
+        # the (rest of the) prior is teacher-forced token by token (it also warms every kernel up before capture)
+        for p in range(first, P):
+            step(sample_into_out=(p == P - 1) and length > 0)
             if return_probs:
-                put_probs(P + p)
+                put_probs(p)
+            if p + 1 < P:
+                tok.copy_(prior_i[:, p + 1])
+        remaining = length - 1 if length > 0 else 0
+        if use_graph and not return_probs and remaining > 2:
+            replay_graphs(subs, remaining, lambda r: decode_step(w, r, sampler, ragged, True))
+        else:
+            for p in range(remaining):
+                step(True)
+                if return_probs:
+                    put_probs(P + p)
     model.train(was_training)
-    if return_cache and ragged:                           # prefill rows a short row's decode never reached
+    if return_cache and window is not None:               # what earlier windows and the prefill left beyond the last step's row
+        cache.zero_rows_from(torch.tensor(final_t, dtype=torch.int32, device=dev) + 1)
+    elif return_cache and ragged:                         # prefill rows a short row's decode never reached
         cache.zero_rows_from(lens_dev + (length - 1))
     pad = torch.nn.functional.pad                         # equal prior_lengths P < Pmax: pad_token / zeros up to Pmax + length
     toks = pad(out_tokens, (0, extra), value=model.pad_token) if extra else out_tokens
     res = (toks, pad(probs_all, (0, 0, 0, extra)) if extra else probs_all) if return_probs else toks
+    if window is not None:                                # the cache grows to the rows the full-width call would have
+        extra = min(window, total + extra) - cache_rows
     return (res, *(cache.grow(extra) if extra else cache).result()) if return_cache else res

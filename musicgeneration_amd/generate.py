@@ -45,8 +45,14 @@ def get_options(argv=None):
                            'its first 500 MIDI-like events that sample\'s prompt (KV-cache decode over prompts of different '
                            'lengths)')
     parser.add_option('--kv-cache', dest='kv_cache', type='choice', choices=['bf16', 'fp8'], default='bf16',
-                      help='K/V cache of the KV-cache decode (--grammar, --condition-files): bf16 (default) or fp8, '
+                      help='K/V cache of the KV-cache decode (--grammar, --condition-files, --window): bf16 (default) or fp8, '
                            'e4m3fn codes with one scale per row -- half the bytes per key, samples differ from bf16')
+    parser.add_option('--window', dest='window', type='int', default=0,
+                      help='generate past -M with the KV-cache decode: a window of at most W tokens that is re-anchored (oldest '
+                           'tokens dropped, positions renumbered from 0, K/V rebuilt in one pass) every --hop tokens; 0 = off. '
+                           "--window 499 --hop 1 is the reference's threshold_len = 500 window")
+    parser.add_option('--hop', dest='hop', type='int', default=0,
+                      help='tokens dropped per re-anchor of --window (0 = default, max(1, W // 8))')
     return parser.parse_args(argv)[0]
 
 
@@ -68,7 +74,7 @@ def _ragged_priors(o):
         ids.append(a)
         print('Prompt: {} events from {}'.format(len(a), f))
     lens = [len(a) for a in ids]
-    if max(lens) + o.max_len > o.max_seq:
+    if not o.window and max(lens) + o.max_len > o.max_seq:
         raise SystemExit(f'--condition-files: the longest prompt ({max(lens)} events) + -l {o.max_len} exceeds -M {o.max_seq}')
     pad = vocab_of(o.repr) - 1
     prior = np.full((len(ids), max(lens)), pad, dtype=np.int64)
@@ -79,9 +85,15 @@ def _ragged_priors(o):
 
 def main(argv=None):
     o = get_options(argv)
-    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None):
+    if o.hop and not o.window:
+        raise SystemExit('--hop is the stride of --window: add --window W')
+    if o.window and o.reference_mask:
+        raise SystemExit('--reference-mask cannot be combined with --window (the KV-cache decode is causal)')
+    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window):
         raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
                          '(the default sampler recomputes the window and keeps no cache)')
+    # with --window every branch below samples through the KV-cache decode and its re-anchored window
+    cached = dict(kv_cache=o.kv_cache, window=o.window or None, hop=o.hop or None)
     ragged = _ragged_priors(o) if o.condition_files is not None else None     # checked before any model or device work
     device = torch.device('cuda:0')
     vocab = vocab_of(o.repr)
@@ -104,7 +116,7 @@ def main(argv=None):
     if ragged is not None:
         prior, lens = ragged
         res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                 prior_lengths=lens, kv_cache=o.kv_cache).cpu().numpy()
+                                 prior_lengths=lens, **cached).cpu().numpy()
         res = [row[:n + o.max_len] for row, n in zip(res, lens)]             # without the pad tail
         _write(o, res)
         return
@@ -129,7 +141,9 @@ def main(argv=None):
         bar = Codec.feat_ranges()['bar'][0]
         prior = torch.full((o.batch_size, 1), bar, dtype=torch.long, device=device)
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                 grammar=Codec.next_token_table(), kv_cache=o.kv_cache).cpu().numpy()
+                                 grammar=Codec.next_token_table(), **cached).cpu().numpy()
+    elif o.window:
+        res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached).cpu().numpy()
     else:
         res = mt.generate(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                           reference_mask=o.reference_mask).cpu().numpy()

@@ -320,9 +320,10 @@ class MusicTransformer(torch.nn.Module):
     def generate_cached(self, prior: torch.Tensor, length: int, temperature: float = 1.0, top_k: int = 0,
                         top_p: float = 1.0, seed: int = 0, use_graph: bool = True, return_probs: bool = False,
                         grammar=None, prefill: str = "auto", return_cache: bool = False, groups: Optional[int] = None,
-                        masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16"):
+                        masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
+                        hop: Optional[int] = None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
-        0..P+length-1 (requires P+length <= max_seq; no sliding window).  Every step runs
+        0..P+length-1 (requires P+length <= max_seq unless ``window`` is given, see below).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
         sampler; the position lives on the device, so after a warm-up step the whole step is captured in
         one graph and replayed per token.  Returns int32 [B, P+length] (and, if ``return_probs``, the
@@ -352,9 +353,29 @@ class MusicTransformer(torch.nn.Module):
         the memory.  Every K / V row is quantized as it enters the cache (the batched prefill through ops.kv_store_fp8), so the
         distributions and samples differ from the bf16 run.  Works with every option above; with
         ``return_cache`` the result is (res, K codes, V codes, K scales, V scales) per layer, the codes as float8_e4m3fn
-        [B, h, L, 64] and the scales f32 [B, h, L]."""
+        [B, h, L, 64] and the scales f32 [B, h, L].
+
+        ``window`` (2 .. max_seq) and ``hop`` (default max(1, window // 8)): generate past max_seq.  The cache holds a window of
+        at most ``window`` tokens of every row, numbered from position 0 (the model's positional encoding is absolute, so a
+        cache cannot slide by one token: every cached row would belong to the wrong position).  Row b keeps on the device the
+        output column ``base_b`` of its window position 0 and the window position ``t_b`` of the step's input token; a prompt
+        longer than the window starts from its last ``window`` tokens.  Whenever the longest row has filled the window
+        (max_b t_b == window) every row is re-anchored: the oldest ``hop`` tokens are dropped (t_b -= hop, base_b += hop), the
+        rest renumbered from 0 and their K / V rebuilt by one batched causal pass of window - hop rows (the prefill, for either
+        ``kv_cache``); the sampler draws by the absolute step base_b + t_b, so segments do not repeat random numbers.  Each
+        step's distribution is the causal forward of the tokens out[b, base_b : base_b + t_b + 1]: with hop = 1 the window of
+        ``generate`` (whose forward sees config.threshold_len - 1 tokens: ``window`` = 499), with a larger hop a window
+        of between window - hop + 1 and window tokens at one forward pass per hop tokens.  ``decode.window_schedule`` gives the whole
+        schedule on the host; nothing is read back and the step graph is captured once and replayed across re-anchors.
+        ``prior.shape[1] + length`` may exceed max_seq; the prefill is always batched ("token" is refused, as are ``groups`` and
+        ``masked_groups``), ``hop`` + the spread of the rows' start positions must stay below ``window``, and
+        window - hop rounded up to 32 rows must fit max_seq.  Returns int32 [B, Pmax+length] as above; with ``return_probs``
+        row b carries the distributions after columns P_b-1 .. P_b+length-2 and zeros elsewhere (uniform prompts too); with
+        ``return_cache`` the last window's caches, min(window, Pmax+length) rows, zero beyond the row of each row's last input
+        token.  While no re-anchor happens (window >= Pmax + length) tokens, distributions and caches are bitwise those of the
+        call without ``window`` and with the batched prefill."""
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
-                                      prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache)
+                                      prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop)
 
     def test(self):
         self.eval()

@@ -656,25 +656,57 @@ def rel_attn_decode(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace=None, *,
     return ctx
 
 
+def _check_base(base, pos_dev, what):
+    """the window's base (ABI 21) has the shape of the positions: one shared int32, or one per row"""
+    if base.dtype != torch.int32 or pos_dev.dtype != torch.int32 or base.numel() != pos_dev.numel() or not base.is_contiguous():
+        raise ValueError(f"{what}: base must be a contiguous int32 tensor of the positions' {pos_dev.numel()} entries "
+                         f"(got {base.dtype}, {base.numel()} entries)")
+
+
 def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=None, temperature=1.0, top_k=0, top_p=1.0,
-                     seed=0, advance=True, allow_table=None, row0=0, *, ragged=False):
+                     seed=0, advance=True, allow_table=None, row0=0, *, ragged=False, base=None):
     """allow_table: optional int32/uint32 [V, ceil(V/32)] grammar mask on the device (bit v of row t: v may follow t);
     row0: index of the first row in the whole batch when the tensors are a sub-batch's rows (the draw is by global row);
-    ragged: row b's position is pos_dev[b] (draw, out_tokens column pos_dev[b] + 1, and every entry advanced)"""
-    _need_cuda(logits, pos_dev, next_tok, out_tokens, probs_out, allow_table)
+    ragged: row b's position is pos_dev[b] (draw, out_tokens column pos_dev[b] + 1, and every entry advanced);
+    base (ABI 21): int32 of pos_dev's shape, the out_tokens column of window position 0 -- the draw and the column written
+    take base + pos_dev in place of pos_dev; advance moves pos_dev only"""
+    _need_cuda(logits, pos_dev, next_tok, out_tokens, probs_out, allow_table, base)
     ld = logits.shape[-1]
     B = logits.numel() // ld
     sfx = _check_pos_rows(pos_dev, B, ragged)
-    name = "mgx_sample_topk_topp" + (sfx or "_rows")
     if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
                                     or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4
                                     or not allow_table.is_contiguous()):
         raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
-    check(getattr(_lib.load(), name)(ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed),
-                                     ptr(pos_dev), ptr(next_tok), ptr(out_tokens),
-                                     0 if out_tokens is None else out_tokens.shape[-1], ptr(probs_out), B, int(row0),
-                                     1 if advance else 0, ptr(allow_table), stream_ptr()), "mgx_sample_topk_topp" + sfx)
+    head = (ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed), ptr(pos_dev))
+    tail = (ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[-1], ptr(probs_out), B, int(row0),
+            1 if advance else 0, ptr(allow_table))
+    if base is not None:
+        _check_base(base, pos_dev, "sample_topk_topp")
+        check(_lib.load().mgx_sample_topk_topp_window(*head, ptr(base), *tail, 1 if ragged else 0, stream_ptr()),
+              "mgx_sample_topk_topp_window")
+        return next_tok
+    name = "mgx_sample_topk_topp" + (sfx or "_rows")
+    check(getattr(_lib.load(), name)(*head, *tail, stream_ptr()), "mgx_sample_topk_topp" + sfx)
     return next_tok
+
+
+def decode_reanchor(pos_dev, base, out_tokens, seq, hop, pad_token, *, ragged=False):
+    """the re-anchor of the decode window (ABI 21): pos_dev -= hop and base += hop (int32 [1] shared, or [B] with ``ragged``),
+    then seq int32 [B, n_pad] = the window's tokens out_tokens[b, base_b : base_b + pos_b], right-padded with pad_token"""
+    _need_cuda(pos_dev, base, out_tokens, seq)
+    B, n_pad = seq.shape
+    _check_pos_rows(pos_dev, B, ragged)
+    _check_base(base, pos_dev, "decode_reanchor")
+    if not ragged and pos_dev.numel() != 1:
+        raise ValueError(f"decode_reanchor: a shared position is one int32, got {pos_dev.numel()} entries")
+    if (out_tokens.dtype != torch.int32 or seq.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B
+            or not out_tokens.is_contiguous() or not seq.is_contiguous()):
+        raise ValueError(f"decode_reanchor: out_tokens and seq must be contiguous int32 [{B}, ...], got {out_tokens.dtype} "
+                         f"{tuple(out_tokens.shape)} and {seq.dtype} {tuple(seq.shape)}")
+    check(_lib.load().mgx_decode_reanchor(ptr(pos_dev), ptr(base), ptr(out_tokens), out_tokens.shape[1], ptr(seq), n_pad, int(hop),
+                                          int(pad_token), B, 1 if ragged else 0, stream_ptr()), "mgx_decode_reanchor")
+    return seq
 
 
 # --------------------------------------------------------------------------------------------------
