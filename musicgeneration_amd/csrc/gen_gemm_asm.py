@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Generator of the hand-scheduled gfx950 main loops of the four-wave ring GEMMs (linear.hip): the weight-gradient kernel
+"""Generator of the hand-scheduled gfx950 main loops of the four-wave ring GEMMs (linear_ring.hip): the weight-gradient kernel
 linear_dw_ring4_kernel (first half of this file) and the forward / dX kernel linear_ring4_kernel (second half: ring_tile).
 
     python musicgeneration_amd/csrc/gen_gemm_asm.py            -> musicgeneration_amd/csrc/linear_dw_ring4_loop.inc, linear_ring4_loop.inc
 
 Diagnostic builds (results are garbage, timing only; tools/dw4_clock.sh, tools/ring4_times.py): MGX_DW4_NODMA / NOREAD / NOMFMA / NOSYNC and
 MGX_RING4_DIAG in the environment of the build leave parts of the loops out; such loops are written to linear_*_loop_diag.inc (untracked),
-which linear.hip includes instead of the tracked files when built with -DMGX_GEMM_DIAG=1.
+which linear_ring.hip includes instead of the tracked files when built with -DMGX_GEMM_DIAG=1.
 
 Weight gradient:
 
@@ -53,7 +53,7 @@ NOMFMA = bool(os.environ.get("MGX_DW4_NOMFMA"))
 NOREAD = bool(os.environ.get("MGX_DW4_NOREAD"))
 RING_DIAG = os.environ.get("MGX_RING4_DIAG", "")     # "noa" / "nob": no DMA of the A / B image; "nora" / "norb": no fragment reads of A / B
 NOSYNC = os.environ.get("MGX_DW4_NOSYNC", "")        # "1": no wait, no barrier; "w": no wait; "b": no barrier
-# any of the knobs above: the (wrong-result) loops go to linear_*_loop_diag.inc, which linear.hip includes under -DMGX_GEMM_DIAG=1 --
+# any of the knobs above: the (wrong-result) loops go to linear_*_loop_diag.inc, which linear_ring.hip includes under -DMGX_GEMM_DIAG=1 --
 # never into the tracked files a product build reads (an exported knob used to turn the next auto-build into a garbage GEMM library)
 DIAG = bool(NODMA or NOMFMA or NOREAD or RING_DIAG or NOSYNC)
 
@@ -200,7 +200,7 @@ def loop_tail(g: Gen, slot: int, tag: str):
 
 
 # which of its four dY fragments a wave sums for the bias gradient (parameter word 9): the waves that hold the same dY fragments -- wn = 0, 1
-# of every k-tile of a weight's tile row -- share the work (linear.hip: linear_dw_ring4_kernel)
+# of every k-tile of a weight's tile row -- share the work (linear_ring.hip: linear_dw_ring4_kernel)
 BIAS_VARIANTS = {1: (0, 1, 2, 3), 2: (0, 1), 3: (2, 3), 4: (0,), 5: (1,), 6: (2,), 7: (3,)}
 
 
@@ -240,7 +240,7 @@ def generate():
 
 
 # =====================================================================================================================================
-# Forward / dX ring GEMM with four waves (linear.hip: linear_ring4_kernel<BTRANS, PRE>):  C[256 m][256 n] += A[m][r] B[n][r]  (NT,
+# Forward / dX ring GEMM with four waves (linear_ring.hip: linear_ring4_kernel<BTRANS, PRE>):  C[256 m][256 n] += A[m][r] B[n][r]  (NT,
 # forward) or A[m][r] B[r][n] (NN, dX), one asm statement per TILE: the HIP tile loop around it fills the wave's parameter block and runs
 # the epilogue (bias / ReLU / mask / addend, bf16, row-major stores); the LDS-DMA ring runs on across the statement's end -- the requests
 # of the next tile's first two stages are in flight during the epilogue -- and its state (source pointers, requests left in the tile)
@@ -275,7 +275,7 @@ RS_DA, RS_DB, RS_CNT, RS_PARAM = 56, 57, 58, 59
 RS_T = 60                        # ..63
 RS_FIRST, RS_LAST = 36, 63
 RG_DSTAGE = 65536
-EPI_STORES = 32                  # global stores of one wave's epilogue (linear.hip: store_wave_block4): a LOWER bound is what is safe here
+EPI_STORES = 32                  # global stores of one wave's epilogue (linear_ring.hip: store_wave_block4): a LOWER bound is what is safe here
 
 
 def rfrag(fs, kind, i):

@@ -48,7 +48,7 @@ def test_ring4_tile_statement_waits_are_sized_for_the_epilogue_hipcc_emits(tmp_p
     stages, requested by the previous statement, and, younger, the epilogue's global stores -- and its first counted waits
     (`s_waitcnt vmcnt(16 + MGX_RING4_EPI_STORES)` for stage 0) are only right if the epilogue hipcc compiled issues AT LEAST
     MGX_RING4_EPI_STORES VMEM operations per wave (more is the safe direction: the wait then covers some of them too).
-    Compile linear.hip to gfx950 assembly and count: every instantiation must hold >= EPI_STORES global stores outside the
+    Compile linear_ring.hip to gfx950 assembly and count: every instantiation must hold >= EPI_STORES global stores outside the
     statement, and the statement itself must no longer open with a full drain (which made those counted waits dead code)."""
     import re
     import shutil
@@ -64,7 +64,7 @@ def test_ring4_tile_statement_waits_are_sized_for_the_epilogue_hipcc_emits(tmp_p
         assert f"s_waitcnt vmcnt({16 + epi})" in inc
     out = tmp_path / "linear.s"
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S",
-                        "--cuda-device-only", "-w", os.path.join(CSRC, "linear.hip"), "-o", str(out)], capture_output=True, text=True, timeout=600)
+                        "--cuda-device-only", "-w", os.path.join(CSRC, "linear_ring.hip"), "-o", str(out)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     asm = out.read_text()
     found = 0

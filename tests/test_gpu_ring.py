@@ -1,4 +1,4 @@
-"""The 256 x 256 ring GEMMs (linear.hip: linear_ring_kernel, eight waves, HIP; linear_ring4_kernel, four waves, generated asm tile
+"""The 256 x 256 ring GEMMs (linear_ring.hip: linear_ring_kernel, eight waves, HIP; linear_ring4_kernel, four waves, generated asm tile
 statement) against the 128 x 128 kernels they replace for the big projections:
 same inputs through both paths in two child processes (the path is chosen once per process by MGX_GEMM_RING, a knob that
 exists in EXPERIMENT builds only: the test builds `libmgx_ringab.so` with `_build.py --experiments` and loads it through
@@ -287,3 +287,36 @@ def test_linear_kernel_id_follows_the_stream_cu_count():
             masked = ops.linear_fwd(a, w, b, 0)
         side.stream.synchronize()
         assert torch.equal(whole.view(torch.int16), masked.view(torch.int16))
+
+
+# (M, N, K, family) on a 256-CU device.  A ring needs whole 256 x 256 tiles of the output, a reduction that is a multiple of 32 and at
+# least 128, and at least 3/4 of the CUs busy = 192 tiles; the four-wave kernel a reduction >= 512 in multiples of 128, an output at
+# least 512 columns wide and smaller than 2^32 bytes (its epilogue's 32-bit offsets); M <= 32 is the skinny kernel's.
+_SKINNY, _TILE128, _RING8, _RING4 = 0, 1, 2, 3
+_FWD_BOUNDARIES = [
+    (32, 512, 512, _SKINNY), (33, 512, 512, _TILE128),                                   # M <= 32
+    (24576, 512, 512, _RING4), (24320, 512, 512, _TILE128),                              # 192 / 190 tiles
+    (24704, 512, 512, _TILE128), (24576, 520, 512, _TILE128),                            # M % 256, N % 256
+    (24576, 512, 64, _TILE128),                                                          # reduction < 128
+    (24576, 512, 256, _RING8), (24576, 512, 384, _RING8),                                # reduction < 512
+    (24576, 512, 576, _RING8), (24576, 512, 640, _RING4),                                # reduction % 128
+    (24576, 256, 512, _TILE128), (49152, 256, 512, _RING8),                              # 96 tiles; a 256-column output
+    (2097152, 1024, 512, _RING8),                                                        # an output of 2^32 bytes
+]
+_DX_BOUNDARIES = [(24576, 512, 512, _RING4), (49152, 512, 256, _RING8), (24320, 512, 512, _TILE128)]
+
+
+def test_linear_kernel_id_boundaries():
+    """both sides of every routing rule of mgx_linear_fwd / mgx_linear_dx on the whole device, as mgx_linear_kernel_id states them
+    (the function returns the decision the entry points switch on); no launch.  dX [M,K] = dY [M,N] . W [N,K] has its output
+    width in K and its reduction in N, and routes alike with no epilogue operand, a ReLU mask or an addend (kinds 1, 2, 3)."""
+    import torch
+    from musicgeneration_amd import _lib
+    if torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the table is written for 256 CUs")
+    lib = _lib.load()
+    for M, N, K, fam in _FWD_BOUNDARIES:
+        assert lib.mgx_linear_kernel_id(0, M, N, K, None) == fam, f"forward ({M}, {N}, {K})"
+    for M, N, K, fam in _DX_BOUNDARIES:
+        for kind in (1, 2, 3):
+            assert lib.mgx_linear_kernel_id(kind, M, N, K, None) == fam, f"dX kind {kind} ({M}, {N}, {K})"
