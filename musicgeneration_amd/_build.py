@@ -9,7 +9,7 @@ macros: the timing-only "peel" / in-kernel "stamp" builds the profile notes quot
 tracked sources, and loaded with `MGX_LIB_PATH=musicgeneration_amd/libmgx_NAME.so` (tools/peel_*.sh, tools/ab.sh).
 `--experiments` additionally compiles the alternative kernels kept under tools/experiments/ (two forward-attention
 structures and the 64-keys-per-wave dK/dV kernel, all measured slower) and defines MGX_EXPERIMENTS=1, which is also what enables the environment knobs
-(MGX_ATTN_FWD64, MGX_FWD_LDS, MGX_DKV_LDS, MGX_ATTN_BGROUP): the product library reads none of them."""
+(MGX_ATTN_FWD64, MGX_FWD_LDS, MGX_ATTN_BGROUP): the product library reads none of them."""
 from __future__ import annotations
 
 import fcntl
@@ -22,8 +22,9 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmgx.so")
-SOURCES = ["api.cpp", "rowwise_ops.hip", "rel_attn_fwd.hip", "rel_attn_bwd.hip", "rel_attn_dkv64.hip", "linear.hip", "linear_tile128.hip",
-           "linear_ring.hip", "linear_skinny.hip", "decode.hip", "gru_train.hip"]
+SOURCES = ["api.cpp", "rowwise_ops.hip", "rel_attn_fwd.hip", "rel_attn_bwd.hip", "rel_attn_dkv32.hip", "rel_attn_dkv64.hip", "rel_attn_dq_lite.hip",
+           "rel_attn_de_tiles.hip", "rel_attn_bwd_recompute.hip", "linear.hip", "linear_tile128.hip", "linear_ring.hip", "linear_skinny.hip",
+           "decode.hip", "gru_train.hip"]
 EXPERIMENT_DIR = os.path.join(ROOT, "tools", "experiments")
 EXPERIMENT_SOURCES = ["rel_attn_fwd2.hip", "rel_attn_fwd3.hip", "rel_attn_fwd64.hip"]      # --experiments builds only
 # per-file flags.  The 64-rows-per-wave attention kernels run one wave per SIMD with the whole 512-entry register file:

@@ -8,7 +8,7 @@ The kernel's address set-up and its epilogue (the dk / dv stores) stay HIP; the 
 assigned to its shadow, counted waits, and the hazards hipcc does not pad inside an asm statement checked (and padded) here.
 Two loops of six body variants each: "masked" bodies for the steps of the diagonal block (a sub-tile not started / on its
 diagonal) and for key blocks with padded keys, and the branch-free main bodies a wave switches to once both its sub-tiles are
-full (query tile n >= wk + 2).  What a step computes, and the layouts, are those of rel_attn_bwd.hip
+full (query tile n >= wk + 2).  What a step computes, and the layouts, are those of rel_attn_dkv32.hip
 (dkv_kernel) / tools/experiments/rel_attn_bwd64.hip; results are bit-identical to both.
 
 Structure of one iteration n (query tile n against the wave's key tiles J, J+1 = sub-tiles 0, 1), 44 MFMAs:

@@ -20,7 +20,7 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int IMG = BM * BK * 2;             // 16 KiB: 128 rows x 64 k (image R)  or  4 sub-tiles of 32 x 64 (image T)
 constexpr int LDS_BYTES = 4 * IMG;           // two operands, double buffered = 64 KiB -> 2 workgroups / CU
 
-// natural-k transposed fragment (see rel_attn_bwd.hip): X[16*ks + 8*hh + j][32*ct + (lane&31)]
+// natural-k transposed fragment (see rel_attn_de_tiles.hip): X[16*ks + 8*hh + j][32*ct + (lane&31)]
 MGX_DEV bf16x8 fragTn(const char* tile, int lane, int ks, int ct) {
     const int i = lane & 15, g = lane >> 4, hh = lane >> 5;
     const int rq = i >> 2;

@@ -1,4 +1,4 @@
-// Shared pieces of the relative-attention kernels (forward + the three backward kernels).
+// Shared pieces of the relative-attention kernels (forward and backward), and the declarations of the backward launchers.
 //
 // Geometry (all kernels): MFMA v_mfma_f32_32x32x16_bf16, dh = 64, tiles of 32 queries x 32 keys.
 //   A operand lane l: row (l&31), k = 8*(l>>5)+j, j=0..7  -> 16 contiguous bytes of a row-major row
@@ -46,10 +46,11 @@ MGX_DEV bf16x8 frag_R(const char* tile, int row, int hh, int ks) {
     return *(const bf16x8*)(tile + imgR_off(row, 2 * ks + hh));
 }
 
-// Transposed fragment from an image-T tile holding X[32 rows][64 cols]:
-// returns, for this lane, X[kappa(j)][col0 + (lane&31)], j = 0..7, with
-// kappa(j) = 16*s + 8*(j>>2) + 4*hh + (j&3)  -- the k order of an accumulator tile used as operand.
-MGX_DEV bf16x8 frag_T(const char* tile, int lane, int s, int ct) {
+// Transposed fragment (ds_read_b64_tr_b16) of a tile image X[32 rows][64 cols] laid out by IMG_OFF: returns, for this lane,
+// X[kappa(j)][32*ct + (lane&31)], j = 0..7, with kappa(j) = 16*s + 8*(j>>2) + 4*hh + (j&3) -- the k order of an accumulator tile
+// used as operand (acc_to_frag).
+template <int (*IMG_OFF)(int, int)>
+MGX_DEV bf16x8 frag_tr(const char* tile, int lane, int s, int ct) {
     const int i = lane & 15, g = lane >> 4, hh = lane >> 5;
     const int rq = i >> 2;                               // row within the 4-row block this lane addresses
     const int chunk = 4 * ct + 2 * (g & 1) + ((i & 3) >> 1);
@@ -58,52 +59,14 @@ MGX_DEV bf16x8 frag_T(const char* tile, int lane, int s, int ct) {
 #pragma unroll
     for (int jq = 0; jq < 2; ++jq) {
         const int row = 16 * s + 8 * jq + 4 * hh + rq;
-        const char* p = tile + imgT_off(row, chunk) + byte_in;
-        bf16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)p);
+        bf16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(tile + IMG_OFF(row, chunk) + byte_in));
         out[4 * jq + 0] = t[0]; out[4 * jq + 1] = t[1]; out[4 * jq + 2] = t[2]; out[4 * jq + 3] = t[3];
     }
     return out;
 }
-
-// transposed fragment read from an image-R tile (2-way bank conflict, saves a second LDS image):
-// X[kappa(j)][32*ct + (lane&31)], kappa(j) = 16*s + 8*(j>>2) + 4*hh + (j&3)
-MGX_DEV bf16x8 frag_T_onR(const char* tile, int lane, int s, int ct) {
-    const int i = lane & 15, g = lane >> 4, hh = lane >> 5;
-    const int rq = i >> 2;
-    const int chunk = 4 * ct + 2 * (g & 1) + ((i & 3) >> 1);
-    const int byte_in = 8 * (i & 1);
-    bf16x8 out;
-#pragma unroll
-    for (int jq = 0; jq < 2; ++jq) {
-        const int row = 16 * s + 8 * jq + 4 * hh + rq;
-        bf16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(tile + imgR_off(row, chunk) + byte_in));
-        out[4 * jq + 0] = t[0]; out[4 * jq + 1] = t[1]; out[4 * jq + 2] = t[2]; out[4 * jq + 3] = t[3];
-    }
-    return out;
-}
-
-// LDS image "B" (both): the chunk XORed with a permutation of (row>>1)&7 whose bit 2 is bit 1 of the row -- the eight same-parity rows a
-// ds_read_b128 lane group touches still get eight different values (conflict-free row fragments, as on image R), and rows q and q+2 of a
-// 4-row block differ in bit 2 (conflict-free ds_read_b64_tr_b16, as on image T): ONE image serves both kinds of fragment reads.
-MGX_DEV int imgB_swz(int row) { return (((row >> 1) & 1) << 2) | (((row >> 3) & 1) << 1) | ((row >> 2) & 1); }
-MGX_DEV int imgB_off(int row, int chunk) { return row * 128 + ((chunk ^ imgB_swz(row)) << 4); }
-MGX_DEV bf16x8 frag_B(const char* tile, int row, int hh, int ks) {
-    return *(const bf16x8*)(tile + imgB_off(row, 2 * ks + hh));
-}
-MGX_DEV bf16x8 frag_T_onB(const char* tile, int lane, int s, int ct) {      // as frag_T_onR
-    const int i = lane & 15, g = lane >> 4, hh = lane >> 5;
-    const int rq = i >> 2;
-    const int chunk = 4 * ct + 2 * (g & 1) + ((i & 3) >> 1);
-    const int byte_in = 8 * (i & 1);
-    bf16x8 out;
-#pragma unroll
-    for (int jq = 0; jq < 2; ++jq) {
-        const int row = 16 * s + 8 * jq + 4 * hh + rq;
-        bf16x4 t = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(tile + imgB_off(row, chunk) + byte_in));
-        out[4 * jq + 0] = t[0]; out[4 * jq + 1] = t[1]; out[4 * jq + 2] = t[2]; out[4 * jq + 3] = t[3];
-    }
-    return out;
-}
+// from an image-T tile (conflict-free), and from an image-R tile (2-way bank conflict, saves a second LDS image)
+MGX_DEV bf16x8 frag_T(const char* tile, int lane, int s, int ct) { return frag_tr<imgT_off>(tile, lane, s, ct); }
+MGX_DEV bf16x8 frag_T_onR(const char* tile, int lane, int s, int ct) { return frag_tr<imgR_off>(tile, lane, s, ct); }
 
 MGX_DEV u32x4 scale8(const u32x4& raw, float sc) {
     float f[8];
@@ -257,6 +220,41 @@ static inline void launch_er_frag(const uint16_t* Er, u32x4* EfA, u32x4* EfT, in
     hipLaunchKernelGGL(er_frag_kernel, dim3((n + 255) / 256), dim3(256), 0, s, Er, EfA, EfT, L);
 }
 
+// ---- host side ---------------------------------------------------------------------------------------------------------
+#ifndef MGX_EXPERIMENTS
+#define MGX_EXPERIMENTS 0   // 1 (experiment builds only): environment knobs that change which kernel runs / its residency, and the two
+#endif                      // alternative forward kernels of tools/experiments/.  The product library reads no environment variable here.
+
+// Batch rows per grid group: the largest divisor of B whose tensors -- `tensors_per_row` arrays of L x d bf16 per batch row: q/k/v/ctx
+// in the forward (4), plus dO in the backward (5) -- stay near 100 MB, so that one group's tensors stay inside the Infinity Cache while
+// its workgroups run (see rel_attn_fwd.hip).
+static inline int batch_group(int B, int L, int d, int tensors_per_row) {
+    const double per_row = (double)L * d * 2 * tensors_per_row;
+    int g = B;
+#if MGX_EXPERIMENTS
+    static const int forced = [] { const char* e = getenv("MGX_ATTN_BGROUP"); return e ? atoi(e) : 0; }();   // experiment knob
+    if (forced > 0 && B % forced == 0) return forced;
+#endif
+    while (g > 1 && (g * per_row > 110e6 || B % g != 0)) --g;
+    return g;
+}
+
+// The launchers of the backward kernels, one file each (rel_attn_bwd.hip plans the call); `grid` is the plan's (b,h) x 128-row-block grid.
+// rel_attn_dkv32.hip: dK / dV with 32 keys per wave (any L % 32 == 0)
+void dkv32_launch(const uint16_t* qkv, const void* EfA, const uint32_t* padbits, const uint16_t* dctx, const float* nlse2,
+                  const float* ndelta, uint16_t* dqkv, uint16_t* dst, dim3 grid, int L, int d, int bg, void* stream);
+// rel_attn_dq_lite.hip: dQ from the stored dS tiles
+void dq_lite_launch(const uint16_t* qkv, const void* EfT, const uint16_t* dst, uint16_t* dqkv, dim3 grid, int L, int d, int bg,
+                    void* stream);
+// rel_attn_de_tiles.hip: dE from the stored dS tiles.  The grouping belongs to the call's plan; the launch can only fail on the deterministic-mode scratch
+struct DeTilesPlan { bool dealt /* to the XCDs, or laid out in sequence */; int rows /* per group */, ngroups; long wg_per_group, grid; };
+DeTilesPlan de_tiles_plan(int B, int L, int d, int bg);
+int de_tiles_launch(const uint16_t* qkv, const uint16_t* dst, float* dEr, const DeTilesPlan& p, int L, int d, void* stream);
+// rel_attn_bwd_recompute.hip: dQ and dE by recomputation (cross-checks; nothing in training calls them)
+void dq_recompute_launch(const uint16_t* qkv, const void* EfA, const void* EfT, const uint32_t* padbits, const uint16_t* dctx,
+                         const float* lse, const float* delta, uint16_t* dqkv, dim3 grid, int L, int d, int bg, void* stream);
+void de_recompute_launch(const uint16_t* qkv, const uint16_t* Er, const uint32_t* padbits, const uint16_t* dctx, const float* lse,
+                         const float* delta, float* dEr, int B, int L, int d, void* stream);
 // rel_attn_dkv64.hip: dK / dV with 64 keys per wave and the generated asm main loop (L % 128 == 0)
 int dkv64_launch(const uint16_t* qkv, const void* EfA, const uint32_t* padbits, const uint16_t* dctx, const float* nlse2,
                  const float* ndelta, uint16_t* dqkv, uint16_t* dst, int B, int L, int d, int bg, void* stream);

@@ -35,9 +35,6 @@
 
 using namespace relattn;
 
-#ifndef MGX_EXPERIMENTS
-#define MGX_EXPERIMENTS 0   // 1 (experiment builds only): environment knobs that change which kernel runs / its residency, and the two
-#endif                      // alternative forward kernels of tools/experiments/.  The product library reads no environment variable here.
 // (round 3 experiment, removed in round 4: the Q.Er^T product one step ahead of its tile -- band read at the top of the step, the
 //  product's MFMAs under the softmax -- ran 0.567-0.569 ms against 0.562-0.563 at cfg2 batch 64: with three waves per SIMD the
 //  shorter per-wave chain buys nothing; profiles/README.md)
@@ -369,18 +366,6 @@ static void set_fwd_attrs() {
 
 extern "C" size_t mgx_rel_attn_fwd_workspace(int L) { return L > 0 ? er_frag_bytes(L) : 0; }
 
-// batch rows per grid group: the largest divisor of B whose q/k/v/ctx bytes stay near 100 MB (see the kernel)
-static int batch_group(int B, int L, int d) {
-    const double per_row = (double)L * d * 2 * 4;
-    int g = B;
-#if MGX_EXPERIMENTS
-    static const int forced = [] { const char* e = getenv("MGX_ATTN_BGROUP"); return e ? atoi(e) : 0; }();   // experiment knob
-    if (forced > 0 && B % forced == 0) return forced;
-#endif
-    while (g > 1 && (g * per_row > 110e6 || B % g != 0)) --g;
-    return g;
-}
-
 static int fwd_common_checks(const char* who, const void* ws, size_t ws_bytes, int B, int L, int d, int M) {
     MGX_REQUIRE(B > 0 && L > 0 && d > 0 && d % 64 == 0 && L % 32 == 0 && M >= L, MGX_ERR_SHAPE,
                 "%s: need d%%64==0, L%%32==0, M>=L (got B=%d L=%d d=%d M=%d)", who, B, L, d, M);
@@ -397,7 +382,7 @@ extern "C" int mgx_rel_attn_fwd(const uint16_t* qkv, const uint16_t* E, const ui
     if (int rc = fwd_common_checks("mgx_rel_attn_fwd", workspace, ws_bytes, B, L, d, M)) return rc;
     set_fwd_attrs();
     launch_er_frag(E + (size_t)(M - L) * 64, (u32x4*)workspace, nullptr, L, (hipStream_t)stream);
-    const int bg = batch_group(B, L, d);
+    const int bg = batch_group(B, L, d, 4);                 // q, k, v, ctx
 #if MGX_EXPERIMENTS
     // experiment builds only (`_build.py --variant NAME --experiments`, tools/experiments/), all measured slower: MGX_ATTN_FWD64 = 3 the
     // 64-rows-per-wave kernel with the generated asm sweep (rel_attn_fwd64.hip; L % 128 == 0, L <= 8192), 2 the ping-pong kernel

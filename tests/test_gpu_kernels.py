@@ -312,7 +312,10 @@ def test_adam_matches_torch():
                                               (3, 96, 192, 96, 1), (5, 32, 64, 40, 0),
                                               # long sweeps with L % 128 == 32: every main loop of dq_lite / dK/dV plus their tails,
                                               # nine diagonal groups of de_tiles with a ragged last one
-                                              (1, 1056, 64, 1056, 1), (2, 800, 64, 1024, 0)])
+                                              (1, 1056, 64, 1056, 1), (2, 800, 64, 1024, 0),
+                                              # B % 8 == 0: the dE groups dealt to the XCDs (one batch row each), a ragged second
+                                              # diagonal group, the 32-key dK/dV kernel, E longer than L
+                                              (8, 160, 64, 192, 1)])
 def test_rel_attn_bwd_matches_oracle_autograd(B, L, d, M, padcase):
     """dq/dk/dv/dE of the backward kernels (dK/dV storing dS, dQ and dE from the stored tiles) vs autograd through the oracle
     (fp32, same bf16 inputs)."""

@@ -2,7 +2,7 @@
     python -m musicgeneration_amd._build --variant dkvstamp -DMGX_DKV_STAMP        (here, cross-compiles)
     MGX_LIB_PATH=musicgeneration_amd/libmgx_dkvstamp.so python tools/dkv_stamp.py [--B 32]   (GPU box)
 Reads the s_memtime sums lane 0 of every wave leaves in its first dk row and prints, per key-block rank, cycles per step split at
-the stamps of rel_attn_bwd.hip (DKV_STAMP)."""
+the stamps of rel_attn_dkv32.hip (DKV_STAMP)."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
 """MFMA spacing of the dK/dV main loops, before / after (no GPU needed):
-   (a) the hipcc-scheduled two-step main loop of the 32-key kernel (rel_attn_bwd.hip, from `hipcc -save-temps`),
+   (a) the hipcc-scheduled two-step main loop of the 32-key kernel (rel_attn_dkv32.hip, from `hipcc -save-temps`),
    (b) one main body of the generated 64-key loop (csrc/rel_attn_dkv64_loop.inc).
 For each: instructions per MFMA, the histogram of gap lengths (non-MFMA instructions between consecutive MFMAs), runs of back-to-back
 MFMAs, and the first gaps verbatim.   python tools/mfma_spacing.py > profiles/r05_isa_mfma_spacing.txt"""
@@ -52,9 +52,9 @@ def report(name, body, show=3):
 # (a) hipcc
 with tempfile.TemporaryDirectory() as td:
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT}/include", f"-I{ROOT}/musicgeneration_amd/csrc", "-Wno-unused-value",
-           "-Wno-unused-result", "-c", "-x", "hip", f"{ROOT}/musicgeneration_amd/csrc/rel_attn_bwd.hip", "-o", "bwd.o", "-save-temps"]
+           "-Wno-unused-result", "-c", "-x", "hip", f"{ROOT}/musicgeneration_amd/csrc/rel_attn_dkv32.hip", "-o", "dkv32.o", "-save-temps"]
     subprocess.run(cmd, cwd=td, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    lines = open(os.path.join(td, "rel_attn_bwd-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
+    lines = open(os.path.join(td, "rel_attn_dkv32-hip-amdgcn-amd-amdhsa-gfx950.s")).read().split("\n")
 k0 = next(i for i, l in enumerate(lines) if l.startswith("_Z19rel_attn_dkv_kernel"))
 k1 = next((i for i in range(k0 + 1, len(lines)) if re.match(r"^[A-Za-z_][\w$.]*:\s*(;.*)?$", lines[i]) and not lines[i].startswith(".L")), len(lines))
 labels = {m.group(1): i for i in range(k0, k1) if (m := re.match(r"^(\.LBB\d+_\d+):", lines[i]))}

@@ -2,7 +2,7 @@
 # What a dq_lite step is made of: builds of the kernel with one part compiled out (timing only, the results are wrong).
 #   here (no GPU):  bash tools/peel_dq_lite.sh build      -> musicgeneration_amd/libmgx_dqlpeel<mask>.so for every mask below
 #   GPU box:        bash tools/peel_dq_lite.sh run [B]     -> one line per build: dq_lite ms (tools/attn_bench.py --parts 4)
-# masks (MGX_DQL_PEEL, rel_attn_bwd.hip): 1 dS^T patch stores | 2 three quarters of the band stores | 4 half of dS K |
+# masks (MGX_DQL_PEEL, rel_attn_dq_lite.hip): 1 dS^T patch stores | 2 three quarters of the band stores | 4 half of dS K |
 #   8 half of dS_rel ErT | 16 K / ErT ring refills (the step then only streams dS) | 31 everything
 MASKS="0 1 2 4 8 16 31"
 if [ "$1" = build ]; then
