@@ -204,7 +204,11 @@ int mgx_cast_bf16(const float* p, uint16_t* shadow, size_t n, void* stream);
 /* ---- K2/K5/K7/K8: C = act(A @ W^T + bias)                         layers.py:71-84,108,157-158; network.py:39
  * A bf16 [M,K] row-major, W bf16 [N,K] row-major (torch.nn.Linear layout), bias f32 [N] or NULL,
  * C bf16 [M,N].  act: 0 none, 1 ReLU.  K % 64 == 0, N % 4 == 0 (pad the weight rows, as the
- * vocabulary projection does); M arbitrary (edge tiles are masked).   */
+ * vocabulary projection does); M arbitrary (edge tiles are masked).
+ * Epilogue contract, the same in every kernel family (tests/test_gpu_gemm_kernels.py): the sum is accumulated in fp32, the bias
+ * is added and the ReLU applied IN FP32, then the value is rounded to bf16 ONCE, to nearest even.  The ReLU PROPAGATES NaN:
+ * a NaN pre-activation of either sign gives NaN (a diverged run stays recognisable), +inf gives +inf, -inf and -0 give +0.
+ * Nothing outside C's M x N elements is written, nothing outside A, W, bias is read.                                    */
 int mgx_linear_fwd(const uint16_t* A, const uint16_t* W, const float* bias, uint16_t* C,
                    int M, int N, int K, int act, void* stream);
 
@@ -237,7 +241,11 @@ int mgx_decode_embed_linear_frag(const int32_t* tok, const float* table, const f
  * relu_y <= 0 (the backward of a ReLU fused into the producer of this layer's input); if addend
  * (bf16 [M,K]) is given it is added last -- the gradient arriving over the residual connection
  * (layers.py:155,160: out = LN(x + branch(x))) joins the branch's input gradient without a separate pass.
- * N % 8 == 0, K % 8 == 0.                                                                         */
+ * N % 8 == 0, K % 8 == 0.
+ * Epilogue contract, the same in every kernel family: the fp32 product is ROUNDED to bf16 (nearest even); the mask KEEPS an
+ * element iff relu_y > 0 as an IEEE comparison (so +0, -0, negative values, -inf and NaN of either sign zero it, the smallest
+ * subnormal and +inf keep it) and writes +0 otherwise; the addend is added to that bf16 value in fp32 and the sum is rounded
+ * to bf16 ONCE MORE.  With no addend the output is the (masked) first rounding.                                          */
 int mgx_linear_dx(const uint16_t* dY, const uint16_t* W, const uint16_t* relu_y, const uint16_t* addend,
                   uint16_t* dX, int M, int N, int K, void* stream);
 /* gW f32 [N,K] += dY^T @ X (dY bf16 [M,N], X bf16 [M,K]); gb f32 [N] += column sums of dY (or NULL).
@@ -245,8 +253,8 @@ int mgx_linear_dx(const uint16_t* dY, const uint16_t* W, const uint16_t* relu_y,
 int mgx_linear_dw(const uint16_t* dY, const uint16_t* X, float* gW, float* gb,
                   int M, int N, int K, void* stream);
 /* ABI 18: which kernel family mgx_linear_fwd (kind 0: C [M,N], reduction K) or mgx_linear_dx (kind 1 / 2 / 3: no epilogue
- * operand / ReLU mask / residual addend; dX [M,K], reduction N) launches for this shape on `stream` -- no launch, no device
- * access.  For tests and profiles: which of the binary's GEMM kernels a measured or checked call really ran.              */
+ * operand / ReLU mask / residual addend; kind 4: both, which always takes the 128 x 128 kernel; dX [M,K], reduction N)
+ * launches for this shape on `stream` -- no launch, no device access.  For tests and profiles: which of the binary's GEMM kernels a measured or checked call really ran.              */
 #define MGX_GEMM_SKINNY 0    /* M <= 32: weight-streaming kernel */
 #define MGX_GEMM_TILE128 1   /* 128 x 128 tiles, four waves */
 #define MGX_GEMM_RING8 2     /* 256 x 256 tiles, persistent LDS-DMA ring, eight waves */

@@ -81,10 +81,10 @@ extern "C" int mgx_linear_dx(const uint16_t* dY, const uint16_t* W, const uint16
 
 // Which kernel family a forward / dX call of this shape takes on `stream` (mgx.h: mgx_linear_kernel_id; tests assert that the
 // bench-shape calls they check really run the ring kernels of THIS binary): the decision the two entry points above switch on.
-// kind 0: forward; 1 / 2 / 3: dX with no epilogue operand / a ReLU mask / a residual addend.
+// kind 0: forward; 1 / 2 / 3 / 4: dX with no epilogue operand / a ReLU mask / a residual addend / both.
 extern "C" int mgx_linear_kernel_id(int kind, int M, int N, int K, void* stream) {
-    MGX_REQUIRE(kind >= 0 && kind <= 3 && M > 0 && N > 0 && K > 0, MGX_ERR_SHAPE, "mgx_linear_kernel_id: kind 0..3, positive sizes");
-    return (kind == 0 ? fwd_route(M, N, K, stream) : dx_route(M, N, K, kind == 2, kind == 3, stream)).family;
+    MGX_REQUIRE(kind >= 0 && kind <= 4 && M > 0 && N > 0 && K > 0, MGX_ERR_SHAPE, "mgx_linear_kernel_id: kind 0..4, positive sizes");
+    return (kind == 0 ? fwd_route(M, N, K, stream) : dx_route(M, N, K, kind == 2 || kind == 4, kind == 3 || kind == 4, stream)).family;
 }
 
 // ---- weight gradients -----------------------------------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 // linear_dw_ring_kernel) and, round 5, four waves with 128 x 128 wave tiles whose main loops are generated gfx950 assembly owning all
 // 256 accumulators of a wave (linear_ring4_kernel, linear_dw_ring4_kernel; gen_gemm_asm.py).  All produce forward / dX results
 // bit-identical to the 128 x 128 kernels' (linear_tile128.hip).  Diagnostic builds (tools/README.md): MGX_RING_PEEL, MGX_RING_STAMP,
-// MGX_DW4_TIMES, MGX_GEMM_DIAG.
+// MGX_DW4_TIMES, MGX_GEMM_DIAG.  All families keep the epilogue contract of mgx.h (bias and ReLU in fp32 before the one rounding, a NaN
+// stays a NaN; dX: round, mask, add, round): tests/test_gpu_gemm_kernels.py.
 #include "linear_common.hpp"
 
 using namespace relattn;
@@ -49,12 +50,10 @@ MGX_DEV int imgH_off(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 
 // through a 4 KB swizzled patch (32 rows x 128 B, 16-byte chunk c of row r at chunk c ^ (r & 7)): every global store
 // instruction writes 8 full 128-byte row segments.  bias / ReLU on the accumulator side; ReLU-backward mask and residual
 // addend on the row-major side (coalesced loads).  The block lies inside the matrix: 16 unconditional stores.
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-// max(x, 0) on a packed bf16 pair: as 16-bit integers a negative bf16 (-0 included) is negative and a positive one keeps its order
-// (v_pk_max_i16) -- the same result as v_max_f32 before the conversion, one instruction per pair instead of two per element
-MGX_DEV uint32_t relu_bf16x2(uint32_t p) {
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p), (s16x2)(0)));
-}
+// ReLU on the fp32 side, before the conversion (relu_f32, mgx_common.hpp: one v_maximum3_f32 per element, NaN stays NaN).  Until
+// round 15 it was a 16-bit integer maximum on the packed bf16 pair, half an instruction per element -- which kept a NaN with a clear
+// sign bit and turned one with the sign bit set into 0, where the 128 x 128 kernels' fmaxf turned both into 0.
+MGX_DEV uint32_t pack_relu_bf16x2(float lo, float hi) { return pack_bf16x2(relu_f32(lo), relu_f32(hi)); }
 // FWD: bias / ReLU (forward projection); !FWD: ReLU-backward mask / residual addend (dX).  The variants a kernel cannot take are
 // compiled out and `act` selects between two straight-line bodies: the epilogue used to be ~1,500 instructions per wave (per-element
 // v_max + v_cndmask on the runtime `act`, both operand paths) -- 5.5 K cycles per tile with the MFMA pipe idle, 17 % of a K = 512
@@ -90,9 +89,9 @@ MGX_DEV void store_wave_block(uint16_t* __restrict__ C, const uint16_t* __restri
         for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
-                uint32_t p0 = pack_bf16x2(acc[rt][ct][4 * g4 + 0], acc[rt][ct][4 * g4 + 1]);
-                uint32_t p1 = pack_bf16x2(acc[rt][ct][4 * g4 + 2], acc[rt][ct][4 * g4 + 3]);
-                if (RELU) { p0 = relu_bf16x2(p0); p1 = relu_bf16x2(p1); }
+                const f32x16& a = acc[rt][ct];
+                const uint32_t p0 = RELU ? pack_relu_bf16x2(a[4 * g4 + 0], a[4 * g4 + 1]) : pack_bf16x2(a[4 * g4 + 0], a[4 * g4 + 1]);
+                const uint32_t p1 = RELU ? pack_relu_bf16x2(a[4 * g4 + 2], a[4 * g4 + 3]) : pack_bf16x2(a[4 * g4 + 2], a[4 * g4 + 3]);
                 *(u32x2*)(wr + (((4 * ct + g4) ^ sw) << 4)) = u32x2{p0, p1};
             }
     };
@@ -483,9 +482,10 @@ MGX_DEV void store_wave_block4(uint16_t* __restrict__ C, const uint16_t* __restr
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4) {
                         const f32x16& a = acc[rt][2 * half + ct];
-                        uint32_t p0 = pack_bf16x2(a[4 * g4 + 0] + b[ct][g4].x, a[4 * g4 + 1] + b[ct][g4].y);
-                        uint32_t p1 = pack_bf16x2(a[4 * g4 + 2] + b[ct][g4].z, a[4 * g4 + 3] + b[ct][g4].w);
-                        if (RELU) { p0 = relu_bf16x2(p0); p1 = relu_bf16x2(p1); }
+                        const float v0 = a[4 * g4 + 0] + b[ct][g4].x, v1 = a[4 * g4 + 1] + b[ct][g4].y;
+                        const float v2 = a[4 * g4 + 2] + b[ct][g4].z, v3 = a[4 * g4 + 3] + b[ct][g4].w;
+                        const uint32_t p0 = RELU ? pack_relu_bf16x2(v0, v1) : pack_bf16x2(v0, v1);
+                        const uint32_t p1 = RELU ? pack_relu_bf16x2(v2, v3) : pack_bf16x2(v2, v3);
                         *(u32x2*)(wr + (((4 * ct + g4) ^ sw) << 4)) = u32x2{p0, p1};
                     }
             };

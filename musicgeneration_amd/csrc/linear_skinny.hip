@@ -50,7 +50,7 @@ MGX_DEV void skinny_store(const f32x16& acc, const SkinnyLane& s, const float* _
         const int m = m4 + k;
         if (m < M) {
             float v = part[0][n][m] + part[1][n][m] + part[2][n][m] + part[3][n][m] + bv;
-            if (act == 1) v = fmaxf(v, 0.f);
+            if (act == 1) v = relu_f32(v);
             C[(size_t)m * N + s.n0 + n] = f32_to_bf16(v);
         }
     }

@@ -61,7 +61,7 @@ MGX_DEV void store_tileT(uint16_t* __restrict__ C, const uint16_t* __restrict__ 
                 }
                 if (act == 1) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], 0.f);
+                    for (int k = 0; k < 4; ++k) v[k] = relu_f32(v[k]);
                 }
                 if (relu_y) {
                     const u32x2 y = *(const u32x2*)(relu_y + (size_t)m * N + n);
@@ -116,7 +116,7 @@ MGX_DEV void store_tile_lds(uint16_t* __restrict__ C, const uint16_t* __restrict
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     v[k] = acc[rt][ct][4 * g4 + k] + bv[ct][g4][k];
-                    if (act == 1) v[k] = fmaxf(v[k], 0.f);
+                    if (act == 1) v[k] = relu_f32(v[k]);
                 }
                 *(u32x2*)(patch + l31 * EPI_STRIDE + (32 * ct + 8 * g4 + 4 * hh) * 2) =
                     u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};

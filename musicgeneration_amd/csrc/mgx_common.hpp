@@ -26,6 +26,10 @@ MGX_DEV uint32_t pack_bf16x2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, r);
 }
 MGX_DEV uint16_t f32_to_bf16(float x) { return (uint16_t)(pack_bf16x2(x, 0.f) & 0xffffu); }
+// The ReLU of every GEMM epilogue (mgx.h: "the ReLU propagates NaN"): IEEE 754-2019 maximum(v, 0) -- NaN of either sign stays NaN,
+// -0 and -inf become +0 -- one v_maximum3_f32.  fmaxf(v, 0.f) is maximumNumber: it turns a NaN pre-activation into 0, and a
+// diverged run goes on with finite numbers.
+MGX_DEV float relu_f32(float v) { return __builtin_elementwise_maximum(v, 0.f); }
 
 MGX_DEV void unpack8(const u32x4& w, float* f) {
     f[0] = bf16lo(w.x); f[1] = bf16hi(w.x); f[2] = bf16lo(w.y); f[3] = bf16hi(w.y);

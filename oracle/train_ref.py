@@ -406,6 +406,69 @@ def proj(a, w, bias=None):
     return c, S
 
 
+def relu(v) -> torch.Tensor:
+    """max(v, 0) that keeps a NaN a NaN (IEEE 754-2019 maximum); -0 and -inf give +0"""
+    v = _d(v)
+    return torch.where(v > 0, v, torch.where(torch.isnan(v), v, torch.zeros((), dtype=F64)))
+
+
+def linear_fwd(a, w, bias=None, act=0):
+    """mgx_linear_fwd before its one rounding: act(a [M, K] @ w [N, K]^T + bias) in fp64 -> (v [M, N], S = sum_k |a_k w_k| +
+    |bias|).  The kernel's output is ``bf16_round(v)`` (mgx.h: bias and ReLU in fp32, then one RNE rounding)."""
+    c, S = proj(a, w, bias)
+    return (relu(c) if act else c), S
+
+
+def linear_dx(dy, w, relu_y=None, addend=None):
+    """mgx_linear_dx: p = dy [M, N] @ w [N, K] in fp64, unrounded, S = sum_n |dy_n w_n|, and the value mgx.h promises for p:
+    the product rounded to bf16, zeroed where not relu_y > 0 (an IEEE comparison: NaN and -0 zero it), the addend added in fp32,
+    rounded once more -> (p, S, final).  ``final`` is the kernel's output to the bit wherever p and the sum are
+    fp32-representable (integer data); otherwise the tests bound the distance from ``masked p + addend``."""
+    p, S = proj(dy, _d(w).T)
+    v = bf16_round(p)
+    if relu_y is not None:
+        v = torch.where(_d(relu_y) > 0, v, torch.zeros((), dtype=F64))
+    if addend is not None:
+        v = bf16_round(v + _d(addend))
+    return p, S, v
+
+
+def linear_dw(dy, x, gw0=None, gb0=None):
+    """mgx_linear_dw / mgx_linear_dw_grouped: gW [N, K] = gw0 + dy [M, N]^T @ x [M, K], gb [N] = gb0 + column sums of dy, in fp64
+    -> (gW, gb, S_W, S_b) with S the sum of |terms|, |gw0| / |gb0| included"""
+    dy, x = _d(dy), _d(x)
+    gW, SW = dy.T @ x, dy.abs().T @ x.abs()
+    gb, Sb = dy.sum(0), dy.abs().sum(0)
+    if gw0 is not None:
+        gW, SW = gW + _d(gw0), SW + _d(gw0).abs()
+    if gb0 is not None:
+        gb, Sb = gb + _d(gb0), Sb + _d(gb0).abs()
+    return gW, gb, SW, Sb
+
+
+def on_bf16_tie(v) -> torch.Tensor:
+    """where an fp32-representable value lies exactly half way between two bf16 values (the low 16 bits of its fp32 image are
+    0x8000): RNE and every other rounding rule differ there"""
+    v = _d(v)
+    f = v.to(F32)
+    assert (f.to(F64) == v)[torch.isfinite(v)].all(), "not fp32-representable"
+    return (f.view(torch.int32) & 0xFFFF) == 0x8000
+
+
+def dw_mchunk(M, tiles, target):
+    """Python twin of dw_mchunk (csrc/linear_tile128.hip): rows per M-split of the 128 x 128 weight-gradient kernels"""
+    splits = (target + tiles - 1) // tiles
+    return ((M + splits - 1) // splits + 63) // 64 * 64
+
+
+def dw_tile_plan(M, shapes, grouped):
+    """-> (mchunk, exact path?, reduction tiles per split nm) of mgx_linear_dw (one weight, ``grouped`` False) or of the grouped
+    128 x 128 kernel for weights [(N, K), ..]: target 256 workgroups below 32 tiles, 384 from there, 480 for a group"""
+    tiles = sum(((N + 127) // 128) * ((K + 127) // 128) for N, K in shapes)
+    mchunk = dw_mchunk(M, tiles, 480 if grouped else (384 if tiles >= 32 else 256))
+    return mchunk, M % mchunk == 0, (min(M, mchunk) + 63) // 64
+
+
 def proj_floor(a, w, bias, ref, S):
     """fp32 product with the reduction reversed against fp64, + 2^-24 S (the classical unit of an fp32 accumulation)"""
     a32, w32 = torch.as_tensor(a).to(F32).flip(-1), torch.as_tensor(w).to(F32).flip(-1)
@@ -480,3 +543,85 @@ def ce_targets(rows, V, pad, seed=0):
     if rows > 8:
         t[torch.rand(rows, generator=g) < 0.1] = pad
     return t.to(torch.int32)
+
+
+# ---- the training GEMMs (tests/test_gpu_gemm_kernels.py) ------------------------------------------------------------------------
+GEMM_KINDS = ("exact", "gauss", "far")
+EXACT_OPERAND, EXACT_BIAS, EXACT_ADDEND, EXACT_GRAD = 7, 2000, 128, 1000      # magnitudes of the integer data
+
+
+def _gen(*seed):
+    return torch.Generator().manual_seed(sum((i + 1) * 7919 * int(s) for i, s in enumerate(seed)) % (2 ** 31))
+
+
+def _ints(g, lim, *shape):
+    return torch.randint(-lim, lim + 1, shape, generator=g).float()
+
+
+def gemm_operands(kind, M, N, R, seed=0):
+    """a [M, R], b [N, R] (both reduction-contiguous; bf16) of one product c[m, n] = sum_r a[m, r] b[n, r]:
+      exact  integers of magnitude <= 7 (exact in bf16; any partial sum in any order is an integer below 2^24 as long as S is:
+             fp32 accumulation is then exact whatever its order).  Planted (R >= 6): a[0] = 7 on r < 6, else 0; b[0] = 7 on r < 5,
+             6 at r = 5 -> c[0, 0] = 287, between the bf16 neighbours 286 and 288: a tie, and >= 256
+      gauss  a ~ N(0, 1), b ~ N(0, 1 / R)
+      far    rows far from zero: a[m] = an offset of +-16 .. 60 plus N(0, 1/16); b[n] = u_n * (+1, -1, +1, ..) plus N(0, 1/400),
+             so the offsets cancel in the sum and S >> |c|"""
+    g = _gen(M, N, R, seed, GEMM_KINDS.index(kind))
+    if kind == "exact":
+        a, b = _ints(g, EXACT_OPERAND, M, R), _ints(g, EXACT_OPERAND, N, R)
+        if R >= 6:
+            a[0], b[0] = 0.0, 0.0
+            a[0, :6], b[0, :5], b[0, 5] = 7.0, 7.0, 6.0
+    elif kind == "gauss":
+        a, b = torch.randn(M, R, generator=g), torch.randn(N, R, generator=g) / R ** 0.5
+    elif kind == "far":
+        off = torch.randint(16, 61, (M, 1), generator=g).float() * torch.where(torch.arange(M)[:, None] % 2 == 0, 1.0, -1.0)
+        a = off + 0.25 * torch.randn(M, R, generator=g)
+        alt = torch.where(torch.arange(R) % 2 == 0, 1.0, -1.0)
+        b = torch.randn(N, 1, generator=g) * alt + 0.05 * torch.randn(N, R, generator=g)
+    else:
+        raise ValueError(kind)
+    return a.to(BF), b.to(BF)
+
+
+def gemm_bias(kind, N, seed=0):
+    """f32 [N]: integers of magnitude <= 2000 (0 in column 0, which holds the planted tie), or N(0, 1)"""
+    g = _gen(N, seed, 11)
+    if kind == "exact":
+        b = _ints(g, EXACT_BIAS, N)
+        b[0] = 0.0
+        return b
+    return torch.randn(N, generator=g)
+
+
+def gemm_addend(kind, M, K, seed=0):
+    """bf16 [M, K]: integers of magnitude <= 128 (1 at [0, 0]: the planted 287 rounds to 288 and 288 + 1 is a tie again), or N(0, 1)"""
+    g = _gen(M, K, seed, 12)
+    if kind == "exact":
+        a = _ints(g, EXACT_ADDEND, M, K)
+        a[0, 0] = 1.0
+        return a.to(BF)
+    return torch.randn(M, K, generator=g).to(BF)
+
+
+def gemm_grad0(kind, *shape, seed=0):
+    """f32 start value of a gW / gb slot: integers of magnitude <= 1000, or N(0, 1)"""
+    g = _gen(*shape, seed, 13)
+    return _ints(g, EXACT_GRAD, *shape) if kind == "exact" else torch.randn(*shape, generator=g)
+
+
+MASK_SPECIALS = (0x0000, 0x8000, 0x0001, 0x0080, 0xBC00, 0x7F80, 0xFF80, 0x7FC0, 0xFFC0)
+MASK_KEPT = (False, False, True, True, False, True, False, False, False)
+
+
+def relu_mask(M, K, seed=0):
+    """bf16 [M, K] mask operand of mgx_linear_dx: N(0, 1) with a quarter of the elements exactly +0 (what a ReLU really leaves),
+    [0, 0] = 1 (the planted tie is kept) and, from [0, 1] on, MASK_SPECIALS: +0, -0, the smallest subnormal, the smallest
+    normal, a small negative, +inf, -inf, NaN of both signs (K >= 16; kept iff > 0 as an IEEE comparison: MASK_KEPT)"""
+    g = _gen(M, K, seed, 14)
+    y = torch.randn(M, K, generator=g)
+    y = torch.where(torch.rand(M, K, generator=g) < 0.25, torch.zeros(()), y).to(BF)
+    y[0, 0] = 1.0
+    if K >= 16:
+        y.view(torch.int16)[0, 1:1 + len(MASK_SPECIALS)] = torch.tensor(MASK_SPECIALS, dtype=torch.int32).to(torch.int16)
+    return y

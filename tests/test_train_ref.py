@@ -262,3 +262,95 @@ def test_dropout_twin_constants_hash_words_and_keep_rate():
         assert abs(keep - (1 - thr / 65536)) < 4 * math.sqrt(0.25 / (1 << 20)) + 1e-6, (p, keep)
     assert (T.drop_mult(0.0, 42, 64) == 1).all()
     assert (T.drop_mult(0.5, 42, 1 << 12)[:64] == T.drop_mult(0.5, 42, 64)).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the training GEMMs (tests/test_gpu_gemm_kernels.py)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", T.GEMM_KINDS)
+def test_gemm_references_are_autograd_of_relu_linear_in_float64(kind):
+    """linear_fwd / linear_dx / linear_dw against torch autograd of relu(F.linear(x, w, b)) on the same values in fp64: the mask of
+    the dX is the forward's output, the addend a gradient arriving beside it"""
+    M, N, K = 37, 24, 64
+    x, w = T.gemm_operands(kind, M, N, K)
+    b = T.gemm_bias(kind, N)
+    xd, wd, bd = (t.double().requires_grad_(True) for t in (x, w, b))
+    y = torch.relu(torch.nn.functional.linear(xd, wd, bd))
+    v, S = T.linear_fwd(x, w, b, 1)
+    assert torch.equal(v, y.detach()) and (S >= v.abs()).all()
+    lin, _ = T.linear_fwd(x, w, b, 0)
+    assert torch.equal(lin, torch.nn.functional.linear(xd, wd, bd).detach())
+    dy = T.gemm_addend(kind, M, N, seed=3)                                    # any bf16 [M, N]
+    y.backward(dy.double())
+    dz = dy.double() * (y.detach() > 0)                                       # the gradient below the ReLU
+    # dX of this layer is dz @ w; the kernel applies a mask to its OUTPUT, so check the two pieces separately
+    p, Sp, final = T.linear_dx(dz.to(T.BF), w)                                # (dz is bf16-exact: dy or 0)
+    assert torch.allclose(p, xd.grad, rtol=1e-13, atol=1e-13) and (Sp >= p.abs() * (1 - 1e-12)).all()
+    assert torch.equal(final, T.bf16_round(p))
+    mask = T.relu_mask(M, K)
+    add = T.gemm_addend(kind, M, K, seed=4)
+    _, _, fin2 = T.linear_dx(dz.to(T.BF), w, mask, add)
+    want = T.bf16_round(torch.where(mask.double() > 0, T.bf16_round(p), torch.zeros((), dtype=T.F64)) + add.double())
+    assert torch.equal(fin2, want)
+    gw0, gb0 = T.gemm_grad0(kind, N, K), T.gemm_grad0(kind, N)
+    gW, gb, SW, Sb = T.linear_dw(dz.to(T.BF), x, gw0, gb0)
+    assert torch.allclose(gW - gw0.double(), wd.grad, rtol=1e-13, atol=1e-12) and torch.allclose(gb - gb0.double(), bd.grad, rtol=1e-13, atol=1e-12)
+    assert (SW >= gW.abs() * (1 - 1e-12)).all() and (Sb >= gb.abs() * (1 - 1e-12)).all()
+
+
+def test_relu_reference_propagates_nan_and_bf16_round_is_torchs_cast_on_ties():
+    v = torch.tensor([float("nan"), -float("nan"), float("inf"), -float("inf"), -0.0, 0.0, -3.0, 2.5], dtype=T.F64)
+    r = T.relu(v)
+    assert torch.isnan(r[:2]).all() and r[2] == float("inf") and (r[3:7] == 0).all() and r[7] == 2.5
+    # ties: 257 -> 256 (even mantissa below), 259 -> 260, 287 -> 288, 289 -> 288, -257 -> -256; 2^-133 * 1.5 (a subnormal tie) -> 2^-132
+    t = torch.tensor([257.0, 259.0, 287.0, 289.0, -257.0, 1.5 * 2.0 ** -133, 258.0, 0.0], dtype=T.F64)
+    assert T.on_bf16_tie(t).tolist() == [True, True, True, True, True, True, False, False]
+    assert T.bf16_round(t).tolist() == [256.0, 260.0, 288.0, 288.0, -256.0, 2.0 ** -132, 258.0, 0.0]
+    assert torch.equal(T.bf16_round(t), t.float().bfloat16().double())
+    # every bf16 tie between 256 and 1024, against round-half-even done in integers
+    ints = torch.arange(256, 1024, dtype=T.F64)
+    ulp = torch.where(ints < 512, 2.0, 4.0).double()
+    q = ints / ulp
+    want = torch.where(q - q.floor() == 0.5, 2 * torch.round(q / 2), torch.round(q)) * ulp      # torch.round is half-even on x.5
+    assert torch.equal(T.bf16_round(ints), want) and torch.equal(T.on_bf16_tie(ints), q - q.floor() == 0.5)
+
+
+@pytest.mark.parametrize("M,N,R", ((33, 4, 64), (129, 132, 192), (8, 8, 8), (128, 128, 16384 * 7)))
+def test_gemm_builders_preconditions(M, N, R):
+    """what tests/test_gpu_gemm_kernels.py assumes of its inputs, from the references alone"""
+    a, b = T.gemm_operands("exact", M, N, R)
+    bias = T.gemm_bias("exact", N)
+    for t, lim in ((a, T.EXACT_OPERAND), (b, T.EXACT_OPERAND), (bias, T.EXACT_BIAS)):
+        assert (t.double() == t.double().round()).all() and t.double().abs().max() <= lim
+    v, S = T.linear_fwd(a, b, bias, 0)
+    assert S.max() < 2 ** 24 and (v == v.round()).all()                       # every partial sum is an integer below 2^24
+    assert v[0, 0] == 287 and T.on_bf16_tie(v)[0, 0] and T.bf16_round(v)[0, 0] == 288
+    add = T.gemm_addend("exact", M, N)
+    assert add.double().abs().max() <= T.EXACT_ADDEND and add[0, 0] == 1 and T.on_bf16_tie(T.bf16_round(v) + add.double())[0, 0]
+    g0 = T.gemm_grad0("exact", N, 8)
+    assert g0.abs().max() <= T.EXACT_GRAD and (g0 == g0.round()).all() and g0.dtype == torch.float32
+    # weight gradient of the same integers over R rows: |gW0| + 49 R stays below 2^24 up to the largest M of the GPU tests
+    assert T.EXACT_GRAD + T.EXACT_OPERAND ** 2 * 16384 * 7 < 2 ** 24
+    if M * N >= 64 and R <= 512:
+        assert (v.abs() >= 256).any() and T.on_bf16_tie(torch.relu(v)).any()
+    # far: S >> |ref| for most elements
+    a, b = T.gemm_operands("far", M, N, R)
+    v, S = T.linear_fwd(a, b, None, 0)
+    assert (S / v.abs().clamp(min=1e-300)).median() > 20
+    # the mask operand: both sides of zero, exact zeros, and the special values where they are promised
+    y = T.relu_mask(M, max(N, 16))
+    yd = y.double()
+    assert (yd > 0).any() and (yd < 0).any() and (yd == 0).sum() > 0 and y[0, 0] == 1
+    sp = y.view(torch.int16)[0, 1:1 + len(T.MASK_SPECIALS)].int() & 0xFFFF
+    assert sp.tolist() == list(T.MASK_SPECIALS) and (yd[0, 1:1 + len(T.MASK_KEPT)] > 0).tolist() == list(T.MASK_KEPT)
+
+
+def test_dw_mchunk_twin_gives_the_intended_reduction_tiles():
+    """the table of test_tile_dw_pipeline_remainders: one 128 x 128 tile, M = 16384 nm -> 256 splits of nm reduction tiles on the
+    exact path; 8 rows fewer -> the guarded path with as many"""
+    for nm in range(1, 8):
+        assert T.dw_tile_plan(16384 * nm, [(128, 128)], False) == (64 * nm, True, nm)
+        assert T.dw_tile_plan(16384 * nm - 8, [(128, 128)], False) == (64 * nm, False, nm)
+    for M in (1, 63, 64, 65):
+        assert T.dw_tile_plan(M, [(136, 200)], False) == (64, M == 64, 1)          # (65: a second split of one row)
+    assert T.dw_tile_plan(6144, [(8, 8), (72, 200), (136, 8), (128, 128), (64, 64), (256, 128), (8, 200), (136, 200)], True) == (192, True, 3)
