@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor */
-#define MGX_ABI_VERSION 21
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack */
+#define MGX_ABI_VERSION 22
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -387,6 +387,52 @@ int mgx_sample_topk_topp_window(const uint16_t* logits, int V, int ld, float tem
  * out_tokens is not read (seq gets pad_token there).                                                                    */
 int mgx_decode_reanchor(int32_t* pos_dev, int32_t* base_dev, const int32_t* out_tokens, int out_ld, int32_t* seq,
                         int n_pad, int hop, int pad_token, int B, int per_row, void* stream);
+
+/* ---- Beam search on the KV-cache decode (ABI 22).  R = B * K rows: row r = b * K + k is beam k (0 <= k < K <= 16) of prompt b.
+ * A step runs the ragged decode chain on all R rows (pos_rows int32 [R]; the K beams of a prompt always hold one position), then
+ * mgx_beam_select in place of the sampler, then mgx_kv_beam_reorder once per cache tensor; mgx_beam_backtrack ends the search.
+ *
+ * mgx_beam_select: the K best of the K * V one-token expansions of every prompt's beams.
+ *   logits bf16 [R,ld]: only columns < V are read.  V <= 1024, K <= min(16, V), temperature > 0.
+ *   score f32 [B,K], in/out: the sum of log-probabilities of beam k; -inf marks a DEAD beam (it has no expansions).
+ *   tok int32 [R], in/out: in, every beam's last token (read only for allow_table); out, slot j's chosen token.
+ *   parent int32 [R], out: the LOCAL index 0..K-1 of the beam that slot j extends.
+ *   pos_rows int32 [R]: t, the position of the step's input token, the same for the K rows of a prompt (the kernel reads row
+ *     b * K); advance != 0 adds 1 to each of the R entries.
+ *   hist_tok, hist_parent int32 [R,out_ld]: column t + 1 of row b * K + j receives slot j's token and parent; no other column
+ *     is written.  Contract (not checked on the host: t lives on the device): 0 <= t + 1 < out_ld; outside it nothing is stored.
+ *   allow_table (optional, NULL = none): the sampler's grammar mask uint32 [V, ceil(V/32)], the row taken by the beam's own
+ *     tok (clamped to 0..V-1), under the sampler's rule: disallowed logits are -inf, and a grammar row that leaves no finite
+ *     logit is ignored for that beam.
+ * Definition, all arithmetic in f32.  For a live beam k and an id v, with x = logit * (1 / temperature):
+ *     logp[k,v] = x[k,v] - logsumexp over the allowed ids of x[k,.]          (-inf for a disallowed id)
+ *     cand[k,v] = score[k] + logp[k,v]                                        (-inf for every v of a dead beam)
+ *   stochastic == 0: key = cand.   stochastic != 0: key = cand + g with g = -log(-log(min(u, 1 - 2^-24))) and u the sampler's
+ *   counter-based uniform of (seed, t, (b * K + k) * 1024 + v) -- the same hash, with that number as its row.
+ *   Slots j = 0..K-1 receive the K candidates of largest key among those with cand > -inf, in descending order of key; exactly
+ *   equal keys are ordered by the smaller flat index k * V + v.  A candidate with cand = -inf is never chosen.  Slot j gets
+ *   tok = v, parent = k and score = cand[k,v] -- the UNPERTURBED sum also when stochastic.
+ *   With only n < K finite candidates, slots n..K-1 get slot 0's token and parent and score -inf: they stay dead.  (n = 0, a
+ *   prompt whose beams are all dead: every slot keeps beam 0's token, parent 0, score -inf.)
+ *   One workgroup per prompt; a beam's own K best are found first (it cannot contribute more), so K * K candidates are merged. */
+int mgx_beam_select(const uint16_t* logits, int V, int ld, float temperature, float* score, int32_t* tok, int32_t* parent,
+                    int32_t* pos_rows, int32_t* hist_tok, int32_t* hist_parent, int out_ld, int B, int K, int advance,
+                    const uint32_t* allow_table, int stochastic, uint64_t seed, void* stream);
+/* mgx_kv_beam_reorder: every slot takes over its parent's cache rows.  src, dst: ONE cache tensor [R,heads,Lmax] whose elements
+ * are rows of row_bytes bytes -- 128 (bf16 K or V), 64 (fp8 codes) or 4 (the fp8 scales) -- in two DIFFERENT buffers, both
+ * 16-byte aligned.  With n_r = pos_rows[r] clamped to 0..Lmax (as it stands when the kernel runs: after the select's advance
+ * these are the rows the step's attention has filled) and p_r = parent[r] clamped to 0..K-1:
+ *     dst[r, h, 0..n_r) = src[(r / K) * K + p_r, h, 0..n_r)         for every r < R, h < heads, bit for bit.
+ * Rows >= n_r of dst and all of src are not written.  The grid is sized from (R, heads, Lmax), never from the device-side n.  */
+int mgx_kv_beam_reorder(void* dst, const void* src, const int32_t* parent, const int32_t* pos_rows, int R, int K, int heads,
+                        int Lmax, int row_bytes, void* stream);
+/* mgx_beam_backtrack: the token sequence of every final beam.  hist_tok, hist_parent int32 [R,out_ld] as mgx_beam_select left
+ * them after `steps` steps whose first wrote column c0_rows[r] (int32 [R], the same for the K rows of a prompt).  For row
+ * r = b * K + k:  cur = k;  for s = steps-1 .. 0:  out[r, c0 + s] = hist_tok[b * K + cur, c0 + s], then
+ * cur = hist_parent[b * K + cur, c0 + s] (clamped to 0..K-1).  out int32 [R,out_ld]: only columns c0 .. c0 + steps - 1 are written
+ * (the prompt columns are the caller's); a row with c0 < 0 or c0 + steps > out_ld is left alone.  One thread per row.           */
+int mgx_beam_backtrack(const int32_t* hist_tok, const int32_t* hist_parent, const int32_t* c0_rows, int32_t* out, int out_ld,
+                       int R, int K, int steps, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

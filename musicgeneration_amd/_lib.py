@@ -13,7 +13,7 @@ _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 
 # the ABI the SIGNATURES table below was written for (MGX_ABI_VERSION of include/mgx.h).  A left-over
 # libmgx.so of another ABI still exports the same names: calling it with this table would shift arguments.
-EXPECTED_ABI = 21
+EXPECTED_ABI = 22
 
 # name -> argtypes ; every symbol declared in include/mgx.h (restype int unless noted)
 SIGNATURES = {
@@ -63,6 +63,10 @@ SIGNATURES = {
     # ABI 21: the re-anchored decode window (base beside pos; shared or per row by a flag)
     "mgx_sample_topk_topp_window": [_vp, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp],
     "mgx_decode_reanchor": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    # ABI 22: beam search on the KV-cache decode
+    "mgx_beam_select": [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _u64, _vp],
+    "mgx_kv_beam_reorder": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "mgx_beam_backtrack": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "mgx_gather_rows": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "mgx_gru_gates": [_vp, _vp, _vp, _vp, _i, _i, _vp],
     "mgx_linear_dx": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],

@@ -321,12 +321,7 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(const uint16_t* __res
 // ---------------------------------------------------------------------------------------------------
 // sampling: one wave per row, V <= 64 * 16
 // ---------------------------------------------------------------------------------------------------
-constexpr int SMP_PER_LANE = 16;
-MGX_DEV float u01(uint64_t seed, uint32_t step, uint32_t row) {
-    uint32_t x = hash32((uint32_t)seed ^ hash32(step * 0x9e3779b9u + 0x7f4a7c15u) ^ hash32(row + 0x85ebca6bu) ^
-                        hash32((uint32_t)(seed >> 32) + 0xc2b2ae35u));
-    return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f);      // (0,1)
-}
+constexpr int SMP_PER_LANE = 16;                         // the uniform: u01 (mgx_common.hpp)
 
 template <bool PER_ROW>
 __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__ logits, int V, int ld, float inv_temp,

@@ -47,6 +47,13 @@ MGX_DEV uint32_t hash32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
     return x;
 }
+// The counter-based uniform of the sampler and of the stochastic beam select: a pure function of (seed, step, row), in (0, 1);
+// oracle.decode_ref.u01 is the same function on the host.
+MGX_DEV float u01(uint64_t seed, uint32_t step, uint32_t row) {
+    uint32_t x = hash32((uint32_t)seed ^ hash32(step * 0x9e3779b9u + 0x7f4a7c15u) ^ hash32(row + 0x85ebca6bu) ^
+                        hash32((uint32_t)(seed >> 32) + 0xc2b2ae35u));
+    return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+}
 struct DropCfg {
     uint32_t thr16;   // drop iff 16-bit random < thr16
     uint32_t mix;     // seed mix

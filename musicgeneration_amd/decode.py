@@ -2,7 +2,9 @@
 ``generate_cached`` below is the driver: ``check_args`` holds every refusal and runs before any device work, ``KVCache`` is
 the only place that knows the two cache formats, ``SubBatch`` is where ``groups`` cuts the batch and where a row's position
 lives (``pos``, on the device: one shared counter, or one per row when prompts differ in length).  ``window_schedule`` is the
-host-side plan of the re-anchored window (``window=``), the one way to generate past max_seq with the cache."""
+host-side plan of the re-anchored window (``window=``), the one way to generate past max_seq with the cache.
+``generate_beam`` (with ``check_beam_args``) is the second driver: beam search over the same step, which ends in
+ops.beam_select instead of the sampler and hands every surviving beam its parent's cache rows (ops.kv_beam_reorder)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -236,8 +238,8 @@ def prefill_batched(w: Weights, cache: KVCache, tokens: torch.Tensor, n: Optiona
         hh = ops.add_ln_fwd(f, o1, ly["g2"], ly["b2"], 1e-6)[0]
 
 
-def decode_step(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_into_out: bool) -> None:
-    """one token for the rows of ``r``; ``sampler``: keyword arguments of ops.sample_topk_topp.  In the fused chain (decode-size
+def step_logits(w: Weights, r: SubBatch, ragged: bool) -> torch.Tensor:
+    """the step of the rows of ``r`` up to the logits, bf16 [rows, vocab_padded].  In the fused chain (decode-size
     batches) every LayerNorm rides in the projection that consumes it (mgx_linear_ln_fwd) and the embedding in the first QKV
     projection (mgx_decode_embed_linear): 39 launches per token instead of 46"""
     def ln_linear(x, res, g, b, wt, bias, act):           # z = LN(x + res) and y = act(z wt^T + bias): returns (y, z)
@@ -258,8 +260,13 @@ def decode_step(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_int
         f = ops.linear_fwd(f, ly["w2"], ly["bb2"], 0)
         wn, bn = (L[i + 1]["wqkv"], L[i + 1]["bqkv"]) if i + 1 < len(L) else (w.wv_step, w.bv)
         qkv, h = ln_linear(f, o1, ly["g2"], ly["b2"], wn, bn, 0)      # the next layer's qkv; after the last layer the logits
-    ops.sample_topk_topp(qkv, w.V, r.pos, r.tok, r.out if sample_into_out else None, r.probs, advance=True, row0=r.b0,
-                         ragged=ragged, base=r.base, **sampler)
+    return qkv
+
+
+def decode_step(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_into_out: bool) -> None:
+    """one token for the rows of ``r``; ``sampler``: keyword arguments of ops.sample_topk_topp"""
+    ops.sample_topk_topp(step_logits(w, r, ragged), w.V, r.pos, r.tok, r.out if sample_into_out else None, r.probs, advance=True,
+                         row0=r.b0, ragged=ragged, base=r.base, **sampler)
 
 
 def replay_graphs(subs, steps: int, step_rows, before=None) -> None:
@@ -439,3 +446,88 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     if window is not None:                                # the cache grows to the rows the full-width call would have
         extra = min(window, total + extra) - cache_rows
     return (res, *(cache.grow(extra) if extra else cache).result()) if return_cache else res
+
+
+# ---- beam search ------------------------------------------------------------------------------------------------------------
+BEAM_MAX = 16                                             # mgx_beam_select's limit
+
+
+def check_beam_args(model, prior, length: int, beam_size: int, temperature: float, prior_lengths, kv_cache: str):
+    """every refusal of generate_beam (ValueError), on the host.  Returns (P, lens) as check_args does"""
+    top = min(BEAM_MAX, model.vocab_size)
+    if not 1 <= int(beam_size) <= top:
+        raise ValueError(f"beam_size must lie in 1 .. min({BEAM_MAX}, vocabulary) = {top}, got {beam_size}")
+    if not temperature > 0:
+        raise ValueError(f"temperature must be > 0, got {temperature}")
+    if length < 1:
+        raise ValueError(f"length must be >= 1 (a search of no steps has nothing to choose), got {length}")
+    # the prompt-length rules of ragged prompts, prior + length <= max_seq and the fit of the one batched prefill pass
+    P, lens, _, _ = check_args(model, prior, length, False, "batched", prior_lengths, kv_cache)
+    return P, lens
+
+
+def generate_beam(model, prior, length, beam_size, temperature, stochastic, seed, grammar, prior_lengths, kv_cache, use_graph,
+                  return_beams):
+    """MusicTransformer.generate_beam (documented there).  Rows r = b * K + k: beam k of prompt b.  Two caches of R rows, X and
+    Y: a step attends on one and mgx_kv_beam_reorder gathers the survivors' parents into the other, so consecutive steps
+    alternate X -> Y, Y -> X.  A graph captures fixed pointers, hence TWO steps per graph."""
+    P, lens = check_beam_args(model, prior, length, beam_size, temperature, prior_lengths, kv_cache)
+    extra, prior = prior.shape[1] - P, prior[:, :P]
+    st = model.store()
+    st.sync_shadow()
+    was_training = model.training
+    model.eval()
+    B, K, total, dev = prior.shape[0], int(beam_size), P + length, st.param.device
+    R, d, V = B * K, model.embedding_dim, model.vocab_size
+    prior_i = prior.to(torch.int32).to(dev)
+    lens_dev = torch.tensor(lens or [P] * B, dtype=torch.int32, device=dev)
+    if lens is not None:                                  # the right padding becomes pad_token, as in generate_cached
+        prior_i = torch.where(torch.arange(P, device=dev)[None, :] < lens_dev[:, None], prior_i, model.pad_token)
+    w = Weights(model, st, fused=R <= 32 and d <= 1024)
+    first = KVCache(kv_cache, B, d // 64, total, model.num_layer, dev)
+    if P > 1:                                             # positions 0..P-2 of the B prompts in one pass
+        prefill_batched(w, first, prior_i[:, :P - 1])
+    X = first._map(lambda t: t.repeat_interleave(K, 0))   # every prompt's K beams start from its prefill
+    Y = X._map(torch.zeros_like)
+    rows_b = torch.arange(B, device=dev)
+    pos = (lens_dev - 1).repeat_interleave(K).contiguous()                         # every row resumes at its last prompt token
+    tok = prior_i[rows_b, lens_dev.long() - 1].repeat_interleave(K).contiguous()
+    parent = torch.zeros(R, dtype=torch.int32, device=dev)
+    score = torch.full((B, K), float("-inf"), dtype=torch.float32, device=dev)
+    score[:, 0] = 0.0                                     # ONE live beam: duplicates of the first expansion cannot fill the beam
+    hist_tok, hist_parent = (torch.zeros(R, total, dtype=torch.int32, device=dev) for _ in range(2))
+    out = torch.full((R, total), model.pad_token, dtype=torch.int32, device=dev)
+    out[:, :P] = prior_i.repeat_interleave(K, 0)
+    hbuf, ctxbuf = (torch.empty(R, d, dtype=BF16, device=dev) for _ in range(2))
+    ws = ops.rel_attn_decode_workspace(R, total, d, dev)
+    stream = torch.cuda.Stream()
+    onX, onY = (SubBatch(0, pos, tok, out, hbuf, ctxbuf, None, c, ws, stream) for c in (X, Y))
+    allow = None
+    if grammar is not None:
+        allow = torch.as_tensor(np.ascontiguousarray(grammar).view(np.int32) if isinstance(grammar, np.ndarray) else grammar)
+        allow = allow.to(device=dev, dtype=torch.int32).contiguous()
+
+    def step(r: SubBatch, into: KVCache):                 # attend on r's cache, select, gather the parents' rows into ``into``
+        ops.beam_select(step_logits(w, r, True), V, score, tok, parent, pos, hist_tok, hist_parent, temperature=temperature,
+                        allow_table=allow, stochastic=stochastic, seed=seed)
+        c = r.cache
+        for dst, src in zip(into.k + into.v + into.kscale + into.vscale, c.k + c.v + c.kscale + c.vscale):
+            ops.kv_beam_reorder(dst, src, parent, pos, K)
+
+    step(onX, Y)                                          # the first step also warms every kernel up before capture
+    pairs = (length - 1) // 2 if use_graph and length - 1 >= 4 else 0
+    if pairs:
+        replay_graphs([onY], pairs, lambda _: (step(onY, X), step(onX, Y)))
+    for s in range(length - 1 - 2 * pairs):               # the odd last step, or every step without a graph
+        step(*((onY, X) if s % 2 == 0 else (onX, Y)))
+    ops.beam_backtrack(hist_tok, hist_parent, lens_dev.repeat_interleave(K).contiguous(), out, K, length)
+    model.train(was_training)
+    # the best beam: the largest score, the first slot among equal ones (stochastic slots are ordered by their perturbed keys)
+    slots = torch.arange(K, device=dev)[None, :]
+    best = torch.where(score == score.amax(-1, keepdim=True), slots, K).amin(-1).clamp_(max=K - 1)
+    pad = torch.nn.functional.pad                         # equal prior_lengths P < Pmax: pad_token up to Pmax + length
+    beams = pad(out, (0, extra), value=model.pad_token).view(B, K, total + extra)
+    res = (beams[rows_b, best], score[rows_b, best])
+    if return_beams:
+        res += (beams, score, pad(hist_tok, (0, extra)).view(B, K, -1), pad(hist_parent, (0, extra)).view(B, K, -1))
+    return res

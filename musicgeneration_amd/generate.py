@@ -53,7 +53,30 @@ def get_options(argv=None):
                            "--window 499 --hop 1 is the reference's threshold_len = 500 window")
     parser.add_option('--hop', dest='hop', type='int', default=0,
                       help='tokens dropped per re-anchor of --window (0 = default, max(1, W // 8))')
+    parser.add_option('-B', '--beam-size', dest='beam_size', type='int', default=0,
+                      help='beam search over the KV-cache decode with this many beams per sample (1 .. 16; 1 = greedy); 0 = off, '
+                           'sample.  Each of the -b samples is searched with its own beam and the best beam is written')
+    parser.add_option('-S', '--stochastic-beam-search', dest='stochastic_beam_search', action='store_true', default=False,
+                      help='with -B: choose the surviving beams by Gumbel-perturbed scores')
     return parser.parse_args(argv)[0]
+
+
+def _check_beam_options(o):
+    """-B / -S against the options a search does not offer, before any model or device work"""
+    if o.stochastic_beam_search and not o.beam_size:
+        raise SystemExit('-S/--stochastic-beam-search chooses the beams of a search: add -B K')
+    if not o.beam_size:
+        return
+    if not 1 <= o.beam_size <= 16:
+        raise SystemExit(f'-B/--beam-size must lie in 1 .. 16 (0 = off), got {o.beam_size}')
+    if o.window:
+        raise SystemExit('-B/--beam-size cannot be combined with --window (a search keeps every beam\'s whole cache)')
+    if o.top_k:
+        raise SystemExit('-B/--beam-size cannot be combined with --top-k (a search ranks all events; top-k filters a sampler)')
+    if o.top_p != 1.0:
+        raise SystemExit('-B/--beam-size cannot be combined with --top-p (a search ranks all events; top-p filters a sampler)')
+    if o.reference_mask:
+        raise SystemExit('-B/--beam-size cannot be combined with --reference-mask (the KV-cache decode is causal)')
 
 
 def _ragged_priors(o):
@@ -85,13 +108,14 @@ def _ragged_priors(o):
 
 def main(argv=None):
     o = get_options(argv)
+    _check_beam_options(o)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
         raise SystemExit('--reference-mask cannot be combined with --window (the KV-cache decode is causal)')
-    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window):
+    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size):
         raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
-                         '(the default sampler recomputes the window and keeps no cache)')
+                         '(or -B K; the default sampler recomputes the window and keeps no cache)')
     # with --window every branch below samples through the KV-cache decode and its re-anchored window
     cached = dict(kv_cache=o.kv_cache, window=o.window or None, hop=o.hop or None)
     ragged = _ragged_priors(o) if o.condition_files is not None else None     # checked before any model or device work
@@ -113,8 +137,17 @@ def main(argv=None):
                 m = ms(pred, torch.from_numpy(y).to(device, dtype=torch.int))
             print('Test >>>> Loss: {:6.6}, Accuracy: {}'.format(m['loss'], m['accuracy']))
     mt.test()
+
+    def search(prior, **kw):                              # -B: the best beam of every sample
+        res, scores = mt.generate_beam(prior, o.max_len, o.beam_size, temperature=o.temperature, stochastic=o.stochastic_beam_search,
+                                       kv_cache=o.kv_cache, **kw)
+        print('Beam search ({} beams): log-probabilities {}'.format(o.beam_size, [round(v, 3) for v in scores.tolist()]))
+        return res.cpu().numpy()
     if ragged is not None:
         prior, lens = ragged
+        if o.beam_size:
+            _write(o, [row[:n + o.max_len] for row, n in zip(search(prior.to(device), prior_lengths=lens), lens)])
+            return
         res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  prior_lengths=lens, **cached).cpu().numpy()
         res = [row[:n + o.max_len] for row, n in zip(res, lens)]             # without the pad tail
@@ -140,8 +173,13 @@ def main(argv=None):
             raise SystemExit('--grammar is defined for --repr remi and --repr mumidi')
         bar = Codec.feat_ranges()['bar'][0]
         prior = torch.full((o.batch_size, 1), bar, dtype=torch.long, device=device)
+        if o.beam_size:
+            _write(o, search(prior, grammar=Codec.next_token_table()))
+            return
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  grammar=Codec.next_token_table(), **cached).cpu().numpy()
+    elif o.beam_size:
+        res = search(prior)
     elif o.window:
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached).cpu().numpy()
     else:

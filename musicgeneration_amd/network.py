@@ -377,6 +377,28 @@ class MusicTransformer(torch.nn.Module):
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
                                       prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop)
 
+    @torch.no_grad()
+    def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,
+                      seed: int = 0, grammar=None, prior_lengths=None, kv_cache: str = "bf16", use_graph: bool = True,
+                      return_beams: bool = False):
+        """Beam search over the KV-cache decode: the ``beam_size`` (K, 1 .. min(16, V)) best continuations of ``length`` events
+        of every prompt of ``prior`` [B,P], each prompt searched with its own beam.  A beam's score is the sum of its events'
+        log softmax(logits / temperature) (under ``grammar``: over the allowed events, the sampler's rule).  The search starts
+        from ONE live beam per prompt (the others at -inf, as ``Event_Melody_RNN.beam_search``); every step runs the decode
+        chain on the B * K rows, keeps the K best of the K * V expansions on the device (mgx_beam_select; exact ties go to the
+        smaller k * V + v) and hands every survivor its parent's cache rows (mgx_kv_beam_reorder, between two caches), so the
+        step is graph-captured -- two steps per graph -- and nothing is read back.  ``stochastic``: survivors are chosen by
+        Gumbel-perturbed scores, a pure function of (``seed``, position, row, event); the scores carried and returned stay the
+        unperturbed sums.  With fewer than K finite candidates (a grammar that allows fewer) the spare beams are dead: score
+        -inf, their tokens copies of the best beam's.  ``prior_lengths``, ``kv_cache`` and ``grammar`` as in ``generate_cached``;
+        P + length <= max_seq, the prompt is prefilled in one batched pass.  K = 1 is greedy decoding.
+        Returns (tokens int32 [B, Pmax+length] of the best beam of every prompt, padded as ``generate_cached`` pads ragged
+        rows; scores f32 [B]).  ``return_beams`` appends all beams int32 [B, K, Pmax+length], their scores f32 [B, K] and the
+        two history tables int32 [B, K, Pmax+length]: column c of slot j holds the token chosen for that slot at column c and
+        the slot (0..K-1) of the previous column that it extends."""
+        return decode.generate_beam(self, prior, length, beam_size, temperature, stochastic, seed, grammar, prior_lengths, kv_cache,
+                                    use_graph, return_beams)
+
     def test(self):
         self.eval()
         self.infer = True

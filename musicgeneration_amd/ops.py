@@ -709,6 +709,68 @@ def decode_reanchor(pos_dev, base, out_tokens, seq, hop, pad_token, *, ragged=Fa
     return seq
 
 
+# ---- beam search on the decode path (ABI 22; contracts in include/mgx.h) ---------------------------------------------
+def _check_int32_rows(what, R, **ts):
+    for name, t in ts.items():
+        if t.dtype != torch.int32 or t.shape[0] != R or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of {R} rows, got {t.dtype} {tuple(t.shape)}")
+
+
+def beam_select(logits, V, score, tok, parent, pos_rows, hist_tok, hist_parent, temperature=1.0, allow_table=None,
+                stochastic=False, seed=0, advance=True):
+    """the K best expansions of every prompt's K beams: logits bf16 [B*K, ld], score f32 [B, K] (in/out, -inf = dead beam),
+    tok / parent / pos_rows int32 [B*K], hist_tok / hist_parent int32 [B*K, out_ld] (column pos + 1 is written)"""
+    _need_cuda(logits, score, tok, parent, pos_rows, hist_tok, hist_parent, allow_table)
+    if score.dim() != 2 or score.dtype != torch.float32 or not score.is_contiguous():
+        raise ValueError(f"beam_select: score must be contiguous float32 [B, K], got {score.dtype} {tuple(score.shape)}")
+    B, K = score.shape
+    ld = logits.shape[-1]
+    if logits.dtype != torch.bfloat16 or logits.numel() != B * K * ld or not logits.is_contiguous():
+        raise ValueError(f"beam_select: logits must be contiguous bf16 [{B * K}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    _check_int32_rows("beam_select", B * K, tok=tok, parent=parent, pos_rows=pos_rows, hist_tok=hist_tok, hist_parent=hist_parent)
+    if tok.dim() != 1 or parent.dim() != 1 or pos_rows.dim() != 1 or hist_tok.dim() != 2 or hist_parent.shape != hist_tok.shape:
+        raise ValueError("beam_select: tok, parent, pos_rows are [B*K]; hist_tok and hist_parent [B*K, out_ld] of one shape")
+    if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
+                                    or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4
+                                    or not allow_table.is_contiguous()):
+        raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
+    check(_lib.load().mgx_beam_select(ptr(logits), int(V), ld, float(temperature), ptr(score), ptr(tok), ptr(parent), ptr(pos_rows),
+                                      ptr(hist_tok), ptr(hist_parent), hist_tok.shape[1], B, K, 1 if advance else 0,
+                                      ptr(allow_table), 1 if stochastic else 0, int(seed), stream_ptr()), "mgx_beam_select")
+    return tok
+
+
+def kv_beam_reorder(dst, src, parent, pos_rows, K):
+    """dst[r, h, :n_r] = src[(r // K) * K + parent[r], h, :n_r] with n_r = pos_rows[r], for one cache tensor [R, h, Lmax, 64]
+    (bf16, or the 8-bit codes) or [R, h, Lmax] (f32: the 8-bit cache's scales); dst and src are two buffers of one shape"""
+    _need_cuda(dst, src, parent, pos_rows)
+    if dst.shape != src.shape or dst.dtype != src.dtype or dst.dim() not in (3, 4) or not (dst.is_contiguous() and src.is_contiguous()):
+        raise ValueError(f"kv_beam_reorder: dst and src must be contiguous [R, h, Lmax(, 64)] of one shape and dtype, got "
+                         f"{dst.dtype} {tuple(dst.shape)} and {src.dtype} {tuple(src.shape)}")
+    R, heads, Lmax = dst.shape[:3]
+    row_bytes = dst.element_size() * (dst.shape[3] if dst.dim() == 4 else 1)
+    if row_bytes not in (128, 64, 4) or (dst.dim() == 4 and dst.shape[3] != 64):
+        raise ValueError(f"kv_beam_reorder: rows of 64 bf16 values, 64 8-bit codes or one f32 scale, got {dst.dtype} {tuple(dst.shape)}")
+    _check_int32_rows("kv_beam_reorder", R, parent=parent, pos_rows=pos_rows)
+    if R % int(K):
+        raise ValueError(f"kv_beam_reorder: {R} rows are no multiple of the beam size {K}")
+    check(_lib.load().mgx_kv_beam_reorder(ptr(dst), ptr(src), ptr(parent), ptr(pos_rows), R, int(K), heads, Lmax, row_bytes,
+                                          stream_ptr()), "mgx_kv_beam_reorder")
+    return dst
+
+
+def beam_backtrack(hist_tok, hist_parent, c0_rows, out, K, steps):
+    """out[r, c0_r : c0_r + steps] = the tokens of final beam r, walked back through hist_parent (all int32 [R, out_ld])"""
+    _need_cuda(hist_tok, hist_parent, c0_rows, out)
+    R = out.shape[0]
+    _check_int32_rows("beam_backtrack", R, hist_tok=hist_tok, hist_parent=hist_parent, c0_rows=c0_rows, out=out)
+    if out.dim() != 2 or hist_tok.shape != out.shape or hist_parent.shape != out.shape or c0_rows.dim() != 1 or R % int(K):
+        raise ValueError("beam_backtrack: hist_tok, hist_parent and out are [R, out_ld] of one shape, c0_rows [R], R a multiple of K")
+    check(_lib.load().mgx_beam_backtrack(ptr(hist_tok), ptr(hist_parent), ptr(c0_rows), ptr(out), out.shape[1], R, int(K), int(steps),
+                                         stream_ptr()), "mgx_beam_backtrack")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # autograd glue
 #
