@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack */
-#define MGX_ABI_VERSION 22
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event */
+#define MGX_ABI_VERSION 23
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -477,6 +477,47 @@ int mgx_dropout_bf16(const uint16_t* x, uint16_t* out, size_t n, float p_drop, u
 /* dst f32 [V,cols] row idx[r] += src bf16 [n,ld] row r, columns 0..cols-1 (nn.Embedding backward).                */
 int mgx_scatter_add_rows(const int32_t* idx, const uint16_t* src, float* dst, int n, int ld, int cols, int V,
                          void* stream);
+
+/* ---- Scheduled sampling for Event_Melody_RNN (ABI 23): the free-running TRAINING forward of Event_MelodyRNN/train.py:221-245,
+ * model.generate(..., events, teacher_forcing_ratio, output_type='logit') -> network.py:144-162.  Step t + 1 of every layer
+ * depends on step t of the top layer, so the forward runs step-major: per step one mgx_gru_step_x_fwd_save per layer,
+ * mgx_dropout_bf16_at between layers, the output projection, then mgx_gru_next_event, which chooses the next input of every row.
+ * What it leaves behind is what the backward-through-time above reads; no gradient flows through the choice of a token.
+ *
+ * mgx_gru_step_x_fwd_save is mgx_gru_step_x_fwd with two more outputs, same arguments, same requirements:
+ *   gi_out, gh_out bf16 [B,3H]: the bf16-rounded x W_ih^T + b_ih and h_prev_bf16 W_hh^T + b_hh the cell consumed -- the form in
+ *   which mgx_gru_step_bwd reads gi and gh of the step.  h_next and y are bit for bit those of mgx_gru_step_x_fwd on the same
+ *   inputs (one kernel body, a compile-time switch).  Rows >= B of no output are written.                                   */
+int mgx_gru_step_x_fwd_save(const uint16_t* x, const uint16_t* Wih, const float* bih, int Kx, const uint16_t* h_prev_bf16,
+                            const float* h_prev, const uint16_t* Whh, const float* bhh, float* h_next, uint16_t* y,
+                            uint16_t* gi_out, uint16_t* gh_out, int B, int H, void* stream);
+/* mgx_dropout_bf16 on a slice of a larger buffer.  x, out: the n elements of the slice itself (16-byte aligned), which are
+ * elements index0 .. index0 + n - 1 of the buffer; n % 8 == 0, index0 % 8 == 0, 0 <= p_drop < 1.  The mask is mgx_dropout_bf16's
+ * function of (seed, index0 + i), and the seed is READ FROM DEVICE MEMORY when the kernel runs (seed_dev uint64[1]), so a
+ * captured launch does not bake it in.  Slices that tile a buffer give, bit for bit, what one mgx_dropout_bf16 call over the
+ * whole buffer gives with the same seed: that whole-buffer call on the gradient is still the backward.                    */
+int mgx_dropout_bf16_at(const uint16_t* x, uint16_t* out, size_t n, size_t index0, float p_drop, const uint64_t* seed_dev,
+                        void* stream);
+/* mgx_gru_next_event: the next input of every row, and its embedding.  One workgroup per row.
+ *   logits bf16 [B,ld]: only columns < V are read.  0 < V <= 1024, ld >= V, temperature > 0.
+ *   flag_dev int32[1], read when the kernel runs: bit 0 = this step is FORCED, bit 1 = this step is GREEDY.
+ *   events int32 [B] or NULL: the ground-truth next event of every row; NULL: no step is forced, whatever bit 0 says.
+ *   seed_dev uint64[1], read when the kernel runs; step: the host's step counter.
+ *   emb bf16 [V,Ep], Ep % 8 == 0 (the padded embedding table of mgx_gather_rows).
+ *   out: tok int32 [B], used_out int32 [B] (the same value: the running token and the record of what was fed),
+ *        x_out bf16 [B,Ep] = emb[tok], bit for bit.  Nothing else is written.
+ * Rule per row b:
+ *   forced:              tok = events[b], clamped to 0..V-1.
+ *   greedy, not forced:  the smallest id whose logit equals the row maximum (bf16 values compare exactly; -0 equals +0).  A NaN
+ *                        logit never wins and never counts as the maximum; a row without any finite logit gives id 0.
+ *   neither:             x_v = logit_v * (1 / temperature) in f32, p_v = exp(x_v - max x) (0 for a NaN logit, and for every id
+ *                        when the maximum is not finite), mass = sum p, u = the sampler's counter-based uniform of
+ *                        (seed, step, b).  tok = the first id, in id order, with p > 0 whose inclusive CDF reaches u * mass; if
+ *                        rounding leaves none, the last id with p > 0; if no id has p > 0, id 0.  The CDF is summed in fp32 in
+ *                        an order of the kernel's choosing: it is within V * 2^-23 * mass of the exact one.                 */
+int mgx_gru_next_event(const uint16_t* logits, int V, int ld, const int32_t* flag_dev, const int32_t* events, float temperature,
+                       const uint64_t* seed_dev, uint32_t step, const uint16_t* emb, int Ep, int32_t* tok, int32_t* used_out,
+                       uint16_t* x_out, int B, void* stream);
 
 #ifdef __cplusplus
 }

@@ -181,11 +181,15 @@ __global__ __launch_bounds__(256) void gru_step_fwd_kernel(const uint16_t* __res
 // Same decomposition as the training step above; all fragment loads of both projections are requested before the first MFMA
 // (one L2 round trip), the two reductions go through the same LDS buffer one after the other.  h is NOT updated in place:
 // other workgroups still read h_{t-1} as their operand, the host alternates two state buffers.
+// SAVE: the step of the free-running TRAINING forward (scheduled sampling) -- the same arithmetic, and the two rounded projections
+// are stored as well, in the layout mgx_gru_step_bwd reads gi[t] / gh[t] in.
+template <bool SAVE>
 __global__ __launch_bounds__(256) void gru_step_x_fwd_kernel(const uint16_t* __restrict__ x, const uint16_t* __restrict__ Wih,
                                                              const float* __restrict__ bih, int Kx,
                                                              const uint16_t* __restrict__ hp_bf, const float* __restrict__ h_prev,
                                                              const uint16_t* __restrict__ Whh, const float* __restrict__ bhh,
-                                                             float* __restrict__ h_next, uint16_t* __restrict__ y, int B, int H) {
+                                                             float* __restrict__ h_next, uint16_t* __restrict__ y,
+                                                             uint16_t* __restrict__ gi_out, uint16_t* __restrict__ gh_out, int B, int H) {
     __shared__ float part[4][96][33];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -287,6 +291,14 @@ __global__ __launch_bounds__(256) void gru_step_x_fwd_kernel(const uint16_t* __r
     }
     *(f32x4*)(h_next + ho) = f32x4{hv[0], hv[1], hv[2], hv[3]};
     *(u32x2*)(y + ho) = u32x2{pack_bf16x2(hv[0], hv[1]), pack_bf16x2(hv[2], hv[3])};
+    if constexpr (SAVE) {
+        const size_t go = (size_t)m * 3 * H + u0 + u4;       // m < B here
+#pragma unroll
+        for (int g = 0; g < 3; ++g) {
+            *(u32x2*)(gi_out + go + g * H) = u32x2{pack_bf16x2(giv[g][0], giv[g][1]), pack_bf16x2(giv[g][2], giv[g][3])};
+            *(u32x2*)(gh_out + go + g * H) = u32x2{pack_bf16x2(ghv[g][0], ghv[g][1]), pack_bf16x2(ghv[g][2], ghv[g][3])};
+        }
+    }
 }
 
 // NS waves split the reduction over the 3H gates.  final != 0: no cell, dh_out = dh_direct + dgh_next W_hh (the gradient of
@@ -412,6 +424,125 @@ __global__ __launch_bounds__(256) void dropout_bf16_kernel(const uint16_t* __res
     *(u32x4*)(out + g * 8) = pack8(f);
 }
 
+// The same on a slice of a larger buffer: x / out point at element index0 = 8 * g0 of it and the mask is that of the whole
+// buffer's elements index0 .. index0 + n - 1.  The seed comes from device memory (a captured launch must not bake it in).
+__global__ __launch_bounds__(256) void dropout_bf16_at_kernel(const uint16_t* __restrict__ x, uint16_t* __restrict__ out, size_t n8,
+                                                              size_t g0, DropCfg dc, const uint64_t* __restrict__ seed_dev) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n8) return;
+    if (dc.thr16) dc.mix = drop_mix(*seed_dev);              // p = 0: make_drop leaves mix = 0, and nothing reads it
+    float f[8], m[8];
+    unpack8(*(const u32x4*)(x + g * 8), f);
+    drop_mult8(dc, (uint32_t)(g0 + g), m);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] *= m[k];
+    *(u32x4*)(out + g * 8) = pack8(f);
+}
+
+// Next input of the free-running training forward (Event_MelodyRNN/network.py:151-162: _sample_event, then the teacher-forcing
+// coin): one workgroup per batch row, thread i owns the ids 4i .. 4i+3 (V <= 1024), so a prefix over threads is a prefix over ids.
+//   flag bit 0 (and events given): the ground-truth event;  bit 1: the smallest id at the row maximum;  neither: the first id
+//   whose inclusive CDF of exp(x - max x) reaches u * mass, u = u01(seed, step, row).  Then x_out[row] = emb[token].
+__global__ __launch_bounds__(256) void gru_next_event_kernel(const uint16_t* __restrict__ logits, int V, int ld,
+                                                             const int32_t* __restrict__ flag_dev, const int32_t* __restrict__ events,
+                                                             float inv_t, const uint64_t* __restrict__ seed_dev, uint32_t step,
+                                                             const uint16_t* __restrict__ emb, int Ep, int32_t* __restrict__ tok,
+                                                             int32_t* __restrict__ used_out, uint16_t* __restrict__ x_out) {
+    __shared__ float s_v[4];
+    __shared__ int s_i[4];
+    __shared__ int s_first, s_last;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int flag = flag_dev[0];
+    const float ninf = -__builtin_inff();
+    int chosen = 0;
+    if ((flag & 1) && events) {                              // uniform over the workgroup
+        const int e = events[b];
+        chosen = e < 0 ? 0 : (e >= V ? V - 1 : e);
+    } else {
+        float lg[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int id = 4 * tid + k;
+            lg[k] = id < V ? bf16_to_f32(logits[(size_t)b * ld + id]) : __builtin_nanf("");     // NaN: takes no part below
+        }
+        if (flag & 2) {
+            // (value, id) maximum under "larger value, then smaller id"; NaN never enters; -inf may (a row of -inf and finite values)
+            float bv = ninf;
+            int bi = 1 << 30, fin = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float v = lg[k];
+                if (v == v && (v > bv || (v == bv && 4 * tid + k < bi))) { bv = v; bi = 4 * tid + k; }
+                fin |= (v == v && fabsf(v) < __builtin_inff());
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            }
+            if (lane == 0) { s_v[w] = bv; s_i[w] = bi; }
+            fin = __syncthreads_or(fin);                     // also the barrier for s_v / s_i
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float ov = s_v[q];
+                const int oi = s_i[q];
+                if (q == 0 || ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+            }
+            chosen = (fin && bi < V) ? bi : 0;               // a row without any finite logit: id 0
+        } else {
+            if (tid == 0) { s_first = 1 << 30; s_last = -1; }
+            float x[4], mx = ninf;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                x[k] = lg[k] * inv_t;
+                if (x[k] == x[k]) mx = fmaxf(mx, x[k]);
+            }
+            mx = wave_max(mx);
+            if (lane == 0) s_v[w] = mx;
+            __syncthreads();
+            mx = fmaxf(fmaxf(s_v[0], s_v[1]), fmaxf(s_v[2], s_v[3]));
+            float p[4], c[4], run = 0.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float e = expf(x[k] - mx);
+                p[k] = (e == e && e < __builtin_inff()) ? e : 0.f;     // NaN logit, or a row maximum that is not finite: no mass
+                run += p[k];
+                c[k] = run;
+            }
+            float inc = run;                                 // inclusive prefix over the wave's threads
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const float up = __shfl_up(inc, o, 64);
+                if (lane >= o) inc += up;
+            }
+            __syncthreads();                                 // s_v is read above
+            if (lane == 63) s_v[w] = inc;
+            __syncthreads();
+            float base = 0.f;
+            for (int q = 0; q < w; ++q) base += s_v[q];
+            const float mass = ((s_v[0] + s_v[1]) + s_v[2]) + s_v[3];          // the last thread's inclusive prefix
+            const float target = u01(*seed_dev, step, (uint32_t)b) * mass;
+            const float excl = base + (inc - run);
+            int first = 1 << 30, last = -1;
+#pragma unroll
+            for (int k = 3; k >= 0; --k)
+                if (p[k] > 0.f) {
+                    if (last < 0) last = 4 * tid + k;
+                    if (excl + c[k] >= target) first = 4 * tid + k;
+                }
+            if (first < (1 << 30)) atomicMin(&s_first, first);
+            if (last >= 0) atomicMax(&s_last, last);
+            __syncthreads();
+            chosen = s_first < (1 << 30) ? s_first : (s_last >= 0 ? s_last : 0);
+        }
+    }
+    if (tid == 0) { tok[b] = chosen; used_out[b] = chosen; }
+    const u32x4* src = (const u32x4*)(emb + (size_t)chosen * Ep);
+    u32x4* dst = (u32x4*)(x_out + (size_t)b * Ep);
+    for (int i = tid; i < (Ep >> 3); i += 256) dst[i] = src[i];
+}
+
 // dst f32 [V,cols] row idx[r] += src bf16 [n,ld] row r   (embedding gradient; float atomics, 128-byte segments per wave)
 __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const int32_t* __restrict__ idx, const uint16_t* __restrict__ src,
                                                                float* __restrict__ dst, int n, int ld, int cols, int V) {
@@ -499,8 +630,46 @@ extern "C" int mgx_gru_step_x_fwd(const uint16_t* x, const uint16_t* Wih, const 
                 "(other workgroups still read h_prev): pass a second pair of buffers");
     MGX_REQUIRE(B > 0 && H > 0 && H % 64 == 0 && Kx > 0 && Kx % 64 == 0, MGX_ERR_SHAPE,
                 "mgx_gru_step_x_fwd: need H %% 64 == 0 and Kx %% 64 == 0 (got B=%d H=%d Kx=%d)", B, H, Kx);
-    hipLaunchKernelGGL(gru_step_x_fwd_kernel, dim3(H / 32, (B + 31) / 32), dim3(256), 0, (hipStream_t)stream, x, Wih, bih, Kx,
-                       h_prev_bf, h_prev, Whh, bhh, h_next, y, B, H);
+    hipLaunchKernelGGL(gru_step_x_fwd_kernel<false>, dim3(H / 32, (B + 31) / 32), dim3(256), 0, (hipStream_t)stream, x, Wih, bih, Kx,
+                       h_prev_bf, h_prev, Whh, bhh, h_next, y, (uint16_t*)nullptr, (uint16_t*)nullptr, B, H);
     MGX_CHECK_LAUNCH("mgx_gru_step_x_fwd");
+    return MGX_OK;
+}
+
+extern "C" int mgx_gru_step_x_fwd_save(const uint16_t* x, const uint16_t* Wih, const float* bih, int Kx, const uint16_t* h_prev_bf,
+                                       const float* h_prev, const uint16_t* Whh, const float* bhh, float* h_next, uint16_t* y,
+                                       uint16_t* gi_out, uint16_t* gh_out, int B, int H, void* stream) {
+    MGX_REQUIRE(x && Wih && bih && h_prev_bf && h_prev && Whh && bhh && h_next && y && gi_out && gh_out, MGX_ERR_NULL,
+                "mgx_gru_step_x_fwd_save: NULL pointer");
+    MGX_REQUIRE(h_next != h_prev && y != h_prev_bf, MGX_ERR_SHAPE, "mgx_gru_step_x_fwd_save: the state is not updated in place "
+                "(other workgroups still read h_prev): pass a second pair of buffers");
+    MGX_REQUIRE(B > 0 && H > 0 && H % 64 == 0 && Kx > 0 && Kx % 64 == 0, MGX_ERR_SHAPE,
+                "mgx_gru_step_x_fwd_save: need H %% 64 == 0 and Kx %% 64 == 0 (got B=%d H=%d Kx=%d)", B, H, Kx);
+    hipLaunchKernelGGL(gru_step_x_fwd_kernel<true>, dim3(H / 32, (B + 31) / 32), dim3(256), 0, (hipStream_t)stream, x, Wih, bih, Kx,
+                       h_prev_bf, h_prev, Whh, bhh, h_next, y, gi_out, gh_out, B, H);
+    MGX_CHECK_LAUNCH("mgx_gru_step_x_fwd_save");
+    return MGX_OK;
+}
+
+extern "C" int mgx_dropout_bf16_at(const uint16_t* x, uint16_t* out, size_t n, size_t index0, float p_drop,
+                                   const uint64_t* seed_dev, void* stream) {
+    MGX_REQUIRE(x && out && seed_dev, MGX_ERR_NULL, "mgx_dropout_bf16_at: NULL pointer");
+    MGX_REQUIRE(n > 0 && n % 8 == 0 && index0 % 8 == 0 && p_drop >= 0.f && p_drop < 1.f, MGX_ERR_SHAPE,
+                "mgx_dropout_bf16_at: need n %% 8 == 0, index0 %% 8 == 0 and 0 <= p < 1");
+    hipLaunchKernelGGL(dropout_bf16_at_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, out,
+                       n / 8, index0 / 8, make_drop(p_drop, 0), seed_dev);
+    MGX_CHECK_LAUNCH("mgx_dropout_bf16_at");
+    return MGX_OK;
+}
+
+extern "C" int mgx_gru_next_event(const uint16_t* logits, int V, int ld, const int32_t* flag_dev, const int32_t* events,
+                                  float temperature, const uint64_t* seed_dev, uint32_t step, const uint16_t* emb, int Ep,
+                                  int32_t* tok, int32_t* used_out, uint16_t* x_out, int B, void* stream) {
+    MGX_REQUIRE(logits && flag_dev && seed_dev && emb && tok && used_out && x_out, MGX_ERR_NULL, "mgx_gru_next_event: NULL pointer");
+    MGX_REQUIRE(B > 0 && V > 0 && V <= 1024 && ld >= V && Ep > 0 && Ep % 8 == 0 && temperature > 0.f, MGX_ERR_SHAPE,
+                "mgx_gru_next_event: need 0 < V <= 1024, ld >= V, Ep %% 8 == 0 and temperature > 0 (got V=%d ld=%d Ep=%d)", V, ld, Ep);
+    hipLaunchKernelGGL(gru_next_event_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, V, ld, flag_dev, events,
+                       1.0f / temperature, seed_dev, step, emb, Ep, tok, used_out, x_out);
+    MGX_CHECK_LAUNCH("mgx_gru_next_event");
     return MGX_OK;
 }

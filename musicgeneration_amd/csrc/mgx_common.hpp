@@ -59,6 +59,11 @@ struct DropCfg {
     uint32_t mix;     // seed mix
     float scale;      // 1/(1-p_actual)
 };
+// the seed's part of DropCfg (host and device: a kernel that reads its seed from device memory mixes it itself)
+__host__ __device__ static inline uint32_t drop_mix(uint64_t seed) {
+    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
+    return lo * 0x9e3779b9u + (hi ^ 0x85ebca6bu) * 0xc2b2ae35u + 0x27d4eb2fu;
+}
 static inline DropCfg make_drop(float p, uint64_t seed) {
     DropCfg c;
     if (p <= 0.f) { c.thr16 = 0; c.scale = 1.f; c.mix = 0; return c; }
@@ -67,8 +72,7 @@ static inline DropCfg make_drop(float p, uint64_t seed) {
     if (thr > 65535u) thr = 65535u;
     c.thr16 = thr;
     c.scale = (float)(1.0 / (1.0 - (double)thr / 65536.0));
-    uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-    c.mix = lo * 0x9e3779b9u + (hi ^ 0x85ebca6bu) * 0xc2b2ae35u + 0x27d4eb2fu;
+    c.mix = drop_mix(seed);
     return c;
 }
 // multipliers (0 or scale) for the 8 consecutive elements of group g (g = element_index / 8)

@@ -6,8 +6,12 @@ projection and the fused sampler; the whole step is captured in a graph when it 
 
 ``Train`` (teacher-forced logits) is differentiable: ``_GRUSeq`` runs the sequence's input projections as one GEMM per
 layer, the recurrent projection + fused cell per step, and backward-through-time with one cell-backward kernel and one
-recurrent dX GEMM per step; weight gradients are batched over the whole sequence.  Not built: packed variable-length
-batches (``lengths``) and beam search (broken in the reference)."""
+recurrent dX GEMM per step; weight gradients are batched over the whole sequence.
+
+``generate(..., events=..., output_type='logit')`` under grad mode is differentiable too (scheduled sampling, the reference's
+``window`` training mode with teacher forcing < 1): ``_GRUSched`` runs the forward STEP-major -- step t + 1 of every layer waits
+for the token chosen from step t's logits -- as one hipGraph, and shares ``_GRUSeq``'s backward-through-time, run over the
+tokens that were actually fed.  Not combined: scheduled sampling with packed batches (``lengths``)."""
 from __future__ import annotations
 
 import numpy as np
@@ -65,6 +69,64 @@ class _WsLease:
     __del__ = release
 
 
+def coin_schedule(seed, steps, greedy=1.0, teacher_forcing_ratio=1.0):
+    """The host coins of ``generate`` (network.py:146,160 draw them from the global numpy state, one pair per step): for
+    ``RandomState(seed)`` the first ``steps`` draws decide the arg-max steps (``< greedy``), the next ``steps`` draws the forced
+    ones (``<= teacher_forcing_ratio``).  -> (greedy bool [steps], forced bool [steps]); entry t governs the input of step t + 1."""
+    rng = np.random.RandomState(seed)
+    return rng.random_sample(steps) < greedy, rng.random_sample(steps) <= teacher_forcing_ratio
+
+
+def _bptt(pk, ws, cfg, xs, x_last, tok, shapes, dlogits):
+    """Backward-through-time over the activations a forward left in ``ws`` (gi, gh, h_all, hp of every layer): ``xs[l]`` bf16
+    [T*B, in] is layer l's input, ``x_last`` the top layer's output, ``tok`` int32 [T*B] the tokens that were fed (the embedding
+    gradient scatters to them).  -> (dh0 f32 [layers,B,H], [gradient per parameter, in ``shapes`` order])."""
+    T, B, H, nl, p_drop, seed = cfg
+    dev = dlogits.device
+    V, Vp = shapes[0][0], pk["wo"].shape[0]
+    dl = torch.zeros(T * B, Vp, dtype=BF16, device=dev)
+    dl[:, :V] = dlogits.reshape(T * B, V)
+    g_wo = torch.zeros(Vp, H, device=dev)
+    g_bo = torch.zeros(Vp, device=dev)
+    ops.linear_dw(dl, x_last, g_wo, g_bo)
+    dx = ops.linear_dx(dl, pk["wo"])                                            # [T*B, H]
+    dh0 = torch.empty(nl, B, H, device=dev)
+    layer_grads = [None] * nl
+    for l in reversed(range(nl)):
+        ly, wl = pk["layers"][l], ws["layers"][l]
+        gi, gh, h_all, hp = wl["gi"], wl["gh"], wl["h_all"], wl["hp"]
+        dgi, dgh, dy, dh_dir, dh0_l = wl["dgi"], wl["dgh"], wl["dy"], wl["dh"], wl["dh0"]
+        if l < nl - 1:
+            dx = ops.dropout_bf16(dx, p_drop, seed + l)
+        dy.view(T * B, H).copy_(dx)
+
+        def steps(gi=gi, gh=gh, h_all=h_all, dgi=dgi, dgh=dgh, dy=dy, dh_dir=dh_dir, dh0_l=dh0_l, ly=ly):
+            for t in reversed(range(T)):
+                last = t == T - 1
+                ops.gru_step_bwd(gi[t], gh[t], h_all[t], None if last else dh_dir[(t + 1) & 1], None if last else dgh[t + 1],
+                                 ly["whhT_f"], dy[t], dgi[t], dgh[t], dh_dir[t & 1])
+            ops.gru_step_bwd(None, None, None, dh_dir[0], dgh[0], ly["whhT_f"], None, None, None, dh0_l, final=True)
+        _captured(ws, ("bwd", l), steps, ws["use_graph"])
+        dh0[l] = dh0_l
+        in_p = ly["wih"].shape[1]
+        g_wih = torch.zeros(3 * H, in_p, device=dev)
+        g_whh = torch.zeros(3 * H, H, device=dev)
+        g_bih = torch.zeros(3 * H, device=dev)
+        g_bhh = torch.zeros(3 * H, device=dev)
+        ops.linear_dw_grouped([(dgi.view(T * B, 3 * H), xs[l], g_wih, g_bih),
+                               (dgh.view(T * B, 3 * H), hp[:-1].reshape(T * B, H), g_whh, g_bhh)])
+        layer_grads[l] = (g_wih, g_whh, g_bih, g_bhh)
+        dx = ops.linear_dx(dgi.view(T * B, 3 * H), ly["wih"])                   # gradient of the layer's input
+    g_emb = torch.zeros(shapes[0], device=dev)
+    ops.scatter_add_rows(tok, dx, g_emb)
+    grads = [g_emb]
+    for l in range(nl):
+        g_wih, g_whh, g_bih, g_bhh = layer_grads[l]
+        grads += [g_wih[:, : shapes[1 + 4 * l][1]], g_whh, g_bih, g_bhh]
+    grads += [g_wo[:V], g_bo[:V]]
+    return dh0, grads
+
+
 class _GRUSeq(torch.autograd.Function):
     """Teacher-forced multi-layer GRU + output projection over a whole sequence (network.py:63-84 SeqForward with the
     primary step folded in as step 0), forward and backward-through-time on the libmgx kernels.
@@ -117,52 +179,95 @@ class _GRUSeq(torch.autograd.Function):
         if ctx.lease is None or ctx.lease.ws is not ws:
             raise RuntimeError("Event_Melody_RNN.Train: backward through a forward that ran without gradients enabled, or twice "
                                "through the same forward (its sequence buffers have been handed back)")
-        T, B, H, nl, p_drop, seed = ctx.cfg
-        dev = dlogits.device
-        V, Vp = ctx.shapes[0][0], pk["wo"].shape[0]
-        dl = torch.zeros(T * B, Vp, dtype=BF16, device=dev)
-        dl[:, :V] = dlogits.reshape(T * B, V)
-        g_wo = torch.zeros(Vp, H, device=dev)
-        g_bo = torch.zeros(Vp, device=dev)
-        ops.linear_dw(dl, ctx.x_last, g_wo, g_bo)
-        dx = ops.linear_dx(dl, pk["wo"])                                            # [T*B, H]
-        dh0 = torch.empty(nl, B, H, device=dev)
-        layer_grads = [None] * nl
-        for l in reversed(range(nl)):
-            ly, wl = pk["layers"][l], ws["layers"][l]
-            gi, gh, h_all, hp = wl["gi"], wl["gh"], wl["h_all"], wl["hp"]
-            dgi, dgh, dy, dh_dir, dh0_l = wl["dgi"], wl["dgh"], wl["dy"], wl["dh"], wl["dh0"]
-            if l < nl - 1:
-                dx = ops.dropout_bf16(dx, p_drop, seed + l)
-            dy.view(T * B, H).copy_(dx)
-
-            def steps(gi=gi, gh=gh, h_all=h_all, dgi=dgi, dgh=dgh, dy=dy, dh_dir=dh_dir, dh0_l=dh0_l, ly=ly):
-                for t in reversed(range(T)):
-                    last = t == T - 1
-                    ops.gru_step_bwd(gi[t], gh[t], h_all[t], None if last else dh_dir[(t + 1) & 1], None if last else dgh[t + 1],
-                                     ly["whhT_f"], dy[t], dgi[t], dgh[t], dh_dir[t & 1])
-                ops.gru_step_bwd(None, None, None, dh_dir[0], dgh[0], ly["whhT_f"], None, None, None, dh0_l, final=True)
-            _captured(ws, ("bwd", l), steps, ws["use_graph"])
-            dh0[l] = dh0_l
-            in_p = ly["wih"].shape[1]
-            g_wih = torch.zeros(3 * H, in_p, device=dev)
-            g_whh = torch.zeros(3 * H, H, device=dev)
-            g_bih = torch.zeros(3 * H, device=dev)
-            g_bhh = torch.zeros(3 * H, device=dev)
-            ops.linear_dw_grouped([(dgi.view(T * B, 3 * H), ctx.xs[l], g_wih, g_bih),
-                                   (dgh.view(T * B, 3 * H), hp[:-1].reshape(T * B, H), g_whh, g_bhh)])
-            layer_grads[l] = (g_wih, g_whh, g_bih, g_bhh)
-            dx = ops.linear_dx(dgi.view(T * B, 3 * H), ly["wih"])                   # gradient of the layer's input
-        g_emb = torch.zeros(ctx.shapes[0], device=dev)
-        ops.scatter_add_rows(ctx.tok, dx, g_emb)
-        grads = [g_emb]
-        for l in range(nl):
-            g_wih, g_whh, g_bih, g_bhh = layer_grads[l]
-            grads += [g_wih[:, : ctx.shapes[1 + 4 * l][1]], g_whh, g_bih, g_bhh]
-        grads += [g_wo[:V], g_bo[:V]]
+        dh0, grads = _bptt(pk, ws, ctx.cfg, ctx.xs, ctx.x_last, ctx.tok, ctx.shapes, dlogits)
         ctx.xs = None
         ctx.lease.release()
         return (None, dh0, None, None, None, None, None) + tuple(grads)
+
+
+class _GRUSched(torch.autograd.Function):
+    """The free-running training forward (network.py:119-164 ``generate`` with ``events`` and ``output_type='logit'``, as
+    train.py:231 calls it): logits of T steps where the input of step t + 1 is the ground-truth event or the model's own choice
+    from step t's logits, by a coin per step.  Step t + 1 of every layer waits for step t of the top layer, so the loop is
+    step-major: per step one ``mgx_gru_step_x_fwd_save`` per layer (both projections + the cell, storing gi / gh as the backward
+    reads them), ``mgx_dropout_bf16_at`` between layers, the output projection, and ``mgx_gru_next_event``, which writes the
+    step's token and the layer-0 input of the next step.  The whole loop is ONE hipGraph per buffer set: coins, events, seeds and
+    the initial state live in buffers of that set and are refreshed before a replay.
+
+    forward(h0 f32 [layers,B,H], pk, ws, run (dict: flags int32 [T] numpy, events int32 [T-1,B] or None, p_drop, drop_seed,
+    sample_seed, temperature, primary, use_graph), *params) -> (logits f32 [T,B,V], used int64 [T,B]).  No gradient flows
+    through the choice of a token, so the backward is ``_GRUSeq``'s, over ``used``."""
+
+    @staticmethod
+    def forward(ctx, h0, pk, ws, run, *params):
+        nl, B, H = h0.shape
+        T = len(run["flags"])
+        V, Ep, Vp = params[0].shape[0], pk["Ep"], pk["wo"].shape[0]
+        p_drop, temperature = run["p_drop"], run["temperature"]
+        dev = h0.device
+        lease = _WsLease(ws)
+        ss = ws.get("sched")
+        if ss is None:
+            mk = lambda *shape, dt=BF16: torch.empty(*shape, dtype=dt, device=dev)
+            ss = ws["sched"] = dict(x0=mk(T, B, Ep), xd=None, logits=mk(T, B, Vp), used=mk(T, B, dt=torch.int32),
+                                    tok=mk(B, dt=torch.int32), flags=mk(T, dt=torch.int32),
+                                    events=torch.zeros(T, B, dtype=torch.int32, device=dev),
+                                    seeds=mk(nl + 1, dt=torch.int64), h0=mk(nl, B, H, dt=torch.float32))
+        if p_drop > 0 and nl > 1 and ss["xd"] is None:
+            ss["xd"] = torch.empty(nl - 1, T, B, H, dtype=BF16, device=dev)
+        # what differs from call to call: refreshed in place, the captured launches read it when they run
+        ss["flags"].copy_(torch.from_numpy(np.ascontiguousarray(run["flags"], dtype=np.int32)))
+        if T > 1:
+            ss["events"][: T - 1].copy_(run["events"])
+        ss["seeds"].copy_(torch.tensor([run["drop_seed"] + l for l in range(nl)] + [run["sample_seed"]], dtype=torch.int64))
+        ss["h0"].copy_(h0)
+        ss["used"][0].fill_(run["primary"])
+        x0, xd, logits, used = ss["x0"], ss["xd"] if p_drop > 0 else None, ss["logits"], ss["used"]
+        lib = _load()
+
+        def loop():
+            for l in range(nl):
+                wl = ws["layers"][l]
+                wl["h_all"][0].copy_(ss["h0"][l])
+                wl["hp"][0].copy_(ss["h0"][l])               # hp[t] = bf16(h_{t-1})
+            check(lib.mgx_gather_rows(ptr(used[0]), ptr(pk["emb"]), ptr(x0[0]), B, Ep, V, stream_ptr()), "mgx_gather_rows")
+            for t in range(T):
+                x = x0[t]
+                for l, ly in enumerate(pk["layers"]):
+                    wl = ws["layers"][l]
+                    ops.gru_step_x_fwd_save(x, ly["wih_f"], ly["bih"], wl["hp"][t], wl["h_all"][t], ly["whh_f"], ly["bhh"],
+                                            wl["h_all"][t + 1], wl["hp"][t + 1], wl["gi"][t], wl["gh"][t])
+                    x = wl["hp"][t + 1]
+                    if xd is not None and l < nl - 1:        # the mask of the whole [T,B,H] buffer: the backward's one call undoes it
+                        ops.dropout_bf16_at(x, xd[l][t], t * B * H, p_drop, ss["seeds"][l:l + 1])
+                        x = xd[l][t]
+                check(lib.mgx_linear_fwd(ptr(x), ptr(pk["wo"]), ptr(pk["bo"]), ptr(logits[t]), B, Vp, H, 0, stream_ptr()),
+                      "mgx_linear_fwd")
+                if t < T - 1:
+                    ops.gru_next_event(logits[t], V, ss["flags"][t:t + 1], ss["events"][t], temperature, ss["seeds"][nl:], t,
+                                       pk["emb"], ss["tok"], used[t + 1], x0[t + 1])
+        _captured(ws, ("sched", p_drop, temperature), loop, ws["use_graph"] and run["use_graph"])
+        xs = [x0.view(T * B, Ep)]
+        for l in range(1, nl):
+            xs.append((xd[l - 1] if xd is not None else ws["layers"][l - 1]["hp"][1:]).reshape(T * B, H))
+        ctx.pk, ctx.ws, ctx.lease, ctx.xs = pk, ws, lease, xs
+        ctx.cfg = (T, B, H, nl, p_drop, run["drop_seed"])
+        ctx.x_last = ws["layers"][nl - 1]["hp"][1:].reshape(T * B, H)
+        ctx.shapes = [p.shape for p in params]
+        used_out = used.long()
+        ctx.mark_non_differentiable(used_out)
+        return logits[:, :, :V].float(), used_out
+
+    @staticmethod
+    def backward(ctx, dlogits, _dused):
+        pk, ws = ctx.pk, ctx.ws
+        if ctx.lease is None or ctx.lease.ws is not ws:
+            raise RuntimeError("Event_Melody_RNN.generate: backward twice through the same forward (its sequence buffers have "
+                               "been handed back)")
+        dh0, grads = _bptt(pk, ws, ctx.cfg, ctx.xs, ctx.x_last, ws["sched"]["used"].view(-1), ctx.shapes, dlogits.contiguous())
+        ctx.xs = None
+        ctx.lease.release()
+        return (dh0, None, None, None) + tuple(grads)
 
 
 class _GruState:
@@ -315,10 +420,10 @@ class Event_Melody_RNN(nn.Module):
     def forward(self, event, hidden=None):
         return self.gen_forward(event, hidden)
 
-    def Train(self, init, events, lengths=None):
+    def Train(self, init, events, lengths=None, *, dropout_seed=None):
         """Teacher-forced logits [T+1,B,V] (network.py:63-84,109-116): the primary event, then ``events``, through the
         GRU from ``init_to_hidden(init)``; differentiable (backward-through-time on the libmgx kernels), with nn.GRU's
-        inter-layer dropout in training mode.
+        inter-layer dropout in training mode (``dropout_seed`` pins its mask; by default every call draws another).
 
         ``lengths`` (the reference's ``sequence`` mode, train.py:263-287): ``events`` is then SeqBatchify's BATCH-FIRST
         ``X [B,Tmax]`` (rows sorted by length, zero padded) and the result is batch-first ``[B, Tmax+1, V]``: the
@@ -342,7 +447,7 @@ class Event_Melody_RNN(nn.Module):
             evt = ev.t().contiguous()
             if Tb != Tmax:
                 evt = torch.cat([evt, torch.zeros(Tb - Tmax, evt.shape[1], dtype=evt.dtype, device=evt.device)], 0)
-            full = self.Train(init, evt)[: Tmax + 1]                         # [Tmax+1, B, V], padded steps included
+            full = self.Train(init, evt, dropout_seed=dropout_seed)[: Tmax + 1]                         # [Tmax+1, B, V], padded steps included
             steps = torch.arange(full.shape[0], device=full.device)[:, None]
             valid = steps <= lens.to(full.device)[None, :]                   # step 0 = primary event, steps 1..len = events
             fill = self.output_fc.bias.to(full.dtype)                        # output_fc applied to a zero (padded) GRU output
@@ -352,20 +457,67 @@ class Event_Melody_RNN(nn.Module):
         B = init.shape[0]
         tokens = torch.cat([self.get_primary_event(B), events.to(pk["dev"]).long()], 0).to(torch.int32).contiguous()
         p_drop = float(self.rnn.dropout) if self.training else 0.0
-        self._train_calls = getattr(self, "_train_calls", 0) + 1
+        ws = self._train_workspace(pk, tokens.shape[0], B)
+        return _GRUSeq.apply(tokens, hidden, pk, ws, p_drop, self._dropout_seed(dropout_seed), torch.is_grad_enabled(),
+                             *self._train_params())
+
+    def _train_params(self):
+        """the parameters in the order the training Functions return their gradients in"""
         params = [self.event_embedding.weight]
         for l in range(self.rnn_layers):
             params += [getattr(self.rnn, f"{n}_l{l}") for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
-        params += [self.output_fc.weight, self.output_fc.bias]
-        seed = (torch.initial_seed() + 7919 * self._train_calls) & 0x7FFFFFFFFFFF
-        ws = self._train_workspace(pk, tokens.shape[0], B)
-        return _GRUSeq.apply(tokens, hidden, pk, ws, p_drop, seed, torch.is_grad_enabled(), *params)
+        return params + [self.output_fc.weight, self.output_fc.bias]
+
+    def _dropout_seed(self, dropout_seed):
+        """seed of a training forward's inter-layer dropout (layer l uses seed + l): another one per call unless pinned"""
+        self._train_calls = getattr(self, "_train_calls", 0) + 1
+        if dropout_seed is not None:
+            return int(dropout_seed) & 0x7FFFFFFFFFFF
+        return (torch.initial_seed() + 7919 * self._train_calls) & 0x7FFFFFFFFFFF
+
+    def generate(self, init, steps, events=None, greedy=1.0, temperature=1.0, teacher_forcing_ratio=1.0,
+                 output_type='index', verbose=False, seed=0, use_graph=True, return_used=False, *, dropout_seed=None):
+        """network.py:119-164.  ``greedy`` is the probability of an arg-max step (host coin per step, as in the
+        reference); otherwise the event is drawn from softmax(logits / temperature) by the fused sampler.
+
+        With ``events``, ``output_type='logit'`` and grad mode on -- the call of the reference's ``window`` training mode
+        (train.py:231) -- the logits are DIFFERENTIABLE: the steps run as ``_GRUSched`` (scheduled sampling when
+        ``teacher_forcing_ratio < 1``; at 1.0 the computation of ``Train``), with nn.GRU's inter-layer dropout in training
+        mode (``dropout_seed`` pins its mask).  There a free step takes the smallest id at the maximum of its bf16 logits when
+        its coin says greedy, and otherwise the first id whose CDF of softmax(logits / temperature) reaches the step's
+        counter-based uniform of (seed, step, row).  Every other call runs without gradients.
+
+        ``return_used=True`` additionally returns ``used`` int64 [steps, B], the event fed at every step (row 0 is the primary
+        event).  ``coin_schedule(seed, steps, greedy, teacher_forcing_ratio)`` gives the coins of either route."""
+        if events is not None and output_type == 'logit' and torch.is_grad_enabled():
+            logits, used = self._generate_train(init, steps, events, greedy, temperature, teacher_forcing_ratio, seed, use_graph,
+                                                dropout_seed)
+        else:
+            logits, used = self._generate(init, steps, events, greedy, temperature, teacher_forcing_ratio, output_type, seed,
+                                          use_graph)
+        return (logits, used) if return_used else logits
+
+    def _generate_train(self, init, steps, events, greedy, temperature, teacher_forcing_ratio, seed, use_graph, dropout_seed):
+        B = init.shape[0]
+        assert init.shape[1] == self.init_dim and steps > 0
+        assert len(events.shape) == 2 and events.shape[0] >= steps - 1 and events.shape[1] == B
+        if not temperature > 0:
+            raise ValueError("temperature must be positive")
+        if self.event_dim > 1024:
+            raise ValueError("the differentiable generate chooses among at most 1024 events (mgx_gru_next_event)")
+        pk = self._pack()
+        hidden = self.init_to_hidden(init).float().contiguous()
+        g_coins, tf_coins = coin_schedule(seed, steps, greedy, teacher_forcing_ratio)
+        run = dict(flags=tf_coins.astype(np.int32) + 2 * g_coins.astype(np.int32),
+                   events=events[:steps - 1].to(pk["dev"]).to(torch.int32), p_drop=float(self.rnn.dropout) if self.training else 0.0,
+                   drop_seed=self._dropout_seed(dropout_seed), sample_seed=int(seed) & 0x7FFFFFFFFFFFFFFF,
+                   temperature=float(temperature), primary=self.primary_event, use_graph=bool(use_graph))
+        ws = self._train_workspace(pk, steps, B)
+        return _GRUSched.apply(hidden, pk, ws, run, *self._train_params())
 
     @torch.no_grad()
-    def generate(self, init, steps, events=None, greedy=1.0, temperature=1.0, teacher_forcing_ratio=1.0,
-                 output_type='index', verbose=False, seed=0, use_graph=True):
-        """network.py:119-164.  ``greedy`` is the probability of an arg-max step (host coin per step, as in the
-        reference); otherwise the event is drawn from softmax(logits / temperature) by the fused sampler."""
+    def _generate(self, init, steps, events, greedy, temperature, teacher_forcing_ratio, output_type, seed, use_graph):
+        """the sampling loop of ``generate`` -> (result, used int64 [steps, B])"""
         batch_size = init.shape[0]
         assert init.shape[1] == self.init_dim and steps > 0
         use_teacher_forcing = events is not None
@@ -379,10 +531,8 @@ class Event_Melody_RNN(nn.Module):
         tok = torch.full((batch_size,), self.primary_event, dtype=torch.int32, device=dev)
         pos = torch.zeros(1, dtype=torch.int32, device=dev)
         probs = torch.empty(batch_size, V, device=dev) if output_type == 'softmax' else None
-        rng = np.random.RandomState(seed)
-        coins = rng.random_sample(steps) < greedy
-        tf_coins = rng.random_sample(steps) <= teacher_forcing_ratio
-        outputs = []
+        coins, tf_coins = coin_schedule(seed, steps, greedy, teacher_forcing_ratio)
+        outputs, used = [], []
         plain = output_type == 'index' and not use_teacher_forcing
         out_tokens = torch.zeros(batch_size, steps + 1, dtype=torch.int32, device=dev) if plain else None
 
@@ -411,6 +561,7 @@ class Event_Melody_RNN(nn.Module):
                 graphs[key].replay()
                 st.cur ^= 1
                 continue
+            used.append(tok.clone())
             logits = one(g)
             if output_type == 'index':
                 outputs.append(tok.clone().long().unsqueeze(0))
@@ -423,8 +574,9 @@ class Event_Melody_RNN(nn.Module):
             if use_teacher_forcing and step < steps - 1 and tf_coins[step]:
                 tok.copy_(events[step].to(torch.int32))
         if plain:
-            return out_tokens[:, 1:].t().contiguous().long()
-        return torch.cat(outputs, 0)
+            out = out_tokens[:, 1:].t().contiguous().long()
+            return out, torch.cat([self.get_primary_event(batch_size), out[:-1]], 0)
+        return torch.cat(outputs, 0), torch.stack(used).long()
 
     @torch.no_grad()
     def beam_search(self, init, steps, beam_size, temperature=1.0, stochastic=False, verbose=False, seed=0):

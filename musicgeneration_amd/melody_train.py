@@ -1,12 +1,14 @@
 """Drop-in for mg/model/Event_MelodyRNN/train.py: same optparse flags (train.py:22-100), same loop for the
-``segment`` mode (train.py:327-362, the reference's configured mode) and for ``window`` with teacher forcing 1.0
-(train.py:217-262, where ``generate(..., output_type='logit')`` equals ``Train``): random init vector -> ``Train`` ->
+``segment`` mode (train.py:327-362, the reference's configured mode): random init vector -> ``Train`` ->
 cross-entropy -> ``clip_grad_norm_`` -> Adam, one ``state_dict`` checkpoint per epoch
-(``{mode}_512_3_1_epoch_{n}.pth``, train.py:188-195).  ``sequence`` mode (train.py:263-287): whole variable-length
+(``{mode}_512_3_1_epoch_{n}.pth``, train.py:188-195).  ``window`` mode (train.py:217-262) trains through
+``generate(init, window, events=events[:-1], teacher_forcing_ratio=-T, output_type='logit')`` as the reference does:
+with ``-T 1.0`` that is ``Train``'s computation, below 1 it is scheduled sampling (a coin per time step decides whether
+the next input is the ground-truth event or the model's own arg-max); the coins of iteration n come from seed n.
+``sequence`` mode (train.py:263-287): whole variable-length
 sequences, ``SeqBatchify`` collate (sorted, zero-padded ``X [B,Tmax]``, concatenated labels ``X[i,1:len_i]``),
 ``Train(init, X, lengths)`` and the loss over ``flatten_padded_sequences`` -- the computation the reference's loop is
-written for (its own ``SeqForward`` mixes the batch and time axes and cannot run).  Not built: teacher forcing < 1
-(sampling inside the training graph)."""
+written for (its own ``SeqForward`` mixes the batch and time axes and cannot run)."""
 from __future__ import annotations
 
 import optparse
@@ -57,8 +59,8 @@ def main(argv=None):
     o = get_options(argv)
     if o.mode not in ('segment', 'window', 'sequence'):
         raise ValueError("--mode must be segment, window or sequence")
-    if o.mode == 'window' and o.teacher_forcing_ratio != 1.0:
-        raise NotImplementedError("teacher forcing < 1 samples inside the training graph: not built")
+    if not 0.0 <= o.teacher_forcing_ratio <= 1.0:
+        raise ValueError("--teacher-forcing-ratio must lie in [0, 1]")
     model_config = dict(MODEL)
     for k, v in utils.params2dict(o.model_params).items():
         model_config[k] = type(MODEL.get(k, v))(v)
@@ -102,6 +104,7 @@ def main(argv=None):
 
     last = time.time()
     model.train()
+    n_iter = 0
     for epoch in range(o.epochs):
         try:
             l_sum, n = 0.0, 0
@@ -116,8 +119,13 @@ def main(argv=None):
                     loss = loss_function(flatten_padded_sequences(outputs[:, 1:], lengths), label)
                 else:
                     events = torch.from_numpy(np.ascontiguousarray(batch).astype(np.int64)).to(device)     # [T, B]
-                    outputs = model.Train(init, events=events[:-1])
-                    loss = loss_function(outputs.view(-1, event_dim), events.view(-1))
+                    if o.mode == 'window':                                                                 # train.py:231-232
+                        outputs = model.generate(init, events.shape[0], events=events[:-1], output_type='logit',
+                                                 teacher_forcing_ratio=o.teacher_forcing_ratio, seed=n_iter)
+                    else:
+                        outputs = model.Train(init, events=events[:-1])
+                    loss = loss_function(outputs.reshape(-1, event_dim), events.view(-1))
+                n_iter += 1
                 model.zero_grad()
                 loss.backward()
                 l_sum += loss.item()

@@ -494,6 +494,44 @@ def gru_step_x_fwd(x, wih, bih, h_prev_bf, h_prev, whh, bhh, h_next, y):
                                          ptr(h_next), ptr(y), B, H, stream_ptr()), "mgx_gru_step_x_fwd")
 
 
+def gru_step_x_fwd_save(x, wih, bih, h_prev_bf, h_prev, whh, bhh, h_next, y, gi_out, gh_out):
+    """gru_step_x_fwd that also stores the two rounded projections, gi_out / gh_out bf16 [B,3H], as gru_step_bwd reads them
+    (the step of the free-running training forward); h_next / y are bit-identical to gru_step_x_fwd's"""
+    _need_cuda(x, wih, bih, h_prev_bf, h_prev, whh, bhh, h_next, y, gi_out, gh_out)
+    B, H = h_prev.shape
+    if x.shape != (B, wih.shape[1]) or gi_out.shape != (B, 3 * H) or gh_out.shape != (B, 3 * H) or h_next.shape != (B, H) or y.shape != (B, H):
+        raise ValueError("gru_step_x_fwd_save: x [B,Kx], gi_out / gh_out [B,3H], h_next / y [B,H]")
+    check(_lib.load().mgx_gru_step_x_fwd_save(ptr(x), ptr(wih), ptr(bih), wih.shape[1], ptr(h_prev_bf), ptr(h_prev), ptr(whh),
+                                              ptr(bhh), ptr(h_next), ptr(y), ptr(gi_out), ptr(gh_out), B, H, stream_ptr()),
+          "mgx_gru_step_x_fwd_save")
+
+
+def dropout_bf16_at(x, out, index0, p_drop, seed_dev):
+    """dropout_bf16 on a slice: x / out hold elements index0 .. of a larger buffer and get that buffer's mask; the seed is read from
+    ``seed_dev`` (an int64 [1] view of device memory) when the kernel runs"""
+    _need_cuda(x, out, seed_dev)
+    if out.numel() != x.numel() or out.dtype != BF16 or x.dtype != BF16 or seed_dev.dtype != torch.int64 or seed_dev.numel() < 1:
+        raise ValueError("dropout_bf16_at: x / out bf16 of one size, seed_dev int64 [1]")
+    check(_lib.load().mgx_dropout_bf16_at(ptr(x), ptr(out), x.numel(), int(index0), float(p_drop), ptr(seed_dev), stream_ptr()),
+          "mgx_dropout_bf16_at")
+
+
+def gru_next_event(logits, V, flag_dev, events, temperature, seed_dev, step, emb, tok, used_out, x_out):
+    """next input of every row of the free-running training forward (mgx.h: forced / greedy / drawn by the step's device-side
+    flag) and its embedding: tok, used_out int32 [B], x_out bf16 [B,Ep] = emb[tok]"""
+    _need_cuda(logits, flag_dev, events, seed_dev, emb, tok, used_out, x_out)
+    B, ld = logits.shape
+    Ep = emb.shape[1]
+    if (logits.dtype != BF16 or emb.dtype != BF16 or x_out.dtype != BF16 or emb.shape[0] < V or x_out.shape != (B, Ep)
+            or flag_dev.dtype != torch.int32 or seed_dev.dtype != torch.int64
+            or any(t.dtype != torch.int32 or t.numel() != B for t in (tok, used_out) + (() if events is None else (events,)))):
+        raise ValueError("gru_next_event: logits bf16 [B,ld], emb bf16 [>=V,Ep], x_out bf16 [B,Ep], flag int32 [1], seed int64 [1], "
+                         "tok / used_out / events int32 [B]")
+    check(_lib.load().mgx_gru_next_event(ptr(logits), V, ld, ptr(flag_dev), ptr(events), float(temperature), ptr(seed_dev),
+                                         int(step) & 0xFFFFFFFF, ptr(emb), Ep, ptr(tok), ptr(used_out), ptr(x_out), B, stream_ptr()),
+          "mgx_gru_next_event")
+
+
 def gru_step_bwd(gi, gh, h_prev, dh_direct, dgh_next, whh_t, dy, dgi, dgh, dh_out, final=False):
     """one fused backward step: d_rec = dgh_next @ W_hh (whh_t = pack_frag(W_hh.T)), then the cell backward (see mgx.h)"""
     _need_cuda(gi, gh, h_prev, dh_direct, dgh_next, whh_t, dy, dgi, dgh, dh_out)
