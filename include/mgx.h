@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event */
-#define MGX_ABI_VERSION 23
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce */
+#define MGX_ABI_VERSION 24
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -518,6 +518,41 @@ int mgx_dropout_bf16_at(const uint16_t* x, uint16_t* out, size_t n, size_t index
 int mgx_gru_next_event(const uint16_t* logits, int V, int ld, const int32_t* flag_dev, const int32_t* events, float temperature,
                        const uint64_t* seed_dev, uint32_t step, const uint16_t* emb, int Ep, int32_t* tok, int32_t* used_out,
                        uint16_t* x_out, int B, void* stream);
+
+/* ---- Scoring (ABI 24): the log-probability the model gives to every event of a sequence -- the log-softmax and the gather of the
+ * target's entry of criterion.py:43-67 without the label smoothing, and the arg-max against the target of metrics.py:40-52.  The
+ * three entry points share these rules.  All arithmetic is f32.  For row r, over the ALLOWED ids v (all ids without a grammar):
+ *     x_v = logit_v * (1 / temperature),   lse = logsumexp_v x_v
+ *     logp[r] = x_t - lse for t = target[r] in 0..V-1 (-inf for a disallowed t)
+ *     hit[r]  = 1 if t is the SMALLEST allowed id whose logit equals the row maximum, else 0 (-0 equals +0; a NaN never wins)
+ *   A row with target[r] < 0 or >= V is UNSCORED: logp = 0, hit = -1; lse_out is still written.
+ *   A NaN or +inf among a row's allowed logits gives logp = lse = NaN, and so does a row whose allowed logits are all -inf: a
+ *   diverged run stays recognisable.
+ *   logp f32, hit int32, lse_out f32 (optional, NULL = not wanted): `rows` (M) elements each; nothing else is written.
+ *
+ * mgx_token_logprob: on logits that exist.  logits bf16 [rows,ld]: only columns < V are read; any V >= 1, ld >= V,
+ *   temperature > 0.  allow_table and prev int32 [rows] are both given or both NULL: allow_table is the sampler's grammar mask
+ *   uint32 [V, ceil(V/32)], the row taken by prev[r] clamped to 0..V-1, under the sampler's rule -- a disallowed id counts as
+ *   -inf, and a table row that leaves no finite logit (the NaN-ignoring maximum over its ids is -inf) is ignored for that row.
+ *   This is mgx_beam_select's logp.  hit compares the bf16 values exactly.  One wave per row.                               */
+int mgx_token_logprob(const uint16_t* logits, int V, int ld, const int32_t* target, const int32_t* prev,
+                      const uint32_t* allow_table, float temperature, float* logp, float* lse_out, int32_t* hit, int rows,
+                      void* stream);
+/* mgx_linear_logprob: the vocabulary projection fused with the above; the logits never leave the accumulators.
+ *   A bf16 [M,K] (the last LayerNorm's output), W bf16 [V,K] (fc.weight), bias f32 [V] or NULL.  K % 64 == 0, 64 <= K <= 1024,
+ *   V >= 1, temperature > 0; other shapes return MGX_ERR_SHAPE.
+ *     x_v = (sum_k A[r,k] W[v,k] + bias_v) * (1 / temperature)
+ *   with the sum accumulated in fp32 on the MFMA units, bias and scale applied in fp32: NO rounding to bf16 anywhere.  No grammar.
+ *   hit compares the fp32 values and takes the smallest id among equal maxima.  Exactly V rows of W and V elements of bias are
+ *   read.  A workgroup owns 32 rows of A (staged once in LDS) and walks V in tiles of 32 ids with a running
+ *   (max, sum, target logit, arg-max) per row; the summation order is fixed, so two calls give the same bits.               */
+int mgx_linear_logprob(const uint16_t* A, const uint16_t* W, const float* bias, const int32_t* target, float temperature,
+                       float* logp, float* lse_out, int32_t* hit, int M, int V, int K, void* stream);
+/* mgx_score_reduce: per-sequence totals of logp f32 [B,L] and hit int32 [B,L].  count[b] = columns with hit >= 0,
+ *   hits[b] = columns with hit == 1, sum[b] (f64) = the sum of logp over the counted columns, accumulated in fp64 in a fixed
+ *   order (two calls give the same bits); a counted -inf or NaN propagates.  One workgroup per row b.                       */
+int mgx_score_reduce(const float* logp, const int32_t* hit, double* sum, int32_t* count, int32_t* hits, int B, int L,
+                     void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 
 # the ABI the SIGNATURES table below was written for (MGX_ABI_VERSION of include/mgx.h).  A left-over
 # libmgx.so of another ABI still exports the same names: calling it with this table would shift arguments.
-EXPECTED_ABI = 23
+EXPECTED_ABI = 24
 
 # name -> argtypes ; every symbol declared in include/mgx.h (restype int unless noted)
 SIGNATURES = {
@@ -80,6 +80,10 @@ SIGNATURES = {
     "mgx_gru_step_x_fwd_save": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "mgx_dropout_bf16_at": [_vp, _vp, _sz, _sz, _f, _vp, _vp],
     "mgx_gru_next_event": [_vp, _i, _i, _vp, _vp, _f, _vp, C.c_uint32, _vp, _i, _vp, _vp, _vp, _i, _vp],
+    # ABI 24: scoring
+    "mgx_token_logprob": [_vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp],
+    "mgx_linear_logprob": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "mgx_score_reduce": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "mgx_scatter_add_rows": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "mgx_linear_ln_fwd": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "mgx_decode_embed_linear": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],

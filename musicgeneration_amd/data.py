@@ -73,6 +73,10 @@ class Data:
                 raise ValueError(f"{fname}: token id {int(arr.max())} outside the vocabulary [0, {vocab_size}) "
                                  f"(dataset written for another event representation?)")
 
+    def array(self, fname) -> np.ndarray:
+        """the whole event array of a kept file (held in RAM since construction)"""
+        return self._get_seq(fname)
+
     def _get_seq(self, fname, max_length=None):
         """random crop of max_length events (data.py:96-107); IndexError when the file is too short"""
         data = self._cache.get(fname)

@@ -58,6 +58,9 @@ def get_options(argv=None):
                            'sample.  Each of the -b samples is searched with its own beam and the best beam is written')
     parser.add_option('-S', '--stochastic-beam-search', dest='stochastic_beam_search', action='store_true', default=False,
                       help='with -B: choose the surviving beams by Gumbel-perturbed scores')
+    parser.add_option('--best-of', dest='best_of', type='int', default=1,
+                      help='draw N candidates per sample (a batch of b * N rows, every prompt repeated N times), score every '
+                           'continuation with the model at temperature 1 (MusicTransformer.score) and write the most likely one')
     return parser.parse_args(argv)[0]
 
 
@@ -77,6 +80,29 @@ def _check_beam_options(o):
         raise SystemExit('-B/--beam-size cannot be combined with --top-p (a search ranks all events; top-p filters a sampler)')
     if o.reference_mask:
         raise SystemExit('-B/--beam-size cannot be combined with --reference-mask (the KV-cache decode is causal)')
+
+
+def _check_best_of(o):
+    """--best-of against -B, before any model or device work"""
+    if o.best_of < 1:
+        raise SystemExit(f'--best-of must be at least 1, got {o.best_of}')
+    if o.best_of > 1 and o.beam_size:
+        raise SystemExit('--best-of cannot be combined with -B/--beam-size (a search returns its best beam; --best-of ranks samples)')
+
+
+def _best_of(o, mt, res, prompt_lens, grammar=None):
+    """--best-of N: rows b * N + k of ``res`` are the N candidates of sample b.  Scores every continuation (the events from the
+    row's prompt length on) in one ``score`` call at temperature 1 and returns the best row of every group"""
+    N = o.best_of
+    if N == 1:
+        return res
+    x = torch.from_numpy(np.asarray(res)).to(torch.device('cuda:0'))
+    lengths = [n + o.max_len for n in prompt_lens]
+    out = mt.score(x, lengths=lengths, from_pos=prompt_lens, temperature=1.0, grammar=grammar)
+    sums = out['sum'].view(-1, N).cpu()
+    best = sums.argmax(1)
+    print('Best of {}: log-probabilities {}'.format(N, [round(float(sums[i, k]), 3) for i, k in enumerate(best.tolist())]))
+    return np.asarray(res)[[i * N + k for i, k in enumerate(best.tolist())]]
 
 
 def _ragged_priors(o):
@@ -108,6 +134,7 @@ def _ragged_priors(o):
 
 def main(argv=None):
     o = get_options(argv)
+    _check_best_of(o)
     _check_beam_options(o)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
@@ -145,15 +172,19 @@ def main(argv=None):
         return res.cpu().numpy()
     if ragged is not None:
         prior, lens = ragged
+        if o.best_of > 1:                                  # every prompt N times, side by side
+            prior, lens = prior.repeat_interleave(o.best_of, 0), [n for n in lens for _ in range(o.best_of)]
         if o.beam_size:
             _write(o, [row[:n + o.max_len] for row, n in zip(search(prior.to(device), prior_lengths=lens), lens)])
             return
         res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  prior_lengths=lens, **cached).cpu().numpy()
+        res, lens = _best_of(o, mt, res, lens), lens[::o.best_of]
         res = [row[:n + o.max_len] for row, n in zip(res, lens)]             # without the pad tail
         _write(o, res)
         return
-    prior = torch.tensor([[24, 28, 31]] * o.batch_size, dtype=torch.long, device=device)
+    rows = o.batch_size * o.best_of                        # --best-of N: N candidates per sample, side by side
+    prior = torch.tensor([[24, 28, 31]] * rows, dtype=torch.long, device=device)
     if o.condition_file is not None:
         # generate.py:101-105: MIDI -> notes -> MIDI-like events -> the first 500 indices, repeated for the batch
         if o.repr != 'midi_like':
@@ -162,7 +193,7 @@ def main(argv=None):
         ids = EventSeq.from_note_seq(NoteSeq.from_midi_file(o.condition_file)).to_array()[:500]
         if len(ids) == 0:
             raise SystemExit(f'{o.condition_file}: no notes in the MIDI-like pitch range')
-        prior = torch.from_numpy(np.array([ids] * o.batch_size, dtype=np.int64)).to(device)
+        prior = torch.from_numpy(np.array([ids] * rows, dtype=np.int64)).to(device)
         print('Prompt: {} events from {}'.format(len(ids), o.condition_file))
     if o.grammar:
         if o.repr == 'remi':
@@ -172,12 +203,13 @@ def main(argv=None):
         else:
             raise SystemExit('--grammar is defined for --repr remi and --repr mumidi')
         bar = Codec.feat_ranges()['bar'][0]
-        prior = torch.full((o.batch_size, 1), bar, dtype=torch.long, device=device)
+        prior = torch.full((rows, 1), bar, dtype=torch.long, device=device)
         if o.beam_size:
             _write(o, search(prior, grammar=Codec.next_token_table()))
             return
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  grammar=Codec.next_token_table(), **cached).cpu().numpy()
+        res = _best_of(o, mt, res, [1] * rows, Codec.next_token_table())
     elif o.beam_size:
         res = search(prior)
     elif o.window:
@@ -185,6 +217,8 @@ def main(argv=None):
     else:
         res = mt.generate(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                           reference_mask=o.reference_mask).cpu().numpy()
+    if not o.grammar:
+        res = _best_of(o, mt, res, [prior.shape[1]] * rows)
     _write(o, res)
 
 

@@ -104,7 +104,15 @@ class MusicTransformer(torch.nn.Module):
     # ------------------------------------------------------------------------------------------
     # the hot path: tokens -> logits                 network.py:37-39 + layers.py:223-233,152-161
     # ------------------------------------------------------------------------------------------
-    def _logits(self, x: torch.Tensor, wsink: Optional[list] = None) -> torch.Tensor:
+    def _bucket_hooks(self, training: bool):
+        """name -> the callback that tells the data-parallel wrapper that a gradient bucket is complete (None outside it)"""
+        dp = self._dp
+        return ((lambda name: (lambda: dp.bucket_ready(name))) if (dp is not None and (dp.world > 1 or dp.force) and training)
+                else (lambda name: None))
+
+    def _hidden(self, x: torch.Tensor, wsink: Optional[list] = None) -> torch.Tensor:
+        """everything up to the last LayerNorm: tokens [B, L] -> bf16 [B, Lp, d], Lp = L rounded up to the kernels' 32-key tile
+        (rows >= L belong to trailing pad tokens)"""
         st = self.store()
         st.sync_shadow()
         training = self.training and torch.is_grad_enabled()
@@ -124,9 +132,7 @@ class MusicTransformer(torch.nn.Module):
         d = self.embedding_dim
         p = self.dropout_rate if self.training else 0.0
         seed = self._next_seed()
-        dp = self._dp
-        done = ((lambda name: (lambda: dp.bucket_ready(name))) if (dp is not None and (dp.world > 1 or dp.force) and training)
-                else (lambda name: None))
+        done = self._bucket_hooks(training)
 
         if self._pad_flag is None or self._pad_flag.device != tok.device:
             self._pad_flag = torch.zeros(1, dtype=torch.int32, device=tok.device)
@@ -147,14 +153,23 @@ class MusicTransformer(torch.nn.Module):
         for i, lp in enumerate(layer_params):
             # the layer's gradient bucket is complete when the block's backward (ending in the QKV projection) has run
             h = ops.encoder_layer(h, lp, padbits, p, seed + 4 * i, done(f"layer{i}"), wsink)
-        Vp = self.vocab_padded
-        logits = ops.linear(h, P["fc.weight"], st.padded_view("fc.weight", Vp, d), st.padded_view("fc.bias", Vp, None, "param"),
-                            0, st.padded_view("fc.weight", Vp, d, "grad"), st.padded_view("fc.bias", Vp, None, "grad"),
-                            done("fc"))
         if wsink is not None and Lp != L:
             wsink[:] = [w_[:, :, :L, :L] for w_ in wsink]
-        # [B, Lp, Vp] storage, [B, L, V] view: columns >= V are exact zeros (zero weight rows, zero bias)
-        return logits[:, :L, : self.vocab_size]
+        return h
+
+    def _logits_padded(self, x: torch.Tensor, wsink: Optional[list] = None) -> torch.Tensor:
+        """the vocabulary projection of ``_hidden``: the whole bf16 [B, Lp, Vp] storage; columns >= V are exact zeros (zero
+        weight rows, zero bias)"""
+        h = self._hidden(x, wsink)
+        st, d, Vp = self.store(), self.embedding_dim, self.vocab_padded
+        done = self._bucket_hooks(self.training and torch.is_grad_enabled())
+        return ops.linear(h, st.params["fc.weight"], st.padded_view("fc.weight", Vp, d), st.padded_view("fc.bias", Vp, None, "param"),
+                          0, st.padded_view("fc.weight", Vp, d, "grad"), st.padded_view("fc.bias", Vp, None, "grad"),
+                          done("fc"))
+
+    def _logits(self, x: torch.Tensor, wsink: Optional[list] = None) -> torch.Tensor:
+        # [B, Lp, Vp] storage, [B, L, V] view
+        return self._logits_padded(x, wsink)[:, : x.shape[1], : self.vocab_size]
 
     def _params_for_padded_E(self, layer_params, extra, done, training):
         """per-layer operand sets whose relative embedding has `extra` zero rows in front (see _logits), and a bucket callback
@@ -398,6 +413,39 @@ class MusicTransformer(torch.nn.Module):
         the slot (0..K-1) of the previous column that it extends."""
         return decode.generate_beam(self, prior, length, beam_size, temperature, stochastic, seed, grammar, prior_lengths, kv_cache,
                                     use_graph, return_beams)
+
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, lengths=None, from_pos=None, temperature: float = 1.0, grammar=None, logits: str = "auto",
+              window: Optional[int] = None, stride: Optional[int] = None):
+        """The log-probability the model gives to every event of ``x`` [B, L]: ``logp[b, i] = log p(x[b, i] | x[b, :i])`` under
+        softmax(logits / temperature).  Runs without gradients and with dropout off whatever ``self.training`` is (the mode is
+        restored).  Returns a dict: ``logp`` f32 [B, L]; ``hit`` int32 [B, L] (1: the event is the model's arg-max, the smallest id
+        among equal maxima; 0: it is not; -1: unscored); ``sum`` f64 [B], ``count`` and ``hits`` int32 [B], the totals over a row's
+        scored events (mgx_score_reduce).
+
+        Event i of row b is scored iff i >= max(1, from_pos[b]), i < lengths[b] (when ``lengths`` is given) and
+        x[b, i] != pad_token; everything else is unscored: logp 0, hit -1.  Column 0 never is scored: the model has no start
+        token.  ``lengths`` and ``from_pos`` are host integers (one per row; ``from_pos`` may be one for all).
+
+        ``logits``: "fp32" takes the log-sum-exp from the fp32 accumulators of the vocabulary projection and never stores the
+        logits (mgx_linear_logprob on ``_hidden``); "bf16" runs ``_logits`` and then mgx_token_logprob on the bf16 logits, as the
+        decode path reads them -- ``generate_beam``'s scores are sums of these; "auto" is fp32 unless a ``grammar`` is given or
+        d > 1024.  ``grammar``: a ``next_token_table()`` as in ``generate_cached`` (the log-softmax runs over the events that may
+        follow x[b, i-1]; a disallowed event scores -inf); refused with "fp32".
+
+        ``window`` (W, 2 .. max_seq; default max_seq) and ``stride`` (1 .. W - 1; default max(1, W // 2)): a row of more than W
+        events is scored in overlapping windows (``scoring.score_schedule``), each renumbered from position 0 as a training crop
+        is; every event is scored exactly once, outside the first window with at least W - stride events of context.  Rows of
+        different lengths are scheduled per row and their windows batched by width; rows that fit W ride in one window.
+        A NaN or +inf logit makes the row's entries NaN.  Leading pads follow ``forward``'s rule (``check_no_leading_pads``).
+        Nothing is read back: the call makes no host synchronisation."""
+        from . import scoring
+        was = self.training
+        self.eval()
+        try:
+            return scoring.score(self, x, lengths, from_pos, temperature, grammar, logits, window, stride)
+        finally:
+            self.train(was)
 
     def test(self):
         self.eval()

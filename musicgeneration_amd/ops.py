@@ -809,6 +809,80 @@ def beam_backtrack(hist_tok, hist_parent, c0_rows, out, K, steps):
     return out
 
 
+# ---- scoring (ABI 24; contracts in include/mgx.h) --------------------------------------------------------------------
+def _score_outputs(rows, dev, want_lse):
+    return (torch.empty(rows, dtype=torch.float32, device=dev), torch.empty(rows, dtype=torch.float32, device=dev) if want_lse else None,
+            torch.empty(rows, dtype=torch.int32, device=dev))
+
+
+def token_logprob(logits, target, temperature=1.0, prev=None, allow_table=None, want_lse=True):
+    """log p(target) of every row of logits bf16 [..., V]: a view whose rows are evenly spaced in memory (columns contiguous, e.g.
+    [B, Lp, V] cut out of [B, Lp, Vp]).  target (and prev, with allow_table uint32/int32 [V, ceil(V/32)]) int32, one per row.
+    Returns (logp f32 [rows], lse f32 [rows] or None, hit int32 [rows])"""
+    if logits.dim() < 1 or logits.dtype != BF16:
+        raise ValueError(f"token_logprob: logits must be bf16 [..., V], got {logits.dtype} {tuple(logits.shape)}")
+    V = logits.shape[-1]
+    rows = logits.numel() // V if V else 0
+    if V < 1 or rows < 1:
+        raise ValueError(f"token_logprob: logits must hold at least one row of at least one column, got {tuple(logits.shape)}")
+    # the leading dimensions must collapse into ONE row stride (dimensions of one entry have no say)
+    lg, ld = logits, V
+    dims = [(lg.shape[i], lg.stride(i)) for i in range(lg.dim() - 1) if lg.shape[i] != 1]
+    if dims:
+        ld = dims[-1][1]
+    if (V > 1 and lg.stride(-1) != 1) or ld < V or any(dims[i][1] != dims[i + 1][1] * dims[i + 1][0] for i in range(len(dims) - 1)):
+        raise ValueError(f"token_logprob: the rows of logits must be evenly spaced and their columns contiguous "
+                         f"(shape {tuple(lg.shape)}, strides {lg.stride()})")
+    if not lg.is_cuda:
+        raise _lib.MgxError("mgx ops need CUDA/HIP tensors (no CPU fallback); got a CPU tensor")
+    _need_cuda(target, prev, allow_table)
+    for name, t in (("target", target), ("prev", prev)):
+        if t is not None and (t.dtype != torch.int32 or t.numel() != rows):
+            raise ValueError(f"token_logprob: {name} must be int32 with one entry per row ({rows}), got {t.dtype} {tuple(t.shape)}")
+    if (prev is None) != (allow_table is None):
+        raise ValueError("token_logprob: prev and allow_table are given together or not at all")
+    if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
+                                    or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4):
+        raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
+    logp, lse, hit = _score_outputs(rows, lg.device, want_lse)
+    check(_lib.load().mgx_token_logprob(ptr(lg), V, int(ld), ptr(target), ptr(prev), ptr(allow_table), float(temperature), ptr(logp),
+                                        ptr(lse), ptr(hit), rows, stream_ptr()), "mgx_token_logprob")
+    return logp, lse, hit
+
+
+def linear_logprob(a, w, bias, target, temperature=1.0, want_lse=True):
+    """log p(target) under softmax((a w^T + bias) / temperature) without storing the logits: a bf16 [M, K], w bf16 [V, K], bias f32
+    [V] or None, target int32 [M].  Returns (logp f32 [M], lse f32 [M] or None, hit int32 [M])"""
+    _need_cuda(a, w, bias, target)
+    if a.dim() != 2 or w.dim() != 2 or a.dtype != BF16 or w.dtype != BF16 or a.shape[1] != w.shape[1]:
+        raise ValueError(f"linear_logprob: a bf16 [M, K] and w bf16 [V, K], got {a.dtype} {tuple(a.shape)} and {w.dtype} {tuple(w.shape)}")
+    M, K = a.shape
+    V = w.shape[0]
+    if bias is not None and (bias.dtype != torch.float32 or bias.shape != (V,)):
+        raise ValueError(f"linear_logprob: bias must be float32 [{V}], got {bias.dtype} {tuple(bias.shape)}")
+    if target.dtype != torch.int32 or target.numel() != M:
+        raise ValueError(f"linear_logprob: target must be int32 with one entry per row ({M}), got {target.dtype} {tuple(target.shape)}")
+    logp, lse, hit = _score_outputs(M, a.device, want_lse)
+    check(_lib.load().mgx_linear_logprob(ptr(a), ptr(w), ptr(bias), ptr(target), float(temperature), ptr(logp), ptr(lse), ptr(hit), M, V,
+                                         K, stream_ptr()), "mgx_linear_logprob")
+    return logp, lse, hit
+
+
+def score_reduce(logp, hit):
+    """per-row totals of logp f32 [B, L] and hit int32 [B, L]: (sum f64 [B] over the entries with hit >= 0, their count int32 [B],
+    the count of hit == 1 int32 [B])"""
+    _need_cuda(logp, hit)
+    if logp.dim() != 2 or logp.dtype != torch.float32 or hit.dtype != torch.int32 or hit.shape != logp.shape:
+        raise ValueError(f"score_reduce: logp float32 [B, L] and hit int32 [B, L], got {logp.dtype} {tuple(logp.shape)} and "
+                         f"{hit.dtype} {tuple(hit.shape)}")
+    B, L = logp.shape
+    total = torch.empty(B, dtype=torch.float64, device=logp.device)
+    count = torch.empty(B, dtype=torch.int32, device=logp.device)
+    hits = torch.empty(B, dtype=torch.int32, device=logp.device)
+    check(_lib.load().mgx_score_reduce(ptr(logp), ptr(hit), ptr(total), ptr(count), ptr(hits), B, L, stream_ptr()), "mgx_score_reduce")
+    return total, count, hits
+
+
 # --------------------------------------------------------------------------------------------------
 # autograd glue
 #

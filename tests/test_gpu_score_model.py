@@ -1,0 +1,268 @@
+"""MusicTransformer.score on the device: against the bf16-emulating oracle (log_softmax of oracle.ref_cpu.model_forward), as the
+composition of its parts, over the window schedule of sequences longer than the model's window, against the scores beam search
+carries, and through the two command lines (generate.py --best-of, python -m musicgeneration_amd.score).
+
+Bound against the oracle, for both logit paths: |logp - ref| <= 4 * 2^-8 * max |ref logits| -- twice the per-logit bound
+test_gpu_model.py uses against that oracle, because x_t and lse each move by at most one such bound."""
+import glob
+import json
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda:0")
+V, D, NL = 40, 64, 2
+PAD = V - 1
+_CACHE = {}
+
+
+def _model(max_seq, seed=0):
+    """(MusicTransformer on the device, the oracle's parameters): oracle.ref_cpu.init_params, V = 40, d = 64, 2 layers"""
+    from musicgeneration_amd.network import MusicTransformer
+    from oracle import ref_cpu as R
+    key = (max_seq, seed)
+    if key not in _CACHE:
+        p0 = R.init_params(V, D, NL, max_seq, seed=seed)
+        mt = MusicTransformer(embedding_dim=D, vocab_size=V, num_layer=NL, max_seq=max_seq, dropout=0.1)
+        mt.load_state_dict({k: v.clone() for k, v in p0.items()})
+        _CACHE[key] = (mt.cuda().eval(), p0)
+    return _CACHE[key]
+
+
+def _oracle_logp(p0, x):
+    """(fp64 log_softmax of the bf16-emulating oracle's logits [N, n, V], max |logits|)"""
+    from oracle import ref_cpu as R
+    R.EMULATE_BF16 = True
+    try:
+        with torch.no_grad():
+            logits, _ = R.model_forward(p0, x, PAD)
+    finally:
+        R.EMULATE_BF16 = False
+    return torch.log_softmax(logits.to(torch.float64), -1).numpy(), float(logits.abs().max())
+
+
+def _scored(x, lengths, from_pos):
+    x = x.numpy()
+    B, L = x.shape
+    col = np.arange(L)[None, :]
+    return (col >= np.maximum(1, np.asarray(from_pos))[:, None]) & (col < np.asarray(lengths)[:, None]) & (x != PAD)
+
+
+@pytest.mark.parametrize("max_seq,L", [(64, 50), (40, 7), (128, 128)])
+@pytest.mark.parametrize("path", ["fp32", "bf16"])
+def test_score_matches_the_oracle(max_seq, L, path):
+    mt, p0 = _model(max_seq)
+    g = torch.Generator().manual_seed(L)
+    B = 4
+    x = torch.randint(0, V - 1, (B, L), generator=g)
+    lengths = [L, max(2, L - 3), max(1, L // 2), L]
+    from_pos = [0, 2, 1, min(5, L - 1)]
+    x[3, L - 2:] = PAD                                        # trailing pads inside the stated length
+    for b, n in enumerate(lengths):
+        x[b, n:] = PAD
+    mt.train()                                                # dropout 0.1 and training mode: score must switch both off
+    out = mt.score(x.to(DEV), lengths=lengths, from_pos=from_pos, logits=path)
+    assert mt.training
+    mt.eval()
+    mt.check_no_leading_pads()
+    ls, mx = _oracle_logp(p0, x)
+    scored = _scored(x, lengths, from_pos)
+    ref = np.zeros((B, L))
+    for b in range(B):
+        for i in range(1, L):
+            if scored[b, i]:
+                ref[b, i] = ls[b, i - 1, x[b, i]]
+    logp, hit = out["logp"].cpu().numpy(), out["hit"].cpu().numpy()
+    assert logp.shape == (B, L) and logp.dtype == np.float32 and hit.dtype == np.int32
+    err = np.abs(logp - ref)[scored].max()
+    print(f"[{path}] max_seq={max_seq} L={L}: max |logp - ref| {err:.4f}, bound {4 * 2.0 ** -8 * mx:.4f}")
+    assert err <= 4 * 2.0 ** -8 * mx
+    assert (logp[~scored] == 0).all() and (hit[~scored] == -1).all() and np.isin(hit[scored], (0, 1)).all()
+    assert out["count"].cpu().tolist() == scored.sum(1).tolist()
+    assert out["hits"].cpu().tolist() == (hit == 1).sum(1).tolist()
+    want = np.array([logp[b][scored[b]].astype(np.float64).sum() for b in range(B)])
+    assert out["sum"].dtype == torch.float64 and np.abs(out["sum"].cpu().numpy() - want).max() <= 1e-12 * np.abs(want).max()
+    # the arg-max agrees with the oracle's where the oracle's top two logits are further apart than the bound
+    top = np.sort(ls, -1)
+    clear = np.zeros((B, L), bool)
+    clear[:, 1:] = (top[:, :-1, -1] - top[:, :-1, -2]) > 4 * 2.0 ** -8 * mx
+    am = np.zeros((B, L), int)
+    am[:, 1:] = ls[:, :-1].argmax(-1)
+    m = scored & clear
+    assert (hit[m] == (am[m] == x.numpy()[m])).all()
+
+
+def test_score_is_the_composition_of_its_parts():
+    from musicgeneration_amd import ops
+    mt, _ = _model(64)
+    g = torch.Generator().manual_seed(7)
+    B, L = 3, 64
+    x = torch.randint(0, V - 1, (B, L), generator=g).to(DEV)
+    nxt = torch.cat([x[:, 1:], torch.full((B, 1), -1, device=DEV)], 1).to(torch.int32).contiguous()
+    for temperature in (1.0, 0.8):
+        out = mt.score(x, logits="fp32", temperature=temperature)
+        with torch.no_grad():
+            h = mt._hidden(x)
+        assert h.shape == (B, L, D) and h.dtype == torch.bfloat16
+        lp, _, hit = ops.linear_logprob(h.reshape(B * L, D), mt.fc.weight.detach().to(torch.bfloat16).contiguous(),
+                                        mt.fc.bias.detach().float().contiguous(), nxt.view(-1), temperature)
+        assert torch.equal(out["logp"][:, 1:], lp.view(B, L)[:, :-1]) and torch.equal(out["hit"][:, 1:], hit.view(B, L)[:, :-1])
+        out = mt.score(x, logits="bf16", temperature=temperature)
+        with torch.no_grad():
+            logits, _ = mt(x)
+        lp, _, hit = ops.token_logprob(logits, nxt, temperature)
+        assert torch.equal(out["logp"][:, 1:], lp.view(B, L)[:, :-1]) and torch.equal(out["hit"][:, 1:], hit.view(B, L)[:, :-1])
+        assert (out["logp"][:, 0] == 0).all() and (out["hit"][:, 0] == -1).all()
+    # "auto" is the fp32 path without a grammar, and _logits is what it was: the projection of _hidden
+    assert torch.equal(mt.score(x)["logp"], mt.score(x, logits="fp32")["logp"])
+    with torch.no_grad():
+        a, b = mt._logits(x[:, :50]), mt._logits_padded(x[:, :50])
+    assert a.shape == (B, 50, V) and b.shape == (B, 64, mt.vocab_padded) and torch.equal(a, b[:, :50, :V])
+
+
+@pytest.mark.parametrize("stride", (1, 16, 31))
+def test_window_schedule_on_the_device(stride):
+    from musicgeneration_amd.scoring import score_schedule
+    W = 32
+    mt, p0 = _model(W)
+    g = torch.Generator().manual_seed(stride)
+    ns = [33, 70, 100, 20]                                    # the last row fits the window: it rides in one window of 20
+    B, L = len(ns), max(ns)
+    x = torch.randint(0, V - 1, (B, L), generator=g)
+    for b, n in enumerate(ns):
+        x[b, n:] = PAD
+    # the reference: the oracle on every window of the schedule, one batch per width
+    wins = [(b, s, w, f) for b, n in enumerate(ns) for (s, w, f) in score_schedule(n, W, stride)]
+    assert sorted({w for _, _, w, _ in wins}) == [20, W]
+    ref, seen, mx = np.zeros((B, L)), np.zeros((B, L), int), 0.0
+    for width in (20, W):
+        group = [t for t in wins if t[2] == width]
+        ls, m = _oracle_logp(p0, torch.stack([x[b, s:s + width] for b, s, _, _ in group]))
+        mx = max(mx, m)
+        for k, (b, s, w, f) in enumerate(group):
+            for j in range(f, w):
+                ref[b, s + j] = ls[k, j - 1, x[b, s + j]]
+                seen[b, s + j] += 1
+    for path in (("fp32", "bf16") if stride == 16 else ("fp32",)):
+        out = mt.score(x.to(DEV), lengths=ns, logits=path, stride=stride)
+        logp, hit = out["logp"].cpu().numpy(), out["hit"].cpu().numpy()
+        for b, n in enumerate(ns):
+            assert (seen[b, 1:n] == 1).all() and (hit[b, 1:n] >= 0).all() and (logp[b, 1:n] < 0).all()
+            assert hit[b, 0] == -1 and logp[b, 0] == 0 and (hit[b, n:] == -1).all() and (logp[b, n:] == 0).all()
+        err = np.abs(logp - ref).max()
+        print(f"[{path}] stride={stride}: max |logp - ref| {err:.4f}, bound {4 * 2.0 ** -8 * mx:.4f}")
+        assert err <= 4 * 2.0 ** -8 * mx
+        assert out["count"].cpu().tolist() == [n - 1 for n in ns]
+    # without lengths the pad tails are windows of pads only: nothing there is scored and no leading-pad record is raised
+    out = mt.score(x.to(DEV), stride=stride)
+    assert out["count"].cpu().tolist() == [n - 1 for n in ns]
+    mt.check_no_leading_pads()
+    # n <= W: bitwise the call without window
+    short = x[:, :30].to(DEV)
+    a, b = mt.score(short, window=31, stride=stride if stride < 31 else 30), mt.score(short)
+    assert all(torch.equal(a[k], b[k]) for k in a)
+    mt.check_no_leading_pads()
+
+
+@pytest.mark.parametrize("grammar", (False, True))
+def test_score_agrees_with_beam_search(grammar):
+    """an off-by-one detector: a shifted column changes a sum by about log V per event"""
+    from musicgeneration_amd.network import MusicTransformer
+    from musicgeneration_amd.REMI import REMI_EventSeq
+    from oracle import ref_cpu as R
+    table = REMI_EventSeq.next_token_table() if grammar else None
+    Vb = 337
+    p0 = R.init_params(Vb, 128, 2, 64, seed=5)
+    p0["Decoder.embedding.weight"] = p0["Decoder.embedding.weight"] * 0.1
+    mt = MusicTransformer(embedding_dim=128, vocab_size=Vb, num_layer=2, max_seq=64, dropout=0.0)
+    mt.load_state_dict(p0)
+    mt = mt.cuda().eval()
+    g = torch.Generator().manual_seed(3)
+    prior = torch.randint(0, Vb - 1, (2, 5), generator=g).to(DEV)
+    toks, scores, beams, bscores, _, _ = mt.generate_beam(prior, 10, 3, temperature=0.8, grammar=table, return_beams=True)
+    seqs = beams.reshape(6, 15)
+    out = mt.score(seqs, from_pos=5, temperature=0.8, grammar=table, logits="bf16")
+    assert out["count"].cpu().tolist() == [10] * 6
+    with torch.no_grad():
+        mx = float(mt(seqs)[0].float().abs().max())
+    got, want = out["sum"].cpu().numpy(), bscores.reshape(6).double().cpu().numpy()
+    live = np.isfinite(want)
+    assert live.sum() >= 4
+    err = np.abs(got[live] - want[live]).max()
+    print(f"grammar={grammar}: max |score sum - beam score| {err:.4f}, bound {10 * 4 * 2.0 ** -8 * mx:.4f}, scores {want}")
+    assert err <= 10 * 4 * 2.0 ** -8 * mx
+    assert abs(float(scores[0]) - got[0]) <= 10 * 4 * 2.0 ** -8 * mx          # the returned best beam is beam 0
+
+
+def _checkpoint(path, vocab, d, nl, max_seq, seed):
+    from musicgeneration_amd.network import MusicTransformer
+    torch.manual_seed(seed)
+    mt = MusicTransformer(embedding_dim=d, vocab_size=vocab, num_layer=nl, max_seq=max_seq, dropout=0)
+    torch.save({"net": mt.state_dict()}, path)
+    return mt
+
+
+def test_generate_cli_best_of(tmp_path, capsys, monkeypatch):
+    from musicgeneration_amd import generate
+    from musicgeneration_amd.train import vocab_of
+    ck = str(tmp_path / "random.pth")
+    mt = _checkpoint(ck, vocab_of("midi_like"), 128, 1, 64, 1).cuda().eval()
+    seen = {}
+    inner = generate._best_of
+
+    def spy(o, model, res, prompt_lens, grammar=None):
+        seen["res"], seen["lens"] = np.asarray(res).copy(), list(prompt_lens)
+        seen["chosen"] = inner(o, model, res, prompt_lens, grammar)
+        return seen["chosen"]
+    monkeypatch.setattr(generate, "_best_of", spy)
+    out = str(tmp_path / "g") + "/"
+    generate.main(["-s", ck, "-o", out, "-b", "2", "-l", "12", "--best-of", "3", "--num-layers", "1", "--d-model", "128", "-M", "64",
+                   "-d", str(tmp_path / "none")])
+    log = capsys.readouterr().out
+    assert len(glob.glob(out + "gen-*.mid")) == 2
+    printed = [float(v) for v in re.search(r"Best of 3: log-probabilities \[(.*)\]", log).group(1).split(",")]
+    assert seen["res"].shape == (6, 15) and seen["lens"] == [3] * 6 and len(printed) == 2
+    sums = mt.score(torch.from_numpy(seen["res"]).to(DEV), from_pos=3)["sum"].view(2, 3).cpu()
+    assert [round(float(v), 3) for v in sums.max(1).values] == printed
+    assert np.array_equal(seen["chosen"], seen["res"][[0 + int(sums[0].argmax()), 3 + int(sums[1].argmax())]])
+
+
+def test_score_cli(tmp_path, capsys):
+    from musicgeneration_amd import score
+    from musicgeneration_amd.data import Data
+    from musicgeneration_amd.train import vocab_of
+    vocab = vocab_of("midi_like")
+    data = tmp_path / "data"
+    data.mkdir()
+    rng = np.random.default_rng(0)
+    for i in range(20):                                       # the test split is the last tenth: two files
+        torch.save(rng.integers(0, vocab - 1, 40 + 5 * i).astype(np.uint16), str(data / f"piece{i:02d}.data"))
+    ck = str(tmp_path / "random.pth")
+    mt = _checkpoint(ck, vocab, 128, 1, 32, 2).cuda().eval()
+    js = str(tmp_path / "score.json")
+    fig = score.main(["-s", ck, "-d", str(data), "--split", "test", "-M", "32", "--d-model", "128", "--num-layers", "1",
+                      "--stride", "8", "--json", js])
+    log = capsys.readouterr().out
+    ds = Data(str(data), 2)
+    files = ds.file_dict["test"]
+    assert len(files) == 2
+    # score() on the same windows: the batch the tool builds, both files side by side, trailing pads after the shorter
+    lens = [len(ds.array(f)) for f in files]
+    x = np.full((2, max(lens)), vocab - 1, dtype=np.int64)
+    for r, f in enumerate(files):
+        x[r, :lens[r]] = ds.array(f)
+    assert min(lens) > 32
+    r = mt.score(torch.from_numpy(x).to(DEV), lengths=lens, stride=8)
+    total, count = float(r["sum"].sum()), int(r["count"].sum())
+    assert count == sum(len(ds.array(f)) - 1 for f in files) == fig["events"]
+    nats = float(re.search(r"nats/event: ([0-9.]+)", log).group(1))
+    assert abs(nats - (-total / count)) < 2e-6 and f"events: {count}" in log and "perplexity" in log and "accuracy" in log
+    rep = json.load(open(js))
+    assert [os.path.basename(e["file"]) for e in rep["files"]] == [os.path.basename(f) for f in files]
+    assert rep["total"]["events"] == count and abs(rep["total"]["bits_per_event"] - nats / np.log(2)) < 1e-5
+    assert all(e["events"] == len(ds.array(e["file"])) - 1 for e in rep["files"])
