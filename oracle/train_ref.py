@@ -22,6 +22,10 @@ For sums over rows or tokens (dgamma, dbeta, dxsum, dtable, stats[0], scatter) t
 The dropout mask is a pure integer function of (seed, element index): ``make_drop`` / ``hash32`` / ``drop_mult8`` are its
 integer twin and return the exact multiplier (0 or the fp32 constant ``scale``) of every element.
 
+The training attention (``csrc/rel_attn_*.hip``) has its references here too: ``rel_attn_fwd`` / ``rel_attn_bwd``, the per-element
+bounds ``attn_fwd_bounds`` / ``attn_weights_bound`` / ``attn_bwd_bounds`` and the seeded inputs of ``tests/test_gpu_attn_kernels.py``
+(Gaussian, far, the two selectors with an exact answer, the pad patterns), each asserting its preconditions from the reference.
+
 ``tests/test_train_ref.py`` ties these to independent fp64 computations (torch's own layer_norm / GRUCell / Adam / autograd,
 ``oracle.ref_cpu.smooth_ce``); ``tests/test_gpu_rowwise_kernels.py`` and ``tests/test_gpu_gru_kernels.py`` compare the
 kernels with them element by element.
@@ -625,3 +629,351 @@ def relu_mask(M, K, seed=0):
     if K >= 16:
         y.view(torch.int16)[0, 1:1 + len(MASK_SPECIALS)] = torch.tensor(MASK_SPECIALS, dtype=torch.int32).to(torch.int16)
     return y
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# K3 + K4: the training attention (tests/test_gpu_attn_kernels.py)
+# ---------------------------------------------------------------------------------------------------------------------
+TINY = 2.0 ** -124                                  # fp32 / bf16 underflow: a result below the smallest normal 2^-126 may be flushed to 0; four such steps
+U_BF = 2.0 ** -8                                    # unit roundoff of bf16 (8 significant bits) under RNE (pack_bf16x2): 1 + 2^-8 rounds to 1
+
+
+class Ref(dict):
+    """a dict whose entries read and write as attributes; hashed and compared by identity (a key of a cache)"""
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+    __setattr__ = dict.__setitem__
+    __hash__ = object.__hash__
+    __eq__ = object.__eq__
+
+
+def _attn_operands(qkv, E, heads, M):
+    """-> qs = q / 8, k, v [B, h, L, 64]; Eg [L, L, 64] with Eg[i, j] = Er[i - j] = E[M - 1 - (i - j)] for j <= i and 0 above the
+    diagonal; low [L, L] = (j <= i)"""
+    qkv, E = _d(qkv), _d(E)
+    B, L, d3 = qkv.shape
+    d = d3 // 3
+    assert d == 64 * heads and tuple(E.shape) == (M, 64) and M >= L
+    hd = lambda t: t.reshape(B, L, heads, 64).permute(0, 2, 1, 3)                                    # noqa: E731
+    i, j = torch.arange(L)[:, None], torch.arange(L)[None, :]
+    low = j <= i
+    Er = E[M - L:].flip(0)
+    Eg = Er[(i - j).clamp(min=0)] * low[..., None]
+    return hd(qkv[..., :d]) / 8.0, hd(qkv[..., d:2 * d]), hd(qkv[..., 2 * d:]), Eg, low
+
+
+def _merge(t):
+    """[B, h, L, 64] -> [B, L, h * 64]"""
+    B, h, L, c = t.shape
+    return t.permute(0, 2, 1, 3).reshape(B, L, h * c)
+
+
+def _heads(t, heads):
+    B, L = t.shape[:2]
+    return _d(t).reshape(B, L, heads, 64).permute(0, 2, 1, 3)
+
+
+def _attn_logits(qkv, E, pad_mask, heads, M, causal, Lk):
+    qs, k, v, Eg, low = _attn_operands(qkv, E, heads, M)
+    B, L = qs.shape[0], qs.shape[2]
+    S = qs @ k.transpose(-1, -2) + torch.einsum("bhic,ijc->bhij", qs, Eg)
+    A = qs.abs() @ k.abs().transpose(-1, -2) + torch.einsum("bhic,ijc->bhij", qs.abs(), Eg.abs())
+    # R: what the logit's rounding is proportional to.  Every kernel forms it from eight MFMA instructions of 16 columns each, D = C +
+    # sum of 16 exact products, 17 addends in an order of the hardware's own: at most 17 2^-24 (sum |products| + |C|) each.  Over the
+    # instructions the sums of |products| add up to A; the C operands are the partial sums of the relative term over 16, 32, 48 columns
+    # (pE), of the content term likewise (pK), and -- where the four K instructions continue the accumulator of the four Er ones
+    # (forward, dK/dV, recompute dQ) -- the whole relative term SE four times; the recompute dE kernel adds two chains: |S| once
+    SE = torch.einsum("bhic,ijc->bhij", qs, Eg)
+    R = A + 4 * SE.abs() + S.abs()
+    for c in (16, 32, 48):
+        R = R + (qs[..., :c] @ k[..., :c].transpose(-1, -2)).abs() + torch.einsum("bhic,ijc->bhij", qs[..., :c], Eg[..., :c]).abs()
+    A = Ref(A=A, R=R)
+    if causal:
+        assert Lk is None
+        vis = low[None, None].expand(B, 1, L, L)
+        if pad_mask is not None:
+            vis = vis & ~torch.as_tensor(pad_mask).bool()[:, None, None, :]
+    else:
+        assert pad_mask is None
+        vis = (torch.arange(L) < (L if Lk is None else Lk))[None, None, None, :].expand(B, 1, L, L)
+    assert vis.any(-1).all(), "a row without a visible key is outside the contract"
+    return qs, k, v, Eg, S, A, vis
+
+
+def rel_attn_fwd(qkv, E, pad_mask, heads, M, causal=True, Lk=None):
+    """mgx_rel_attn_fwd (causal: keys j <= i that are not padded; pad_mask bool [B, L], True = padded key) and
+    mgx_rel_attn_fwd_nomask (causal=False: keys j < Lk, the relative term for j <= i only), per (b, h) in fp64:
+      S [B, h, L, L]  qs_i . k_j + qs_i . Er[i - j], qs = q / 8 (unmasked values)      vis  the visible (i, j)
+      lse [B, h, L]   log sum_visible exp S          P = exp(S - lse) on visible, 0 elsewhere      ctx [B, L, d] = P v
+      A [B, h, L, L]  sum_c |qs_ic| (|k_jc| + |Er[i - j]_c|); R: A + the |C| operands of the eight MFMAs (_attn_logits)                           PV [B, L, d] = sum_j P_ij |v_jc|
+      V1 [B, L, d]    sum over the visible j of |v_jc| (the weight of an underflowed P)"""
+    qs, k, v, Eg, S, AR, vis = _attn_logits(qkv, E, pad_mask, heads, M, causal, Lk)
+    A, R = AR.A, AR.R
+    Sm = torch.where(vis, S, torch.full((), -float("inf"), dtype=F64))
+    lse = torch.logsumexp(Sm, -1)
+    P = torch.exp(Sm - lse[..., None])
+    return Ref(S=S, vis=vis, lse=lse, P=P, ctx=_merge(P @ v), A=A, R=R, PV=_merge(P @ v.abs()), V1=_merge(vis.to(F64) @ v.abs()), L=S.shape[-1])
+
+
+def attn_weights(ref, lse_in):
+    """mgx_rel_attn_weights on the lse it is handed: exp(S - lse_in) on visible entries, 0 elsewhere -> [B, h, L, L]"""
+    return torch.where(ref.vis, torch.exp(ref.S - _d(lse_in)[..., None]), torch.zeros((), dtype=F64))
+
+
+def _skew_sum(W, X):
+    """sum_{b, h, i} W[b, h, i, i - dl] X[b, h, i, c] -> [L, 64] by relative distance dl (W is zero above the diagonal)"""
+    L = W.shape[-1]
+    i, dl = torch.arange(L)[:, None], torch.arange(L)[None, :]
+    Wk = torch.gather(W, -1, (i - dl).clamp(min=0).expand(W.shape)) * (dl <= i)
+    return torch.einsum("bhid,bhic->dc", Wk, X)
+
+
+def rel_attn_bwd(qkv, E, pad_mask, ctx_in, lse_in, dctx, heads, M, causal=True, Lk=None):
+    """mgx_rel_attn_bwd / _parts: the formula block of csrc/rel_attn_bwd.hip on the values the kernels are HANDED -- ctx_in and
+    lse_in are inputs and are not recomputed:
+      P = exp(S - lse_in) on visible entries     dP = dO v^T     delta = rowsum(dO o ctx_in)     dS = P o (dP - delta)
+      dq = (sum_j dS_ij (k_j + Er[i - j])) / 8    dk_j = sum_i dS_ij qs_i    dv_j = sum_i P_ij dO_i    dEr[dl] = sum_{b,h,i} dS[i, i - dl] qs_i
+    -> dqkv [B, L, 3d], dE [M, 64] (the UPDATE: rows < M - L are zero), and what the bounds need: S, A, P, dS, dP - delta (dPd),
+    qs, k, Eg, dO per head, DV[i, j] = sum_c |dO_ic| |v_jc|, DC[i] = sum_c |dO_ic| |ctx_in_ic|"""
+    qs, k, v, Eg, S, AR, vis = _attn_logits(qkv, E, pad_mask, heads, M, causal, Lk)     # (causal=False: the CPU tie alone)
+    A, R = AR.A, AR.R
+    L = S.shape[-1]
+    dO, O = _heads(dctx, heads), _heads(ctx_in, heads)
+    lse_in = _d(lse_in)
+    P = torch.where(vis, torch.exp(S - lse_in[..., None]), torch.zeros((), dtype=F64))
+    dPd = dO @ v.transpose(-1, -2) - (dO * O).sum(-1, keepdim=True)
+    dS = P * dPd
+    dq = (dS @ k + torch.einsum("bhij,ijc->bhic", dS, Eg)) / 8.0
+    dk, dv = dS.transpose(-1, -2) @ qs, P.transpose(-1, -2) @ dO
+    dE = torch.zeros(M, 64, dtype=F64)
+    dE[M - L:] = _skew_sum(dS, qs).flip(0)
+    return Ref(dqkv=torch.cat([_merge(dq), _merge(dk), _merge(dv)], -1), dE=dE, S=S, A=A, R=R, P=P, dS=dS, dPd=dPd, qs=qs, k=k, Eg=Eg, dO=dO, vis=vis,
+               lse=lse_in, DV=dO.abs() @ v.abs().transpose(-1, -2), DC=(dO.abs() * O.abs()).sum(-1), L=L, M=M)
+
+
+LOGIT_U = 17 * EPS32                                # per MFMA instruction: 17 addends (16 exact bf16 products and C), any order
+
+
+def attn_eps(R, S, lse, vis_or_P):
+    """the relative error of P_ij as the kernels form it: eps_ij = expm1(17 2^-24 R_ij + 2^-22 (|S_ij| + |lse_i|)) + 2^-21, 0 on
+    entries that are not visible (R: _attn_logits; tests/test_gpu_attn_kernels.py derives the rest)"""
+    e = torch.expm1(LOGIT_U * R + 2.0 ** -22 * (S.abs() + lse.abs()[..., None])) + 2.0 ** -21
+    return torch.where(vis_or_P, e, torch.zeros((), dtype=F64))
+
+
+def attn_fwd_bounds(ref):
+    """-> per-element bounds (ctx [B, L, d], lse [B, h, L], eps [B, h, L, L]) of the forward"""
+    L = ref.L
+    eps = attn_eps(ref.R, ref.S, ref.lse, ref.vis)
+    eps_i = eps.amax(-1)                                                     # [B, h, L]
+    rel = U_BF + 2 * eps_i + (L + 2) * EPS32
+    rel = rel[..., None].expand(*eps_i.shape, 64)
+    ctx = 2.0 ** -8 * ref.ctx.abs() + (1 + 2.0 ** -8) * (_merge(rel) * ref.PV + TINY * ref.V1)
+    # lse: log-sum-exp moves by a weighted mean of the logits' errors (mean value theorem), the weights a softmax at a point between
+    # the exact and the computed logits: within exp(2 max error) of P.  The row sum l is added up five deep inside a tile (exp_tile's
+    # four chains), once per tile, once across the lane halves, and is rescaled: L / 32 + 8 roundings.  __logf and the last add: 2 ulp
+    Rv = torch.where(ref.vis, ref.R, torch.zeros((), dtype=F64))
+    lse = LOGIT_U * (ref.P * Rv).sum(-1) * torch.exp(2 * LOGIT_U * Rv.amax(-1)) + (L // 32 + 8) * EPS32 + 2 * ulp32(ref.lse)
+    return ctx, lse, eps
+
+
+def attn_weights_bound(ref, lse_in, W):
+    return (attn_eps(ref.R, ref.S, _d(lse_in), ref.vis) + 2.0 ** -23) * W + TINY * ref.vis
+
+
+def attn_bwd_bounds(r, B_total, dE0=None):
+    """-> per-element bounds (dqkv [B, L, 3d], dE [M, 64]) of the backward from its reference ``r``; dE0 the start value of dE"""
+    L, M = r.L, r.M
+    heads = r.qs.shape[1]
+    eps = attn_eps(r.R, r.S, r.lse, r.P > 0)
+    g = r.P * (eps * r.dPd.abs() + 66 * EPS32 * (r.DV + r.DC[..., None])) + U_BF * r.dS.abs() + TINY * r.vis * (r.dPd.abs() + 1)
+    G = g + L * EPS32 * r.dS.abs()
+    W = (eps + U_BF + L * EPS32) * r.P + TINY * r.vis
+    bq = (G @ r.k.abs() + torch.einsum("bhij,ijc->bhic", G, r.Eg.abs())) / 8.0
+    bk, bv = G.transpose(-1, -2) @ r.qs.abs(), W.transpose(-1, -2) @ r.dO.abs()
+    b = 2.0 ** -8 * r.dqkv.abs() + (1 + 2.0 ** -8) * torch.cat([_merge(bq), _merge(bk), _merge(bv)], -1)
+    start = torch.zeros(M, 64, dtype=F64) if dE0 is None else _d(dE0)
+    bE = torch.zeros(M, 64, dtype=F64)
+    bE[M - L:] = _skew_sum(g + B_total * heads * L * EPS32 * r.dS.abs(), r.qs.abs()).flip(0)
+    bE[M - L:] += ulp32(torch.maximum(start.abs(), (start + r.dE).abs()))[M - L:]
+    return b, bE
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------------
+ATTN_PADS = ("none", "trailing", "interior", "tile", "second", "bits")
+
+
+def attn_pads(name, B, L, seed=0):
+    """bool [B, L] (True = padded key) or None.  Position 0 is always real, so every row sees a key.
+      trailing  the last 1 .. L/2 keys of every batch row            interior  four single keys per row
+      tile      a whole 32-key tile (keys 32 .. 63; at L = 32 the upper half of the only tile) of batch row 0, one key elsewhere
+      second    every second key (1, 3, 5, ..)
+      bits      bit 31 of a word (key 31, and key L - 1) and bit 0 of a word (key 32 and key L - 32, where L >= 64)"""
+    if name == "none":
+        return None
+    g = _gen(B, L, seed, 21 + ATTN_PADS.index(name))
+    m = torch.zeros(B, L, dtype=torch.bool)
+    if name == "trailing":
+        for b in range(B):
+            m[b, L - int(torch.randint(1, L // 2 + 1, (1,), generator=g)):] = True
+    elif name == "interior":
+        for b in range(B):
+            m[b, torch.randint(1, L, (4,), generator=g)] = True
+    elif name == "tile":
+        m[0, (32 if L >= 64 else 16):(64 if L >= 64 else 32)] = True
+        m[1:, L // 2] = True
+    elif name == "second":
+        m[:, 1::2] = True
+    elif name == "bits":
+        m[:, 31] = True
+        m[:, L - 1] = True
+        if L >= 64:
+            m[:, 32] = True
+            m[:, L - 32] = True
+    else:
+        raise ValueError(name)
+    assert not m[:, 0].any() and m.any()
+    return m
+
+
+def pack_padbits(mask):
+    """the bitmap of mgx_pad_bitmap: int32 [B, L / 32] holding uint32 words, bit (j & 31) of word j >> 5 set iff key j is padded"""
+    B, L = mask.shape
+    w = (mask.reshape(B, L // 32, 32).numpy().astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1).astype(np.uint32)
+    return torch.from_numpy(w.view(np.int32).copy())
+
+
+def attn_gauss(B, L, heads, M, seed=0):
+    """the scales of tests/test_gpu_kernels.py: qkv 0.8, E 0.5, dctx 1.0, all bf16 -> (qkv, E, dctx)"""
+    g = _gen(B, L, heads, M, seed, 31)
+    d = 64 * heads
+    return ((torch.randn(B, L, 3 * d, generator=g) * 0.8).to(BF), (torch.randn(M, 64, generator=g) * 0.5).to(BF),
+            torch.randn(B, L, d, generator=g).to(BF))
+
+
+def attn_far(B, L, heads, M, seed=0):
+    """Gaussian data of scale 0.3 in which query row L - 20 of (batch row 0, head 0) is 4.0 in every column and so is key 40
+    (L < 160) or 70 (key tile 1 or 2): that logit is 64 * 16 / 8 = 128 + the relative term.  The forward's lazy softmax reference
+    then lags by far more than 40 nats when the sweep reaches that tile (its redo and rescale branch; the kernel's threshold is a
+    tile sum of 1e24, 55.3 nats); at L >= 160 the tile lies in the branch-free main loop of the last query block.  Without pads.
+    The jump is asserted from the reference -> (qkv, E, dctx, (i, j))"""
+    assert L >= 96
+    g = _gen(B, L, heads, M, seed, 32)
+    d = 64 * heads
+    qkv, E = (torch.randn(B, L, 3 * d, generator=g) * 0.3).to(BF), (torch.randn(M, 64, generator=g) * 0.3).to(BF)
+    i, j = L - 20, (40 if L < 160 else 70)
+    qkv[0, i, :64] = 4.0
+    qkv[0, j, d:d + 64] = 4.0
+    S = rel_attn_fwd(qkv, E, None, heads, M).S[0, 0, i]
+    t = j // 32
+    assert t >= 1 and 32 * (t + 1) <= (i // 128) * 128 or L < 160
+    jump = (S[32 * t:32 * t + 32].max() - S[:32 * t].max()).item()
+    assert jump > 60.0 and S[j] == S[:i + 1].max(), jump
+    return qkv, E, torch.randn(B, L, d, generator=g).to(BF), (i, j)
+
+
+SEL_MARGIN = 256.0                                   # nats: exp2(-256 log2 e) = 2^-369 is 0 in fp32 (smallest subnormal 2^-149)
+SEL_REL_DELTAS = (0, 1, 31, 32, 33, 127, 128, -1)    # -1 stands for L - 1
+
+
+def _small_ints(g, lim, *shape):
+    """non-zero-mean small integers of magnitude <= lim"""
+    return torch.randint(-lim, lim + 1, shape, generator=g).float()
+
+
+def _selector_check(qkv, E, dctx, pad_mask, heads, M, sel, rows, causal=True, Lk=None):
+    """from the reference alone: on the rows ``rows`` [B, L] the softmax is one-hot on key sel [B, L] by SEL_MARGIN nats; the values
+    and the sums of the exact answer are integers that bf16 / fp32 hold exactly -> the exact answer (ctx, dv) as fp64"""
+    B, L = sel.shape
+    d = 64 * heads
+    ref = rel_attn_fwd(qkv, E, pad_mask, heads, M, causal, Lk)
+    Sm = torch.where(ref.vis, ref.S, torch.full((), -float("inf"), dtype=F64))
+    top = Sm.gather(-1, sel[:, None, :, None].expand(B, heads, L, 1))[..., 0]
+    rest = Sm.scatter(-1, sel[:, None, :, None].expand(B, heads, L, 1), -float("inf")).amax(-1)
+    ok = rows[:, None, :].expand(B, heads, L)
+    assert ok.any() and (top - rest)[ok].min() >= SEL_MARGIN, "the margin does not hold"
+    v, dO = _d(qkv[..., 2 * d:]), _d(dctx)
+    assert (v == v.round()).all() and (dO == dO.round()).all()
+    ctx = torch.gather(v, 1, sel[..., None].expand(B, L, d))
+    dv = torch.zeros(B, L, d, dtype=F64).scatter_add_(1, sel[..., None].expand(B, L, d), dO * rows[..., None])
+    absum = torch.zeros(B, L, d, dtype=F64).scatter_add_(1, sel[..., None].expand(B, L, d), dO.abs() * rows[..., None])
+    assert (bf16_round(dv) == dv).all() and absum.max() < 2 ** 8, "an integer sum is not exact in bf16"
+    assert (dO.abs().sum(-1).max() * v.abs().max()) * 64 < 2 ** 24                      # delta, dP: exact in fp32 in any order
+    real = torch.ones(B, L, dtype=torch.bool) if pad_mask is None else ~torch.as_tensor(pad_mask)
+    if not causal:
+        real = real & (torch.arange(L) < (Lk or L))[None, :]
+    tiles = [(sel[rows] // 32 == t).any().item() for t in range(L // 32) if real[:, 32 * t:32 * t + 32].any()]
+    return ref, ctx, dv, all(tiles)
+
+
+def attn_selector_rel(B, L, heads, M, delta0, pad_mask, seed=0):
+    """the RELATIVE selector: k = 0, q_i = 8 u for one fixed +-1 vector u, E zero except row M - 1 - delta0 = c u with c =
+    4 (exact in bf16): S[i, i - delta0] = 64 c = 256 and every other logit is 0, so row i >= delta0 attends to key i - delta0 alone
+    (unless that key is padded; rows i < delta0, and rows whose key is padded, attend uniformly and are held to the bounds alone).  v and dO are integers of magnitude <= 8 and <= 3.
+    -> (qkv, E, dctx, sel [B, L], rows bool [B, L] = the rows with the exact answer, exact ctx, exact dv)"""
+    g = _gen(B, L, heads, M, delta0, seed, 33)
+    d = 64 * heads
+    u = torch.where(torch.rand(64, generator=g) < 0.5, 1.0, -1.0)         # one E serves every head: one u
+    qkv = torch.zeros(B, L, 3 * d)
+    qkv[..., :d] = 8.0 * u.repeat(heads)
+    qkv[..., 2 * d:] = _small_ints(g, 8, B, L, d)
+    E = torch.zeros(M, 64)
+    c = 4.0
+    E[M - 1 - delta0] = c * u
+    dctx = _small_ints(g, 3, B, L, d)
+    i = torch.arange(L)[None, :].expand(B, L)
+    sel = (i - delta0).clamp(min=0)
+    rows = i >= delta0
+    if pad_mask is not None:
+        rows = rows & ~torch.gather(pad_mask, 1, sel)
+    qkv, E, dctx = qkv.to(BF), E.to(BF), dctx.to(BF)
+    assert E[M - 1 - delta0, 0].abs().item() == c
+    ref, ctx, dv, _ = _selector_check(qkv, E, dctx, pad_mask, heads, M, sel, rows)
+    return qkv, E, dctx, sel, rows, ctx, dv
+
+
+def attn_code(idx):
+    """+-1 [.., 64]: bit (c % 9) of the index decides column c, so two different indices below 512 differ in >= 7 columns"""
+    bits = (torch.as_tensor(idx)[..., None] >> (torch.arange(64) % 9)) & 1
+    return (1.0 - 2.0 * bits).float()
+
+
+def attn_selector_content(B, L, heads, M, pad_mask, seed=0, causal=True, Lk=None):
+    """the CONTENT selector: E = 0, k_j = c code(j) with c = 148 (exact in bf16), q_i = code(t(i)): S[i, j] = c (64 - 2 #differing
+    columns) / 8 is 1184 at j = t(i) and at most 1184 - 259 elsewhere.  t(i) is a seeded choice among the real keys the row may see
+    (j <= i; j < Lk without the causal mask) that also crosses tile and 128-row block boundaries; rows 32 t + 31 take a key of tile t,
+    so that every tile that has a real key is selected.  Every row is one-hot: dq, dk and dE are exactly 0.
+    -> (qkv, E, dctx, sel, rows (all True), exact ctx, exact dv)"""
+    assert L < 512
+    g = _gen(B, L, heads, M, seed, 34, int(causal), Lk or 0)
+    d = 64 * heads
+    c = 148.0
+    real = torch.ones(B, L, dtype=torch.bool) if pad_mask is None else ~pad_mask
+    sel = torch.zeros(B, L, dtype=torch.long)
+    for b in range(B):
+        for i in range(L):
+            hi = (i + 1) if causal else (Lk or L)
+            cand = torch.nonzero(real[b, :hi])[:, 0]
+            if i % 32 == 31:
+                own = cand[(cand >= i - 31) & (cand <= i)]
+                cand = own if own.numel() else cand
+            sel[b, i] = cand[int(torch.randint(0, cand.numel(), (1,), generator=g))]
+    qkv = torch.zeros(B, L, 3 * d)
+    qkv[..., :d] = attn_code(sel).repeat(1, 1, heads)
+    qkv[..., d:2 * d] = c * attn_code(torch.arange(L)).repeat(1, heads)
+    qkv[..., 2 * d:] = _small_ints(g, 8, B, L, d)
+    E, dctx = torch.zeros(M, 64), _small_ints(g, 3, B, L, d)
+    qkv, E, dctx = qkv.to(BF), E.to(BF), dctx.to(BF)
+    assert (qkv[0, 1, d:2 * d].float().abs() == c).all()
+    rows = torch.ones(B, L, dtype=torch.bool)
+    if not causal:
+        rows = rows & (torch.arange(L) < (Lk or L))[None, :]
+    ref, ctx, dv, every_tile = _selector_check(qkv, E, dctx, pad_mask, heads, M, sel, rows, causal, Lk)
+    assert every_tile, "a key tile with a real key is never selected"
+    if causal and L >= 160:
+        assert ((sel // 128) < (torch.arange(L)[None, :] // 128)).any(), "no row selects a key of an earlier 128-row block"
+    return qkv, E, dctx, sel, rows, ctx, dv

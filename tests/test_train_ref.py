@@ -1,6 +1,7 @@
 """oracle/train_ref.py (the fp64 references of the row-wise and GRU training kernels) against independent fp64 computations:
 torch's own layer_norm / GRUCell / Adam / index_add_ and autograd, oracle.ref_cpu.smooth_ce, and hand-computed words of the
-dropout hash.  Also the preconditions of the inputs the GPU tests build.  No GPU."""
+dropout hash; the attention references against oracle.ref_cpu.attn_core in fp64 and its autograd.  Also the preconditions of the
+inputs the GPU tests build.  No GPU."""
 import math
 
 import numpy as np
@@ -354,3 +355,102 @@ def test_dw_mchunk_twin_gives_the_intended_reduction_tiles():
     for M in (1, 63, 64, 65):
         assert T.dw_tile_plan(M, [(136, 200)], False) == (64, M == 64, 1)          # (65: a second split of one row)
     assert T.dw_tile_plan(6144, [(8, 8), (72, 200), (136, 8), (128, 128), (64, 64), (256, 128), (8, 200), (136, 200)], True) == (192, True, 3)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the training attention
+# ---------------------------------------------------------------------------------------------------------------------
+ATTN_TIES = [(2, 32, 1, 32, "none", None), (2, 64, 2, 65, "trailing", None), (1, 96, 3, 196, "interior", None), (2, 160, 1, 160, "tile", None),
+             (2, 96, 2, 100, "second", None), (1, 64, 1, 64, "bits", None), (2, 64, 2, 70, "none", 64), (1, 96, 1, 96, "none", 37), (2, 160, 2, 161, "none", 100)]
+
+
+@pytest.mark.parametrize("B,L,heads,M,pads,Lk", ATTN_TIES)
+def test_attention_references_are_attn_core_in_fp64_and_its_autograd(B, L, heads, M, pads, Lk):
+    """rel_attn_fwd == oracle.ref_cpu.attn_core run in fp64 (causal with pads; Lk: the non-causal form, keys >= Lk masked); with
+    ctx_in, lse_in its own fp64 forward, rel_attn_bwd == fp64 autograd through attn_core"""
+    qkv, E, dctx = T.attn_gauss(B, L, heads, M)
+    pm = T.attn_pads(pads, B, L)
+    causal = Lk is None
+    if causal:
+        mask = (torch.arange(L)[None, :] > torch.arange(L)[:, None])[None, None]
+        if pm is not None:
+            mask = mask | pm[:, None, None, :]
+    else:
+        mask = (torch.arange(L) >= Lk)[None, None, None, :]
+    qa, Ea = qkv.double().requires_grad_(), E.double().requires_grad_()
+    ctx, w, logits = R.attn_core(qa, Ea, mask, heads)
+    (ctx * dctx.double()).sum().backward()
+    ref = T.rel_attn_fwd(qkv, E, pm, heads, M, causal, Lk)
+    close(ref.ctx, ctx.detach())
+    close(ref.P, w.detach())
+    close(ref.lse, torch.logsumexp(logits.detach(), -1))
+    assert (ref.P[~ref.vis.expand_as(ref.P)] == 0).all() and (ref.A >= ref.S.abs()).all() and (ref.R >= ref.A).all() and (ref.R <= 12 * ref.A + 1e-300).all() and (ref.PV >= ref.ctx.abs()).all()
+    r = T.rel_attn_bwd(qkv, E, pm, ref.ctx, ref.lse, dctx, heads, M, causal, Lk)
+    close(r.dqkv, qa.grad, 1e-12)
+    close(r.dE, Ea.grad, 1e-12)
+    assert M == L or (r.dE[:M - L] == 0).all()
+    close(T.attn_weights(ref, ref.lse), ref.P)
+    if causal:
+        b, bE = T.attn_bwd_bounds(r, B)
+        cb, lb, eps = T.attn_fwd_bounds(ref)
+        assert (b[r.dqkv != 0] > 0).all() and (b >= 0).all() and (bE[M - L:] > 0).all() and (bE[:M - L] == 0).all() and (cb > 0).all() and (lb > 0).all()
+        # the bounds are bounds of rounding: a bf16 ulp of the output and a few of its absolute sum, far below the data's own scale
+        assert (cb <= 2.0 ** -6 * ref.PV + 1e-300).all() and lb.max() < 2.0 ** -10
+
+
+def test_attention_backward_reference_takes_ctx_and_lse_as_given():
+    """the backward is the kernels' formula on the values handed in: another lse scales P, another ctx moves delta"""
+    qkv, E, dctx = T.attn_gauss(1, 32, 1, 32)
+    ref = T.rel_attn_fwd(qkv, E, None, 1, 32)
+    a = T.rel_attn_bwd(qkv, E, None, ref.ctx, ref.lse, dctx, 1, 32)
+    b = T.rel_attn_bwd(qkv, E, None, ref.ctx, ref.lse + math.log(2.0), dctx, 1, 32)
+    close(b.P, a.P / 2)
+    c = T.rel_attn_bwd(qkv, E, None, torch.zeros_like(ref.ctx), ref.lse, dctx, 1, 32)
+    close(c.dS, a.P * (a.dO @ T._heads(qkv[..., 128:], 1).transpose(-1, -2)))
+
+
+def test_pad_patterns_and_bitmap():
+    for L in (32, 96, 160):
+        for name in T.ATTN_PADS[1:]:
+            m = T.attn_pads(name, 3, L)
+            assert m.shape == (3, L) and not m[:, 0].any() and m.any()
+            w = T.pack_padbits(m).numpy().view(np.uint32)
+            for b, j in ((0, 31), (2, L - 1), (1, L // 2), (0, 1)):
+                assert bool((w[b, j >> 5] >> (j & 31)) & 1) == bool(m[b, j])
+    m = T.attn_pads("bits", 1, 96)
+    assert m[0, 31] and m[0, 32] and m[0, 64] and m[0, 95] and m.sum() == 4
+    assert T.attn_pads("tile", 2, 96)[0, 32:64].all() and T.attn_pads("second", 1, 32)[0, 1::2].all()
+
+
+@pytest.mark.parametrize("L", (32, 96, 160, 288))
+def test_selector_data_has_the_exact_answer_it_claims(L):
+    """the builders assert margin, exactness and tile cover from the reference; here the references reproduce the exact answer
+    and the bounds collapse: about a bf16 ulp of the selected value for ctx, exactly 0 for dq / dk where nothing can contribute"""
+    B, heads, M = 2, 2, L + 1
+    for pads in T.ATTN_PADS:
+        pm = T.attn_pads(pads, B, L)
+        qkv, E, dctx, sel, rows, ctx, dv = T.attn_selector_content(B, L, heads, M, pm)
+        ref = T.rel_attn_fwd(qkv, E, pm, heads, M)
+        assert (ref.ctx - ctx).abs().max() < 1e-100 and rows.all()
+        cb, lb, _ = T.attn_fwd_bounds(ref)
+        assert (cb <= 2.0 ** -4 * ctx.abs() + 2.0 ** -100).all() and (cb[ctx == 0] < 2.0 ** -100).all()          # (the underflow floor)
+        r = T.rel_attn_bwd(qkv, E, pm, ref.ctx.to(BF), ref.lse.float(), dctx, heads, M)
+        d = 64 * heads
+        # (fp64 keeps exp(-259), fp32 does not)
+        assert r.dqkv[..., :2 * d].abs().max() < 1e-100 and r.dE.abs().max() < 1e-100 and (r.dqkv[..., 2 * d:] - dv).abs().max() < 1e-100
+        b, bE = T.attn_bwd_bounds(r, B)
+        assert b[..., 2 * d:].max() < 0.5 and cb.max() < 0.5       # a whole integer off fails outright
+        for d0 in T.SEL_REL_DELTAS:
+            d0 = L - 1 if d0 < 0 else d0
+            if d0 < L:
+                qkv, E, dctx, sel, rows, ctx, dv = T.attn_selector_rel(B, L, heads, M, d0, pm)
+                ref = T.rel_attn_fwd(qkv, E, pm, heads, M)
+                assert (ref.ctx - ctx)[rows].abs().max() < 1e-100
+                r = T.rel_attn_bwd(qkv, E, pm, ref.ctx.to(BF), ref.lse.float(), dctx, heads, M)
+                assert r.dqkv[..., :d][rows].abs().max() < 1e-100
+
+
+def test_far_data_jumps():
+    for L in (96, 160, 288):
+        qkv, E, dctx, (i, j) = T.attn_far(2, L, 2, L)
+        assert j // 32 >= 1 and (L < 160 or j // 32 < (i // 128) * 4)
