@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce */
-#define MGX_ABI_VERSION 24
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped */
+#define MGX_ABI_VERSION 25
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -198,6 +198,41 @@ int mgx_smooth_ce_bwd(const uint16_t* logits, const int32_t* target, const float
  * pass.  step >= 1 (bias correction as torch.optim.Adam), gscale multiplies g (e.g. 1/world).   */
 int mgx_adam_step(float* p, const float* g, float* m, float* v, uint16_t* shadow, size_t n,
                   float lr, float beta1, float beta2, float eps, int step, float gscale, void* stream);
+/* ---- K11b (ABI 25): clip the global gradient norm on the device; skip a non-finite step        torch.nn.utils.clip_grad_norm_
+ * mgx_grad_norm measures g f32 [n] (16-byte aligned) and leaves, in *state, the factor the following mgx_adam_step_clipped
+ * multiplies g by -- no host round trip, no allocation, no synchronisation (capturable); two launches, no atomics:
+ *   1. min(max(ceil(n/4/256), 1), MGX_GRAD_NORM_PARTS) blocks (a function of n only); block b writes workspace[b] = the sum of
+ *      g[i]^2 over its share.  Every square is formed IN FP64 (exact for fp32 inputs) and every addition is fp64, in a fixed
+ *      order: the result is bit-reproducible whatever mgx_set_deterministic says, the relative error of the sum of n
+ *      non-negative terms is <= (n-1) 2^-53 in any order, squares of 1e25 or 1e-30 neither overflow nor vanish, and the sum is
+ *      non-finite IF AND ONLY IF some g[i] is +-inf or NaN.
+ *   2. one block: sum = the partials written, in index order; norm = sqrt(sum) * |gscale|, all in fp64.
+ *        norm finite:  coef = min(1, max_norm / (norm + 1e-6))       (clip_grad_norm_'s formula, in fp64)
+ *                      scale = (float)((double)gscale * coef)        rounded once;  skipped_last = 0;  n_clipped += (coef < 1)
+ *        otherwise:    scale = 0;  skipped_last = 1;  n_skipped += 1
+ *      norm is stored either way (a non-finite one says what was met).
+ *   gscale is the factor the gradient is scaled by anyway (mgx_adam_step's gscale, e.g. 1/world): the norm is that of g * gscale
+ *   (a gscale that is itself inf or NaN makes the norm non-finite: the step is skipped).
+ *   max_norm > 0; +inf = measure and guard, never clip (coef = 1, scale == gscale bit for bit); <= 0 or NaN: MGX_ERR_SHAPE.
+ *   workspace: double [MGX_GRAD_NORM_PARTS], caller-owned, 8-byte aligned; only the first `blocks` entries are written.
+ *   state: 32 bytes, 8-byte aligned, ZEROED ONCE by the caller; the counters then run over the calls.  Nothing else is written. */
+typedef struct {
+    double norm;           /* sqrt(sum g^2) * |gscale| of the last call, before clipping */
+    float scale;           /* what mgx_adam_step_clipped multiplies g by: gscale * coef, or 0 for a skipped step */
+    uint32_t skipped_last; /* 1: the last call met a non-finite gradient */
+    uint64_t n_clipped;    /* calls with coef < 1 */
+    uint64_t n_skipped;    /* calls with a non-finite norm */
+} mgx_clip_state;
+#define MGX_GRAD_NORM_PARTS 1024
+int mgx_grad_norm(const float* g, size_t n, float gscale, float max_norm, double* workspace, mgx_clip_state* state,
+                  void* stream);
+/* mgx_adam_step with gscale = state->scale, read on the device (one uniform load at kernel entry): the same per-element code,
+ * bc1 and bc2s from the host's `step` as in mgx_adam_step -- with max_norm = +inf and finite gradients the result is
+ * BIT-IDENTICAL to mgx_adam_step(..., step, gscale).  If state->skipped_last is set the kernel returns before its first store:
+ * p, m, v and shadow keep their bits.  `step` counts optimiser CALLS, skipped ones included (the bias correction of the step
+ * after a skipped one is that of step + 1): a device-side counter would cost the host a read for every state_dict.        */
+int mgx_adam_step_clipped(float* p, const float* g, float* m, float* v, uint16_t* shadow, size_t n, float lr, float beta1,
+                          float beta2, float eps, int step, const mgx_clip_state* state, void* stream);
 /* shadow bf16 [n] = round(p f32 [n]): nearest even, subnormals kept, +-inf kept, NaN -> a NaN (payload unspecified) */
 int mgx_cast_bf16(const float* p, uint16_t* shadow, size_t n, void* stream);
 

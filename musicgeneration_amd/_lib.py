@@ -13,7 +13,7 @@ _vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
 
 # the ABI the SIGNATURES table below was written for (MGX_ABI_VERSION of include/mgx.h).  A left-over
 # libmgx.so of another ABI still exports the same names: calling it with this table would shift arguments.
-EXPECTED_ABI = 24
+EXPECTED_ABI = 25
 
 # name -> argtypes ; every symbol declared in include/mgx.h (restype int unless noted)
 SIGNATURES = {
@@ -94,6 +94,9 @@ SIGNATURES = {
     "mgx_linear_dw_grouped": [_vp, _i, _i, _vp, _sz, _vp],
     "mgx_linear_dw_grouped_workspace": [_vp, _i, _i],     # returns size_t
     "mgx_linear_dw": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    # ABI 25: global gradient-norm clipping, non-finite-step guard
+    "mgx_grad_norm": [_vp, _sz, _f, _f, _vp, _vp, _vp],
+    "mgx_adam_step_clipped": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _vp, _vp],
 }
 
 _lib = None

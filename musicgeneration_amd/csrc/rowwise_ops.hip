@@ -709,21 +709,27 @@ extern "C" int mgx_smooth_ce_bwd(const uint16_t* logits, const int32_t* target, 
 // =================================================================================================
 // K11  Adam on one flat buffer + bf16 shadow                                train.py:143
 // =================================================================================================
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v,
-                                                   uint16_t* __restrict__ shadow, size_t n, float lr, float b1,
-                                                   float b2, float eps, float bc1, float bc2s, float gscale) {
-    // torch.optim.Adam: p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+// One element of torch.optim.Adam on g * gscale: p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).  Updates m and v, returns the new p.
+MGX_DEV float adam_update(float p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1, float bc2s,
+                          float gscale) {
+    const float gk = g * gscale;
+    m = b1 * m + (1.f - b1) * gk;
+    v = b2 * v + (1.f - b2) * gk * gk;
+    return p - (lr / bc1) * m / (sqrtf(v) / bc2s + eps);
+}
+// The sweep of both Adam kernels: f32x4 groups in a grid-stride loop, then the n % 4 tail by the first threads of the grid.
+MGX_DEV void adam_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                        uint16_t* __restrict__ shadow, size_t n, float lr, float b1, float b2, float eps, float bc1, float bc2s,
+                        float gscale) {
     const size_t n4 = n >> 2;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float gk = gg[k] * gscale;
-            mm[k] = b1 * mm[k] + (1.f - b1) * gk;
-            vv[k] = b2 * vv[k] + (1.f - b2) * gk * gk;
-            pp[k] -= (lr / bc1) * mm[k] / (sqrtf(vv[k]) / bc2s + eps);
+            float mk = mm[k], vk = vv[k];
+            pp[k] = adam_update(pp[k], gg[k], mk, vk, lr, b1, b2, eps, bc1, bc2s, gscale);
+            mm[k] = mk; vv[k] = vk;
         }
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
         if (shadow) {
@@ -735,12 +741,75 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     const size_t t0 = n4 << 2;
     const size_t i = t0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        const float gk = g[i] * gscale;
-        const float mk = b1 * m[i] + (1.f - b1) * gk, vk = b2 * v[i] + (1.f - b2) * gk * gk;
+        float mk = m[i], vk = v[i];
+        const float pk = adam_update(p[i], g[i], mk, vk, lr, b1, b2, eps, bc1, bc2s, gscale);
         m[i] = mk; v[i] = vk;
-        const float pk = p[i] - (lr / bc1) * mk / (sqrtf(vk) / bc2s + eps);
         p[i] = pk;
         if (shadow) shadow[i] = f32_to_bf16(pk);
+    }
+}
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                   float* __restrict__ m, float* __restrict__ v,
+                                                   uint16_t* __restrict__ shadow, size_t n, float lr, float b1,
+                                                   float b2, float eps, float bc1, float bc2s, float gscale) {
+    adam_sweep(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale);
+}
+// The same sweep with the gradient scale of mgx_grad_norm, read from device memory; a skipped step stores nothing.
+__global__ __launch_bounds__(256) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           uint16_t* __restrict__ shadow, size_t n, float lr, float b1,
+                                                           float b2, float eps, float bc1, float bc2s,
+                                                           const mgx_clip_state* __restrict__ state) {
+    const float gscale = state->scale;                 // uniform: one scalar load for the wave
+    if (state->skipped_last) return;
+    adam_sweep(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale);
+}
+
+// Global gradient norm, launch 1: workspace[block] = sum of g[i]^2 over the block's grid-stride share, in fp64 from the first
+// addition (the square of an fp32 is exact in fp64; all terms >= 0).  Fixed order: per thread in index order, then a shuffle
+// tree over the 64 lanes, then the four waves through LDS.  No atomics, so two runs give the same bits.
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const float* __restrict__ g, size_t n, double* __restrict__ workspace) {
+    const size_t n4 = n >> 2;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    double acc = 0.0;
+#pragma unroll 4
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        const f32x4 gg = ((const f32x4*)g)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc += (double)gg[k] * (double)gg[k];
+    }
+    // tail (n % 4), as in adam_sweep
+    const size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) acc += (double)g[i] * (double)g[i];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    __shared__ double wsum[4];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) workspace[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+// Launch 2, one block: the partials in index order, the norm, torch's clip coefficient, the counters.
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const double* __restrict__ workspace, int parts, float gscale,
+                                                                 float max_norm, mgx_clip_state* __restrict__ state) {
+    __shared__ double part[MGX_GRAD_NORM_PARTS];
+    for (int i = threadIdx.x; i < parts; i += 256) part[i] = workspace[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    // a chain of `parts` dependent fp64 additions: unrolled far enough that the LDS reads run ahead of it
+    double sum = 0.0;
+#pragma unroll 64
+    for (int i = 0; i < parts; ++i) sum += part[i];
+    const double norm = sqrt(sum) * fabs((double)gscale);
+    state->norm = norm;
+    if (isfinite(norm)) {
+        const double coef = fmin(1.0, (double)max_norm / (norm + 1e-6));
+        state->scale = (float)((double)gscale * coef);
+        state->skipped_last = 0u;
+        if (coef < 1.0) state->n_clipped += 1;
+    } else {
+        state->scale = 0.f;
+        state->skipped_last = 1u;
+        state->n_skipped += 1;
     }
 }
 __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict__ p, uint16_t* __restrict__ s, size_t n) {
@@ -748,6 +817,14 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) s[i] = f32_to_bf16(p[i]);
 }
 
+// the host's part of both Adam entry points: bias corrections of `step` (bc1 = 1 - b1^step, bc2s = sqrt(1 - b2^step)) and the grid
+struct AdamLaunch { float bc1, bc2s; unsigned blocks; };
+static AdamLaunch adam_launch(size_t n, float beta1, float beta2, int step) {
+    size_t blocks = (n / 4 + 255) / 256;
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    return {1.f - powf(beta1, (float)step), sqrtf(1.f - powf(beta2, (float)step)), (unsigned)blocks};
+}
 extern "C" int mgx_adam_step(float* p, const float* g, float* m, float* v, uint16_t* shadow, size_t n, float lr,
                              float beta1, float beta2, float eps, int step, float gscale, void* stream) {
     MGX_REQUIRE(p && g && m && v, MGX_ERR_NULL, "mgx_adam_step: NULL pointer");
@@ -755,14 +832,44 @@ extern "C" int mgx_adam_step(float* p, const float* g, float* m, float* v, uint1
     MGX_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
                     ((uintptr_t)shadow & 7) == 0,
                 MGX_ERR_SHAPE, "mgx_adam_step: buffers must be 16-byte aligned");
-    const float bc1 = 1.f - powf(beta1, (float)step);
-    const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
-    size_t blocks = (n / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n,
-                       lr, beta1, beta2, eps, bc1, bc2s, gscale);
+    const AdamLaunch a = adam_launch(n, beta1, beta2, step);
+    hipLaunchKernelGGL(adam_kernel, dim3(a.blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n,
+                       lr, beta1, beta2, eps, a.bc1, a.bc2s, gscale);
     MGX_CHECK_LAUNCH("mgx_adam_step");
+    return MGX_OK;
+}
+static unsigned grad_norm_blocks(size_t n) {
+    size_t blocks = (n / 4 + 255) / 256;
+    if (blocks > MGX_GRAD_NORM_PARTS) blocks = MGX_GRAD_NORM_PARTS;
+    if (blocks < 1) blocks = 1;
+    return (unsigned)blocks;
+}
+extern "C" int mgx_grad_norm(const float* g, size_t n, float gscale, float max_norm, double* workspace, mgx_clip_state* state,
+                             void* stream) {
+    MGX_REQUIRE(g && workspace && state, MGX_ERR_NULL, "mgx_grad_norm: NULL pointer");
+    MGX_REQUIRE(n > 0, MGX_ERR_SHAPE, "mgx_grad_norm: need n>0");
+    MGX_REQUIRE(max_norm > 0.f, MGX_ERR_SHAPE, "mgx_grad_norm: max_norm must be > 0 (+inf = never clip), got %g", (double)max_norm);
+    MGX_REQUIRE(((uintptr_t)g & 15) == 0 && (((uintptr_t)workspace | (uintptr_t)state) & 7) == 0, MGX_ERR_SHAPE,
+                "mgx_grad_norm: g must be 16-byte aligned, workspace and state 8-byte aligned");
+    const unsigned blocks = grad_norm_blocks(n);
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g, n, workspace);
+    MGX_CHECK_LAUNCH("mgx_grad_norm (partials)");
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, workspace, (int)blocks, gscale,
+                       max_norm, state);
+    MGX_CHECK_LAUNCH("mgx_grad_norm (finalize)");
+    return MGX_OK;
+}
+extern "C" int mgx_adam_step_clipped(float* p, const float* g, float* m, float* v, uint16_t* shadow, size_t n, float lr,
+                                     float beta1, float beta2, float eps, int step, const mgx_clip_state* state, void* stream) {
+    MGX_REQUIRE(p && g && m && v && state, MGX_ERR_NULL, "mgx_adam_step_clipped: NULL pointer");
+    MGX_REQUIRE(n > 0 && step >= 1, MGX_ERR_SHAPE, "mgx_adam_step_clipped: need n>0 and step>=1 (step=%d)", step);
+    MGX_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 &&
+                    (((uintptr_t)shadow | (uintptr_t)state) & 7) == 0,
+                MGX_ERR_SHAPE, "mgx_adam_step_clipped: buffers must be 16-byte aligned (shadow, state: 8)");
+    const AdamLaunch a = adam_launch(n, beta1, beta2, step);
+    hipLaunchKernelGGL(adam_clipped_kernel, dim3(a.blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n,
+                       lr, beta1, beta2, eps, a.bc1, a.bc2s, state);
+    MGX_CHECK_LAUNCH("mgx_adam_step_clipped");
     return MGX_OK;
 }
 extern "C" int mgx_cast_bf16(const float* p, uint16_t* shadow, size_t n, void* stream) {

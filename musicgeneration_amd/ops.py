@@ -375,6 +375,49 @@ def adam_step(p, g, m, v, shadow, lr, beta1, beta2, eps, step, gscale=1.0):
                                     float(beta2), float(eps), int(step), float(gscale), stream_ptr()), "mgx_adam_step")
 
 
+GRAD_NORM_PARTS = 1024          # include/mgx.h: MGX_GRAD_NORM_PARTS, the doubles of mgx_grad_norm's workspace
+CLIP_STATE_BYTES = 32           # sizeof(mgx_clip_state)
+
+
+def clip_buffers(device):
+    """-> (workspace f64 [GRAD_NORM_PARTS], state: the 32 bytes of mgx_clip_state as int64 [4], zeroed) for grad_norm"""
+    return (torch.empty(GRAD_NORM_PARTS, dtype=torch.float64, device=device),
+            torch.zeros(CLIP_STATE_BYTES // 8, dtype=torch.int64, device=device))
+
+
+def _check_clip_state(state):
+    _need_cuda(state)
+    if state.numel() * state.element_size() < CLIP_STATE_BYTES:
+        raise ValueError(f"state must hold the {CLIP_STATE_BYTES} bytes of mgx_clip_state")
+
+
+def grad_norm(g, gscale, max_norm, workspace, state):
+    """norm of g * gscale and torch's clip coefficient for max_norm (inf = never clip), left in `state` on the device: no host
+    round trip.  A non-finite gradient marks the step as skipped (include/mgx.h: mgx_grad_norm)."""
+    _need_cuda(g, workspace)
+    _check_clip_state(state)
+    if workspace.dtype != torch.float64 or workspace.numel() < GRAD_NORM_PARTS:
+        raise ValueError(f"workspace must be float64 [{GRAD_NORM_PARTS}]")
+    check(_lib.load().mgx_grad_norm(ptr(g), g.numel(), float(gscale), float(max_norm), ptr(workspace), ptr(state), stream_ptr()),
+          "mgx_grad_norm")
+
+
+def adam_step_clipped(p, g, m, v, shadow, lr, beta1, beta2, eps, step, state):
+    """adam_step with the gradient scale grad_norm left in `state`; writes nothing when that call marked the step as skipped"""
+    _need_cuda(p, g, m, v, shadow)
+    _check_clip_state(state)
+    check(_lib.load().mgx_adam_step_clipped(ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow), p.numel(), float(lr), float(beta1),
+                                            float(beta2), float(eps), int(step), ptr(state), stream_ptr()), "mgx_adam_step_clipped")
+
+
+def read_clip_state(state) -> dict:
+    """the fields of mgx_clip_state; copies the 32 bytes to the host, so it SYNCHRONISES"""
+    raw = state.detach().cpu().contiguous().view(torch.uint8)[:CLIP_STATE_BYTES].numpy()
+    return {"norm": float(raw[0:8].view("<f8")[0]), "scale": float(raw[8:12].view("<f4")[0]),
+            "skipped_last": int(raw[12:16].view("<u4")[0]), "clipped": int(raw[16:24].view("<u8")[0]),
+            "skipped": int(raw[24:32].view("<u8")[0])}
+
+
 def cast_bf16(p, shadow):
     _need_cuda(p, shadow)
     check(_lib.load().mgx_cast_bf16(ptr(p), ptr(shadow), p.numel(), stream_ptr()), "mgx_cast_bf16")

@@ -1,17 +1,34 @@
 """Fused Adam over the model's flat buffers (replaces torch.optim.Adam of train.py:143).
 
-One kernel launch updates every parameter, both moments and the bf16 shadow.  ``state_dict`` /
-``load_state_dict`` use torch.optim.Adam's layout (per-parameter ``step``, ``exp_avg``,
+One kernel launch updates every parameter, both moments and the bf16 shadow.  With ``max_norm`` the global gradient norm is
+clipped first -- measured by one pass over the flat gradient buffer and applied inside the Adam kernel as a scale read from
+device memory -- and a step whose gradient holds an inf or a NaN is skipped instead of being written into p, m, v and the shadow.
+``state_dict`` / ``load_state_dict`` use torch.optim.Adam's layout (per-parameter ``step``, ``exp_avg``,
 ``exp_avg_sq``) so the reference's checkpoints (train.py:201-207) round-trip."""
 from __future__ import annotations
+
+import math
+import numbers
 
 import torch
 
 from . import ops
 
 
+def check_clip_args(max_norm) -> float:
+    """max_norm of FusedAdam / --clip-norm: a number > 0; inf = measure the norm and guard against non-finite gradients,
+    never clip.  -> float(max_norm); ValueError otherwise (needs no GPU)"""
+    if isinstance(max_norm, bool) or not isinstance(max_norm, numbers.Real):
+        raise ValueError(f"max_norm must be a number > 0 (inf = guard only), got {max_norm!r}")
+    max_norm = float(max_norm)
+    if math.isnan(max_norm) or max_norm <= 0.0:
+        raise ValueError(f"max_norm must be > 0 (inf = guard only), got {max_norm!r}")
+    return max_norm
+
+
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, model, lr=0.0, betas=(0.9, 0.98), eps=1e-9, grad_scale: float = 1.0):
+    def __init__(self, model, lr=0.0, betas=(0.9, 0.98), eps=1e-9, grad_scale: float = 1.0, max_norm=None):
+        self.max_norm = None if max_norm is None else check_clip_args(max_norm)
         self.model = model
         store = model.store()
         self.store = store
@@ -21,6 +38,8 @@ class FusedAdam(torch.optim.Optimizer):
         self.v = torch.zeros_like(store.param)
         self._t = 0
         self.grad_scale = grad_scale
+        # max_norm=None allocates nothing and keeps the unclipped kernel
+        self._clip = ops.clip_buffers(store.param.device) if self.max_norm is not None else None
 
     def zero_grad(self, set_to_none: bool = False):
         self.store.grad.zero_()
@@ -33,8 +52,23 @@ class FusedAdam(torch.optim.Optimizer):
         ops.join_side_stream(self.store.param.device)      # weight gradients / dE issued on the CU-masked side stream (ops.configure_streams)
         if dp is not None:
             dp.wait_all()                 # gradients of every bucket reduced (sum) before the update
-        ops.adam_step(self.store.param, self.store.grad, self.m, self.v, self.store.shadow, g["lr"], g["betas"][0],
-                      g["betas"][1], g["eps"], self._t, self.grad_scale)
+        st = self.store
+        if self._clip is None:
+            ops.adam_step(st.param, st.grad, self.m, self.v, st.shadow, g["lr"], g["betas"][0], g["betas"][1], g["eps"], self._t,
+                          self.grad_scale)
+            return
+        # after the all-reduce, over the same bytes on every rank, by an order-fixed kernel: every rank gets the same scale.
+        # _t counts optimiser calls, skipped ones included (a device-side counter would need a host read for state_dict)
+        workspace, state = self._clip
+        ops.grad_norm(st.grad, self.grad_scale, self.max_norm, workspace, state)
+        ops.adam_step_clipped(st.param, st.grad, self.m, self.v, st.shadow, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                              self._t, state)
+
+    def clip_stats(self):
+        """{"norm", "scale", "skipped_last", "clipped", "skipped"}: norm, applied gradient scale and skip flag of the last step, and
+        the number of steps clipped / skipped since construction (not saved in checkpoints).  SYNCHRONISES -- the only place of
+        the clipping path that does.  None when max_norm is None."""
+        return None if self._clip is None else ops.read_clip_state(self._clip[1])
 
     # ---- torch.optim.Adam-compatible checkpoint format --------------------------------------------
     # torch (and the reference's ``Adam(mt.parameters())``, train.py:143) number the per-parameter state by

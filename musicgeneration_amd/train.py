@@ -2,7 +2,8 @@
 same prints, same checkpoint dict {'net','optimizer','epoch'} and file name, same loop semantics
 (train.py:252-329: per-epoch batches, loss/accum_grad, Noam schedule step every accum_grad
 micro-batches, 2-sample eval per epoch, save every 50 epochs and on Ctrl-C) -- running on the MI355X
-kernels.  Extras that do not change the defaults: --num-layers --d-model --repr --dropout --dp, and the
+kernels.  Extras that do not change the defaults: --num-layers --d-model --repr --dropout --dp, --clip-norm
+(global gradient-norm clipping on the device; a non-finite step is skipped) and the
 data-parallel co-residency knobs --rccl-cus --nccl-channels --buckets.
 
 The reference parses -b/-e/-l/-w/-S/-i/-g but its loop reads config.* instead; here the
@@ -25,7 +26,7 @@ from .criterion import CustomSchedule, SmoothCrossEntropyLoss
 from .data import Data
 from .metrics import CategoricalAccuracy, LogitsBucketting, MetricsSet
 from .network import MusicTransformer
-from .optim import FusedAdam
+from .optim import FusedAdam, check_clip_args
 
 
 def get_options(argv=None):
@@ -49,6 +50,8 @@ def get_options(argv=None):
     parser.add_option('--accum-grad', dest='accum_grad', type='int', default=config.accum_grad)
     parser.add_option('--field', dest='field', type='string', default=None, help="MuMIDI .data dict field")
     parser.add_option('--max-batches', dest='max_batches', type='int', default=0, help='stop after N micro-batches')
+    parser.add_option('--clip-norm', dest='clip_norm', type='float', default=0.0,
+                      help='clip the global gradient norm to X and skip non-finite steps; inf = guard only; 0 = off')
     # data-parallel co-residency knobs (the same three as bench.py): CUs kept free of the compute stream for
     # RCCL's kernels, the number of RCCL channels, per-layer gradient buckets merged into K groups
     parser.add_option('--rccl-cus', dest='rccl_cus', type='int', default=0, help='multiple of 8; 0 = the compute stream uses the whole chip')
@@ -141,7 +144,8 @@ def _run(options):
     mt.to(device)
     from .dp import DataParallel
     dp = DataParallel(mt, groups=options.buckets or None) if multi_gpu else None
-    opt = FusedAdam(mt, lr=0, betas=(0.9, 0.98), eps=1e-9, grad_scale=dp.grad_scale if dp else 1.0)
+    max_norm = None if options.clip_norm == 0 else check_clip_args(options.clip_norm)
+    opt = FusedAdam(mt, lr=0, betas=(0.9, 0.98), eps=1e-9, grad_scale=dp.grad_scale if dp else 1.0, max_norm=max_norm)
     scheduler = CustomSchedule(config.embedding_dim, optimizer=opt)   # d_model of the schedule = config constant, as in train.py:144
     start_epoch = 0
 
@@ -182,6 +186,7 @@ def _run(options):
 
     log(mt)
     opt.zero_grad()
+    steps_at_start = opt._t                                    # a resumed run: the counters of --clip-norm start at zero, _t does not
     log(">> Train start...")
     idx = 0
     t_meter, ev_meter = time.time(), 0
@@ -236,6 +241,10 @@ def _run(options):
                 log('Train >>>> Loss: {:6.6}, Accuracy: {}'.format(metrics['loss'], metrics['accuracy']))
             log('Eval >>>> Loss: {:6.6}, Accuracy: {}'.format(eval_metrics['loss'], eval_metrics['accuracy']))
             log('Throughput >>>> {:.0f} events/s'.format(ev_meter / max(dt, 1e-9)))
+            if max_norm is not None:
+                cs = opt.clip_stats()                          # reads the device-side state: after the epoch, not per step
+                log('Grad norm >>>> last: {:.6g}, clipped: {}/{} steps, skipped: {}'.format(
+                    cs['norm'], cs['clipped'], opt._t - steps_at_start, cs['skipped']))
             t_meter, ev_meter = time.time(), 0
             if options.max_batches and idx >= options.max_batches:
                 break
