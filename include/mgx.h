@@ -62,6 +62,7 @@ int mgx_device_count(void);
  *   each other's partial sums): every FURTHER stream that issues such calls -- the CU-masked side stream of the backward's
  *   off-critical-path kernels, below -- registers a buffer of its own with mgx_set_deterministic_stream (ABI 18); a stream
  *   without one uses the buffer registered here.                                                                        */
+#define MGX_DET_SCRATCH_BYTES 33554432   /* the 32 MiB above: size and alignment of every scratch */
 int mgx_set_deterministic(void* scratch, size_t bytes);
 int mgx_deterministic(void);          /* 1 while a scratch is registered */
 /* ABI 18: a scratch of its own for the calls issued on `stream` (same requirements as above; NULL forgets it).  The mode must be

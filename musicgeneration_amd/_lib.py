@@ -5,105 +5,76 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MGX_LIB_PATH") or os.path.join(PKG, "libmgx.so")      # override: A/B two builds in one run
 
-_vp, _i, _f, _u64, _sz = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_size_t
-
-# the ABI the SIGNATURES table below was written for (MGX_ABI_VERSION of include/mgx.h).  A left-over
-# libmgx.so of another ABI still exports the same names: calling it with this table would shift arguments.
-EXPECTED_ABI = 25
-
-# name -> argtypes ; every symbol declared in include/mgx.h (restype int unless noted)
-SIGNATURES = {
-    "mgx_abi_version": [],
-    "mgx_device_count": [],
-    "mgx_set_deterministic": [_vp, _sz],
-    "mgx_deterministic": [],
-    "mgx_set_deterministic_stream": [_vp, _vp, _sz],
-    "mgx_stream_create_cu_mask": [_vp, _vp, _i],
-    "mgx_stream_set_cus": [_vp, _i],
-    "mgx_stream_cus": [_vp],
-    "mgx_stream_destroy": [_vp],
-    "mgx_linear_kernel_id": [_i, _i, _i, _i, _vp],
-    "mgx_embed_pe_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _u64, _vp],
-    "mgx_embed_bwd": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _u64, _vp],
-    "mgx_pad_bitmap": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_rel_attn_fwd_workspace": [_i],                  # returns size_t
-    "mgx_rel_attn_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
-    "mgx_rel_attn_fwd_nomask": [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp],
-    "mgx_rel_attn_weights": [_vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
-    "mgx_rel_attn_bwd_workspace": [_i, _i, _i],          # returns size_t
-    "mgx_rel_attn_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
-    "mgx_rel_attn_bwd_parts": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp],
-    "mgx_add_ln_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _f, _u64, _vp],
-    "mgx_add_ln_bwd_workspace": [_i, _i],                 # returns size_t
-    "mgx_add_ln_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _f, _u64, _vp],
-    "mgx_smooth_ce_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    "mgx_smooth_ce_bwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _f, _vp, _vp],
-    "mgx_adam_step": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _f, _vp],
-    "mgx_cast_bf16": [_vp, _vp, _sz, _vp],
-    "mgx_linear_fwd": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_decode_embed": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_rel_attn_decode_workspace": [_i, _i, _i],       # returns size_t
-    "mgx_rel_attn_decode": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
-    "mgx_sample_topk_topp": [_vp, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp],
-    "mgx_sample_topk_topp_rows": [_vp, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp],
-    # ABI 19: per-row positions (ragged prompts); the same arguments as the shared-position namesakes
-    "mgx_decode_embed_ragged": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_decode_embed_linear_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_decode_embed_linear_frag_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_rel_attn_decode_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
-    "mgx_sample_topk_topp_ragged": [_vp, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _vp],
-    # ABI 20: 8-bit (fp8 e4m3fn) K/V cache
-    "mgx_kv_store_fp8": [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_rel_attn_decode_fp8": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
-    "mgx_rel_attn_decode_fp8_ragged": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp],
-    # ABI 21: the re-anchored decode window (base beside pos; shared or per row by a flag)
-    "mgx_sample_topk_topp_window": [_vp, _i, _i, _f, _i, _f, _u64, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp],
-    "mgx_decode_reanchor": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
-    # ABI 22: beam search on the KV-cache decode
-    "mgx_beam_select": [_vp, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _u64, _vp],
-    "mgx_kv_beam_reorder": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    "mgx_beam_backtrack": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_gather_rows": [_vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_gru_gates": [_vp, _vp, _vp, _vp, _i, _i, _vp],
-    "mgx_linear_dx": [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_gru_cell_fwd": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "mgx_gru_cell_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "mgx_gru_step_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "mgx_gru_step_x_fwd": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "mgx_gru_step_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_dropout_bf16": [_vp, _vp, _sz, _f, _u64, _vp],
-    # ABI 23: scheduled sampling for Event_Melody_RNN (the step-major training forward)
-    "mgx_gru_step_x_fwd_save": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "mgx_dropout_bf16_at": [_vp, _vp, _sz, _sz, _f, _vp, _vp],
-    "mgx_gru_next_event": [_vp, _i, _i, _vp, _vp, _f, _vp, C.c_uint32, _vp, _i, _vp, _vp, _vp, _i, _vp],
-    # ABI 24: scoring
-    "mgx_token_logprob": [_vp, _i, _i, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _vp],
-    "mgx_linear_logprob": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _vp],
-    "mgx_score_reduce": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
-    "mgx_scatter_add_rows": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_linear_ln_fwd": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_decode_embed_linear": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_decode_embed_linear_frag": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_skinny_fwd_frag": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_linear_ln_fwd_frag": [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    "mgx_rel_attn_decode_splits": [_i, _i, _i],
-    "mgx_linear_dw_grouped": [_vp, _i, _i, _vp, _sz, _vp],
-    "mgx_linear_dw_grouped_workspace": [_vp, _i, _i],     # returns size_t
-    "mgx_linear_dw": [_vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    # ABI 25: global gradient-norm clipping, non-finite-step guard
-    "mgx_grad_norm": [_vp, _sz, _f, _f, _vp, _vp, _vp],
-    "mgx_adam_step_clipped": [_vp, _vp, _vp, _vp, _vp, _sz, _f, _f, _f, _f, _i, _vp, _vp],
-}
-
-_lib = None
+HEADER = os.path.join(os.path.dirname(PKG), "include", "mgx.h")
 
 
 class MgxError(RuntimeError):
     pass
+
+
+_BY_VALUE = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "int32_t": C.c_int32,
+             "uint32_t": C.c_uint32, "uint64_t": C.c_uint64}
+_RETURNS = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+
+
+def _decl(decl: str, where: str):
+    """`[const] type [*..] name` -> (name, ctypes type); any pointer crosses as void* (callers pass data_ptr() integers and None)"""
+    m = re.fullmatch(r"\s*(?:const\s+)?(\w+)\s*(\**)\s*(\w+)\s*", decl)
+    if m is None or not (m.group(2) or m.group(1) in _BY_VALUE):
+        raise MgxError(f"include/mgx.h: no binding for `{' '.join(decl.split())}` in `{where}`")
+    return m.group(3), C.c_void_p if m.group(2) else _BY_VALUE[m.group(1)]
+
+
+def parse_header(text: str):
+    """-> (defines, structs, functions) of include/mgx.h: {MGX_NAME: int}, {name: ctypes.Structure subclass},
+    {name: (restype, argtypes)}.  The header is strict C99 over a closed set of types (tests/test_cabi.py compiles it that
+    way), so three regular expressions read it; whatever they do not account for is refused, never bound by guesswork."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(MGX_\w+)[ \t]+(-?\w+)[ \t]*$", text, flags=re.M)
+               if re.fullmatch(r"-?(\d+|0[xX][0-9a-fA-F]+)", v)}
+    text = re.sub(r"^[ \t]*#[^\n]*", "", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|^\}\s*$', "", text, flags=re.M)          # the __cplusplus guard's two lines
+    text = re.sub(r"typedef\s+enum\s*\w*\s*\{[^}]*\}\s*\w+\s*;", "", text)      # mgx_status crosses as int
+    structs, functions = {}, {}
+
+    def struct(m):
+        fields = []
+        for decl in filter(str.strip, m.group(1).split(";")):
+            first, *more = decl.split(",")                               # `int N, K;`
+            name, ct = _decl(first, "struct " + m.group(2))
+            if more and (ct is C.c_void_p or not all(re.fullmatch(r"\s*\w+\s*", d) for d in more)):
+                raise MgxError(f"include/mgx.h: no binding for `{' '.join(decl.split())}` in `struct {m.group(2)}`")
+            fields += [(n.strip(), ct) for n in [name] + more]
+        structs[m.group(2)] = type(m.group(2), (C.Structure,), {"_fields_": fields})
+        return ""
+
+    def function(m):
+        ret, name, params = re.sub(r"\s*\*", "*", " ".join(m.group(1).split())), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise MgxError(f"include/mgx.h: no binding for the return type `{ret}` of `{name}`")
+        functions[name] = (_RETURNS[ret], [] if params == "void" else [_decl(p, name)[1] for p in params.split(",")])
+        return ""
+
+    text = re.sub(r"typedef\s+struct\s*\w*\s*\{([^}]*)\}\s*(\w+)\s*;", struct, text)
+    text = re.sub(r"([\w \t*]+?)\b(mgx_\w+)\s*\(([^()]*)\)\s*;", function, text)
+    if text.strip():
+        raise MgxError("include/mgx.h: not understood (a declaration that is neither a struct nor a plain function?): "
+                       + " ".join(text.split())[:120])
+    return defines, structs, functions
+
+
+# The binding IS the header: a second copy kept by hand could shift every argument after an `int` written for a `size_t`.
+with open(HEADER) as _f:
+    DEFINES, STRUCTS, FUNCTIONS = parse_header(_f.read())
+# A left-over libmgx.so of another ABI still exports the same names: calling it with this header's types would shift arguments.
+EXPECTED_ABI = DEFINES["MGX_ABI_VERSION"]
+
+_lib = None
 
 
 def load() -> C.CDLL:
@@ -125,18 +96,18 @@ def load() -> C.CDLL:
     if not os.path.exists(LIB_PATH):
         raise MgxError(f"{LIB_PATH} is missing: run `python -m musicgeneration_amd._build` (needs hipcc)")
     lib = C.CDLL(LIB_PATH)
-    lib.mgx_last_error.restype = C.c_char_p
-    lib.mgx_last_error.argtypes = []
-    lib.mgx_abi_version.restype = C.c_int
-    lib.mgx_abi_version.argtypes = []
-    abi = lib.mgx_abi_version()
+
+    def bind(name):
+        fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly
+        fn.restype, fn.argtypes = FUNCTIONS[name]
+        return fn
+
+    abi = bind("mgx_abi_version")()
     if abi != EXPECTED_ABI:
         raise MgxError(f"{LIB_PATH} has ABI version {abi}, this package binds ABI {EXPECTED_ABI} (include/mgx.h): "
                        "stale build -- rebuild with `python -m musicgeneration_amd._build --force`")
-    for name, argt in SIGNATURES.items():
-        fn = getattr(lib, name)      # AttributeError here = header/library mismatch: fail loudly
-        fn.restype = C.c_size_t if name.endswith("_workspace") else C.c_int
-        fn.argtypes = argt
+    for name in FUNCTIONS:
+        bind(name)
     _lib = lib
     return lib
 

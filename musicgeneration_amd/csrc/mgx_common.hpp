@@ -142,6 +142,7 @@ constexpr float MGX_DET_SCALE = 1073741824.f;              // 2^30: resolution 9
 // for every total outside +-2^61 (= +-2.1e9).  Order-independent like the sum itself.
 constexpr uintptr_t MGX_DET_HALF = (uintptr_t)16 << 20;     // bytes: sums below, poison words above
 constexpr uintptr_t MGX_DET_BYTES = 2 * MGX_DET_HALF;        // size and alignment of a deterministic-mode scratch
+static_assert(MGX_DET_BYTES == MGX_DET_SCRATCH_BYTES, "mgx.h states the scratch size the callers allocate");
 constexpr long long MGX_DET_BAND = 1LL << 61;
 constexpr float MGX_DET_LIMIT = 2147483648.f;              // 2^31
 MGX_DEV bool det_representable(float v) { return fabsf(v) < MGX_DET_LIMIT; }     // false for NaN

@@ -31,7 +31,7 @@ def _need_cuda(*ts):
 # --------------------------------------------------------------------------------------------------
 _det_scratch = None          # the registered buffer must outlive the mode: kept here
 _det_stream_scratch = {}     # stream pointer -> buffer of that stream (mgx_set_deterministic_stream)
-_DET_BYTES = 32 << 20        # include/mgx.h: 16 MiB of sums + 16 MiB of poison words, aligned to 32 MiB
+_DET_BYTES = _lib.DEFINES["MGX_DET_SCRATCH_BYTES"]     # 16 MiB of sums + 16 MiB of poison words, aligned to its size
 
 
 def _det_buffer(dev):
@@ -263,23 +263,10 @@ def rel_attn_weights(qkv, E, padbits, lse) -> torch.Tensor:
     return w
 
 
-_SIDE_STREAMS = {}
-_CONCURRENT_BWD = __import__("os").environ.get("MGX_CONCURRENT_BWD", "0") == "1"
-
-
-def _side_streams(dev):
-    ss = _SIDE_STREAMS.get(dev)
-    if ss is None:
-        ss = _SIDE_STREAMS[dev] = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
-    return ss
-
-
-def rel_attn_bwd(qkv, E, padbits, ctx, dctx, lse, dE, parts=15, dqkv=None, workspace=None, concurrent=None) -> torch.Tensor:
+def rel_attn_bwd(qkv, E, padbits, ctx, dctx, lse, dE, parts=15, dqkv=None, workspace=None) -> torch.Tensor:
     """-> dqkv bf16 [B,L,3d]; dE f32 [M,64] accumulated in place.  parts selects sub-kernels (bench, cross-checks):
     1 pre-pass | 4 dK/dV (stores its dS tiles in the workspace) | 2 dQ from those tiles | 8 dE from those tiles |
-    16 dE by recomputation | 32 dQ by recomputation (instead of 2) | 64 dK/dV by the 32-key kernel (instead of 4: cross-check).
-    concurrent (opt-in, MGX_CONCURRENT_BWD=1): after dK/dV, the two HBM-bound readers of the dS tiles (dQ, dE) run on two
-    streams.  Default is one stream, which keeps per-kernel profiles comparable."""
+    16 dE by recomputation | 32 dQ by recomputation (instead of 2) | 64 dK/dV by the 32-key kernel (instead of 4: cross-check)."""
     _need_cuda(qkv, E, padbits, ctx, dctx, lse, dE)
     B, L, d3 = qkv.shape
     d = d3 // 3
@@ -288,22 +275,9 @@ def rel_attn_bwd(qkv, E, padbits, ctx, dctx, lse, dE, parts=15, dqkv=None, works
     need = lib.mgx_rel_attn_bwd_workspace(B, L, d)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=qkv.device)
-    args = (ptr(qkv), ptr(E), ptr(padbits), ptr(ctx), ptr(dctx), ptr(lse), ptr(dqkv), ptr(dE), ptr(workspace),
-            workspace.numel(), B, L, d, E.shape[0])
-    if concurrent is None:
-        concurrent = (_CONCURRENT_BWD and parts == 15 and not torch.cuda.is_current_stream_capturing())
-    if not concurrent:
-        check(lib.mgx_rel_attn_bwd_parts(*args, int(parts), stream_ptr()), "mgx_rel_attn_bwd")
-        return dqkv
-    main = torch.cuda.current_stream()
-    s1, _ = _side_streams(qkv.device)
-    check(lib.mgx_rel_attn_bwd_parts(*args, 1 | 4, main.cuda_stream), "mgx_rel_attn_bwd(pre, dKV)")
-    ready = torch.cuda.Event()
-    ready.record(main)
-    s1.wait_event(ready)
-    check(lib.mgx_rel_attn_bwd_parts(*args, 8, s1.cuda_stream), "mgx_rel_attn_bwd(dE)")
-    check(lib.mgx_rel_attn_bwd_parts(*args, 2, main.cuda_stream), "mgx_rel_attn_bwd(dQ)")
-    main.wait_stream(s1)
+    check(lib.mgx_rel_attn_bwd_parts(ptr(qkv), ptr(E), ptr(padbits), ptr(ctx), ptr(dctx), ptr(lse), ptr(dqkv), ptr(dE),
+                                     ptr(workspace), workspace.numel(), B, L, d, E.shape[0], int(parts), stream_ptr()),
+          "mgx_rel_attn_bwd")
     return dqkv
 
 
@@ -375,8 +349,9 @@ def adam_step(p, g, m, v, shadow, lr, beta1, beta2, eps, step, gscale=1.0):
                                     float(beta2), float(eps), int(step), float(gscale), stream_ptr()), "mgx_adam_step")
 
 
-GRAD_NORM_PARTS = 1024          # include/mgx.h: MGX_GRAD_NORM_PARTS, the doubles of mgx_grad_norm's workspace
-CLIP_STATE_BYTES = 32           # sizeof(mgx_clip_state)
+GRAD_NORM_PARTS = _lib.DEFINES["MGX_GRAD_NORM_PARTS"]      # the doubles of mgx_grad_norm's workspace
+_ClipState = _lib.STRUCTS["mgx_clip_state"]
+CLIP_STATE_BYTES = ctypes.sizeof(_ClipState)
 
 
 def clip_buffers(device):
@@ -412,10 +387,8 @@ def adam_step_clipped(p, g, m, v, shadow, lr, beta1, beta2, eps, step, state):
 
 def read_clip_state(state) -> dict:
     """the fields of mgx_clip_state; copies the 32 bytes to the host, so it SYNCHRONISES"""
-    raw = state.detach().cpu().contiguous().view(torch.uint8)[:CLIP_STATE_BYTES].numpy()
-    return {"norm": float(raw[0:8].view("<f8")[0]), "scale": float(raw[8:12].view("<f4")[0]),
-            "skipped_last": int(raw[12:16].view("<u4")[0]), "clipped": int(raw[16:24].view("<u8")[0]),
-            "skipped": int(raw[24:32].view("<u8")[0])}
+    s = _ClipState.from_buffer_copy(state.detach().cpu().contiguous().view(torch.uint8)[:CLIP_STATE_BYTES].numpy())
+    return {"norm": s.norm, "scale": s.scale, "skipped_last": s.skipped_last, "clipped": s.n_clipped, "skipped": s.n_skipped}
 
 
 def cast_bf16(p, shadow):
@@ -604,9 +577,7 @@ def scatter_add_rows(idx, src, dst):
 _DW_WS = {}
 
 
-class _DwProblem(ctypes.Structure):          # mirrors mgx_dw_problem (include/mgx.h)
-    _fields_ = [("dY", ctypes.c_void_p), ("X", ctypes.c_void_p), ("gW", ctypes.c_void_p), ("gb", ctypes.c_void_p),
-                ("N", ctypes.c_int), ("K", ctypes.c_int)]
+_DwProblem = _lib.STRUCTS["mgx_dw_problem"]
 
 
 def linear_dw_grouped(problems):

@@ -1,8 +1,11 @@
 """CPU-side checks of the C-ABI boundary: libmgx.so builds/loads, exports every symbol declared in
-include/mgx.h, the ctypes table covers the header, and the product path fails loudly without a GPU."""
+include/mgx.h, the ctypes binding is read from the header, and the product path fails loudly without a GPU."""
 import ctypes
 import os
 import re
+import shutil
+import struct
+import subprocess
 
 import pytest
 import torch
@@ -24,8 +27,12 @@ def test_library_exports_every_declared_symbol():
     assert len(names) >= 16
     for n in names:
         assert hasattr(lib, n), f"{n} declared in mgx.h but not exported by libmgx.so"
-    # the ctypes signature table binds exactly the header's functions (mgx_last_error is bound separately)
-    assert set(_lib.SIGNATURES) | {"mgx_last_error"} == set(names)
+    # the binding, the header (by this file's own regex) and the library's exports are one set of names
+    bound = _lib.load()
+    assert set(_lib.FUNCTIONS) == set(names) and all(getattr(bound, n).argtypes is not None for n in names)
+    if shutil.which("nm") is not None:      # nothing named mgx_* is exported beside them
+        out = subprocess.run(["nm", "-D", "--defined-only", path], capture_output=True, text=True, check=True).stdout
+        assert {ln.split()[-1] for ln in out.splitlines() if ln.split()[-1].startswith("mgx_")} == set(names)
 
 
 def test_no_torch_types_in_the_abi():
@@ -173,3 +180,120 @@ def test_dw_grouped_workspace_says_which_weights_take_the_ring_path():
     assert need(block, 1024) == 0 and need(block, 131072 + 8) == 0       # few rows / M % 32 != 0: the 128 x 128 kernels
     # a mixed group is sized for its ring-shaped weights only
     assert need(block + [(128, 768)], 131072) == n
+
+
+def _header_defines():
+    return {n: int(v) for n, v in re.findall(r"^#define (MGX_\w+) (\d+)", open(os.path.join(ROOT, "include", "mgx.h")).read(), re.M)}
+
+
+def test_binding_matches_pinned_signatures():
+    """load() binds from include/mgx.h; these literal signatures cover every type class the header uses"""
+    from musicgeneration_amd import _lib
+    lib = _lib.load()
+    vp, i, f, sz, u32, u64 = (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_uint32,
+                              ctypes.c_uint64)
+    pinned = {
+        "mgx_rel_attn_fwd_workspace": (sz, [i]),
+        "mgx_rel_attn_decode_splits": (i, [i, i, i]),
+        "mgx_last_error": (ctypes.c_char_p, []),
+        "mgx_stream_create_cu_mask": (i, [vp, vp, i]),                                       # void**, const uint32_t*
+        "mgx_adam_step": (i, [vp, vp, vp, vp, vp, sz, f, f, f, f, i, f, vp]),
+        "mgx_dropout_bf16_at": (i, [vp, vp, sz, sz, f, vp, vp]),                             # const uint64_t*
+        "mgx_gru_next_event": (i, [vp, i, i, vp, vp, f, vp, u32, vp, i, vp, vp, vp, i, vp]),
+        "mgx_sample_topk_topp_window": (i, [vp, i, i, f, i, f, u64, vp, vp, vp, vp, i, vp, i, i, i, vp, i, vp]),
+        "mgx_linear_dw_grouped": (i, [vp, i, i, vp, sz, vp]),                                # const mgx_dw_problem*
+        "mgx_grad_norm": (i, [vp, sz, f, f, vp, vp, vp]),                                    # double*, mgx_clip_state*
+    }
+    assert len(pinned["mgx_sample_topk_topp_window"][1]) == 19
+    for name, (res, args) in pinned.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res, name
+        assert list(fn.argtypes or []) == args and all(a is b for a, b in zip(fn.argtypes or [], args)), name
+
+
+@pytest.mark.parametrize("text, names", [
+    ("int mgx_x(long n);", ("mgx_x", "long n")),
+    ("typedef struct { double a; short s; } mgx_s;", ("mgx_s", "short s")),
+    ("int mgx_x(void (*cb)(int), void* stream);", ("mgx_x",)),
+    ("int mgx_x(int a[4]);", ("mgx_x",)),
+    ("long mgx_x(void);", ("mgx_x", "long")),
+    ("int mgx_ok(int n);\nint mgx_x(unsigned int n);", ("mgx_x", "unsigned int n")),
+])
+def test_parser_refuses_what_it_does_not_understand(text, names):
+    from musicgeneration_amd import _lib
+    with pytest.raises(_lib.MgxError) as e:
+        _lib.parse_header(text)
+    assert all(n in str(e.value) for n in names)
+
+
+def test_parser_reads_a_small_header():
+    from musicgeneration_amd import _lib
+    defines, structs, functions = _lib.parse_header(
+        "#ifndef X_H\n#define X_H\n#define MGX_N 7 /* seven */\n#ifdef __cplusplus\nextern \"C\" {\n#endif\n"
+        "typedef enum { MGX_A = 0, MGX_B = -1 } mgx_e;\n"
+        "typedef struct mgx_t { const float* p; /* ; */ uint32_t a, b;\n uint64_t c; } mgx_t;\n"
+        "// int mgx_gone(long x);\n"
+        "size_t mgx_f(const mgx_t* t,\n   double x, int32_t y, void** out);\nconst char *mgx_g(void);\n"
+        "#ifdef __cplusplus\n}\n#endif\n#endif\n")
+    assert defines == {"MGX_N": 7}
+    assert functions == {"mgx_f": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_void_p]),
+                         "mgx_g": (ctypes.c_char_p, [])}
+    assert list(structs) == ["mgx_t"] and structs["mgx_t"]._fields_ == [
+        ("p", ctypes.c_void_p), ("a", ctypes.c_uint32), ("b", ctypes.c_uint32), ("c", ctypes.c_uint64)]
+
+
+def test_struct_layout_matches_the_c_compiler(tmp_path):
+    """sizeof and every offsetof of the header's structs, as gcc lays them out, against the ctypes classes parsed from it"""
+    import shutil
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not available")
+    from musicgeneration_amd import _lib
+    fields = {"mgx_dw_problem": ["dY", "X", "gW", "gb", "N", "K"],
+              "mgx_clip_state": ["norm", "scale", "skipped_last", "n_clipped", "n_skipped"]}
+    assert set(_lib.STRUCTS) == set(fields)
+    body = "".join(f'    printf("{s} %zu' + " %zu" * len(fs) + f'\\n", sizeof({s})'
+                   + "".join(f", offsetof({s}, {f})" for f in fs) + ");\n" for s, fs in fields.items())
+    src = tmp_path / "layout.c"
+    src.write_text('#include "mgx.h"\n#include <stdio.h>\nint main(void) {\n' + body + "    return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
+                    "-o", exe], check=True)
+    lines = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(lines) == len(fields)
+    for line in lines:
+        name, size, *offsets = line.split()
+        cls = _lib.STRUCTS[name]
+        assert [n for n, _ in cls._fields_] == fields[name]
+        assert ctypes.sizeof(cls) == int(size)
+        assert [getattr(cls, f).offset for f in fields[name]] == [int(o) for o in offsets], name
+
+
+def test_read_clip_state_decodes_the_struct():
+    from musicgeneration_amd import ops
+    import math
+    for norm, scale, last, clipped, skipped in [(3.5, 0.25, 0, 7, 2), (float("nan"), 0.0, 1, (1 << 32) + 5, (1 << 40) + 1),
+                                                (float("inf"), 0.0, 1, 0, (1 << 64) - 1)]:
+        raw = struct.pack("<dfIQQ", norm, scale, last, clipped, skipped)
+        assert len(raw) == 32 == ops.CLIP_STATE_BYTES
+        got = ops.read_clip_state(torch.frombuffer(bytearray(raw), dtype=torch.int64))
+        assert list(got) == ["norm", "scale", "skipped_last", "clipped", "skipped"]
+        assert type(got["norm"]) is float and type(got["scale"]) is float
+        assert all(type(got[k]) is int for k in ("skipped_last", "clipped", "skipped"))
+        assert got["norm"] == norm or (math.isnan(norm) and math.isnan(got["norm"]))
+        assert (got["scale"], got["skipped_last"], got["clipped"], got["skipped"]) == (scale, last, clipped, skipped)
+
+
+def test_constants_come_from_the_header():
+    from musicgeneration_amd import _lib, ops
+    d = _header_defines()
+    assert _lib.EXPECTED_ABI == d["MGX_ABI_VERSION"]
+    assert ops.GRAD_NORM_PARTS == d["MGX_GRAD_NORM_PARTS"]
+    assert ops._DET_BYTES == d["MGX_DET_SCRATCH_BYTES"] == 32 << 20
+    assert ops.CLIP_STATE_BYTES == 32
+    assert ops._DwProblem is _lib.STRUCTS["mgx_dw_problem"]
+    for name in ("MGX_DW_MAX_GROUP", "MGX_GEMM_SKINNY", "MGX_GEMM_TILE128", "MGX_GEMM_RING8", "MGX_GEMM_RING4"):
+        assert _lib.DEFINES[name] == d[name]
+    lib = _lib.load()
+    aligned = ctypes.c_void_p(64 << 20)
+    assert lib.mgx_set_deterministic(aligned, d["MGX_DET_SCRATCH_BYTES"] - 1) == -1 and b"32 MiB" in lib.mgx_last_error()
+    assert lib.mgx_deterministic() == 0
