@@ -23,11 +23,12 @@ slots, so the body exists in 6 variants (buffer parity x E rotation).
 """
 from __future__ import annotations
 
+import functools
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from asm_sched import COST, Gen, Item, a, chain, crow, regs, s, salu_items, schedule, v, write_if_changed  # noqa: E402
+from asm_sched import COST, Gen, a, add_items, chain, crow, fixed_point, regs, s, salu_items, schedule, summary, v, write_inc  # noqa: E402
 
 # ---------------------------------------------------------------------------------------------------------------------
 # register map
@@ -61,10 +62,9 @@ S_N, S_NT, S_WK, S_I, S_DSOFF, S_QSTEP, S_OSTEP, S_LDS, S_NCH, S_KEXP, S_W = 80,
 S_T = 90             # ..97 temporaries (even: pointer pairs at +2, +4, +6)
 S_DQ, S_DST = 99, 100  # LDS destinations of this wave's DMA pieces (images / statistics), buffer 0
 S_DV = 101           # d * 2 (byte offset of V behind K)
-S_FIRST, S_LAST = 36, 101
+S_FIRST, S_LAST = 14, 101   # (from S_PADM below on)
 S_ET, S_EP, S_SP = 32, 34, 30   # E-load temporaries (2), E chunk pointer (2), dS store pointer (2): s30..s35
 S_ST = 29
-S_FIRST = 14
 S_STAMP = 10         # ..13 (stamp builds): s_memtime pair, previous stamp, difference
 S_PADM = 14          # ..17: lanes whose key is padded, sub-tile 0 / 1
 S_FULL = 18          # ..21 (masked bodies): all ones where sub-tile u is below its diagonal (no causal mask), else 0
@@ -86,8 +86,6 @@ PEEL = 0             # timing experiments (results wrong): 1 no dS stores | 2 no
 
 OFF_QR, OFF_OR, OFF_ST = 0, 12288, 24576      # three LDS buffers per image: query tile t in buffer t % 3
 ST_BYTES = 512
-
-
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -149,8 +147,7 @@ class Step:
                     for jq in range(2):
                         dst = base + 4 * (2 * ss + ct) + 2 * jq
                         off = img + self.cur * 4096 + (16 * ss + 8 * jq) * 128 + ((ct ^ jq) << 6)
-                        out.append(lambda dst=dst, off=off: self.g.ds_read(f"ds_read_b64_tr_b16 {v(dst, 2)}, {v(V_ATR)} offset:{off}",
-                                                                           regs("v", V_ATR), regs("v", dst, 2)))
+                        out.append(lambda dst=dst, off=off: self.g.ins(f"ds_read_b64_tr_b16 {v(dst, 2)}, {v(V_ATR)} offset:{off}"))
         return out
 
     def rd_nd(self, u, nxt=False):
@@ -160,7 +157,7 @@ class Step:
         for g4 in range(4):
             dst = V_DP + 16 * u + 4 * g4
             off = buf * ST_BYTES + 128 + 32 * g4         # (V_AST includes OFF_ST)
-            out.append(lambda dst=dst, off=off: self.g.ds_read(f"ds_read_b128 {v(dst, 4)}, {v(V_AST)} offset:{off}", regs("v", V_AST), regs("v", dst, 4)))
+            out.append(lambda dst=dst, off=off: self.g.ins(f"ds_read_b128 {v(dst, 4)}, {v(V_AST)} offset:{off}"))
         return out
 
     def rd_nl(self):
@@ -169,7 +166,7 @@ class Step:
         for g4 in range(4):
             dst = self.T + 16 + 4 * g4
             off = self.cur * ST_BYTES + 32 * g4
-            out.append(lambda dst=dst, off=off: self.g.ds_read(f"ds_read_b128 {v(dst, 4)}, {v(V_AST)} offset:{off}", regs("v", V_AST), regs("v", dst, 4)))
+            out.append(lambda dst=dst, off=off: self.g.ins(f"ds_read_b128 {v(dst, 4)}, {v(V_AST)} offset:{off}"))
         return out
 
     # -- barrier, DMA of tile n+2, row fragments of tile n+1 ---------------------------------------------------------------
@@ -191,18 +188,18 @@ class Step:
     def dma_addr(self):
         """source pointers of tile min(n + 2, nT - 1): q -> S_T+2, dO -> S_T+4, statistics -> S_T+6 (one SALU instruction per item)"""
         g = self.g
-        ops = [(f"s_add_u32 {s(S_T)}, {s(S_N)}, 2", regs("s", S_N), regs("s", S_T)),
-               (f"s_sub_u32 {s(S_T + 1)}, {s(S_NT)}, 1", regs("s", S_NT), regs("s", S_T + 1)),
-               (f"s_min_u32 {s(S_T)}, {s(S_T)}, {s(S_T + 1)}", regs("s", S_T, 2), regs("s", S_T)),
-               (f"s_mul_i32 {s(S_T + 1)}, {s(S_T)}, {s(S_QSTEP)}", regs("s", S_T) | regs("s", S_QSTEP), regs("s", S_T + 1)),
-               (f"s_add_u32 {s(S_T + 2)}, {s(S_QB)}, {s(S_T + 1)}", regs("s", S_QB) | regs("s", S_T + 1), regs("s", S_T + 2)),
-               (f"s_addc_u32 {s(S_T + 3)}, {s(S_QB + 1)}, 0", regs("s", S_QB + 1), regs("s", S_T + 3)),
-               (f"s_mul_i32 {s(S_T + 1)}, {s(S_T)}, {s(S_OSTEP)}", regs("s", S_T) | regs("s", S_OSTEP), regs("s", S_T + 1)),
-               (f"s_add_u32 {s(S_T + 4)}, {s(S_OB)}, {s(S_T + 1)}", regs("s", S_OB) | regs("s", S_T + 1), regs("s", S_T + 4)),
-               (f"s_addc_u32 {s(S_T + 5)}, {s(S_OB + 1)}, 0", regs("s", S_OB + 1), regs("s", S_T + 5)),
-               (f"s_lshl_b32 {s(S_T + 1)}, {s(S_T)}, 7", regs("s", S_T), regs("s", S_T + 1)),
-               (f"s_add_u32 {s(S_T + 6)}, {s(S_STB)}, {s(S_T + 1)}", regs("s", S_STB) | regs("s", S_T + 1), regs("s", S_T + 6)),
-               (f"s_addc_u32 {s(S_T + 7)}, {s(S_STB + 1)}, 0", regs("s", S_STB + 1), regs("s", S_T + 7))]
+        ops = [f"s_add_u32 {s(S_T)}, {s(S_N)}, 2",
+               f"s_sub_u32 {s(S_T + 1)}, {s(S_NT)}, 1",
+               f"s_min_u32 {s(S_T)}, {s(S_T)}, {s(S_T + 1)}",
+               f"s_mul_i32 {s(S_T + 1)}, {s(S_T)}, {s(S_QSTEP)}",
+               f"s_add_u32 {s(S_T + 2)}, {s(S_QB)}, {s(S_T + 1)}",
+               f"s_addc_u32 {s(S_T + 3)}, {s(S_QB + 1)}, 0",
+               f"s_mul_i32 {s(S_T + 1)}, {s(S_T)}, {s(S_OSTEP)}",
+               f"s_add_u32 {s(S_T + 4)}, {s(S_OB)}, {s(S_T + 1)}",
+               f"s_addc_u32 {s(S_T + 5)}, {s(S_OB + 1)}, 0",
+               f"s_lshl_b32 {s(S_T + 1)}, {s(S_T)}, 7",
+               f"s_add_u32 {s(S_T + 6)}, {s(S_STB)}, {s(S_T + 1)}",
+               f"s_addc_u32 {s(S_T + 7)}, {s(S_STB + 1)}, 0"]
         return salu_items(g, ops)
 
     def dma(self, tag):
@@ -212,13 +209,13 @@ class Step:
         for i in range(2):
             for img, ptr, voff in ((OFF_QR, S_T + 2, V_QOFF + i), (OFF_OR, S_T + 4, V_OOFF + i)):
                 def piece(i=i, img=img, ptr=ptr, voff=voff):
-                    g.salu(f"s_add_u32 m0, {s(S_DQ)}, {img + self.dst * 4096 + 2048 * i}", regs("s", S_DQ), {"m0"})
-                    g.vmem_dma(f"global_load_lds_dwordx4 {v(voff)}, {s(ptr, 2)}", tag, regs("v", voff) | regs("s", ptr, 2) | {"m0"})
+                    g.ins(f"s_add_u32 m0, {s(S_DQ)}, {img + self.dst * 4096 + 2048 * i}")
+                    g.ins(f"global_load_lds_dwordx4 {v(voff)}, {s(ptr, 2)}", tag)
                 out.append(piece)
 
         def stat():
-            g.salu(f"s_add_u32 m0, {s(S_DST)}, {self.dst * ST_BYTES}", regs("s", S_DST), {"m0"})
-            g.vmem_dma(f"global_load_lds_dword {v(V_STOFF)}, {s(S_T + 6, 2)}", tag, regs("v", V_STOFF) | regs("s", S_T + 6, 2) | {"m0"})
+            g.ins(f"s_add_u32 m0, {s(S_DST)}, {self.dst * ST_BYTES}")
+            g.ins(f"global_load_lds_dword {v(V_STOFF)}, {s(S_T + 6, 2)}", tag)
         out.append(stat)
         return out
 
@@ -228,8 +225,7 @@ class Step:
         out = []
         for ks in range(4):
             off = img + self.nxt * 4096
-            out.append(lambda ks=ks, off=off: self.g.ds_read(f"ds_read_b128 {v(base + 4 * ks, 4)}, {v(V_AQ + ks)} offset:{off}",
-                                                              regs("v", V_AQ + ks), regs("v", base + 4 * ks, 4)))
+            out.append(lambda ks=ks, off=off: self.g.ins(f"ds_read_b128 {v(base + 4 * ks, 4)}, {v(V_AQ + ks)} offset:{off}"))
         return out
 
     # -- exponentials, dS, packs of tile n ---------------------------------------------------------------------------------
@@ -237,22 +233,21 @@ class Step:
         c, nl = self.T + (0 if u == 0 else 32), self.T + 16
         out = []
         for r in range(16):
-            out.append(lambda r=r: self.g.valu(f"v_fma_f32 {v(c + r)}, {v(c + r)}, {s(S_KEXP)}, {v(nl + r)}", regs("v", c + r) | regs("v", nl + r), regs("v", c + r)))
-            out.append(lambda r=r: self.g.valu(f"v_exp_f32_e32 {v(c + r)}, {v(c + r)}", regs("v", c + r), regs("v", c + r), trans=True))
+            out.append(lambda r=r: self.g.ins(f"v_fma_f32 {v(c + r)}, {v(c + r)}, {s(S_KEXP)}, {v(nl + r)}"))
+            out.append(lambda r=r: self.g.ins(f"v_exp_f32_e32 {v(c + r)}, {v(c + r)}"))
         return out
 
     def soft_ds(self, u):
         c, d = self.T + (0 if u == 0 else 32), V_DP + 16 * u
         out = []
         for r in range(16):
-            out.append(lambda r=r: self.g.valu(f"v_mul_f32_e32 {v(d + r)}, {v(c + r)}, {v(d + r)}", regs("v", c + r) | regs("v", d + r), regs("v", d + r)))
+            out.append(lambda r=r: self.g.ins(f"v_mul_f32_e32 {v(d + r)}, {v(c + r)}, {v(d + r)}"))
         # packs: registers 8ss + 2j, 8ss + 2j + 1 -> 8ss + j (ascending j: a destination has been consumed by then)
         for base in (d, c):                       # dS first: its store and its product come first
             for ss in range(2):
                 for j in range(4):
                     lo, hi, dst = base + 8 * ss + 2 * j, base + 8 * ss + 2 * j + 1, base + 8 * ss + j
-                    out.append(lambda lo=lo, hi=hi, dst=dst: self.g.valu(f"v_cvt_pk_bf16_f32 {v(dst)}, {v(lo)}, {v(hi)}",
-                                                                         regs("v", lo) | regs("v", hi), regs("v", dst)))
+                    out.append(lambda lo=lo, hi=hi, dst=dst: self.g.ins(f"v_cvt_pk_bf16_f32 {v(dst)}, {v(lo)}, {v(hi)}"))
         return out
 
     # -- masked bodies: causal / padding / not-started masks of tile n ---------------------------------------------------------
@@ -261,16 +256,15 @@ class Step:
         g = self.g
         ops = []
         for u in range(2):
-            ops += [(f"s_sub_u32 {s(S_TM)}, {s(S_N)}, {s(S_WK)}", regs("s", S_N) | regs("s", S_WK), regs("s", S_TM))]
+            ops += [f"s_sub_u32 {s(S_TM)}, {s(S_N)}, {s(S_WK)}"]
             if u:
-                ops += [(f"s_sub_u32 {s(S_TM)}, {s(S_TM)}, 1", regs("s", S_TM), regs("s", S_TM))]
-            ops += [(f"s_cmp_gt_i32 {s(S_TM)}, 0", regs("s", S_TM), {"scc"}),
-                    (f"s_cselect_b64 {s(S_FULL + 2 * u, 2)}, -1, 0", {"scc"}, regs("s", S_FULL + 2 * u, 2)),
-                    (f"s_cmp_lt_i32 {s(S_TM)}, 0", regs("s", S_TM), {"scc"}),
-                    (f"s_cselect_b64 {s(S_KILL + 2 * u, 2)}, -1, 0", {"scc"}, regs("s", S_KILL + 2 * u, 2)),
-                    (f"s_or_b64 {s(S_KILL + 2 * u, 2)}, {s(S_KILL + 2 * u, 2)}, {s(S_PADM + 2 * u, 2)}", regs("s", S_KILL + 2 * u, 2) | regs("s", S_PADM + 2 * u, 2),
-                     regs("s", S_KILL + 2 * u, 2))]
-        return [lambda: [g.salu(*o) for o in ops]]          # ONE item: the compare / select pairs pass through SCC, S_TM is a temporary
+                ops += [f"s_sub_u32 {s(S_TM)}, {s(S_TM)}, 1"]
+            ops += [f"s_cmp_gt_i32 {s(S_TM)}, 0",
+                    f"s_cselect_b64 {s(S_FULL + 2 * u, 2)}, -1, 0",
+                    f"s_cmp_lt_i32 {s(S_TM)}, 0",
+                    f"s_cselect_b64 {s(S_KILL + 2 * u, 2)}, -1, 0",
+                    f"s_or_b64 {s(S_KILL + 2 * u, 2)}, {s(S_KILL + 2 * u, 2)}, {s(S_PADM + 2 * u, 2)}"]
+        return [lambda: [g.ins(o) for o in ops]]          # ONE item: the compare / select pairs pass through SCC, S_TM is a temporary
 
     def mask_apply(self, u):
         """c_u[r] = keep ? c_u[r] : -inf, keep = (lanes with key <= query of register r | FULL_u) & ~KILL_u"""
@@ -279,9 +273,9 @@ class Step:
         out = []
         for r in range(16):
             def f(r=r):
-                g.salu(f"s_or_b64 {s(S_TM, 2)}, {s(S_MASK + 2 * r, 2)}, {s(S_FULL + 2 * u, 2)}", regs("s", S_MASK + 2 * r, 2) | regs("s", S_FULL + 2 * u, 2), regs("s", S_TM, 2))
-                g.salu(f"s_andn2_b64 {s(S_TM, 2)}, {s(S_TM, 2)}, {s(S_KILL + 2 * u, 2)}", regs("s", S_TM, 2) | regs("s", S_KILL + 2 * u, 2), regs("s", S_TM, 2))
-                g.valu(f"v_cndmask_b32_e64 {v(c + r)}, {v(V_NEGINF)}, {v(c + r)}, {s(S_TM, 2)}", regs("v", V_NEGINF) | regs("v", c + r) | regs("s", S_TM, 2), regs("v", c + r))
+                g.ins(f"s_or_b64 {s(S_TM, 2)}, {s(S_MASK + 2 * r, 2)}, {s(S_FULL + 2 * u, 2)}")
+                g.ins(f"s_andn2_b64 {s(S_TM, 2)}, {s(S_TM, 2)}, {s(S_KILL + 2 * u, 2)}")
+                g.ins(f"v_cndmask_b32_e64 {v(c + r)}, {v(V_NEGINF)}, {v(c + r)}, {s(S_TM, 2)}")
             out.append(f)
         return out
 
@@ -293,14 +287,13 @@ class Step:
         out = []
         for u in range(2):
             def f(u=u):
-                g.salu(f"s_sub_u32 {s(S_TM)}, {s(S_N)}, {s(S_WK)}", regs("s", S_N) | regs("s", S_WK), regs("s", S_TM))
-                g.salu(f"s_cmp_ge_i32 {s(S_TM)}, {u}", regs("s", S_TM), {"scc"})
-                g.salu(f"s_cselect_b64 exec, -1, 0", {"scc"}, {"exec"})
+                g.ins(f"s_sub_u32 {s(S_TM)}, {s(S_N)}, {s(S_WK)}")
+                g.ins(f"s_cmp_ge_i32 {s(S_TM)}, {u}")
+                g.ins(f"s_cselect_b64 exec, -1, 0")
                 for ss in range(2):
                     src = V_DP + 16 * u + 8 * ss
-                    g.vmem_store(f"global_store_dwordx4 {v(V_L16)}, {v(src, 4)}, {s(S_SP, 2)} offset:{2048 * u + 1024 * ss}{ST_SUFFIX}", tag,
-                                 regs("v", V_L16) | regs("v", src, 4) | regs("s", S_SP, 2))
-                g.salu("s_mov_b64 exec, -1", (), {"exec"})
+                    g.ins(f"global_store_dwordx4 {v(V_L16)}, {v(src, 4)}, {s(S_SP, 2)} offset:{2048 * u + 1024 * ss}{ST_SUFFIX}", tag)
+                g.ins("s_mov_b64 exec, -1")
             out.append(f)
         return out
 
@@ -308,14 +301,14 @@ class Step:
     def ldE_addr(self):
         """pointer of chunk clamp(n + 2 - wk, 0, nchunk - 1) of the fragment-ordered E copy -> S_EP"""
         g = self.g
-        ops = [(f"s_add_u32 {s(S_ET)}, {s(S_N)}, 2", regs("s", S_N), regs("s", S_ET)),
-               (f"s_sub_u32 {s(S_ET)}, {s(S_ET)}, {s(S_WK)}", regs("s", S_ET) | regs("s", S_WK), regs("s", S_ET)),
-               (f"s_sub_u32 {s(S_ET + 1)}, {s(S_NCH)}, 1", regs("s", S_NCH), regs("s", S_ET + 1)),
-               (f"s_min_i32 {s(S_ET)}, {s(S_ET)}, {s(S_ET + 1)}", regs("s", S_ET, 2), regs("s", S_ET)),
-               (f"s_max_i32 {s(S_ET)}, {s(S_ET)}, 0", regs("s", S_ET), regs("s", S_ET)),        # (wave 1's first steps: chunk < 0, product unused)
-               (f"s_lshl_b32 {s(S_ET)}, {s(S_ET)}, 12", regs("s", S_ET), regs("s", S_ET)),
-               (f"s_add_u32 {s(S_EP)}, {s(S_EFA)}, {s(S_ET)}", regs("s", S_EFA) | regs("s", S_ET), regs("s", S_EP)),
-               (f"s_addc_u32 {s(S_EP + 1)}, {s(S_EFA + 1)}, 0", regs("s", S_EFA + 1), regs("s", S_EP + 1))]
+        ops = [f"s_add_u32 {s(S_ET)}, {s(S_N)}, 2",
+               f"s_sub_u32 {s(S_ET)}, {s(S_ET)}, {s(S_WK)}",
+               f"s_sub_u32 {s(S_ET + 1)}, {s(S_NCH)}, 1",
+               f"s_min_i32 {s(S_ET)}, {s(S_ET)}, {s(S_ET + 1)}",
+               f"s_max_i32 {s(S_ET)}, {s(S_ET)}, 0",        # (wave 1's first steps: chunk < 0, product unused)
+               f"s_lshl_b32 {s(S_ET)}, {s(S_ET)}, 12",
+               f"s_add_u32 {s(S_EP)}, {s(S_EFA)}, {s(S_ET)}",
+               f"s_addc_u32 {s(S_EP + 1)}, {s(S_EFA + 1)}, 0"]
         return salu_items(g, ops)
 
     def ld_E(self, tag):
@@ -323,8 +316,7 @@ class Step:
         out = []
         for ks in range(4):
             dst = A_E + 4 * (4 * self.slot_t2 + ks)
-            out.append(lambda ks=ks, dst=dst: g.vmem_load(f"global_load_dwordx4 {a(dst, 4)}, {v(V_L16)}, {s(S_EP, 2)} offset:{1024 * ks}", tag,
-                                                          regs("v", V_L16) | regs("s", S_EP, 2), regs("a", dst, 4)))
+            out.append(lambda ks=ks, dst=dst: g.ins(f"global_load_dwordx4 {a(dst, 4)}, {v(V_L16)}, {s(S_EP, 2)} offset:{1024 * ks}", tag))
         return out
 
     # -- merge + skew of tile n+1 ------------------------------------------------------------------------------------------
@@ -332,23 +324,22 @@ class Step:
         """sub-tile 0: lanes with key <= query take t0, the others t1 -> t0;  sub-tile 1: t1 / t2 -> t2"""
         t0, t1, t2 = self.Tn, self.Tn + 16, self.Tn + 32
         hi, lo, dst = (t0, t1, t0) if u == 0 else (t1, t2, t2)
-        return [lambda r=r: self.g.valu(f"v_cndmask_b32_e64 {v(dst + r)}, {v(lo + r)}, {v(hi + r)}, {s(S_MASK + 2 * r, 2)}",
-                                        regs("v", lo + r) | regs("v", hi + r) | regs("s", S_MASK + 2 * r, 2), regs("v", dst + r)) for r in range(16)]
+        return [lambda r=r: self.g.ins(f"v_cndmask_b32_e64 {v(dst + r)}, {v(lo + r)}, {v(hi + r)}, {s(S_MASK + 2 * r, 2)}") for r in range(16)]
 
     def skew(self, u):
         c = self.Tn + (0 if u == 0 else 32)
-        return [lambda r=r: self.g.emit("lds", f"ds_bpermute_b32 {v(c + r)}, {v(V_RD + r)}, {v(c + r)}", regs("v", V_RD + r) | regs("v", c + r), regs("v", c + r))
+        return [lambda r=r: self.g.ins(f"ds_bpermute_b32 {v(c + r)}, {v(V_RD + r)}, {v(c + r)}")
                 for r in range(16)]
 
     # -- dS stores of tile n -----------------------------------------------------------------------------------------------
     def st_addr(self):
         """pointer of this step's dS tiles -> S_SP; then the offset of the next tile row: I += 1, offset += I << 11"""
         g = self.g
-        ops = [(f"s_add_u32 {s(S_SP)}, {s(S_DSB)}, {s(S_DSOFF)}", regs("s", S_DSB) | regs("s", S_DSOFF), regs("s", S_SP)),
-               (f"s_addc_u32 {s(S_SP + 1)}, {s(S_DSB + 1)}, 0", regs("s", S_DSB + 1), regs("s", S_SP + 1)),
-               (f"s_add_u32 {s(S_I)}, {s(S_I)}, 1", regs("s", S_I), regs("s", S_I)),
-               (f"s_lshl_b32 {s(S_ST)}, {s(S_I)}, 11", regs("s", S_I), regs("s", S_ST)),
-               (f"s_add_u32 {s(S_DSOFF)}, {s(S_DSOFF)}, {s(S_ST)}", regs("s", S_DSOFF) | regs("s", S_ST), regs("s", S_DSOFF))]
+        ops = [f"s_add_u32 {s(S_SP)}, {s(S_DSB)}, {s(S_DSOFF)}",
+               f"s_addc_u32 {s(S_SP + 1)}, {s(S_DSB + 1)}, 0",
+               f"s_add_u32 {s(S_I)}, {s(S_I)}, 1",
+               f"s_lshl_b32 {s(S_ST)}, {s(S_I)}, 11",
+               f"s_add_u32 {s(S_DSOFF)}, {s(S_DSOFF)}, {s(S_ST)}"]
         return salu_items(g, ops)
 
     def st_dS(self, tag):
@@ -364,14 +355,13 @@ class Step:
                     # wave 0's stores move data (wave 1: EXEC = 0, still counted in vmcnt); 512: the same three SALU instructions around
                     # every store with all waves storing (what the wrapper itself costs)
                     if PEEL & 768:
-                        g.salu(f"s_cmp_eq_u32 {s(S_W)}, 0", regs("s", S_W), {"scc"})
-                        g.salu(f"s_cselect_b64 exec, -1, {'0' if PEEL & 256 else '-1'}", {"scc"}, {"exec"})
+                        g.ins(f"s_cmp_eq_u32 {s(S_W)}, 0")
+                        g.ins(f"s_cselect_b64 exec, -1, {'0' if PEEL & 256 else '-1'}")
                     if wave is not None:
-                        g.salu(f"s_mov_b64 exec, {s((S_W0M, S_W1M)[wave], 2)}", regs("s", (S_W0M, S_W1M)[wave], 2), {"exec"})
-                    g.vmem_store(f"global_store_dwordx4 {v(V_L16)}, {v(src, 4)}, {s(S_SP, 2)} offset:{2048 * u + 1024 * ss}{ST_SUFFIX}", tag,
-                                 regs("v", V_L16) | regs("v", src, 4) | regs("s", S_SP, 2))
+                        g.ins(f"s_mov_b64 exec, {s((S_W0M, S_W1M)[wave], 2)}")
+                    g.ins(f"global_store_dwordx4 {v(V_L16)}, {v(src, 4)}, {s(S_SP, 2)} offset:{2048 * u + 1024 * ss}{ST_SUFFIX}", tag)
                     if PEEL & 768 or wave is not None:
-                        g.salu("s_mov_b64 exec, -1", (), {"exec"})
+                        g.ins("s_mov_b64 exec, -1")
                 if STAGGER:
                     out.append(lambda f=f: f(wave=0))
                     out.append(lambda f=f: f(wave=1))
@@ -393,13 +383,8 @@ def body(g: Gen, b: int, do_cur: bool = True, masked: bool = False, listing=None
     mf += st.mfma_QE(0) + st.mfma_QE(1) + st.mfma_QE(2)
     mf += (st.mfma_dVdK(0) + st.mfma_dVdK(1)) if do_cur else none4 * 4
     # ---- the fillers ----
-    I = Item
     items = []
-
-    def add(fns, cost, **kw):
-        out = [I(f, cost, name=kw.get("name", ""), **{k: v_ for k, v_ in kw.items() if k != "name"}) for f in fns]
-        items.extend(out)
-        return out
+    add = functools.partial(add_items, items)
 
     # Three LDS buffers: the barrier at the top of iteration n tells every wave that (a) all pieces of tile n+1 have landed (each wave
     # waited for its own, requested a whole iteration ago) and (b) everybody has left iteration n-1, so the buffer of tile n-1 is free
@@ -507,16 +492,16 @@ def prologue(g: Gen):
     g.comment("==== prologue ====")
     g.drain()
     T = V_T[0]                                   # 24 temporaries for the scalar block
-    g.valu(f"v_mbcnt_lo_u32_b32 {v(V_TMP)}, -1, 0", set(), regs("v", V_TMP))
-    g.valu(f"v_mbcnt_hi_u32_b32 {v(V_TMP)}, -1, {v(V_TMP)}", regs("v", V_TMP), regs("v", V_TMP))          # lane
-    g.valu(f"v_lshlrev_b32_e32 {v(V_L16)}, 4, {v(V_TMP)}", regs("v", V_TMP), regs("v", V_L16))
-    g.valu(f"v_mov_b32_e32 {v(V_TMP + 1)}, %8", set(), regs("v", V_TMP + 1))
+    g.ins(f"v_mbcnt_lo_u32_b32 {v(V_TMP)}, -1, 0")
+    g.ins(f"v_mbcnt_hi_u32_b32 {v(V_TMP)}, -1, {v(V_TMP)}")          # lane
+    g.ins(f"v_lshlrev_b32_e32 {v(V_L16)}, 4, {v(V_TMP)}")
+    g.ins(f"v_mov_b32_e32 {v(V_TMP + 1)}, %8")
     for k in range(6):
-        g.ds_read(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(V_TMP + 1)} offset:{16 * k}", regs("v", V_TMP + 1), regs("v", T + 4 * k, 4))
-    g.valu(f"v_lshl_add_u32 {v(V_TMP + 2)}, {v(V_TMP)}, 2, {v(V_TMP + 1)}", regs("v", V_TMP, 2), regs("v", V_TMP + 2))
+        g.ins(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(V_TMP + 1)} offset:{16 * k}")
+    g.ins(f"v_lshl_add_u32 {v(V_TMP + 2)}, {v(V_TMP)}, 2, {v(V_TMP + 1)}")
     lane_tab = [V_AQ, V_AQ + 1, V_AQ + 2, V_AQ + 3, V_ATR, V_AST, V_QOFF, V_QOFF + 1, V_OOFF, V_OOFF + 1, V_STOFF, V_KOFF]
     for k, dst in enumerate(lane_tab):
-        g.ds_read(f"ds_read_b32 {v(dst)}, {v(V_TMP + 2)} offset:{256 + 256 * k}", regs("v", V_TMP + 2), regs("v", dst))
+        g.ins(f"ds_read_b32 {v(dst)}, {v(V_TMP + 2)} offset:{256 + 256 * k}")
     S_PW = S_TM                                  # the two pad words (temporaries until the masks exist)
     sc = [S_EFA, S_EFA + 1, S_QB, S_QB + 1, S_OB, S_OB + 1, S_STB, S_STB + 1, S_DSB, S_DSB + 1, S_KVB, S_KVB + 1,
           S_N, S_NT, S_WK, S_I, S_QSTEP, S_OSTEP, S_LDS, S_NCH, S_W, S_DV, S_PW, S_PW + 1]
@@ -524,62 +509,62 @@ def prologue(g: Gen):
     g.lgkm = []
     g.nop(1)
     for k, dst in enumerate(sc):
-        g.valu(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}", regs("v", T + k), regs("s", dst))
+        g.ins(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}")
     g.nop(4)                                     # VALU write of an SGPR -> VMEM / SALU users
     # derived scalars
-    g.salu(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 10", regs("s", S_W), regs("s", S_T))
-    g.salu(f"s_add_u32 {s(S_DQ)}, {s(S_LDS)}, {s(S_T)}", regs("s", S_LDS) | regs("s", S_T), regs("s", S_DQ))                  # lds0 + w * 1024
-    g.salu(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 8", regs("s", S_W), regs("s", S_T))
-    g.salu(f"s_add_u32 {s(S_DST)}, {s(S_LDS)}, {s(S_T)}", regs("s", S_LDS) | regs("s", S_T), regs("s", S_DST))
-    g.salu(f"s_add_u32 {s(S_DST)}, {s(S_DST)}, {OFF_ST}", regs("s", S_DST), regs("s", S_DST))                              # lds0 + OFF_ST + w * 256
+    g.ins(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 10")
+    g.ins(f"s_add_u32 {s(S_DQ)}, {s(S_LDS)}, {s(S_T)}")                  # lds0 + w * 1024
+    g.ins(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 8")
+    g.ins(f"s_add_u32 {s(S_DST)}, {s(S_LDS)}, {s(S_T)}")
+    g.ins(f"s_add_u32 {s(S_DST)}, {s(S_DST)}, {OFF_ST}")                              # lds0 + OFF_ST + w * 256
     # every global request of the prologue goes out now (distinct pointer pairs: no wait in between): the K / V row fragments of the
     # wave's two key tiles (HBM: the longest latency), query tile 0 -> buffer 0, E chunk 0 into the slot of the first step's hi chunk
     # (its other two products use chunks < 0: sub-tiles that have not started or lanes beyond the diagonal, masked whatever they hold)
     P_V0, P_K1, P_V1 = S_T + 2, S_T + 4, S_T + 6
-    g.salu(f"s_add_u32 {s(P_V0)}, {s(S_KVB)}, {s(S_DV)}", regs("s", S_KVB) | regs("s", S_DV), regs("s", P_V0))
-    g.salu(f"s_addc_u32 {s(P_V0 + 1)}, {s(S_KVB + 1)}, 0", regs("s", S_KVB + 1), regs("s", P_V0 + 1))
-    g.salu(f"s_add_u32 {s(P_K1)}, {s(S_KVB)}, {s(S_QSTEP)}", regs("s", S_KVB) | regs("s", S_QSTEP), regs("s", P_K1))
-    g.salu(f"s_addc_u32 {s(P_K1 + 1)}, {s(S_KVB + 1)}, 0", regs("s", S_KVB + 1), regs("s", P_K1 + 1))
-    g.salu(f"s_add_u32 {s(P_V1)}, {s(P_K1)}, {s(S_DV)}", regs("s", P_K1) | regs("s", S_DV), regs("s", P_V1))
-    g.salu(f"s_addc_u32 {s(P_V1 + 1)}, {s(P_K1 + 1)}, 0", regs("s", P_K1 + 1), regs("s", P_V1 + 1))
+    g.ins(f"s_add_u32 {s(P_V0)}, {s(S_KVB)}, {s(S_DV)}")
+    g.ins(f"s_addc_u32 {s(P_V0 + 1)}, {s(S_KVB + 1)}, 0")
+    g.ins(f"s_add_u32 {s(P_K1)}, {s(S_KVB)}, {s(S_QSTEP)}")
+    g.ins(f"s_addc_u32 {s(P_K1 + 1)}, {s(S_KVB + 1)}, 0")
+    g.ins(f"s_add_u32 {s(P_V1)}, {s(P_K1)}, {s(S_DV)}")
+    g.ins(f"s_addc_u32 {s(P_V1 + 1)}, {s(P_K1 + 1)}, 0")
     for u, (pk, pv) in enumerate(((S_KVB, P_V0), (P_K1, P_V1))):
         for ks in range(4):
             dk, dv_ = A_KF + 4 * (4 * u + ks), A_VF + 4 * (4 * u + ks)
-            g.vmem_load(f"global_load_dwordx4 {a(dk, 4)}, {v(V_KOFF)}, {s(pk, 2)} offset:{32 * ks}", "kv", regs("v", V_KOFF) | regs("s", pk, 2), regs("a", dk, 4))
-            g.vmem_load(f"global_load_dwordx4 {a(dv_, 4)}, {v(V_KOFF)}, {s(pv, 2)} offset:{32 * ks}", "kv", regs("v", V_KOFF) | regs("s", pv, 2), regs("a", dv_, 4))
+            g.ins(f"global_load_dwordx4 {a(dk, 4)}, {v(V_KOFF)}, {s(pk, 2)} offset:{32 * ks}", "kv")
+            g.ins(f"global_load_dwordx4 {a(dv_, 4)}, {v(V_KOFF)}, {s(pv, 2)} offset:{32 * ks}", "kv")
     for i in range(2):
         for img, ptr, voff in ((OFF_QR, S_QB, V_QOFF + i), (OFF_OR, S_OB, V_OOFF + i)):
-            g.salu(f"s_add_u32 m0, {s(S_DQ)}, {img + 2048 * i}", regs("s", S_DQ), {"m0"})
-            g.vmem_dma(f"global_load_lds_dwordx4 {v(voff)}, {s(ptr, 2)}", "dma_first", regs("v", voff) | regs("s", ptr, 2) | {"m0"})
-    g.salu(f"s_add_u32 m0, {s(S_DST)}, 0", regs("s", S_DST), {"m0"})
-    g.vmem_dma(f"global_load_lds_dword {v(V_STOFF)}, {s(S_STB, 2)}", "dma_first", regs("v", V_STOFF) | regs("s", S_STB, 2) | {"m0"})
+            g.ins(f"s_add_u32 m0, {s(S_DQ)}, {img + 2048 * i}")
+            g.ins(f"global_load_lds_dwordx4 {v(voff)}, {s(ptr, 2)}", "dma_first")
+    g.ins(f"s_add_u32 m0, {s(S_DST)}, 0")
+    g.ins(f"global_load_lds_dword {v(V_STOFF)}, {s(S_STB, 2)}", "dma_first")
     for ks in range(4):
         dst = A_E + 4 * (4 * 0 + ks)             # slot 0 = the hi-chunk slot of the fill iteration (n = -1: (n + 1) % 3)
-        g.vmem_load(f"global_load_dwordx4 {a(dst, 4)}, {v(V_L16)}, {s(S_EFA, 2)} offset:{1024 * ks}", "e0", regs("v", V_L16) | regs("s", S_EFA, 2), regs("a", dst, 4))
+        g.ins(f"global_load_dwordx4 {a(dst, 4)}, {v(V_L16)}, {s(S_EFA, 2)} offset:{1024 * ks}", "e0")
     # ... and the lane-dependent constants are formed while they are in flight
-    g.salu(f"s_mov_b32 {s(S_KEXP)}, 0x3e38aa3b", (), regs("s", S_KEXP))         # 0.125 * log2(e) = 0x3fb8aa3b / 8, exact
-    g.salu(f"s_add_u32 {s(S_T)}, {s(S_I)}, 1", regs("s", S_I), regs("s", S_T))                                              # dS offset of tile row I = I0:
-    g.salu(f"s_mul_i32 {s(S_T)}, {s(S_T)}, {s(S_I)}", regs("s", S_T) | regs("s", S_I), regs("s", S_T))                      #   I (I + 1) / 2 * 2048
-    g.salu(f"s_lshl_b32 {s(S_DSOFF)}, {s(S_T)}, 10", regs("s", S_T), regs("s", S_DSOFF))
-    g.salu(f"s_or_b32 {s(S_PADANY)}, {s(S_PW)}, {s(S_PW + 1)}", regs("s", S_PW, 2), regs("s", S_PADANY))
-    g.valu(f"v_mov_b32_e32 {v(V_NEGINF)}, 0xff800000", set(), regs("v", V_NEGINF))
+    g.ins(f"s_mov_b32 {s(S_KEXP)}, 0x3e38aa3b")         # 0.125 * log2(e) = 0x3fb8aa3b / 8, exact
+    g.ins(f"s_add_u32 {s(S_T)}, {s(S_I)}, 1")                                              # dS offset of tile row I = I0:
+    g.ins(f"s_mul_i32 {s(S_T)}, {s(S_T)}, {s(S_I)}")                      #   I (I + 1) / 2 * 2048
+    g.ins(f"s_lshl_b32 {s(S_DSOFF)}, {s(S_T)}, 10")
+    g.ins(f"s_or_b32 {s(S_PADANY)}, {s(S_PW)}, {s(S_PW + 1)}")
+    g.ins(f"v_mov_b32_e32 {v(V_NEGINF)}, 0xff800000")
     # masks: lanes whose key (lane & 31) <= query crow(r, hh) ; skew source lanes rd[r] = (32 hh + ((crow - bl) & 31)) * 4
     BL, HH4, HH128, X = V_TMP + 3, V_TMP + 4, V_TMP + 5, V_TMP + 6
-    g.valu(f"v_and_b32_e32 {v(BL)}, 31, {v(V_TMP)}", regs("v", V_TMP), regs("v", BL))
-    g.valu(f"v_lshrrev_b32_e32 {v(HH4)}, 5, {v(V_TMP)}", regs("v", V_TMP), regs("v", HH4))
-    g.valu(f"v_lshlrev_b32_e32 {v(HH128)}, 7, {v(HH4)}", regs("v", HH4), regs("v", HH128))       # 32 hh * 4
-    g.valu(f"v_lshlrev_b32_e32 {v(HH4)}, 2, {v(HH4)}", regs("v", HH4), regs("v", HH4))           # 4 hh
+    g.ins(f"v_and_b32_e32 {v(BL)}, 31, {v(V_TMP)}")
+    g.ins(f"v_lshrrev_b32_e32 {v(HH4)}, 5, {v(V_TMP)}")
+    g.ins(f"v_lshlrev_b32_e32 {v(HH128)}, 7, {v(HH4)}")       # 32 hh * 4
+    g.ins(f"v_lshlrev_b32_e32 {v(HH4)}, 2, {v(HH4)}")           # 4 hh
     for u in range(2):                           # lanes whose key is padded: bit (lane & 31) of the key tile's pad word
-        g.valu(f"v_lshrrev_b32_e64 {v(X)}, {v(BL)}, {s(S_PW + u)}", regs("v", BL) | regs("s", S_PW + u), regs("v", X))
-        g.valu(f"v_and_b32_e32 {v(X)}, 1, {v(X)}", regs("v", X), regs("v", X))
-        g.valu(f"v_cmp_ne_u32_e64 {s(S_PADM + 2 * u, 2)}, 0, {v(X)}", regs("v", X), regs("s", S_PADM + 2 * u, 2))
+        g.ins(f"v_lshrrev_b32_e64 {v(X)}, {v(BL)}, {s(S_PW + u)}")
+        g.ins(f"v_and_b32_e32 {v(X)}, 1, {v(X)}")
+        g.ins(f"v_cmp_ne_u32_e64 {s(S_PADM + 2 * u, 2)}, 0, {v(X)}")
     for r in range(16):
-        g.valu(f"v_add_u32_e32 {v(X)}, {crow(r)}, {v(HH4)}", regs("v", HH4), regs("v", X))                             # crow(r, hh)
-        g.valu(f"v_cmp_le_u32_e64 {s(S_MASK + 2 * r, 2)}, {v(BL)}, {v(X)}", regs("v", BL) | regs("v", X), regs("s", S_MASK + 2 * r, 2))
-        g.valu(f"v_sub_u32_e32 {v(X)}, {v(X)}, {v(BL)}", regs("v", X) | regs("v", BL), regs("v", X))
-        g.valu(f"v_and_b32_e32 {v(X)}, 31, {v(X)}", regs("v", X), regs("v", X))
-        g.valu(f"v_lshl_add_u32 {v(V_RD + r)}, {v(X)}, 2, {v(HH128)}", regs("v", X) | regs("v", HH128), regs("v", V_RD + r))
-    g.salu(f"s_mov_b32 {s(S_N)}, -1", (), regs("s", S_N))                            # the fill iteration: "tile -1"
+        g.ins(f"v_add_u32_e32 {v(X)}, {crow(r)}, {v(HH4)}")                             # crow(r, hh)
+        g.ins(f"v_cmp_le_u32_e64 {s(S_MASK + 2 * r, 2)}, {v(BL)}, {v(X)}")
+        g.ins(f"v_sub_u32_e32 {v(X)}, {v(X)}, {v(BL)}")
+        g.ins(f"v_and_b32_e32 {v(X)}, 31, {v(X)}")
+        g.ins(f"v_lshl_add_u32 {v(V_RD + r)}, {v(X)}, 2, {v(HH128)}")
+    g.ins(f"s_mov_b32 {s(S_N)}, -1")                            # the fill iteration: "tile -1"
     g.raw("s_waitcnt lgkmcnt(0)")
     g.lgkm = []
     g.wait_vm_tag("dma_first")                   # tile 0 has landed; the K / V and E fragments may still be in flight (first used by MFMAs)
@@ -588,24 +573,24 @@ def prologue(g: Gen):
 
 def loop_tail(g: Gen, b: int, masked: bool):
     nb = (b + 1) % 6
-    g.salu(f"s_add_u32 {s(S_N)}, {s(S_N)}, 1", regs("s", S_N), regs("s", S_N))
-    g.salu(f"s_cmp_ge_u32 {s(S_N)}, {s(S_NT)}", regs("s", S_N) | regs("s", S_NT), {"scc"})
+    g.ins(f"s_add_u32 {s(S_N)}, {s(S_N)}, 1")
+    g.ins(f"s_cmp_ge_u32 {s(S_N)}, {s(S_NT)}")
     g.raw("s_cbranch_scc1 L_dkv_end_%=")
     if not masked:
         if b == 5:
             g.raw("s_branch L_dkv_u0_%=")
         return
     # a wave stays in the masked bodies while one of its keys is padded or a sub-tile is not below its diagonal yet (n - wk < 2)
-    g.salu(f"s_cmp_lg_u32 {s(S_PADANY)}, 0", regs("s", S_PADANY), {"scc"})
+    g.ins(f"s_cmp_lg_u32 {s(S_PADANY)}, 0")
     g.raw(f"s_cbranch_scc1 L_dkv_m{nb}_%=")
-    g.salu(f"s_sub_u32 {s(S_TM)}, {s(S_N)}, {s(S_WK)}", regs("s", S_N) | regs("s", S_WK), regs("s", S_TM))
-    g.salu(f"s_cmp_lt_i32 {s(S_TM)}, 2", regs("s", S_TM), {"scc"})
+    g.ins(f"s_sub_u32 {s(S_TM)}, {s(S_N)}, {s(S_WK)}")
+    g.ins(f"s_cmp_lt_i32 {s(S_TM)}, 2")
     g.raw(f"s_cbranch_scc1 L_dkv_m{nb}_%=")
     # switch to the main bodies: their counted waits assume the main loop's own history, so start them from a drained state
     if STAGGER:
-        g.salu(f"s_cmp_eq_u32 {s(S_W)}, 0", regs("s", S_W), {"scc"})
-        g.salu(f"s_cselect_b64 {s(S_W0M, 2)}, -1, 0", {"scc"}, regs("s", S_W0M, 2))
-        g.salu(f"s_cselect_b64 {s(S_W1M, 2)}, 0, -1", {"scc"}, regs("s", S_W1M, 2))
+        g.ins(f"s_cmp_eq_u32 {s(S_W)}, 0")
+        g.ins(f"s_cselect_b64 {s(S_W0M, 2)}, -1, 0")
+        g.ins(f"s_cselect_b64 {s(S_W1M, 2)}, 0, -1")
     g.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
     g.raw("s_nop 7")
     g.raw("s_nop 7")
@@ -615,19 +600,15 @@ def loop_tail(g: Gen, b: int, masked: bool):
 
 
 def fixed_point_loop(g: Gen, masked: bool):
-    """three rounds over the six bodies: the second reaches the loop-carried state of the wait / hazard trackers, the third is emitted"""
-    texts = []
-    for rnd in range(3):
-        g.out = []
+    """the six bodies of a loop, generated from the loop's own loop-carried tracker state"""
+    def six_bodies():
         for b in range(6):
             g.out.append(f"L_dkv_{'m' if masked else 'u'}{b}_%=:")
             body(g, b, masked=masked)
             if STAMP and not masked:
                 g.raw(f"v_add_u32_e32 {v(V_STAMP + 7)}, 1, {v(V_STAMP + 7)}")
             loop_tail(g, b, masked)
-        texts.append(list(g.out))
-    assert texts[1] == texts[2], "the loop body is not a fixed point of the wait-count / hazard trackers"
-    return texts[2]
+    return fixed_point(g, six_bodies)
 
 
 def generate():
@@ -637,7 +618,7 @@ def generate():
     body(g, 5, do_cur=False)
     g.drain()
     g.nop(16)
-    g.salu(f"s_mov_b32 {s(S_N)}, 0", (), regs("s", S_N))
+    g.ins(f"s_mov_b32 {s(S_N)}, 0")
     if STAMP:
         for k in range(8):
             g.raw(f"v_mov_b32_e32 {v(V_STAMP + k)}, 0")
@@ -684,23 +665,11 @@ def main():
 def write(here):
     lines, g = generate()
     path = os.path.join(here, "rel_attn_dkv64_loop_stamp.inc" if STAMP else "rel_attn_dkv64_loop_peel.inc" if PEEL else "rel_attn_dkv64_loop.inc")
-    import io
-    f = io.StringIO()
-    if True:
-        f.write("// GENERATED by gen_dkv_asm.py -- do not edit.  The hand-scheduled main loop of rel_attn_dkv64_kernel (one asm statement):\n")
-        f.write("// operands %0..%7 = dk[0][0], dk[0][1], dv[0][0], dv[0][1], dk[1][0], dk[1][1], dv[1][0], dv[1][1] (\"+a\"), %8 = LDS address of the\n")
-        f.write("// wave's parameter block (\"s\").  Register map, schedule and hazard rules: gen_dkv_asm.py.\n")
-        f.write("#define MGX_DKV64_LOOP_ASM \\\n")
-        for ln in lines:
-            if ln.startswith(";"):
-                f.write(f"    /* {ln[1:].strip()} */ \\\n")
-            else:
-                f.write(f'    "{ln}\\n\\t" \\\n')
-        f.write('    ""\n')
-        f.write("#define MGX_DKV64_LOOP_CLOBBERS " + ", ".join(f'"{c}"' for c in clobbers()) + "\n")
-    write_if_changed(path, f.getvalue())
-    n_loop = sum(1 for ln in lines if not ln.startswith(";") and not ln.endswith(":"))
-    print(f"wrote {path}: {n_loop} instructions, s_nop wait states inserted: {g.nops}; counts {g.stats}", file=sys.stderr)
+    write_inc(path, ["GENERATED by gen_dkv_asm.py -- do not edit.  The hand-scheduled main loop of rel_attn_dkv64_kernel (one asm statement):",
+                     "operands %0..%7 = dk[0][0], dk[0][1], dv[0][0], dv[0][1], dk[1][0], dk[1][1], dv[1][0], dv[1][1] (\"+a\"), %8 = LDS address of the",
+                     "wave's parameter block (\"s\").  Register map, schedule and hazard rules: gen_dkv_asm.py."],
+              [("MGX_DKV64_LOOP_ASM", lines)], ("MGX_DKV64_LOOP_CLOBBERS", clobbers()))
+    summary(path, lines, g)
 
 
 if __name__ == "__main__":

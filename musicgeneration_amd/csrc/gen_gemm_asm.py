@@ -24,11 +24,12 @@ Iteration s (stage s in ring slot s % 4):
 """
 from __future__ import annotations
 
+import functools
 import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from asm_sched import COST, Gen, Item, a, chain, regs, s, schedule, v, write_if_changed  # noqa: E402
+from asm_sched import COST, Gen, add_items, fixed_point, regs, s, schedule, summary, v, write_inc  # noqa: E402
 
 V_L = 16             # lane
 V_VOY = 17           # ..20 DMA source offsets of this wave's four pieces of the dY image
@@ -68,31 +69,31 @@ def prologue(g: Gen):
     g.comment("==== prologue ====")
     g.drain()
     T = V_TMP
-    g.valu(f"v_mbcnt_lo_u32_b32 {v(V_L)}, -1, 0", set(), regs("v", V_L))
-    g.valu(f"v_mbcnt_hi_u32_b32 {v(V_L)}, -1, {v(V_L)}", regs("v", V_L), regs("v", V_L))
-    g.valu(f"v_mov_b32_e32 {v(T + 12)}, %20", set(), regs("v", T + 12))
+    g.ins(f"v_mbcnt_lo_u32_b32 {v(V_L)}, -1, 0")
+    g.ins(f"v_mbcnt_hi_u32_b32 {v(V_L)}, -1, {v(V_L)}")
+    g.ins(f"v_mov_b32_e32 {v(T + 12)}, %20")
     for k in range(3):
-        g.ds_read(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(T + 12)} offset:{16 * k}", regs("v", T + 12), regs("v", T + 4 * k, 4))
-    g.valu(f"v_lshl_add_u32 {v(T + 13)}, {v(V_L)}, 2, {v(T + 12)}", regs("v", V_L) | regs("v", T + 12), regs("v", T + 13))
+        g.ins(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(T + 12)} offset:{16 * k}")
+    g.ins(f"v_lshl_add_u32 {v(T + 13)}, {v(V_L)}, 2, {v(T + 12)}")
     tab = [V_VOY, V_VOY + 1, V_VOY + 2, V_VOY + 3, V_VOX, V_VOX + 1, V_VOX + 2, V_VOX + 3, V_TA, V_TA + 1, V_TB, V_TB + 1]
     for k, dst in enumerate(tab):
-        g.ds_read(f"ds_read_b32 {v(dst)}, {v(T + 13)} offset:{256 + 256 * k}", regs("v", T + 13), regs("v", dst))
+        g.ins(f"ds_read_b32 {v(dst)}, {v(T + 13)} offset:{256 + 256 * k}")
     sc = [S_YP, S_YP + 1, S_XP, S_XP + 1, S_YSTEP, S_XSTEP, S_G, S_LDS, S_W, S_BIAS]
     g.raw("s_waitcnt lgkmcnt(0)")
     g.lgkm = []
     g.nop(1)
     for k, dst in enumerate(sc):
-        g.valu(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}", regs("v", T + k), regs("s", dst))
+        g.ins(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}")
     g.nop(4)
-    g.valu(f"v_mov_b32_e32 {v(V_ONES)}, 0x3f803f80", set(), regs("v", V_ONES))
+    g.ins(f"v_mov_b32_e32 {v(V_ONES)}, 0x3f803f80")
     for k in range(2):
-        g.valu(f"v_add_u32_e32 {v(V_TA2 + k)}, 0x10000, {v(V_TA + k)}", regs("v", V_TA + k), regs("v", V_TA2 + k))
-        g.valu(f"v_add_u32_e32 {v(V_TB2 + k)}, 0x10000, {v(V_TB + k)}", regs("v", V_TB + k), regs("v", V_TB2 + k))
+        g.ins(f"v_add_u32_e32 {v(V_TA2 + k)}, 0x10000, {v(V_TA + k)}")
+        g.ins(f"v_add_u32_e32 {v(V_TB2 + k)}, 0x10000, {v(V_TB + k)}")
     # this wave's pieces q = 4 w .. 4 w + 3 of each image: LDS destination lds0 + slot * 32 KB (+ 16 KB for X) + q * 1 KB
-    g.salu(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 12", regs("s", S_W), regs("s", S_T))
-    g.salu(f"s_add_u32 {s(S_DY)}, {s(S_LDS)}, {s(S_T)}", regs("s", S_LDS) | regs("s", S_T), regs("s", S_DY))
-    g.salu(f"s_add_u32 {s(S_DX)}, {s(S_DY)}, 16384", regs("s", S_DY), regs("s", S_DX))
-    g.salu(f"s_mov_b32 {s(S_S)}, 0", (), regs("s", S_S))
+    g.ins(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 12")
+    g.ins(f"s_add_u32 {s(S_DY)}, {s(S_LDS)}, {s(S_T)}")
+    g.ins(f"s_add_u32 {s(S_DX)}, {s(S_DY)}, 16384")
+    g.ins(f"s_mov_b32 {s(S_S)}, 0")
     for st in range(3):
         pieces, adv = dma_items(g, st, st)
         for f in pieces:
@@ -112,20 +113,20 @@ def dma_items(g: Gen, slot: int, ahead: int):
     for j in range(4):
         for dst, vo, ptr in ((S_DY, V_VOY, S_YP), (S_DX, V_VOX, S_XP)):
             def f(j=j, dst=dst, vo=vo, ptr=ptr):
-                g.salu(f"s_add_u32 m0, {s(dst)}, {slot * RG_STAGE + 1024 * j}", regs("s", dst), {"m0"})
+                g.ins(f"s_add_u32 m0, {s(dst)}, {slot * RG_STAGE + 1024 * j}")
                 if not NODMA:
-                    g.vmem_dma(f"global_load_lds_dwordx4 {v(vo + j)}, {s(ptr, 2)}", f"dma{slot}", regs("v", vo + j) | regs("s", ptr, 2) | {"m0"})
+                    g.ins(f"global_load_lds_dwordx4 {v(vo + j)}, {s(ptr, 2)}", f"dma{slot}")
             out.append(f)
 
     def adv():
-        g.salu(f"s_add_u32 {s(S_T)}, {s(S_S)}, {ahead + 1}", regs("s", S_S), regs("s", S_T))
-        g.salu(f"s_cmp_lt_u32 {s(S_T)}, {s(S_G)}", regs("s", S_T) | regs("s", S_G), {"scc"})
-        g.salu(f"s_cselect_b32 {s(S_T)}, {s(S_YSTEP)}, 0", {"scc"} | regs("s", S_YSTEP), regs("s", S_T))
-        g.salu(f"s_cselect_b32 {s(S_T + 1)}, {s(S_XSTEP)}, 0", {"scc"} | regs("s", S_XSTEP), regs("s", S_T + 1))
-        g.salu(f"s_add_u32 {s(S_YP)}, {s(S_YP)}, {s(S_T)}", regs("s", S_YP) | regs("s", S_T), regs("s", S_YP))
-        g.salu(f"s_addc_u32 {s(S_YP + 1)}, {s(S_YP + 1)}, 0", regs("s", S_YP + 1), regs("s", S_YP + 1))
-        g.salu(f"s_add_u32 {s(S_XP)}, {s(S_XP)}, {s(S_T + 1)}", regs("s", S_XP) | regs("s", S_T + 1), regs("s", S_XP))
-        g.salu(f"s_addc_u32 {s(S_XP + 1)}, {s(S_XP + 1)}, 0", regs("s", S_XP + 1), regs("s", S_XP + 1))
+        g.ins(f"s_add_u32 {s(S_T)}, {s(S_S)}, {ahead + 1}")
+        g.ins(f"s_cmp_lt_u32 {s(S_T)}, {s(S_G)}")
+        g.ins(f"s_cselect_b32 {s(S_T)}, {s(S_YSTEP)}, 0")
+        g.ins(f"s_cselect_b32 {s(S_T + 1)}, {s(S_XSTEP)}, 0")
+        g.ins(f"s_add_u32 {s(S_YP)}, {s(S_YP)}, {s(S_T)}")
+        g.ins(f"s_addc_u32 {s(S_YP + 1)}, {s(S_YP + 1)}, 0")
+        g.ins(f"s_add_u32 {s(S_XP)}, {s(S_XP)}, {s(S_T + 1)}")
+        g.ins(f"s_addc_u32 {s(S_XP + 1)}, {s(S_XP + 1)}, 0")
     return out, adv
 
 
@@ -139,7 +140,7 @@ def read_items(g: Gen, slot: int, ks: int, fs: int):
         for jq in range(2):
             dst = frag(fs, kind, i) + 2 * jq
             off = (slot & 1) * RG_STAGE + 4096 * (i >> 1) + 2048 * ks + 512 * jq
-            out.append((lambda: None) if NOREAD else lambda dst=dst, off=off, base=base: g.ds_read(f"ds_read_b64_tr_b16 {v(dst, 2)}, {v(base)} offset:{off}", regs("v", base), regs("v", dst, 2)))
+            out.append((lambda: None) if NOREAD else lambda dst=dst, off=off, base=base: g.ins(f"ds_read_b64_tr_b16 {v(dst, 2)}, {v(base)} offset:{off}"))
     return out
 
 
@@ -151,16 +152,7 @@ def body(g: Gen, slot: int, bias: tuple):
             for ct in range(4):
                 mf.append((lambda: None) if NOMFMA else lambda fs=fs, rt=rt, ct=ct: g.mfma_op(f"%{4 * rt + ct}", ("v", frag(fs, "x", ct)), ("v", frag(fs, "y", rt))))
     items = []
-
-    def add(fns, cost, spread=0, **kw):
-        """spread: the k-th of the n items not before gap earliest + k * spread // n (an even trickle instead of a burst)"""
-        out = []
-        for k, f in enumerate(fns):
-            kw2 = dict(kw)
-            kw2["earliest"] = kw.get("earliest", 1) + k * spread // len(fns)
-            out.append(Item(f, cost, **kw2))
-        items.extend(out)
-        return out
+    add = functools.partial(add_items, items)
 
     nslot = (slot + 1) & 3
     add(read_items(g, slot, 1, 1), COST["lds"], earliest=1, deadline=13, spread=11, name="rd_k1")          # F1: free since the previous iteration's MFMAs 17-32
@@ -181,7 +173,7 @@ def body(g: Gen, slot: int, bias: tuple):
             for k in range(4):                       # round-robin over the sums: a v_dot2c waits for the previous one into the same register
                 for rt in bias:
                     src = frag(fs, "y", rt) + k
-                    fns.append(lambda rt=rt, src=src: g.valu(f"v_dot2c_f32_bf16_e32 %{16 + rt}, {v(src)}, {v(V_ONES)}", regs("v", src) | regs("v", V_ONES), set()))
+                    fns.append(lambda rt=rt, src=src: g.ins(f"v_dot2c_f32_bf16_e32 %{16 + rt}, {v(src)}, {v(V_ONES)}"))
             add(fns, COST["valu"], earliest=(6, 21)[fs], deadline=15 + 16 * fs, spread=(8, 10)[fs], name=f"bias{fs}")
     table, budget = schedule(items, ngaps=32, budget0=8)
     g.comment(f"per-gap issue budget {budget}")
@@ -192,8 +184,8 @@ def body(g: Gen, slot: int, bias: tuple):
 
 
 def loop_tail(g: Gen, slot: int, tag: str):
-    g.salu(f"s_add_u32 {s(S_S)}, {s(S_S)}, 1", regs("s", S_S), regs("s", S_S))
-    g.salu(f"s_cmp_ge_u32 {s(S_S)}, {s(S_G)}", regs("s", S_S) | regs("s", S_G), {"scc"})
+    g.ins(f"s_add_u32 {s(S_S)}, {s(S_S)}, 1")
+    g.ins(f"s_cmp_ge_u32 {s(S_S)}, {s(S_G)}")
     g.raw("s_cbranch_scc1 L_dw4_end_%=")
     if slot == 3:
         g.raw(f"s_branch L_dw4_{tag}0_%=")
@@ -207,16 +199,13 @@ BIAS_VARIANTS = {1: (0, 1, 2, 3), 2: (0, 1), 3: (2, 3), 4: (0,), 5: (1,), 6: (2,
 def fixed_point_loop(g: Gen, variant: int):
     bias = BIAS_VARIANTS.get(variant, ())
     tag = f"v{variant}_"
-    texts = []
-    for rnd in range(3):
-        g.out = []
+
+    def four_slots():
         for slot in range(4):
             g.out.append(f"L_dw4_{tag}{slot}_%=:")
             body(g, slot, bias)
             loop_tail(g, slot, tag)
-        texts.append(list(g.out))
-    assert NOMFMA or texts[1] == texts[2], "the loop body is not a fixed point of the wait-count / hazard trackers"
-    return texts[2]
+    return fixed_point(g, four_slots, check=not NOMFMA)
 
 
 def generate():
@@ -224,7 +213,7 @@ def generate():
     prologue(g)
     g.drain()                                    # (the loops are generated from their own loop-carried state: enter them drained)
     for k in BIAS_VARIANTS:
-        g.salu(f"s_cmp_eq_u32 {s(S_BIAS)}, {k}", regs("s", S_BIAS), {"scc"})
+        g.ins(f"s_cmp_eq_u32 {s(S_BIAS)}, {k}")
         g.raw(f"s_cbranch_scc1 L_dw4_v{k}_0_%=")
     pro = list(g.out)
     # the prologue issued the requests of stages 0..2 and read F0 of stage 0: that is the state the loop body expects at its top, except
@@ -296,18 +285,18 @@ def ring_requests(g: Gen, slot: int, btrans: bool, which: str):
         off = 1024 * j if which == "a" else ring_b_dst(j, btrans)
 
         def f(j=j, off=off):
-            g.salu(f"s_add_u32 m0, {s(dst)}, {slot * RG_DSTAGE + off}", regs("s", dst), {"m0"})
+            g.ins(f"s_add_u32 m0, {s(dst)}, {slot * RG_DSTAGE + off}")
             if not (NODMA or (RING_DIAG == "noa" and which == "a") or (RING_DIAG == "nob" and which == "b")):
-                g.vmem_dma(f"global_load_lds_dwordx4 {v(vo + j)}, {s(ptr, 2)}", f"dma{which}{slot}", regs("v", vo + j) | regs("s", ptr, 2) | {"m0"})
+                g.ins(f"global_load_lds_dwordx4 {v(vo + j)}, {s(ptr, 2)}", f"dma{which}{slot}")
         out.append(f)
 
     def adv():
-        g.salu(f"s_add_u32 {s(RS_T)}, {s(ptr)}, {s(step)}", regs("s", ptr) | regs("s", step), regs("s", RS_T))
-        g.salu(f"s_addc_u32 {s(RS_T + 1)}, {s(ptr + 1)}, 0", regs("s", ptr + 1), regs("s", RS_T + 1))
-        g.salu(f"s_sub_u32 {s(rq)}, {s(rq)}, 1", regs("s", rq), regs("s", rq))
-        g.salu(f"s_cmp_eq_u32 {s(rq)}, 0", regs("s", rq), {"scc"})
-        g.salu(f"s_cselect_b64 {s(ptr, 2)}, {s(nxt, 2)}, {s(RS_T, 2)}", regs("s", nxt, 2) | regs("s", RS_T, 2), regs("s", ptr, 2))
-        g.salu(f"s_cselect_b32 {s(rq)}, {s(RS_ND)}, {s(rq)}", regs("s", RS_ND) | regs("s", rq), regs("s", rq))
+        g.ins(f"s_add_u32 {s(RS_T)}, {s(ptr)}, {s(step)}")
+        g.ins(f"s_addc_u32 {s(RS_T + 1)}, {s(ptr + 1)}, 0")
+        g.ins(f"s_sub_u32 {s(rq)}, {s(rq)}, 1")
+        g.ins(f"s_cmp_eq_u32 {s(rq)}, 0")
+        g.ins(f"s_cselect_b64 {s(ptr, 2)}, {s(nxt, 2)}, {s(RS_T, 2)}")
+        g.ins(f"s_cselect_b32 {s(rq)}, {s(RS_ND)}, {s(rq)}")
     return out, adv
 
 
@@ -324,12 +313,12 @@ def ring_reads(g: Gen, slot: int, ks: int, btrans: bool, kinds="ba"):
             continue
         if kind == "a" or not btrans:
             base = (RV_AA if kind == "a" else RV_BA) + ks + 4 * slot
-            out.append((lambda dst=dst, base=base, off=4096 * i: g.ds_read(f"ds_read_b128 {v(dst, 4)}, {v(base)} offset:{off}", regs("v", base), regs("v", dst, 4)), COST["lds128"]))
+            out.append((lambda dst=dst, base=base, off=4096 * i: g.ins(f"ds_read_b128 {v(dst, 4)}, {v(base)} offset:{off}"), COST["lds128"]))
         else:
             base = RV_BA + (i & 1) + 2 * slot
             for jq in range(2):
                 off = 16384 * (ks >> 1) + 4096 * (i >> 1) + 2048 * (ks & 1) + 512 * jq
-                out.append((lambda dst=dst + 2 * jq, base=base, off=off: g.ds_read(f"ds_read_b64_tr_b16 {v(dst, 2)}, {v(base)} offset:{off}", regs("v", base), regs("v", dst, 2)), COST["lds"]))
+                out.append((lambda dst=dst + 2 * jq, base=base, off=off: g.ins(f"ds_read_b64_tr_b16 {v(dst, 2)}, {v(base)} offset:{off}"), COST["lds"]))
     return out
 
 
@@ -341,15 +330,7 @@ def ring_body(g: Gen, slot: int, first: bool, btrans: bool):
             for ct in range(4):
                 mf.append(lambda ks=ks, rt=rt, ct=ct: g.mfma_op(f"%{4 * rt + ct}", ("v", rfrag(ks, "b", ct)), ("v", rfrag(ks, "a", rt)), c0=(first and ks == 0)))
     items = []
-
-    def add(fns, spread=0, **kw):
-        out = []
-        for k, (f, cost) in enumerate(fns):
-            kw2 = dict(kw)
-            kw2["earliest"] = kw.get("earliest", 1) + k * spread // len(fns)
-            out.append(Item(f, cost, **kw2))
-        items.extend(out)
-        return out
+    add = functools.partial(add_items, items)          # (ring_reads: (function, cost) pairs)
 
     oslot = slot ^ 1
     # B is read out first (all of its fragments by MFMA 27), A progressively: the two images of a slot are released -- and requested again --
@@ -365,20 +346,20 @@ def ring_body(g: Gen, slot: int, first: bool, btrans: bool):
         # issued (an LDS-DMA piece served by L2 lands 250+ cycles after its issue; a queue of LDS reads can be that long)
         g.prewait(set().union(*[regs("v", rfrag(ks, "b", i), 4) for ks in (1, 2, 3) for i in range(4)]))
         g.raw("s_barrier")
-    bar1 = add([(barrier1, COST["sync"])], pin=28, deadline=64, deps=rb1 + rb2 + rb3, name="barrier1")   # every wave has read B
+    bar1 = add([barrier1], COST["sync"], pin=28, deadline=64, deps=rb1 + rb2 + rb3, name="barrier1")   # every wave has read B
     pb_, advb = ring_requests(g, slot, btrans, "b")
-    dmb = add([(f, COST["salu"] + COST["vmem"]) for f in pb_], earliest=29, deadline=40, spread=8, deps=bar1, name="dma_b")
-    add([(advb, 6 * COST["salu"])], earliest=37, deadline=63, deps=dmb, name="adv_b")
+    dmb = add(pb_, COST["salu"] + COST["vmem"], earliest=29, deadline=40, spread=8, deps=bar1, name="dma_b")
+    add([advb], 6 * COST["salu"], earliest=37, deadline=63, deps=dmb, name="adv_b")
     ra3 = add(ring_reads(g, slot, 3, btrans, "a"), earliest=30, deadline=41, spread=8, name="rd_a3")
 
     def barrier2():
         g.wait_vm_tag(f"dmaa{oslot}")                      # this wave's pieces of the next stage have landed (its B image is older)
         g.prewait(set().union(*[regs("v", rfrag(ks, "a", i), 4) for ks in (1, 2, 3) for i in range(4)]))     # ... and its reads of A have returned
         g.raw("s_barrier")
-    bar2 = add([(barrier2, COST["sync"])], pin=44, deadline=64, deps=ra1 + ra2 + ra3, name="barrier2")     # ... and every wave has read A
+    bar2 = add([barrier2], COST["sync"], pin=44, deadline=64, deps=ra1 + ra2 + ra3, name="barrier2")     # ... and every wave has read A
     pa_, adva = ring_requests(g, slot, btrans, "a")
-    dma_ = add([(f, COST["salu"] + COST["vmem"]) for f in pa_], earliest=45, deadline=56, spread=8, deps=bar2, name="dma_a")
-    add([(adva, 6 * COST["salu"])], earliest=53, deadline=63, deps=dma_, name="adv_a")
+    dma_ = add(pa_, COST["salu"] + COST["vmem"], earliest=45, deadline=56, spread=8, deps=bar2, name="dma_a")
+    add([adva], 6 * COST["salu"], earliest=53, deadline=63, deps=dma_, name="adv_a")
     add(ring_reads(g, oslot, 0, btrans), earliest=46, deadline=62, spread=14, deps=bar2, name="rd_k0")   # F0: read by MFMAs 1-16
     table, budget = schedule(items, ngaps=64, budget0=8)
     g.comment(f"per-gap issue budget {budget}")
@@ -399,64 +380,64 @@ def ring_tile(btrans: bool):
     # counts sized for it.
     g.raw("s_waitcnt lgkmcnt(0)")
     g.lgkm = []
-    g.valu(f"v_mbcnt_lo_u32_b32 {v(RV_L)}, -1, 0", set(), regs("v", RV_L))
-    g.valu(f"v_mbcnt_hi_u32_b32 {v(RV_L)}, -1, {v(RV_L)}", regs("v", RV_L), regs("v", RV_L))
-    g.valu(f"v_mov_b32_e32 {v(RV_PB)}, %16", set(), regs("v", RV_PB))
-    g.salu(f"s_mov_b32 {s(RS_PARAM)}, %16", (), regs("s", RS_PARAM))
+    g.ins(f"v_mbcnt_lo_u32_b32 {v(RV_L)}, -1, 0")
+    g.ins(f"v_mbcnt_hi_u32_b32 {v(RV_L)}, -1, {v(RV_L)}")
+    g.ins(f"v_mov_b32_e32 {v(RV_PB)}, %16")
+    g.ins(f"s_mov_b32 {s(RS_PARAM)}, %16")
     for k in range(5):
-        g.ds_read(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(RV_PB)} offset:{16 * k}", regs("v", RV_PB), regs("v", T + 4 * k, 4))
-    g.valu(f"v_lshl_add_u32 {v(RV_PB + 1)}, {v(RV_L)}, 2, {v(RV_PB)}", regs("v", RV_L) | regs("v", RV_PB), regs("v", RV_PB + 1))
+        g.ins(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(RV_PB)} offset:{16 * k}")
+    g.ins(f"v_lshl_add_u32 {v(RV_PB + 1)}, {v(RV_L)}, 2, {v(RV_PB)}")
     # lane table: DMA offsets of the wave's pieces 0 and 1 of either image (the others: + j * 8 rows), fragment addresses in slot 0
     tab = [RV_VOA, RV_VOA + 1, RV_VOB, RV_VOB + 1, RV_AA, RV_BA, RV_BA + 1]
     for k, dst in enumerate(tab):
-        g.ds_read(f"ds_read_b32 {v(dst)}, {v(RV_PB + 1)} offset:{1024 + 256 * k}", regs("v", RV_PB + 1), regs("v", dst))
+        g.ins(f"ds_read_b32 {v(dst)}, {v(RV_PB + 1)} offset:{1024 + 256 * k}")
     g.raw("s_waitcnt lgkmcnt(0)")
     g.lgkm = []
     g.nop(1)
     sc = [RS_AP, RS_AP + 1, RS_BP, RS_BP + 1, RS_ANEXT, RS_ANEXT + 1, RS_BNEXT, RS_BNEXT + 1, RS_ASTEP, RS_BSTEP, RS_ND, RS_RQ, RS_LDS, RS_W,
           RS_FIRSTF, RS_AROW8, RS_BIASP, RS_BIASP + 1, RS_BROW8, RS_RQB]
     for k, dst in enumerate(sc):
-        g.valu(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}", regs("v", T + k), regs("s", dst))
+        g.ins(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}")
     g.nop(4)
     # the other pieces' offsets: piece j = piece (j & 1) + (j - (j & 1)) * 8 rows (the images' swizzles repeat every 16 rows);
     # NN B: piece j = piece 0 + (8 (j & 3) + 32 (j >> 2)) rows
     for j in range(7, -1, -1):
         if j >= 2:
-            g.salu(f"s_mul_i32 {s(RS_T)}, {s(RS_AROW8)}, {j - (j & 1)}", regs("s", RS_AROW8), regs("s", RS_T))
-            g.valu(f"v_add_u32_e32 {v(RV_VOA + j)}, {s(RS_T)}, {v(RV_VOA + (j & 1))}", regs("s", RS_T) | regs("v", RV_VOA + (j & 1)), regs("v", RV_VOA + j))
+            g.ins(f"s_mul_i32 {s(RS_T)}, {s(RS_AROW8)}, {j - (j & 1)}")
+            g.ins(f"v_add_u32_e32 {v(RV_VOA + j)}, {s(RS_T)}, {v(RV_VOA + (j & 1))}")
         if not btrans:
             if j >= 2:
-                g.salu(f"s_mul_i32 {s(RS_T)}, {s(RS_BROW8)}, {j - (j & 1)}", regs("s", RS_BROW8), regs("s", RS_T))
-                g.valu(f"v_add_u32_e32 {v(RV_VOB + j)}, {s(RS_T)}, {v(RV_VOB + (j & 1))}", regs("s", RS_T) | regs("v", RV_VOB + (j & 1)), regs("v", RV_VOB + j))
+                g.ins(f"s_mul_i32 {s(RS_T)}, {s(RS_BROW8)}, {j - (j & 1)}")
+                g.ins(f"v_add_u32_e32 {v(RV_VOB + j)}, {s(RS_T)}, {v(RV_VOB + (j & 1))}")
         elif j >= 1:
-            g.salu(f"s_mul_i32 {s(RS_T)}, {s(RS_BROW8)}, {(j & 3) + 4 * (j >> 2)}", regs("s", RS_BROW8), regs("s", RS_T))
-            g.valu(f"v_add_u32_e32 {v(RV_VOB + j)}, {s(RS_T)}, {v(RV_VOB)}", regs("s", RS_T) | regs("v", RV_VOB), regs("v", RV_VOB + j))
+            g.ins(f"s_mul_i32 {s(RS_T)}, {s(RS_BROW8)}, {(j & 3) + 4 * (j >> 2)}")
+            g.ins(f"v_add_u32_e32 {v(RV_VOB + j)}, {s(RS_T)}, {v(RV_VOB)}")
     # fragment addresses: k-step ks = address of k-step 0 ^ (32 ks) (the chunk field), slot 1 = + 64 KB
     for ks in range(1, 4):
-        g.valu(f"v_xor_b32_e32 {v(RV_AA + ks)}, {32 * ks}, {v(RV_AA)}", regs("v", RV_AA), regs("v", RV_AA + ks))
+        g.ins(f"v_xor_b32_e32 {v(RV_AA + ks)}, {32 * ks}, {v(RV_AA)}")
     for ks in range(4):
-        g.valu(f"v_add_u32_e32 {v(RV_AA + 4 + ks)}, 0x10000, {v(RV_AA + ks)}", regs("v", RV_AA + ks), regs("v", RV_AA + 4 + ks))
+        g.ins(f"v_add_u32_e32 {v(RV_AA + 4 + ks)}, 0x10000, {v(RV_AA + ks)}")
     if not btrans:
         for ks in range(1, 4):
-            g.valu(f"v_xor_b32_e32 {v(RV_BA + ks)}, {32 * ks}, {v(RV_BA)}", regs("v", RV_BA), regs("v", RV_BA + ks))
+            g.ins(f"v_xor_b32_e32 {v(RV_BA + ks)}, {32 * ks}, {v(RV_BA)}")
         for ks in range(4):
-            g.valu(f"v_add_u32_e32 {v(RV_BA + 4 + ks)}, 0x10000, {v(RV_BA + ks)}", regs("v", RV_BA + ks), regs("v", RV_BA + 4 + ks))
+            g.ins(f"v_add_u32_e32 {v(RV_BA + 4 + ks)}, 0x10000, {v(RV_BA + ks)}")
     else:
         for k in range(2):
-            g.valu(f"v_add_u32_e32 {v(RV_BA + 2 + k)}, 0x10000, {v(RV_BA + k)}", regs("v", RV_BA + k), regs("v", RV_BA + 2 + k))
-    g.valu(f"v_lshlrev_b32_e32 {v(RV_BIASO)}, 2, {v(RV_L)}", regs("v", RV_L), regs("v", RV_BIASO))
+            g.ins(f"v_add_u32_e32 {v(RV_BA + 2 + k)}, 0x10000, {v(RV_BA + k)}")
+    g.ins(f"v_lshlrev_b32_e32 {v(RV_BIASO)}, 2, {v(RV_L)}")
     # LDS destinations of the wave's pieces: A pieces 8 w + j; B: NT the same in the B image, NN pieces 4 w + (j & 3) of either half
-    g.salu(f"s_lshl_b32 {s(RS_T)}, {s(RS_W)}, 13", regs("s", RS_W), regs("s", RS_T))
-    g.salu(f"s_add_u32 {s(RS_DA)}, {s(RS_LDS)}, {s(RS_T)}", regs("s", RS_LDS) | regs("s", RS_T), regs("s", RS_DA))
+    g.ins(f"s_lshl_b32 {s(RS_T)}, {s(RS_W)}, 13")
+    g.ins(f"s_add_u32 {s(RS_DA)}, {s(RS_LDS)}, {s(RS_T)}")
     if btrans:
-        g.salu(f"s_lshl_b32 {s(RS_T)}, {s(RS_W)}, 12", regs("s", RS_W), regs("s", RS_T))
-        g.salu(f"s_add_u32 {s(RS_DB)}, {s(RS_LDS)}, {s(RS_T)}", regs("s", RS_LDS) | regs("s", RS_T), regs("s", RS_DB))
-        g.salu(f"s_add_u32 {s(RS_DB)}, {s(RS_DB)}, 32768", regs("s", RS_DB), regs("s", RS_DB))
+        g.ins(f"s_lshl_b32 {s(RS_T)}, {s(RS_W)}, 12")
+        g.ins(f"s_add_u32 {s(RS_DB)}, {s(RS_LDS)}, {s(RS_T)}")
+        g.ins(f"s_add_u32 {s(RS_DB)}, {s(RS_DB)}, 32768")
     else:
-        g.salu(f"s_add_u32 {s(RS_DB)}, {s(RS_DA)}, 32768", regs("s", RS_DA), regs("s", RS_DB))
-    g.salu(f"s_lshr_b32 {s(RS_CNT)}, {s(RS_ND)}, 1", regs("s", RS_ND), regs("s", RS_CNT))
-    g.salu(f"s_sub_u32 {s(RS_CNT)}, {s(RS_CNT)}, 1", regs("s", RS_CNT), regs("s", RS_CNT))       # loop rounds after the tile's first two stages
-    g.salu(f"s_cmp_lg_u32 {s(RS_FIRSTF)}, 0", regs("s", RS_FIRSTF), {"scc"})
+        g.ins(f"s_add_u32 {s(RS_DB)}, {s(RS_DA)}, 32768")
+    g.ins(f"s_lshr_b32 {s(RS_CNT)}, {s(RS_ND)}, 1")
+    g.ins(f"s_sub_u32 {s(RS_CNT)}, {s(RS_CNT)}, 1")       # loop rounds after the tile's first two stages
+    g.ins(f"s_cmp_lg_u32 {s(RS_FIRSTF)}, 0")
     g.raw("s_cbranch_scc1 L_r4_first_%=")
     # not the workgroup's first tile: in the in-order queue stand the requests of this tile's stages 0 and 1 (issued by the previous
     # statement's last two stages) and, younger, the epilogue's stores: stage 0 has landed when all but stage 1 and the stores have
@@ -486,41 +467,40 @@ def ring_tile(btrans: bool):
     # two instructions fetch nothing but still count in vmcnt, which the counted waits below rely on.  (Starting the accumulators from
     # the bias -- C of the tile's first MFMAs -- would save the epilogue 128 v_pk_add per tile, but the sum then rounds differently from
     # the 128 x 128 kernels': the bit-identity between the GEMM paths is worth more than ~3 % of the forward GEMMs)
-    g.salu(f"s_add_u32 m0, {s(RS_PARAM)}, 512", regs("s", RS_PARAM), {"m0"})
-    g.salu(f"s_cmp_eq_u64 {s(RS_BIASP, 2)}, 0", regs("s", RS_BIASP, 2), {"scc"})
-    g.salu("s_cselect_b64 exec, 0, -1", {"scc"}, {"exec"})
-    g.vmem_dma(f"global_load_lds_dword {v(RV_BIASO)}, {s(RS_BIASP, 2)}", "bias", regs("v", RV_BIASO) | regs("s", RS_BIASP, 2) | {"m0"})
-    g.vmem_dma(f"global_load_lds_dword {v(RV_BIASO)}, {s(RS_BIASP, 2)} offset:256", "bias", regs("v", RV_BIASO) | regs("s", RS_BIASP, 2) | {"m0"})
-    g.salu("s_mov_b64 exec, -1", (), {"exec"})
+    g.ins(f"s_add_u32 m0, {s(RS_PARAM)}, 512")
+    g.ins(f"s_cmp_eq_u64 {s(RS_BIASP, 2)}, 0")
+    g.ins("s_cselect_b64 exec, 0, -1")
+    g.ins(f"global_load_lds_dword {v(RV_BIASO)}, {s(RS_BIASP, 2)}", "bias")
+    g.ins(f"global_load_lds_dword {v(RV_BIASO)}, {s(RS_BIASP, 2)} offset:256", "bias")
+    g.ins("s_mov_b64 exec, -1")
     g.raw("s_barrier")
     for f, _ in ring_reads(g, 0, 0, btrans):
         f()
     for slot in range(2):
         ring_body(g, slot, slot == 0, btrans)
     head = list(g.out)
-    texts = []
-    for rnd in range(3):
-        g.out = ["L_r4_loop_%=:"]
+
+    def two_slots():
+        g.out.append("L_r4_loop_%=:")
         for slot in range(2):
             ring_body(g, slot, False, btrans)
-        g.salu(f"s_sub_u32 {s(RS_CNT)}, {s(RS_CNT)}, 1", regs("s", RS_CNT), regs("s", RS_CNT))
-        g.salu(f"s_cmp_lg_u32 {s(RS_CNT)}, 0", regs("s", RS_CNT), {"scc"})
+        g.ins(f"s_sub_u32 {s(RS_CNT)}, {s(RS_CNT)}, 1")
+        g.ins(f"s_cmp_lg_u32 {s(RS_CNT)}, 0")
         g.raw("s_cbranch_scc1 L_r4_loop_%=")
-        texts.append(list(g.out))
-    assert texts[1] == texts[2], "the ring loop is not a fixed point of the wait-count / hazard trackers"
+    loop = fixed_point(g, two_slots)
     g.out = []
     g.comment("==== exit: the ring's state back to the parameter block (its requests stay in flight) ====")
     for k, src in enumerate([RS_AP, RS_AP + 1, RS_BP, RS_BP + 1]):
-        g.valu(f"v_mov_b32_e32 {v(T + k)}, {s(src)}", regs("s", src), regs("v", T + k))
-    g.valu(f"v_mov_b32_e32 {v(T + 4)}, {s(RS_RQ)}", regs("s", RS_RQ), regs("v", T + 4))
-    g.valu(f"v_mov_b32_e32 {v(T + 5)}, {s(RS_RQB)}", regs("s", RS_RQB), regs("v", T + 5))
+        g.ins(f"v_mov_b32_e32 {v(T + k)}, {s(src)}")
+    g.ins(f"v_mov_b32_e32 {v(T + 4)}, {s(RS_RQ)}")
+    g.ins(f"v_mov_b32_e32 {v(T + 5)}, {s(RS_RQB)}")
     g.raw(f"ds_write_b128 {v(RV_PB)}, {v(T, 4)}")
     g.raw(f"ds_write_b32 {v(RV_PB)}, {v(T + 4)} offset:44")
     g.raw(f"ds_write_b32 {v(RV_PB)}, {v(T + 5)} offset:76")
     g.raw("s_waitcnt lgkmcnt(0)")
     g.lgkm = []
     g.nop(16)
-    return head + texts[2] + g.out, g
+    return head + loop + g.out, g
 
 
 def ring_clobbers():
@@ -529,52 +509,28 @@ def ring_clobbers():
 
 def write_ring(here):
     path = os.path.join(here, "linear_ring4_loop_diag.inc" if DIAG else "linear_ring4_loop.inc")
-    import io
-    f = io.StringIO()
-    if True:
-        f.write("// GENERATED by gen_gemm_asm.py -- do not edit.  One tile of linear_ring4_kernel<BTRANS, PRE> (one asm statement each): operands\n")
-        f.write("// %0..%15 = acc[rt][ct] (\"=a\": all 256 AGPRs, written from C = 0), %16 = LDS address of the wave's parameter block (\"s\").\n")
-        for btrans, name in ((False, "NT"), (True, "NN")):
-            lines, g = ring_tile(btrans)
-            f.write(f"#define MGX_RING4_{name}_ASM \\\n")
-            for ln in lines:
-                if ln.startswith(";"):
-                    f.write(f"    /* {ln[1:].strip()} */ \\\n")
-                else:
-                    f.write(f'    "{ln}\\n\\t" \\\n')
-            f.write('    ""\n')
-            n_ins = sum(1 for ln in lines if not ln.startswith(";") and not ln.endswith(":"))
-            print(f"wrote {path} ({name}): {n_ins} instructions, s_nop wait states inserted: {g.nops}", file=sys.stderr)
-        f.write("#define MGX_RING4_CLOBBERS " + ", ".join(f'"{c}"' for c in ring_clobbers()) + "\n")
-        f.write(f"#define MGX_RING4_EPI_STORES {EPI_STORES}\n")
-    write_if_changed(path, f.getvalue())
+    macros = []
+    for btrans, name in ((False, "NT"), (True, "NN")):
+        lines, g = ring_tile(btrans)
+        macros.append((f"MGX_RING4_{name}_ASM", lines))
+        summary(path, lines, g, label=f" ({name})", counts=False)
+    write_inc(path, ["GENERATED by gen_gemm_asm.py -- do not edit.  One tile of linear_ring4_kernel<BTRANS, PRE> (one asm statement each): operands",
+                     "%0..%15 = acc[rt][ct] (\"=a\": all 256 AGPRs, written from C = 0), %16 = LDS address of the wave's parameter block (\"s\")."],
+              macros, ("MGX_RING4_CLOBBERS", ring_clobbers()), tail=f"#define MGX_RING4_EPI_STORES {EPI_STORES}\n")
 
 
 def clobbers():
-    c = [f"v{i}" for i in range(V_FIRST, V_LAST + 1)] + [f"s{i}" for i in range(S_FIRST, S_LAST + 1)] + ["vcc", "scc", "m0", "memory"]
-    return c
+    return [f"v{i}" for i in range(V_FIRST, V_LAST + 1)] + [f"s{i}" for i in range(S_FIRST, S_LAST + 1)] + ["vcc", "scc", "m0", "memory"]
 
 
 def write(here):
     lines, g = generate()
     path = os.path.join(here, "linear_dw_ring4_loop_diag.inc" if DIAG else "linear_dw_ring4_loop.inc")
-    import io
-    f = io.StringIO()
-    if True:
-        f.write("// GENERATED by gen_gemm_asm.py -- do not edit.  The hand-scheduled main loop of linear_dw_ring4_kernel (one asm statement):\n")
-        f.write("// operands %0..%15 = acc[rt][ct] (\"+a\": all 256 AGPRs), %16..%19 = the bias-gradient partial sums (\"+v\"), %20 = LDS address of the\n")
-        f.write("// wave's parameter block (\"s\").  Register map and schedule: gen_gemm_asm.py.\n")
-        f.write("#define MGX_DW4_LOOP_ASM \\\n")
-        for ln in lines:
-            if ln.startswith(";"):
-                f.write(f"    /* {ln[1:].strip()} */ \\\n")
-            else:
-                f.write(f'    "{ln}\\n\\t" \\\n')
-        f.write('    ""\n')
-        f.write("#define MGX_DW4_LOOP_CLOBBERS " + ", ".join(f'"{c}"' for c in clobbers()) + "\n")
-    write_if_changed(path, f.getvalue())
-    n_ins = sum(1 for ln in lines if not ln.startswith(";") and not ln.endswith(":"))
-    print(f"wrote {path}: {n_ins} instructions, s_nop wait states inserted: {g.nops}; counts {g.stats}", file=sys.stderr)
+    write_inc(path, ["GENERATED by gen_gemm_asm.py -- do not edit.  The hand-scheduled main loop of linear_dw_ring4_kernel (one asm statement):",
+                     "operands %0..%15 = acc[rt][ct] (\"+a\": all 256 AGPRs), %16..%19 = the bias-gradient partial sums (\"+v\"), %20 = LDS address of the",
+                     "wave's parameter block (\"s\").  Register map and schedule: gen_gemm_asm.py."],
+              [("MGX_DW4_LOOP_ASM", lines)], ("MGX_DW4_LOOP_CLOBBERS", clobbers()))
+    summary(path, lines, g)
 
 
 if __name__ == "__main__":

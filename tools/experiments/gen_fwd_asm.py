@@ -27,11 +27,12 @@ as branch-free "main" bodies (tile n+1 strictly below both diagonals, no padded 
 """
 from __future__ import annotations
 
+import functools
 import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "musicgeneration_amd", "csrc"))
-from asm_sched import COST, Gen, Item, a, chain, crow, regs, s, salu_items, schedule, v, write_if_changed  # noqa: E402
+from asm_sched import COST, Gen, a, add_items, chain, crow, fixed_point, regs, s, salu_items, schedule, summary, v, write_inc  # noqa: E402
 
 # ---------------------------------------------------------------------------------------------------------------------
 # register map
@@ -117,8 +118,7 @@ class Step:
     # ---- LDS -------------------------------------------------------------------------------------------------------
     def rd_K(self):
         buf = self.t1 % 3
-        return [lambda ks=ks: self.g.ds_read(f"ds_read_b128 {a(A_KF + 4 * ks, 4)}, {v(V_AK + ks)} offset:{OFF_K + 4096 * buf}",
-                                             regs("v", V_AK + ks), regs("a", A_KF + 4 * ks, 4)) for ks in range(4)]
+        return [lambda ks=ks: self.g.ins(f"ds_read_b128 {a(A_KF + 4 * ks, 4)}, {v(V_AK + ks)} offset:{OFF_K + 4096 * buf}") for ks in range(4)]
 
     def rd_V(self):
         buf = self.t0 % 3
@@ -128,23 +128,20 @@ class Step:
                 for jq in range(2):
                     dst = A_VF + 4 * (2 * ss + ct) + 2 * jq
                     off = OFF_V + 4096 * buf + (16 * ss + 8 * jq) * 128
-                    out.append(lambda dst=dst, off=off, ct=ct: self.g.ds_read(f"ds_read_b64_tr_b16 {a(dst, 2)}, {v(V_ATR + ct)} offset:{off}",
-                                                                             regs("v", V_ATR + ct), regs("a", dst, 2)))
+                    out.append(lambda dst=dst, off=off, ct=ct: self.g.ins(f"ds_read_b64_tr_b16 {a(dst, 2)}, {v(V_ATR + ct)} offset:{off}"))
         return out
 
     def band_put(self, X):
         """chunk product of tile t2 -> band X at the parity of its chunk index (dq - 1 = I_X - t2 - 1: parity (X + t2 + 1) & 1, I_A even)"""
         par = (X + self.t2 + 1) & 1
         q = V_QE + 16 * X
-        return [lambda r=r: self.g.emit("lds", f"ds_write_b32 {v(V_WCL[par] + r)}, {v(q + r)} offset:{r * BAND_STRIDE + X * BAND_BYTES}",
-                                        regs("v", V_WCL[par] + r) | regs("v", q + r), set()) for r in range(16)]
+        return [lambda r=r: self.g.ins(f"ds_write_b32 {v(V_WCL[par] + r)}, {v(q + r)} offset:{r * BAND_STRIDE + X * BAND_BYTES}") for r in range(16)]
 
     def band_get(self, X):
         """Srel^T of tile t2 (D / 32 = dq = I_X - t2: parity (X + t2) & 1) -> the score registers of tile t2"""
         par = (X + self.t2) & 1
         d = self.sset(self.t2, X)
-        return [lambda g4=g4: self.g.ds_read(f"ds_read_b128 {v(d + 4 * g4, 4)}, {v(V_RB)} offset:{X * BAND_BYTES + 128 * par + 32 * g4}",
-                                             regs("v", V_RB), regs("v", d + 4 * g4, 4)) for g4 in range(4)]
+        return [lambda g4=g4: self.g.ins(f"ds_read_b128 {v(d + 4 * g4, 4)}, {v(V_RB)} offset:{X * BAND_BYTES + 128 * par + 32 * g4}") for g4 in range(4)]
 
     # ---- exponentials ------------------------------------------------------------------------------------------------
     def exp_items(self, t, X, lo, hi):
@@ -152,8 +149,8 @@ class Step:
         sr, p = self.sset(t, X), self.pset(t, X)
         out = []
         for r in range(lo, hi):
-            out.append(lambda r=r: self.g.valu(f"v_fma_f32 {v(p + r)}, {v(sr + r)}, {s(S_LOG2E)}, {v(V_MNEG + X)}", regs("v", sr + r) | regs("v", V_MNEG + X), regs("v", p + r)))
-            out.append(lambda r=r: self.g.valu(f"v_exp_f32_e32 {v(p + r)}, {v(p + r)}", regs("v", p + r), regs("v", p + r), trans=True))
+            out.append(lambda r=r: self.g.ins(f"v_fma_f32 {v(p + r)}, {v(sr + r)}, {s(S_LOG2E)}, {v(V_MNEG + X)}"))
+            out.append(lambda r=r: self.g.ins(f"v_exp_f32_e32 {v(p + r)}, {v(p + r)}"))
         return out
 
     def sum_items(self, t, X):
@@ -163,15 +160,15 @@ class Step:
         p, ls, c = self.pset(t, X), V_LSUM + X, V_SUMT + 4 * X
         out, need = [], []
         for j in range(4):
-            out.append(lambda j=j: self.g.valu(f"v_add_f32_e32 {v(c + j)}, {v(p + j)}, {v(p + j + 4)}", regs("v", p + j) | regs("v", p + j + 4), regs("v", c + j)))
+            out.append(lambda j=j: self.g.ins(f"v_add_f32_e32 {v(c + j)}, {v(p + j)}, {v(p + j + 4)}"))
             need.append((j, j + 4))
         for k in (8, 12):
             for j in range(4):
-                out.append(lambda j=j, k=k: self.g.valu(f"v_add_f32_e32 {v(c + j)}, {v(c + j)}, {v(p + j + k)}", regs("v", c + j) | regs("v", p + j + k), regs("v", c + j)))
+                out.append(lambda j=j, k=k: self.g.ins(f"v_add_f32_e32 {v(c + j)}, {v(c + j)}, {v(p + j + k)}"))
                 need.append((j + k,))
-        out.append(lambda: self.g.valu(f"v_add_f32_e32 {v(c)}, {v(c)}, {v(c + 1)}", regs("v", c, 2), regs("v", c)))
-        out.append(lambda: self.g.valu(f"v_add_f32_e32 {v(c + 2)}, {v(c + 2)}, {v(c + 3)}", regs("v", c + 2, 2), regs("v", c + 2)))
-        out.append(lambda: self.g.valu(f"v_add_f32_e32 {v(ls)}, {v(c)}, {v(c + 2)}", regs("v", c) | regs("v", c + 2), regs("v", ls)))
+        out.append(lambda: self.g.ins(f"v_add_f32_e32 {v(c)}, {v(c)}, {v(c + 1)}"))
+        out.append(lambda: self.g.ins(f"v_add_f32_e32 {v(c + 2)}, {v(c + 2)}, {v(c + 3)}"))
+        out.append(lambda: self.g.ins(f"v_add_f32_e32 {v(ls)}, {v(c)}, {v(c + 2)}"))
         need += [(), (), ()]
         return out, need
 
@@ -181,12 +178,12 @@ class Step:
         ls = V_LSUM + X
 
         def f():
-            g.valu(f"v_cmp_nle_f32_e64 vcc, {v(ls)}, {s(S_LSAFE)}", regs("v", ls), {"vcc"})
-            g.salu(f"s_mov_b32 {s(S_RET)}, {site}", (), regs("s", S_RET))
+            g.ins(f"v_cmp_nle_f32_e64 vcc, {v(ls)}, {s(S_LSAFE)}")
+            g.ins(f"s_mov_b32 {s(S_RET)}, {site}")
             g.nop(4)
             g.raw(f"s_cbranch_vccnz L_fwd_redo{X}{t & 1}_%=")
             g.out.append(f"L_fwd_ret{site}_%=:")
-            g.valu(f"v_add_f32_e32 {v(V_L + X)}, {v(V_L + X)}, {v(ls)}", regs("v", V_L + X) | regs("v", ls), regs("v", V_L + X))
+            g.ins(f"v_add_f32_e32 {v(V_L + X)}, {v(V_L + X)}, {v(ls)}")
         return [f]
 
     def pack_items(self, t, X):
@@ -195,7 +192,7 @@ class Step:
         for ss in range(2):
             for j in range(4):
                 lo, hi, dst = p + 8 * ss + 2 * j, p + 8 * ss + 2 * j + 1, p + 8 * ss + j
-                out.append(lambda lo=lo, hi=hi, dst=dst: self.g.valu(f"v_cvt_pk_bf16_f32 {v(dst)}, {v(lo)}, {v(hi)}", regs("v", lo) | regs("v", hi), regs("v", dst)))
+                out.append(lambda lo=lo, hi=hi, dst=dst: self.g.ins(f"v_cvt_pk_bf16_f32 {v(dst)}, {v(lo)}, {v(hi)}"))
         return out
 
     # ---- DMA / E / scalar bookkeeping ------------------------------------------------------------------------------------
@@ -203,19 +200,19 @@ class Step:
         """key tile min(t2, ntw - 1) -> buffer t2 % 3 (this wave's two pieces of each image)"""
         g = self.g
         buf = self.t2 % 3
-        ops = [(f"s_add_u32 {s(S_T)}, {s(S_N)}, 2", regs("s", S_N), regs("s", S_T)),
-               (f"s_sub_u32 {s(S_T + 1)}, {s(S_NTW)}, 1", regs("s", S_NTW), regs("s", S_T + 1)),
-               (f"s_min_i32 {s(S_T)}, {s(S_T)}, {s(S_T + 1)}", regs("s", S_T, 2), regs("s", S_T)),
-               (f"s_max_i32 {s(S_T)}, {s(S_T)}, 0", regs("s", S_T), regs("s", S_T)),
-               (f"s_mul_i32 {s(S_T + 1)}, {s(S_T)}, {s(S_KSTEP)}", regs("s", S_T) | regs("s", S_KSTEP), regs("s", S_T + 1)),
-               (f"s_add_u32 {s(S_T + 2)}, {s(S_KVB)}, {s(S_T + 1)}", regs("s", S_KVB) | regs("s", S_T + 1), regs("s", S_T + 2)),
-               (f"s_addc_u32 {s(S_T + 3)}, {s(S_KVB + 1)}, 0", regs("s", S_KVB + 1), regs("s", S_T + 3))]
+        ops = [f"s_add_u32 {s(S_T)}, {s(S_N)}, 2",
+               f"s_sub_u32 {s(S_T + 1)}, {s(S_NTW)}, 1",
+               f"s_min_i32 {s(S_T)}, {s(S_T)}, {s(S_T + 1)}",
+               f"s_max_i32 {s(S_T)}, {s(S_T)}, 0",
+               f"s_mul_i32 {s(S_T + 1)}, {s(S_T)}, {s(S_KSTEP)}",
+               f"s_add_u32 {s(S_T + 2)}, {s(S_KVB)}, {s(S_T + 1)}",
+               f"s_addc_u32 {s(S_T + 3)}, {s(S_KVB + 1)}, 0"]
         out = salu_items(g, ops)
         for i in range(2):
             for img, voff in ((OFF_K, V_KOFF + i), (OFF_V, V_VOFF + i)):
                 def piece(i=i, img=img, voff=voff):
-                    g.salu(f"s_add_u32 m0, {s(S_DK)}, {img + 4096 * buf + 2048 * i}", regs("s", S_DK), {"m0"})
-                    g.vmem_dma(f"global_load_lds_dwordx4 {v(voff)}, {s(S_T + 2, 2)}", tag, regs("v", voff) | regs("s", S_T + 2, 2) | {"m0"})
+                    g.ins(f"s_add_u32 m0, {s(S_DK)}, {img + 4096 * buf + 2048 * i}")
+                    g.ins(f"global_load_lds_dwordx4 {v(voff)}, {s(S_T + 2, 2)}", tag)
                 out.append(piece)
         return out
 
@@ -223,16 +220,15 @@ class Step:
         """chunk clamp(I_A - t2 - 2, 0, nchunk - 1) -> slot (t2 + 1) & 1 (B's slot at t2 = A's slot at t2 + 1)"""
         g = self.g
         slot = A_E + 16 * ((self.t2 + 1) & 1)
-        ops = [(f"s_sub_u32 {s(S_T + 4)}, {s(S_IA)}, {s(S_N)}", regs("s", S_IA) | regs("s", S_N), regs("s", S_T + 4)),
-               (f"s_sub_u32 {s(S_T + 4)}, {s(S_T + 4)}, 4", regs("s", S_T + 4), regs("s", S_T + 4)),          # I_A - (n + 2) - 2
-               (f"s_max_i32 {s(S_T + 4)}, {s(S_T + 4)}, 0", regs("s", S_T + 4), regs("s", S_T + 4)),
-               (f"s_lshl_b32 {s(S_T + 4)}, {s(S_T + 4)}, 12", regs("s", S_T + 4), regs("s", S_T + 4)),
-               (f"s_add_u32 {s(S_EP)}, {s(S_EFA)}, {s(S_T + 4)}", regs("s", S_EFA) | regs("s", S_T + 4), regs("s", S_EP)),
-               (f"s_addc_u32 {s(S_EP + 1)}, {s(S_EFA + 1)}, 0", regs("s", S_EFA + 1), regs("s", S_EP + 1))]
+        ops = [f"s_sub_u32 {s(S_T + 4)}, {s(S_IA)}, {s(S_N)}",
+               f"s_sub_u32 {s(S_T + 4)}, {s(S_T + 4)}, 4",          # I_A - (n + 2) - 2
+               f"s_max_i32 {s(S_T + 4)}, {s(S_T + 4)}, 0",
+               f"s_lshl_b32 {s(S_T + 4)}, {s(S_T + 4)}, 12",
+               f"s_add_u32 {s(S_EP)}, {s(S_EFA)}, {s(S_T + 4)}",
+               f"s_addc_u32 {s(S_EP + 1)}, {s(S_EFA + 1)}, 0"]
         out = salu_items(g, ops)
         for ks in range(4):
-            out.append(lambda ks=ks: g.vmem_load(f"global_load_dwordx4 {a(slot + 4 * ks, 4)}, {v(V_L16)}, {s(S_EP, 2)} offset:{1024 * ks}", tag,
-                                                 regs("v", V_L16) | regs("s", S_EP, 2), regs("a", slot + 4 * ks, 4)))
+            out.append(lambda ks=ks: g.ins(f"global_load_dwordx4 {a(slot + 4 * ks, 4)}, {v(V_L16)}, {s(S_EP, 2)} offset:{1024 * ks}", tag))
         return out
 
     def barrier_item(self, dma_tag):
@@ -250,13 +246,13 @@ class Step:
 
         def f():
             for X in range(2):
-                g.salu(f"s_sub_u32 {s(S_TM)}, {s(S_IA)}, {s(S_N)}", regs("s", S_IA) | regs("s", S_N), regs("s", S_TM))
+                g.ins(f"s_sub_u32 {s(S_TM)}, {s(S_IA)}, {s(S_N)}")
                 if X == 0:
-                    g.salu(f"s_sub_u32 {s(S_TM)}, {s(S_TM)}, 1", regs("s", S_TM), regs("s", S_TM))
-                g.salu(f"s_cmp_gt_i32 {s(S_TM)}, 0", regs("s", S_TM), {"scc"})
-                g.salu(f"s_cselect_b64 {s(S_FULL + 2 * X, 2)}, -1, 0", {"scc"}, regs("s", S_FULL + 2 * X, 2))
-                g.salu(f"s_cmp_lt_i32 {s(S_TM)}, 0", regs("s", S_TM), {"scc"})
-                g.salu(f"s_cselect_b64 {s(S_KILL + 2 * X, 2)}, -1, 0", {"scc"}, regs("s", S_KILL + 2 * X, 2))
+                    g.ins(f"s_sub_u32 {s(S_TM)}, {s(S_TM)}, 1")
+                g.ins(f"s_cmp_gt_i32 {s(S_TM)}, 0")
+                g.ins(f"s_cselect_b64 {s(S_FULL + 2 * X, 2)}, -1, 0")
+                g.ins(f"s_cmp_lt_i32 {s(S_TM)}, 0")
+                g.ins(f"s_cselect_b64 {s(S_KILL + 2 * X, 2)}, -1, 0")
         return [f]
 
     def padword_items(self):
@@ -265,17 +261,17 @@ class Step:
         T = 242
 
         def rd():
-            g.salu(f"s_add_u32 {s(S_TM)}, {s(S_N)}, 1", regs("s", S_N), regs("s", S_TM))
-            g.salu(f"s_min_u32 {s(S_TM)}, {s(S_TM)}, 255", regs("s", S_TM), regs("s", S_TM))
-            g.salu(f"s_lshl_b32 {s(S_TM)}, {s(S_TM)}, 2", regs("s", S_TM), regs("s", S_TM))
-            g.valu(f"v_add_u32_e32 {v(T)}, {s(S_TM)}, {v(V_PADA)}", regs("s", S_TM) | regs("v", V_PADA), regs("v", T))
-            g.ds_read(f"ds_read_b32 {v(T + 1)}, {v(T)}", regs("v", T), regs("v", T + 1))
+            g.ins(f"s_add_u32 {s(S_TM)}, {s(S_N)}, 1")
+            g.ins(f"s_min_u32 {s(S_TM)}, {s(S_TM)}, 255")
+            g.ins(f"s_lshl_b32 {s(S_TM)}, {s(S_TM)}, 2")
+            g.ins(f"v_add_u32_e32 {v(T)}, {s(S_TM)}, {v(V_PADA)}")
+            g.ins(f"ds_read_b32 {v(T + 1)}, {v(T)}")
 
         def fin():
-            g.valu(f"v_readfirstlane_b32 {s(S_PW)}, {v(T + 1)}", regs("v", T + 1), regs("s", S_PW))
+            g.ins(f"v_readfirstlane_b32 {s(S_PW)}, {v(T + 1)}")
             g.nop(1)
-            g.salu(f"s_cmp_lg_u32 {s(S_PADANY)}, 0", regs("s", S_PADANY), {"scc"})
-            g.salu(f"s_cselect_b32 {s(S_PW)}, {s(S_PW)}, 0", regs("s", S_PW) | {"scc"}, regs("s", S_PW))
+            g.ins(f"s_cmp_lg_u32 {s(S_PADANY)}, 0")
+            g.ins(f"s_cselect_b32 {s(S_PW)}, {s(S_PW)}, 0")
         return [rd, fin]
 
     def mask_apply(self, X):
@@ -285,9 +281,9 @@ class Step:
         out = []
         for r in range(16):
             def f(r=r):
-                g.salu(f"s_or_b64 {s(S_TM, 2)}, {s(S_MASK + 2 * r, 2)}, {s(S_FULL + 2 * X, 2)}", regs("s", S_MASK + 2 * r, 2) | regs("s", S_FULL + 2 * X, 2), regs("s", S_TM, 2))
-                g.salu(f"s_andn2_b64 {s(S_TM, 2)}, {s(S_TM, 2)}, {s(S_KILL + 2 * X, 2)}", regs("s", S_TM, 2) | regs("s", S_KILL + 2 * X, 2), regs("s", S_TM, 2))
-                g.valu(f"v_cndmask_b32_e64 {v(c + r)}, {v(V_NEGINF)}, {v(c + r)}, {s(S_TM, 2)}", regs("v", V_NEGINF) | regs("v", c + r) | regs("s", S_TM, 2), regs("v", c + r))
+                g.ins(f"s_or_b64 {s(S_TM, 2)}, {s(S_MASK + 2 * r, 2)}, {s(S_FULL + 2 * X, 2)}")
+                g.ins(f"s_andn2_b64 {s(S_TM, 2)}, {s(S_TM, 2)}, {s(S_KILL + 2 * X, 2)}")
+                g.ins(f"v_cndmask_b32_e64 {v(c + r)}, {v(V_NEGINF)}, {v(c + r)}, {s(S_TM, 2)}")
             out.append(f)
         return out
 
@@ -298,18 +294,18 @@ class Step:
         T = 244
 
         def f():
-            g.salu(f"s_cmp_eq_u32 {s(S_PW)}, 0", regs("s", S_PW), {"scc"})
+            g.ins(f"s_cmp_eq_u32 {s(S_PW)}, 0")
             g.raw(f"s_cbranch_scc1 L_fwd_nopad{site}_%=")
             for r in range(16):
                 k = crow(r)
-                g.salu(f"s_bitcmp1_b32 {s(S_PW)}, {k}", regs("s", S_PW), {"scc"})
-                g.salu(f"s_cselect_b32 {s(S_TM)}, -1, 0", {"scc"}, regs("s", S_TM))
-                g.salu(f"s_bitcmp1_b32 {s(S_PW)}, {k + 4}", regs("s", S_PW), {"scc"})
-                g.salu(f"s_cselect_b32 {s(S_TM + 1)}, -1, 0", {"scc"}, regs("s", S_TM + 1))
+                g.ins(f"s_bitcmp1_b32 {s(S_PW)}, {k}")
+                g.ins(f"s_cselect_b32 {s(S_TM)}, -1, 0")
+                g.ins(f"s_bitcmp1_b32 {s(S_PW)}, {k + 4}")
+                g.ins(f"s_cselect_b32 {s(S_TM + 1)}, -1, 0")
                 for X in range(2):
                     c = self.sset(self.t1, X)
-                    g.valu(f"v_min_f32_e32 {v(T)}, 0xce6e6b28, {v(c + r)}", regs("v", c + r), regs("v", T))
-                    g.valu(f"v_cndmask_b32_e64 {v(c + r)}, {v(c + r)}, {v(T)}, {s(S_TM, 2)}", regs("v", c + r) | regs("v", T) | regs("s", S_TM, 2), regs("v", c + r))
+                    g.ins(f"v_min_f32_e32 {v(T)}, 0xce6e6b28, {v(c + r)}")
+                    g.ins(f"v_cndmask_b32_e64 {v(c + r)}, {v(c + r)}, {v(T)}, {s(S_TM, 2)}")
             g.out.append(f"L_fwd_nopad{site}_%=:")
         return [f]
 
@@ -326,11 +322,7 @@ def body(g: Gen, b: int, n_min: int = 0, masked: bool = False, site_base: int = 
     mf += (st.mfma_S(0) + st.mfma_S(1)) if has1 else none4 * 2
     mf += (st.mfma_PV(0) + st.mfma_PV(1)) if has0 else none4 * 2
     items = []
-
-    def add(fns, cost, **kw):
-        out = [Item(f, cost, name=kw.get("name", ""), **{k: v_ for k, v_ in kw.items() if k != "name"}) for f in fns]
-        items.extend(out)
-        return out
+    add = functools.partial(add_items, items)
 
     bar = add(st.barrier_item(f"dma{prev_b}"), COST["sync"], pin=1, name="barrier")
     if dma_ok:
@@ -421,33 +413,33 @@ def redo_block(X: int, par: int, nsites: int):
     T, T2, AL = V_TMP, V_TMP + 1, 245
     g.out.append(f"L_fwd_redo{X}{par}_%=:")
     g.nop(4)
-    g.valu(f"v_max_f32_e32 {v(T)}, {v(sr)}, {v(sr + 1)}", regs("v", sr, 2), regs("v", T))
+    g.ins(f"v_max_f32_e32 {v(T)}, {v(sr)}, {v(sr + 1)}")
     for r in range(2, 16):
-        g.valu(f"v_max_f32_e32 {v(T)}, {v(T)}, {v(sr + r)}", regs("v", T) | regs("v", sr + r), regs("v", T))
-    g.emit("lds", f"ds_bpermute_b32 {v(T2)}, {v(V_X32)}, {v(T)}", regs("v", V_X32) | regs("v", T), regs("v", T2))
+        g.ins(f"v_max_f32_e32 {v(T)}, {v(T)}, {v(sr + r)}")
+    g.ins(f"ds_bpermute_b32 {v(T2)}, {v(V_X32)}, {v(T)}")
     g.raw("s_waitcnt lgkmcnt(0)")
     g.lgkm = []
-    g.valu(f"v_max_f32_e32 {v(T)}, {v(T)}, {v(T2)}", regs("v", T, 2), regs("v", T))
-    g.valu(f"v_max_f32_e32 {v(T)}, {v(V_M + X)}, {v(T)}", regs("v", V_M + X) | regs("v", T), regs("v", T))                     # m_new
-    g.valu(f"v_sub_f32_e32 {v(AL)}, {v(V_M + X)}, {v(T)}", regs("v", V_M + X) | regs("v", T), regs("v", AL))
-    g.valu(f"v_mul_f32_e64 {v(AL)}, {v(AL)}, {s(S_LOG2E)}", regs("v", AL), regs("v", AL))
-    g.valu(f"v_exp_f32_e32 {v(AL)}, {v(AL)}", regs("v", AL), regs("v", AL), trans=True)                                      # alpha
-    g.valu(f"v_mov_b32_e32 {v(V_M + X)}, {v(T)}", regs("v", T), regs("v", V_M + X))
-    g.valu(f"v_mul_f32_e64 {v(V_MNEG + X)}, -{v(T)}, {s(S_LOG2E)}", regs("v", T), regs("v", V_MNEG + X))                       # -m_new * log2e
+    g.ins(f"v_max_f32_e32 {v(T)}, {v(T)}, {v(T2)}")
+    g.ins(f"v_max_f32_e32 {v(T)}, {v(V_M + X)}, {v(T)}")                     # m_new
+    g.ins(f"v_sub_f32_e32 {v(AL)}, {v(V_M + X)}, {v(T)}")
+    g.ins(f"v_mul_f32_e64 {v(AL)}, {v(AL)}, {s(S_LOG2E)}")
+    g.ins(f"v_exp_f32_e32 {v(AL)}, {v(AL)}")                                      # alpha
+    g.ins(f"v_mov_b32_e32 {v(V_M + X)}, {v(T)}")
+    g.ins(f"v_mul_f32_e64 {v(V_MNEG + X)}, -{v(T)}, {s(S_LOG2E)}")                       # -m_new * log2e
     for r in range(16):
-        g.valu(f"v_fma_f32 {v(p + r)}, {v(sr + r)}, {s(S_LOG2E)}, {v(V_MNEG + X)}", regs("v", sr + r) | regs("v", V_MNEG + X), regs("v", p + r))
-        g.valu(f"v_exp_f32_e32 {v(p + r)}, {v(p + r)}", regs("v", p + r), regs("v", p + r), trans=True)
+        g.ins(f"v_fma_f32 {v(p + r)}, {v(sr + r)}, {s(S_LOG2E)}, {v(V_MNEG + X)}")
+        g.ins(f"v_exp_f32_e32 {v(p + r)}, {v(p + r)}")
     ls, c = V_LSUM + X, V_SUMT + 4 * X
     g.nop(2)
     for j in range(4):
-        g.valu(f"v_add_f32_e32 {v(c + j)}, {v(p + j)}, {v(p + j + 4)}", regs("v", p + j) | regs("v", p + j + 4), regs("v", c + j))
+        g.ins(f"v_add_f32_e32 {v(c + j)}, {v(p + j)}, {v(p + j + 4)}")
     for k in (8, 12):
         for j in range(4):
-            g.valu(f"v_add_f32_e32 {v(c + j)}, {v(c + j)}, {v(p + j + k)}", regs("v", c + j) | regs("v", p + j + k), regs("v", c + j))
-    g.valu(f"v_add_f32_e32 {v(c)}, {v(c)}, {v(c + 1)}", regs("v", c, 2), regs("v", c))
-    g.valu(f"v_add_f32_e32 {v(c + 2)}, {v(c + 2)}, {v(c + 3)}", regs("v", c + 2, 2), regs("v", c + 2))
-    g.valu(f"v_add_f32_e32 {v(ls)}, {v(c)}, {v(c + 2)}", regs("v", c) | regs("v", c + 2), regs("v", ls))
-    g.valu(f"v_mul_f32_e32 {v(V_L + X)}, {v(V_L + X)}, {v(AL)}", regs("v", V_L + X) | regs("v", AL), regs("v", V_L + X))
+            g.ins(f"v_add_f32_e32 {v(c + j)}, {v(c + j)}, {v(p + j + k)}")
+    g.ins(f"v_add_f32_e32 {v(c)}, {v(c)}, {v(c + 1)}")
+    g.ins(f"v_add_f32_e32 {v(c + 2)}, {v(c + 2)}, {v(c + 3)}")
+    g.ins(f"v_add_f32_e32 {v(ls)}, {v(c)}, {v(c + 2)}")
+    g.ins(f"v_mul_f32_e32 {v(V_L + X)}, {v(V_L + X)}, {v(AL)}")
     for k in range(32):
         ar = A_O + 32 * X + k
         g.raw(f"v_accvgpr_read_b32 {v(T2)}, {a(ar)}")
@@ -472,76 +464,76 @@ def prologue(g: Gen):
     g.comment("==== prologue ====")
     g.drain()
     T = V_QE
-    g.valu(f"v_mbcnt_lo_u32_b32 {v(V_TMP)}, -1, 0", set(), regs("v", V_TMP))
-    g.valu(f"v_mbcnt_hi_u32_b32 {v(V_TMP)}, -1, {v(V_TMP)}", regs("v", V_TMP), regs("v", V_TMP))          # lane
-    g.valu(f"v_lshlrev_b32_e32 {v(V_L16)}, 4, {v(V_TMP)}", regs("v", V_TMP), regs("v", V_L16))
-    g.valu(f"v_mov_b32_e32 {v(V_TMP + 1)}, %16", set(), regs("v", V_TMP + 1))
+    g.ins(f"v_mbcnt_lo_u32_b32 {v(V_TMP)}, -1, 0")
+    g.ins(f"v_mbcnt_hi_u32_b32 {v(V_TMP)}, -1, {v(V_TMP)}")          # lane
+    g.ins(f"v_lshlrev_b32_e32 {v(V_L16)}, 4, {v(V_TMP)}")
+    g.ins(f"v_mov_b32_e32 {v(V_TMP + 1)}, %16")
     for k in range(3):
-        g.ds_read(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(V_TMP + 1)} offset:{16 * k}", regs("v", V_TMP + 1), regs("v", T + 4 * k, 4))
-    g.valu(f"v_lshl_add_u32 {v(V_TMP + 2)}, {v(V_TMP)}, 2, {v(V_TMP + 1)}", regs("v", V_TMP, 2), regs("v", V_TMP + 2))
+        g.ins(f"ds_read_b128 {v(T + 4 * k, 4)}, {v(V_TMP + 1)} offset:{16 * k}")
+    g.ins(f"v_lshl_add_u32 {v(V_TMP + 2)}, {v(V_TMP)}, 2, {v(V_TMP + 1)}")
     for k, dst in enumerate(LANE_TAB):
-        g.ds_read(f"ds_read_b32 {v(dst)}, {v(V_TMP + 2)} offset:{256 + 256 * k}", regs("v", V_TMP + 2), regs("v", dst))
+        g.ins(f"ds_read_b32 {v(dst)}, {v(V_TMP + 2)} offset:{256 + 256 * k}")
     sc = [S_EFA, S_EFA + 1, S_KVB, S_KVB + 1, S_NTW, S_IA, S_KSTEP, S_LDS, S_NCH, S_W, S_PADANY]
     g.raw("s_waitcnt lgkmcnt(0)")
     g.lgkm = []
     g.nop(1)
     for k, dst in enumerate(sc):
-        g.valu(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}", regs("v", T + k), regs("s", dst))
+        g.ins(f"v_readfirstlane_b32 {s(dst)}, {v(T + k)}")
     g.nop(4)
-    g.salu(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 10", regs("s", S_W), regs("s", S_T))
-    g.salu(f"s_add_u32 {s(S_DK)}, {s(S_LDS)}, {s(S_T)}", regs("s", S_LDS) | regs("s", S_T), regs("s", S_DK))
-    g.salu(f"s_mov_b32 {s(S_LOG2E)}, 0x3fb8aa3b", (), regs("s", S_LOG2E))
-    g.salu(f"s_mov_b32 {s(S_LSAFE)}, 0x6753c21c", (), regs("s", S_LSAFE))           # L_SAFE = 1.0e24f
-    g.salu(f"s_mov_b32 {s(S_PW)}, 0", (), regs("s", S_PW))
+    g.ins(f"s_lshl_b32 {s(S_T)}, {s(S_W)}, 10")
+    g.ins(f"s_add_u32 {s(S_DK)}, {s(S_LDS)}, {s(S_T)}")
+    g.ins(f"s_mov_b32 {s(S_LOG2E)}, 0x3fb8aa3b")
+    g.ins(f"s_mov_b32 {s(S_LSAFE)}, 0x6753c21c")           # L_SAFE = 1.0e24f
+    g.ins(f"s_mov_b32 {s(S_PW)}, 0")
     # E chunks of the first products (tile -1): A: chunk I_A in slot 1, B: chunk I_A + 1 in slot 0
     for slot, add in ((1, 0), (0, 1)):
-        g.salu(f"s_add_u32 {s(S_T + 4)}, {s(S_IA)}, {add}", regs("s", S_IA), regs("s", S_T + 4))
-        g.salu(f"s_lshl_b32 {s(S_T + 4)}, {s(S_T + 4)}, 12", regs("s", S_T + 4), regs("s", S_T + 4))
+        g.ins(f"s_add_u32 {s(S_T + 4)}, {s(S_IA)}, {add}")
+        g.ins(f"s_lshl_b32 {s(S_T + 4)}, {s(S_T + 4)}, 12")
         ptr = S_T + 2 if slot else S_EP
-        g.salu(f"s_add_u32 {s(ptr)}, {s(S_EFA)}, {s(S_T + 4)}", regs("s", S_EFA) | regs("s", S_T + 4), regs("s", ptr))
-        g.salu(f"s_addc_u32 {s(ptr + 1)}, {s(S_EFA + 1)}, 0", regs("s", S_EFA + 1), regs("s", ptr + 1))
+        g.ins(f"s_add_u32 {s(ptr)}, {s(S_EFA)}, {s(S_T + 4)}")
+        g.ins(f"s_addc_u32 {s(ptr + 1)}, {s(S_EFA + 1)}, 0")
         for ks in range(4):
             dst = A_E + 16 * slot + 4 * ks
-            g.vmem_load(f"global_load_dwordx4 {a(dst, 4)}, {v(V_L16)}, {s(ptr, 2)} offset:{1024 * ks}", "e0", regs("v", V_L16) | regs("s", ptr, 2), regs("a", dst, 4))
+            g.ins(f"global_load_dwordx4 {a(dst, 4)}, {v(V_L16)}, {s(ptr, 2)} offset:{1024 * ks}", "e0")
     # constants, state
     for r in range(16):
-        g.valu(f"v_xor_b32_e32 {v(V_WCL[1] + r)}, 0x80, {v(V_WCL[0] + r)}", regs("v", V_WCL[0] + r), regs("v", V_WCL[1] + r))
-    g.valu(f"v_mov_b32_e32 {v(V_NEGINF)}, 0xff800000", set(), regs("v", V_NEGINF))
-    g.valu(f"v_xor_b32_e32 {v(V_X32)}, 32, {v(V_TMP)}", regs("v", V_TMP), regs("v", V_X32))
-    g.valu(f"v_lshlrev_b32_e32 {v(V_X32)}, 2, {v(V_X32)}", regs("v", V_X32), regs("v", V_X32))
-    g.valu(f"v_mov_b32_e32 {v(V_TMP + 3)}, {OFF_PAD}", set(), regs("v", V_TMP + 3))
-    g.valu(f"v_add_u32_e32 {v(V_PADA)}, {s(S_LDS)}, {v(V_TMP + 3)}", regs("v", V_TMP + 3) | regs("s", S_LDS), regs("v", V_PADA))
+        g.ins(f"v_xor_b32_e32 {v(V_WCL[1] + r)}, 0x80, {v(V_WCL[0] + r)}")
+    g.ins(f"v_mov_b32_e32 {v(V_NEGINF)}, 0xff800000")
+    g.ins(f"v_xor_b32_e32 {v(V_X32)}, 32, {v(V_TMP)}")
+    g.ins(f"v_lshlrev_b32_e32 {v(V_X32)}, 2, {v(V_X32)}")
+    g.ins(f"v_mov_b32_e32 {v(V_TMP + 3)}, {OFF_PAD}")
+    g.ins(f"v_add_u32_e32 {v(V_PADA)}, {s(S_LDS)}, {v(V_TMP + 3)}")
     for X in range(2):
-        g.valu(f"v_mov_b32_e32 {v(V_M + X)}, 0xfcf0bdc2", set(), regs("v", V_M + X))               # M_INIT = -1.0e37f
-        g.valu(f"v_mov_b32_e32 {v(V_L + X)}, 0", set(), regs("v", V_L + X))
-        g.valu(f"v_mul_f32_e64 {v(V_MNEG + X)}, -{v(V_M + X)}, {s(S_LOG2E)}", regs("v", V_M + X), regs("v", V_MNEG + X))
+        g.ins(f"v_mov_b32_e32 {v(V_M + X)}, 0xfcf0bdc2")               # M_INIT = -1.0e37f
+        g.ins(f"v_mov_b32_e32 {v(V_L + X)}, 0")
+        g.ins(f"v_mul_f32_e64 {v(V_MNEG + X)}, -{v(V_M + X)}, {s(S_LOG2E)}")
     for k in range(64):
         g.raw(f"v_accvgpr_write_b32 {a(A_O + k)}, 0")
     # masks: key crow(r, hh) <= query a  <=>  crow(r, 0) <= a - 4 hh
     AM, X_ = V_TMP + 4, V_TMP + 5
-    g.valu(f"v_and_b32_e32 {v(AM)}, 31, {v(V_TMP)}", regs("v", V_TMP), regs("v", AM))
-    g.valu(f"v_lshrrev_b32_e32 {v(X_)}, 5, {v(V_TMP)}", regs("v", V_TMP), regs("v", X_))
-    g.valu(f"v_lshlrev_b32_e32 {v(X_)}, 2, {v(X_)}", regs("v", X_), regs("v", X_))
-    g.valu(f"v_sub_u32_e32 {v(AM)}, {v(AM)}, {v(X_)}", regs("v", AM) | regs("v", X_), regs("v", AM))          # am (may be negative)
+    g.ins(f"v_and_b32_e32 {v(AM)}, 31, {v(V_TMP)}")
+    g.ins(f"v_lshrrev_b32_e32 {v(X_)}, 5, {v(V_TMP)}")
+    g.ins(f"v_lshlrev_b32_e32 {v(X_)}, 2, {v(X_)}")
+    g.ins(f"v_sub_u32_e32 {v(AM)}, {v(AM)}, {v(X_)}")          # am (may be negative)
     for r in range(16):
-        g.valu(f"v_cmp_ge_i32_e64 {s(S_MASK + 2 * r, 2)}, {v(AM)}, {crow(r)}", regs("v", AM), regs("s", S_MASK + 2 * r, 2))
-    g.salu(f"s_mov_b32 {s(S_N)}, -3", (), regs("s", S_N))
+        g.ins(f"v_cmp_ge_i32_e64 {s(S_MASK + 2 * r, 2)}, {v(AM)}, {crow(r)}")
+    g.ins(f"s_mov_b32 {s(S_N)}, -3")
     g.drain()
     g.raw("s_barrier")
 
 
 def loop_tail(g: Gen, b: int, masked: bool):
     nb = (b + 1) % 6
-    g.salu(f"s_add_u32 {s(S_N)}, {s(S_N)}, 1", regs("s", S_N), regs("s", S_N))
-    g.salu(f"s_cmp_ge_i32 {s(S_N)}, {s(S_NTW)}", regs("s", S_N) | regs("s", S_NTW), {"scc"})
+    g.ins(f"s_add_u32 {s(S_N)}, {s(S_N)}, 1")
+    g.ins(f"s_cmp_ge_i32 {s(S_N)}, {s(S_NTW)}")
     g.raw("s_cbranch_scc1 L_fwd_end_%=")
     if masked:
         if b == 5:
             g.raw("s_branch L_fwd_m0_%=")
         return
     # a wave stays in the main bodies while tile n + 1 is strictly below the diagonal of its first query tile: n + 1 < I_A
-    g.salu(f"s_add_u32 {s(S_TM)}, {s(S_N)}, 1", regs("s", S_N), regs("s", S_TM))
-    g.salu(f"s_cmp_lt_i32 {s(S_TM)}, {s(S_IA)}", regs("s", S_TM) | regs("s", S_IA), {"scc"})
+    g.ins(f"s_add_u32 {s(S_TM)}, {s(S_N)}, 1")
+    g.ins(f"s_cmp_lt_i32 {s(S_TM)}, {s(S_IA)}")
     g.raw(f"s_cbranch_scc1 L_fwd_u{nb}_%=")
     g.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")              # the masked bodies' counted waits assume their own history
     g.raw("s_nop 7")
@@ -550,18 +542,14 @@ def loop_tail(g: Gen, b: int, masked: bool):
 
 
 def fixed_point_loop(g: Gen, masked: bool):
-    texts = []
-    for rnd in range(3):
-        g.out = []
+    def six_bodies():
         for b in range(6):
             g.out.append(f"L_fwd_{'m' if masked else 'u'}{b}_%=:")
             body(g, b, masked=masked, site_base=12 if masked else 0)
             if STAMP:
                 g.raw(f"v_add_u32_e32 {v(246 + (6 if masked else 7))}, 1, {v(246 + (6 if masked else 7))}")      # iterations: [6] masked, [7] main
             loop_tail(g, b, masked)
-        texts.append(list(g.out))
-    assert texts[1] == texts[2], "the loop body is not a fixed point of the wait-count / hazard trackers"
-    return texts[2]
+    return fixed_point(g, six_bodies)
 
 
 def generate():
@@ -571,7 +559,7 @@ def generate():
     # pipeline fill: n = -3 (QE of tile -1: the diagonal chunks), -2 (QE of tile 0, DMA of tile 0), -1 (QE 1, S 0, DMA 1)
     for n in (-3, -2, -1):
         body(g, n % 6, n_min=-n, masked=True, site_base=24 + 12 * (n + 3))      # masked: tile 0 may be a diagonal tile (first query block)
-        g.salu(f"s_add_u32 {s(S_N)}, {s(S_N)}, 1", regs("s", S_N), regs("s", S_N))
+        g.ins(f"s_add_u32 {s(S_N)}, {s(S_N)}, 1")
     g.drain()
     g.nop(16)
     if STAMP:
@@ -579,9 +567,9 @@ def generate():
             g.raw(f"v_mov_b32_e32 {v(246 + k)}, 0")
         g.stamp(None)
     # n = 0: main bodies if tile 1 is strictly below the wave's first diagonal and no key of the batch row is padded
-    g.salu(f"s_cmp_lg_u32 {s(S_PADANY)}, 0", regs("s", S_PADANY), {"scc"})
+    g.ins(f"s_cmp_lg_u32 {s(S_PADANY)}, 0")
     g.raw("s_cbranch_scc1 L_fwd_m0_%=")
-    g.salu(f"s_cmp_gt_i32 {s(S_IA)}, 1", regs("s", S_IA), {"scc"})
+    g.ins(f"s_cmp_gt_i32 {s(S_IA)}, 1")
     g.raw("s_cbranch_scc1 L_fwd_u0_%=")
     g.raw("s_branch L_fwd_m0_%=")
     pro_lines = list(g.out)
@@ -632,23 +620,11 @@ def clobbers():
 def write(here):
     lines, g = generate()
     path = os.path.join(here, "rel_attn_fwd64_loop_stamp.inc" if STAMP else "rel_attn_fwd64_loop.inc")
-    import io
-    f = io.StringIO()
-    if True:
-        f.write("// GENERATED by gen_fwd_asm.py -- do not edit.  The hand-scheduled sweep of rel_attn_fwd64_kernel (one asm statement):\n")
-        f.write("// operands %0..%3 = oA0, oA1, oB0, oB1 (\"=&a\"), %4..%7 = m_A, l_A, m_B, l_B (\"=&v\"), %8..%15 = the scaled q fragments of tiles A, B\n")
-        f.write("// (\"a\"), %16 = LDS address of the wave's parameter block (\"s\").  Register map, schedule and hazard rules: gen_fwd_asm.py.\n")
-        f.write("#define MGX_FWD64_LOOP_ASM \\\n")
-        for ln in lines:
-            if ln.startswith(";"):
-                f.write(f"    /* {ln[1:].strip()} */ \\\n")
-            else:
-                f.write(f'    "{ln}\\n\\t" \\\n')
-        f.write('    ""\n')
-        f.write("#define MGX_FWD64_LOOP_CLOBBERS " + ", ".join(f'"{c}"' for c in clobbers()) + "\n")
-    write_if_changed(path, f.getvalue())
-    n_ins = sum(1 for ln in lines if not ln.startswith(";") and not ln.endswith(":"))
-    print(f"wrote {path}: {n_ins} instructions, s_nop wait states inserted: {g.nops}; counts {g.stats}", file=sys.stderr)
+    write_inc(path, ["GENERATED by gen_fwd_asm.py -- do not edit.  The hand-scheduled sweep of rel_attn_fwd64_kernel (one asm statement):",
+                     "operands %0..%3 = oA0, oA1, oB0, oB1 (\"=&a\"), %4..%7 = m_A, l_A, m_B, l_B (\"=&v\"), %8..%15 = the scaled q fragments of tiles A, B",
+                     "(\"a\"), %16 = LDS address of the wave's parameter block (\"s\").  Register map, schedule and hazard rules: gen_fwd_asm.py."],
+              [("MGX_FWD64_LOOP_ASM", lines)], ("MGX_FWD64_LOOP_CLOBBERS", clobbers()))
+    summary(path, lines, g)
 
 
 if __name__ == "__main__":
