@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped */
-#define MGX_ABI_VERSION 25
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace */
+#define MGX_ABI_VERSION 26
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -469,6 +469,37 @@ int mgx_kv_beam_reorder(void* dst, const void* src, const int32_t* parent, const
  * (the prompt columns are the caller's); a row with c0 < 0 or c0 + steps > out_ld is left alone.  One thread per row.           */
 int mgx_beam_backtrack(const int32_t* hist_tok, const int32_t* hist_parent, const int32_t* c0_rows, int32_t* out, int out_ld,
                        int R, int K, int steps, void* stream);
+
+/* ---- Shared prompt cache (ABI 26): N samples per prompt over ONE copy of the prompt's K/V.  R = Bp * N rows: row r = b * N + n
+ * is sample n (0 <= n < N <= MGX_SHARED_MAX_N) of prompt b.  Per layer two pairs of bf16 tensors:
+ *   kpre, vpre [Bp,h,Lpre,64]: the prompt cache, one per prompt, written by the prefill only -- this call never writes it;
+ *   kown, vown [R,h,Lown,64]:  what every row has appended itself, from row 0 on.
+ * pre_rows int32 [Bp]: p_b, the prompt-cache rows of prompt b.  Logical key j of row r is kpre[b,h,j] for j < p_b and
+ * kown[r,h,j - p_b] for j >= p_b.  pos_rows int32 [R] as in the ragged calls; the N rows of a prompt hold ONE position (the
+ * kernel reads row b * N), as the K beams of mgx_beam_select do.
+ * mgx_rel_attn_decode_shared: with t = pos_rows[b * N] and p = pre_rows[b], row r's k_t, v_t (qkv_new bf16 [R,3d]) are stored at
+ *   kown / vown[r,h,t - p], and ctx bf16 [R,d] = softmax_j((q_r.k_j + q_r.E[M-1-(t-j)])/8) v_j over the logical keys j = 0..t
+ *   (key t is read from qkv_new).  It is what mgx_rel_attn_decode_ragged computes on R rows whose caches are the prompt rows
+ *   followed by the own rows, with a prompt's key, value and E row loaded once for MGX_SHARED_NQ queries at a time.
+ * Contract: 0 <= p <= min(t, Lpre), t - p < Lown, t < M; Lpre >= 1 and Lown >= 1 (p = 0: everything lives in the own cache;
+ *   p = t: the own cache holds the new key only).  t and p live on the device and are not checked on the host; the kernel
+ *   checks them, and no value turns into an access outside the buffers the shapes describe: a prompt whose (t, p) break the
+ *   contract leaves both caches untouched and its N rows of ctx unspecified.
+ * Key splits: a function of the shapes only (the call stays capturable) -- 1 while Lpre + Lown < 1024, else doubled up to
+ *   16 while the workgroups of a split, Bp * h * ceil(N / MGX_SHARED_NQ), times the splits stay below 1024 and a share holds
+ *   512 keys or more.  Ranges are those of mgx_rel_attn_decode over the logical keys 0..t, so a range may straddle p; the
+ *   partials are its 68-float records at [(r * h + head) * splits + split] and its merge kernel serves unchanged.
+ *   workspace >= mgx_rel_attn_decode_shared_workspace() bytes (0 for one split: NULL is accepted then).                       */
+#define MGX_SHARED_MAX_N 16
+#ifndef MGX_SHARED_NQ        /* an A/B build of the library may set another (profiles/r20_shared_prompt_decode.txt) */
+#define MGX_SHARED_NQ 2      /* queries per workgroup: N > MGX_SHARED_NQ takes ceil(N / MGX_SHARED_NQ) workgroups per (b, head, split) */
+#endif
+int mgx_rel_attn_decode_shared_splits(int Bp, int N, int Lpre, int Lown, int d);
+size_t mgx_rel_attn_decode_shared_workspace(int Bp, int N, int Lpre, int Lown, int d);
+int mgx_rel_attn_decode_shared(const uint16_t* qkv_new, const uint16_t* kpre, const uint16_t* vpre, uint16_t* kown,
+                               uint16_t* vown, const uint16_t* E, const int32_t* pos_rows, const int32_t* pre_rows,
+                               uint16_t* ctx, void* workspace, size_t ws_bytes, int Bp, int N, int Lpre, int Lown, int d, int M,
+                               void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

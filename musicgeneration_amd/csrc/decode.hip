@@ -18,6 +18,8 @@
 // Past max_seq (ABI 21) the cache holds a window of the sequence: pos_dev is the position inside the window, a second counter
 // of the same shape, base_dev, the output column of window position 0.  Only the sampler reads it
 // (mgx_sample_topk_topp_window); mgx_decode_reanchor moves both when the host re-anchors the window.
+// mgx_rel_attn_decode_shared (ABI 26) is the per-row attention for N samples per prompt: the prompt's keys are held once per prompt
+// and loaded once for several of its samples' queries (rel_attn_decode_shared_kernel, below the merge kernel).
 #include "mgx_common.hpp"
 
 namespace {
@@ -179,6 +181,166 @@ __global__ __launch_bounds__(64) void rel_attn_decode_merge_kernel(const float* 
         o += pp[s * DEC_PART + c] * a;
     }
     ctx[(size_t)b * d + hd * 64 + c] = f32_to_bf16(o / ll);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Shared prompt cache (ABI 26): R = Bp * N rows, row r = b * N + n is sample n of prompt b.  The N rows of a prompt sit at one
+// position t and share the first p keys (kpre / vpre [Bp, h, Lpre, 64], never written); what a row has appended itself lives
+// in kown / vown [R, h, Lown, 64] from row 0 on, so logical key j is prompt row j (j < p) or own row j - p.
+// One workgroup per (prompt, head, chunk of NQ queries, key split).  It is rel_attn_decode_kernel's walk over the logical keys
+// -- the same (wave, key slot) streams, the same key ranges, the same merge tree -- with NQ online-softmax states per lane.
+// An iteration whose 8 keys all lie below p loads K, E and V once for the NQ queries (plain loads: a prompt's rows are read
+// by every chunk of the prompt and again at the next step, and a prompt cache is 1/N of the repeated call's); from p on every
+// query walks its own rows (nontemporal, as above).  A chunk's spare queries (N % NQ) repeat its last row and store nothing.
+// The positions cannot be checked on the host: a prompt whose (t, p) break the contract gets an empty key range and no append.
+// ---------------------------------------------------------------------------------------------------
+constexpr int SHARED_NQ = MGX_SHARED_NQ;
+
+template <int NQ>
+__global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_shared_kernel(
+    const uint16_t* __restrict__ qkv_new, const uint16_t* __restrict__ kpre, const uint16_t* __restrict__ vpre,
+    uint16_t* __restrict__ kown, uint16_t* __restrict__ vown, const uint16_t* __restrict__ E,
+    const int32_t* __restrict__ pos_rows, const int32_t* __restrict__ pre_rows, uint16_t* __restrict__ ctx,
+    float* __restrict__ partial, int N, int Lpre, int Lown, int d, int M) {
+    const int heads = d >> 6, chunks = (N + NQ - 1) / NQ;
+    const int ch = blockIdx.x % chunks, hd = (blockIdx.x / chunks) % heads, b = blockIdx.x / (chunks * heads);
+    const int nsplit = gridDim.y, sp = blockIdx.y;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int ks = lane >> 3, dg = lane & 7;
+    const int r0 = b * N + ch * NQ, nq = min(NQ, N - ch * NQ);   // the chunk's rows r0 .. r0 + nq - 1
+    int t = pos_rows[b * N], p = pre_rows[b];
+    const bool ok = p >= 0 && p <= Lpre && p <= t && t - p < Lown && t < M;
+    if (!ok) t = p = 0;                                          // nothing below is addressed from a value outside the contract
+    // append every row's k_t, v_t at its own row t - p (split 0; 16 threads per query: 8 for K, 8 for V)
+    if (sp == 0 && ok && tid < 16 * NQ) {
+        const int qi = tid >> 4, kv = (tid >> 3) & 1, c = (tid & 7) * 8;
+        if (qi < nq) {
+            uint16_t* dst = (kv ? vown : kown) + (((size_t)(r0 + qi) * heads + hd) * Lown + (t - p)) * 64 + c;
+            *(u32x4*)dst = *(const u32x4*)(qkv_new + (size_t)(r0 + qi) * 3 * d + (1 + kv) * d + hd * 64 + c);
+        }
+    }
+    const uint16_t* qrow[NQ];
+    size_t own[NQ];                                              // element offset of the query's own rows (wave-uniform)
+    float q[NQ][8], m[NQ], l[NQ], acc[NQ][8];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+        const int r = r0 + min(i, nq - 1);
+        qrow[i] = qkv_new + (size_t)r * 3 * d + hd * 64;
+        own[i] = ((size_t)r * heads + hd) * Lown * 64;
+        unpack8(*(const u32x4*)(qrow[i] + dg * 8), q[i]);
+        m[i] = -INFINITY, l[i] = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { q[i][k] *= 0.125f * LOG2E; acc[i][k] = 0.f; }
+    }
+    int lo = 0, hi = 0;
+    if (ok) dec_key_range(t, nsplit, sp, lo, hi);
+    const uint16_t* kp0 = kpre + ((size_t)b * heads + hd) * Lpre * 64;
+    const uint16_t* vp0 = vpre + ((size_t)b * heads + hd) * Lpre * 64;
+    const uint16_t* Eb = E + (size_t)(M - 1 - t) * 64;
+    // one query's step of the online softmax on the key this lane group holds
+    auto step = [&](int i, const float* ke, const float* vf, bool valid) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += q[i][k] * ke[k];
+        // the key's 8 lanes: the values of the xor-1, -2, -4 butterfly, as DPP adds (NQ butterflies per key through
+        // ds_bpermute would be most of the loop; after two steps a quad holds one sum, so the half-row mirror is the xor-4)
+        s += dpp_mov<0xB1>(s);                                  // quad_perm [1,0,3,2]
+        s += dpp_mov<0x4E>(s);                                  // quad_perm [2,3,0,1]
+        s += dpp_mov<0x141>(s);                                 // row_half_mirror
+        if (!valid) s = -INFINITY;
+        const float mn = fmaxf(m[i], s);
+        const float alpha = (mn == -INFINITY) ? 1.f : __builtin_amdgcn_exp2f(m[i] - mn);
+        const float pr = (mn == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(s - mn);
+        l[i] = l[i] * alpha + pr;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[i][k] = acc[i][k] * alpha + pr * vf[k];
+        m[i] = mn;
+    };
+    // The walk is rel_attn_decode_kernel's, in two phases.  While the wave's 8 keys are prompt rows (j0 + 7 < p; jc <= j0 + 7): one
+    // load of K, E and V for all NQ queries, the next iteration's issued before this one's arithmetic (two workgroups per CU
+    // at NQ = 2, one from NQ = 4 on: little else hides the latency).  From p on (and the iteration that straddles p): row by
+    // row, so a split that holds own rows does NQ times the work per key of one that holds prompt rows.
+    int j0 = lo + (w * 8);
+    const int end_pre = min(hi, p - 7);
+    u32x4 kw, ew, vw;
+    auto load_pre = [&](int at) {
+        const int jc = min(at + ks, hi - 1);
+        kw = *(const u32x4*)(kp0 + (size_t)jc * 64 + dg * 8);
+        ew = *(const u32x4*)(Eb + (size_t)jc * 64 + dg * 8);
+        vw = *(const u32x4*)(vp0 + (size_t)jc * 64 + dg * 8);
+    };
+    if (j0 < end_pre) load_pre(j0);
+    for (; j0 < end_pre; j0 += DEC_WAVES * 8) {
+        const bool valid = j0 + ks < hi;
+        float kf[8], ef[8], vf[8];
+        unpack8(kw, kf);
+        unpack8(ew, ef);
+        unpack8(vw, vf);
+        if (j0 + DEC_WAVES * 8 < end_pre) load_pre(j0 + DEC_WAVES * 8);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) kf[k] += ef[k];
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) step(i, kf, vf, valid);
+    }
+    for (; j0 < hi; j0 += DEC_WAVES * 8) {
+        const int j = j0 + ks;
+        const bool valid = j < hi;
+        const int jc = valid ? j : hi - 1;
+        float kf[8], ef[8], vf[8];
+        unpack8(*(const u32x4*)(Eb + (size_t)jc * 64 + dg * 8), ef);
+#pragma unroll
+        for (int i = 0; i < NQ; ++i) {
+            const uint16_t* kp = jc < p ? kp0 + (size_t)jc * 64 : jc == t ? qrow[i] + d : kown + own[i] + (size_t)(jc - p) * 64;
+            const uint16_t* vp = jc < p ? vp0 + (size_t)jc * 64 : jc == t ? qrow[i] + 2 * d : vown + own[i] + (size_t)(jc - p) * 64;
+            unpack8(__builtin_nontemporal_load((const u32x4*)(kp + dg * 8)), kf);
+            unpack8(__builtin_nontemporal_load((const u32x4*)(vp + dg * 8)), vf);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) kf[k] += ef[k];
+            step(i, kf, vf, valid);
+        }
+    }
+    // dec_finish<8> per query: the key slots of the wave, then the 8 waves through LDS
+    __shared__ float sm[NQ][DEC_WAVES], sl[NQ][DEC_WAVES], sacc[NQ][DEC_WAVES][64];
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) {
+#pragma unroll
+        for (int o = 8; o < 64; o <<= 1) {
+            const float mo = __shfl_xor(m[i], o, 64), lo2 = __shfl_xor(l[i], o, 64);
+            const float mn = fmaxf(m[i], mo);
+            const float a0 = (m[i] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(m[i] - mn);
+            const float a1 = (mo == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(mo - mn);
+            l[i] = l[i] * a0 + lo2 * a1;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[i][k] = acc[i][k] * a0 + __shfl_xor(acc[i][k], o, 64) * a1;
+            m[i] = mn;
+        }
+        if (ks == 0) {
+            if (dg == 0) { sm[i][w] = m[i]; sl[i][w] = l[i]; }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) sacc[i][w][dg * 8 + k] = acc[i][k];
+        }
+    }
+    __syncthreads();
+    for (int i = w; i < nq; i += DEC_WAVES) {                   // wave w merges query w (and w + 8): one output per lane
+        float mm = -INFINITY;
+#pragma unroll
+        for (int u = 0; u < DEC_WAVES; ++u) mm = fmaxf(mm, sm[i][u]);
+        float ll = 0.f, o = 0.f;
+#pragma unroll
+        for (int u = 0; u < DEC_WAVES; ++u) {
+            const float a = (sm[i][u] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(sm[i][u] - mm);
+            ll += sl[i][u] * a;
+            o += sacc[i][u][lane] * a;
+        }
+        const size_t rh = (size_t)(r0 + i) * heads + hd;
+        if (nsplit == 1) {
+            ctx[rh * 64 + lane] = f32_to_bf16(o / ll);
+        } else {                                                // rel_attn_decode_merge_kernel's record of (row, head, split)
+            float* pp = partial + (rh * nsplit + sp) * DEC_PART;
+            if (lane == 0) { pp[64] = mm; pp[65] = ll; }
+            pp[lane] = o;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -566,6 +728,51 @@ extern "C" int mgx_rel_attn_decode_fp8_ragged(const uint16_t* qkv_new, uint8_t* 
                                               void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M, void* stream) {
     return rel_attn_decode<true, true>(qkv_new, kcache, vcache, kscale, vscale, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d,
                                        M, stream, "mgx_rel_attn_decode_fp8_ragged");
+}
+
+// key splits of the shared-prompt attention, from the shapes alone.  A call has Bp * h * ceil(N / NQ) workgroups per split where
+// the repeated call has Bp * N * h, so it splits further than decode_splits: up to 16, shares of 512 keys or more
+static int shared_splits(int Bp, int N, int Lpre, int Lown, int d) {
+    const long long wgs = (long long)Bp * (d / 64) * ((N + SHARED_NQ - 1) / SHARED_NQ), L = (long long)Lpre + Lown;
+    if (L < 1024) return 1;
+    int s = 1;
+    while (s < 16 && wgs * s < 1024 && L / (2 * s) >= 512) s *= 2;
+    return s;
+}
+
+extern "C" int mgx_rel_attn_decode_shared_splits(int Bp, int N, int Lpre, int Lown, int d) {
+    return (Bp <= 0 || N <= 0 || Lpre <= 0 || Lown <= 0 || d <= 0) ? 0 : shared_splits(Bp, N, Lpre, Lown, d);
+}
+
+extern "C" size_t mgx_rel_attn_decode_shared_workspace(int Bp, int N, int Lpre, int Lown, int d) {
+    if (Bp <= 0 || N <= 0 || Lpre <= 0 || Lown <= 0 || d <= 0) return 0;
+    const int s = shared_splits(Bp, N, Lpre, Lown, d);
+    return s == 1 ? 0 : (size_t)Bp * N * (d / 64) * s * DEC_PART * sizeof(float);
+}
+
+extern "C" int mgx_rel_attn_decode_shared(const uint16_t* qkv_new, const uint16_t* kpre, const uint16_t* vpre, uint16_t* kown,
+                                          uint16_t* vown, const uint16_t* E, const int32_t* pos_rows, const int32_t* pre_rows,
+                                          uint16_t* ctx, void* workspace, size_t ws_bytes, int Bp, int N, int Lpre, int Lown, int d,
+                                          int M, void* stream) {
+    const char* name = "mgx_rel_attn_decode_shared";
+    MGX_REQUIRE(qkv_new && kpre && vpre && kown && vown && E && pos_rows && pre_rows && ctx, MGX_ERR_NULL, "%s: NULL pointer", name);
+    MGX_REQUIRE(Bp > 0 && N >= 1 && N <= MGX_SHARED_MAX_N && Lpre >= 1 && Lown >= 1 && d > 0 && d % 64 == 0 && M >= 1, MGX_ERR_SHAPE,
+                "%s: need 1<=N<=%d, Lpre>=1, Lown>=1, d%%64==0, M>=1 (Bp=%d N=%d Lpre=%d Lown=%d d=%d M=%d)", name, MGX_SHARED_MAX_N,
+                Bp, N, Lpre, Lown, d, M);
+    const long long wgs = (long long)Bp * (d / 64) * ((N + SHARED_NQ - 1) / SHARED_NQ);
+    MGX_REQUIRE(wgs <= 0x7fffffff && (long long)Bp * N * (d / 64) <= 0x7fffffff, MGX_ERR_SHAPE, "%s: too many rows (Bp=%d N=%d d=%d)",
+                name, Bp, N, d);
+    const int ns = shared_splits(Bp, N, Lpre, Lown, d);
+    const size_t need = mgx_rel_attn_decode_shared_workspace(Bp, N, Lpre, Lown, d);
+    MGX_REQUIRE(ns == 1 || (workspace && ws_bytes >= need), MGX_ERR_SHAPE,
+                "%s: workspace must hold mgx_rel_attn_decode_shared_workspace() = %zu bytes (got %zu)", name, need, ws_bytes);
+    hipLaunchKernelGGL(rel_attn_decode_shared_kernel<SHARED_NQ>, dim3((unsigned)wgs, ns), dim3(64 * DEC_WAVES), 0, (hipStream_t)stream,
+                       qkv_new, kpre, vpre, kown, vown, E, pos_rows, pre_rows, ctx, (float*)workspace, N, Lpre, Lown, d, M);
+    if (ns > 1)
+        hipLaunchKernelGGL(rel_attn_decode_merge_kernel, dim3(Bp * N * (d / 64)), dim3(64), 0, (hipStream_t)stream,
+                           (const float*)workspace, ctx, ns, d);
+    MGX_CHECK_LAUNCH(name);
+    return MGX_OK;
 }
 
 extern "C" int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* kcache, uint8_t* vcache, float* kscale,

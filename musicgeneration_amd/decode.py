@@ -4,7 +4,9 @@ the only place that knows the two cache formats, ``SubBatch`` is where ``groups`
 lives (``pos``, on the device: one shared counter, or one per row when prompts differ in length).  ``window_schedule`` is the
 host-side plan of the re-anchored window (``window=``), the one way to generate past max_seq with the cache.
 ``generate_beam`` (with ``check_beam_args``) is the second driver: beam search over the same step, which ends in
-ops.beam_select instead of the sampler and hands every surviving beam its parent's cache rows (ops.kv_beam_reorder)."""
+ops.beam_select instead of the sampler and hands every surviving beam its parent's cache rows (ops.kv_beam_reorder).
+``generate_shared`` (with ``check_shared_args`` and ``SharedKVCache``) is generate_cached(samples_per_prompt=N): the ragged step
+on Bp * N rows whose attention reads every prompt's K/V once for the samples of that prompt (ops.rel_attn_decode_shared)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -108,13 +110,16 @@ def window_schedule(lens, length: int, window: int, hop: Optional[int] = None):
 
 
 def check_args(model, prior, length: int, return_probs: bool, prefill: str, prior_lengths, kv_cache: str, window=None, hop=None,
-               groups=None, masked_groups: bool = False):
+               groups=None, masked_groups: bool = False, samples_per_prompt=None, return_cache: bool = False):
     """every refusal of generate_cached (ValueError), on the host.  Returns (P: the columns of ``prior`` to decode from, below its
     width for equal prior_lengths; lens: the per-row prompt lengths if they differ, else None; batched: the prefill that runs;
-    hop: the window's hop, None without ``window``)"""
+    hop: the window's hop, None without ``window``).  With ``samples_per_prompt``: (Pmax, every prompt's length, True, None)"""
     if kv_cache not in KVCache.KINDS:
         raise ValueError(f"kv_cache must be 'bf16' or 'fp8', got {kv_cache!r}")
     max_seq = model.max_seq
+    if samples_per_prompt is not None:
+        return check_shared_args(model, prior, length, prefill, prior_lengths, kv_cache, window, hop, groups, masked_groups,
+                                 samples_per_prompt, return_cache)
     if window is None and hop is not None:
         raise ValueError(f"hop ({hop}) is the stride of the re-anchored window: it needs window")
     if window is not None:
@@ -170,6 +175,67 @@ def check_args(model, prior, length: int, return_probs: bool, prefill: str, prio
     if prefill == "batched" and not fits:
         raise ValueError(f"prefill='batched' pads the {P - 1}-token prompt to {padded} rows > max_seq={max_seq}")
     return P, None, prefill == "batched" or (prefill == "auto" and not return_probs and P > 32 and fits), None
+
+
+def check_shared_args(model, prior, length, prefill, prior_lengths, kv_cache, window, hop, groups, masked_groups, samples_per_prompt,
+                      return_cache):
+    """the refusals of generate_cached(samples_per_prompt=N) (ValueError), on the host: what the shared prompt cache leaves out,
+    then the prompt-length rules of the ragged call"""
+    N = int(samples_per_prompt)
+    if not 1 <= N <= ops.SHARED_MAX_N:
+        raise ValueError(f"samples_per_prompt must lie in 1 .. {ops.SHARED_MAX_N}, got {samples_per_prompt}")
+    if window is not None or hop is not None:
+        raise ValueError("samples_per_prompt is not combined with window / hop (a re-anchor would rebuild every sample's own window)")
+    if kv_cache != "bf16":
+        raise ValueError(f"samples_per_prompt needs kv_cache='bf16' (the shared prompt cache has no 8-bit form), got {kv_cache!r}")
+    if (groups or 1) > 1 or masked_groups:
+        raise ValueError("samples_per_prompt is not combined with groups / masked_groups (the samples of a prompt decode as one group)")
+    if prefill not in ("auto", "token", "batched"):
+        raise ValueError("prefill must be 'auto', 'token' or 'batched'")
+    if prefill == "token":
+        raise ValueError("samples_per_prompt needs prefill='batched' or 'auto': the prompt cache is written by one batched pass")
+    if return_cache:
+        raise ValueError("samples_per_prompt is not combined with return_cache (the prompt rows are held once, not per row)")
+    B, Pmax = prior.shape
+    lens = [Pmax] * B
+    if prior_lengths is not None:
+        lens = [int(v) for v in torch.as_tensor(prior_lengths).reshape(-1).tolist()]
+        if len(lens) != B:
+            raise ValueError(f"prior_lengths has {len(lens)} entries for a batch of {B} prompts")
+        if any(not 1 <= v <= Pmax for v in lens):
+            raise ValueError(f"prior_lengths must lie in 1 .. {Pmax} (the width of prior), got {lens}")
+    if Pmax < 1 or Pmax + length > model.max_seq:
+        raise ValueError(f"the longest prompt ({Pmax}) + length ({length}) must be <= max_seq ({model.max_seq}) and prior non-empty")
+    padded = (Pmax - 1 + 31) // 32 * 32
+    if padded > model.max_seq:
+        raise ValueError(f"the prompts are prefilled in one batched pass, which pads the {Pmax - 1}-token prompt to {padded} rows > "
+                         f"max_seq={model.max_seq}")
+    return Pmax, lens, True, None
+
+
+class SharedKVCache:
+    """KVCache's sibling for N samples per prompt (include/mgx.h, ABI 26): per layer the prompt cache kpre / vpre
+    [Bp, h, Lpre, 64], one per prompt and written by the prefill only, and the own cache kown / vown [Bp * N, h, Lown, 64] of
+    what every sample appended; ``pre_rows`` int32 [Bp]: the prompt-cache rows of every prompt"""
+
+    def __init__(self, Bp: int, N: int, heads: int, Lpre: int, Lown: int, layers: int, device):
+        def zeros(rows, L):
+            return [torch.zeros(rows, heads, L, 64, dtype=BF16, device=device) for _ in range(layers)]
+        self.N = N
+        self.kpre, self.vpre, self.kown, self.vown = zeros(Bp, Lpre), zeros(Bp, Lpre), zeros(Bp * N, Lown), zeros(Bp * N, Lown)
+        self.pre_rows = torch.zeros(Bp, dtype=torch.int32, device=device)
+
+    def store_prefill(self, layer: int, qkv: torch.Tensor, n: int) -> None:
+        """prompt-cache rows 0..n-1 of ``layer`` from the K and V columns of a full-sequence qkv bf16 [Bp, Lrows, 3d]"""
+        B, heads = self.kpre[layer].shape[:2]
+        d = heads * 64
+        self.kpre[layer][:, :, :n] = qkv[:, :n, d:2 * d].view(B, n, heads, 64).permute(0, 2, 1, 3)
+        self.vpre[layer][:, :, :n] = qkv[:, :n, 2 * d:].view(B, n, heads, 64).permute(0, 2, 1, 3)
+
+    def attend(self, layer: int, qkv_new, E, pos, ctx, workspace, ragged: bool):
+        """append every row's k, v to its own cache and attend over the prompt's rows, then the row's own: ctx bf16 [Bp * N, d]"""
+        return ops.rel_attn_decode_shared(qkv_new, self.kpre[layer], self.vpre[layer], self.kown[layer], self.vown[layer], E, pos,
+                                          self.pre_rows, ctx, workspace, self.N)
 
 
 class Weights:
@@ -337,8 +403,11 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
 
 
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
-                    return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None):
+                    return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None):
     """MusicTransformer.generate_cached (documented there)"""
+    if samples_per_prompt is not None:
+        return generate_shared(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
+                               return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop, samples_per_prompt)
     P, lens, batched, hop = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache, window, hop, groups,
                                        masked_groups)
     extra, prior, ragged = prior.shape[1] - P, prior[:, :P], lens is not None      # extra > 0: equal prior_lengths below the width
@@ -446,6 +515,56 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     if window is not None:                                # the cache grows to the rows the full-width call would have
         extra = min(window, total + extra) - cache_rows
     return (res, *(cache.grow(extra) if extra else cache).result()) if return_cache else res
+
+
+def generate_shared(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill, return_cache,
+                    groups, masked_groups, prior_lengths, kv_cache, window, hop, samples_per_prompt):
+    """generate_cached(samples_per_prompt=N): rows r = b * N + n, sample n of prompt b.  One batched prefill of the Bp prompts
+    fills the prompt cache (pre_rows = len_b - 1 rows each); every row then resumes at its prompt's last token and runs the
+    ragged step on R = Bp * N rows, whose attention reads the prompt's rows once for the samples of a prompt and appends to the
+    row's own cache.  Row r draws with (seed, t, r), as it does in the call on the prompts repeated N times"""
+    P, lens, _, _ = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache, window, hop, groups,
+                               masked_groups, samples_per_prompt, return_cache)
+    st = model.store()
+    st.sync_shadow()
+    was_training = model.training
+    model.eval()
+    Bp, N, total, dev = prior.shape[0], int(samples_per_prompt), P + length, st.param.device
+    R, d, V = Bp * N, model.embedding_dim, model.vocab_size
+    Lpre, Lown = max(P - 1, 1), max(length, 1)
+    lens_dev = torch.tensor(lens, dtype=torch.int32, device=dev)
+    # the right padding becomes pad_token (a valid id for the prefill; the result's tail past each row's samples)
+    prior_i = torch.where(torch.arange(P, device=dev)[None, :] < lens_dev[:, None], prior.to(torch.int32).to(dev), model.pad_token)
+    cache = SharedKVCache(Bp, N, d // 64, Lpre, Lown, model.num_layer, dev)
+    cache.pre_rows.copy_(lens_dev - 1)
+    w = Weights(model, st, fused=R <= 32 and d <= 1024)
+    if P > 1:                                             # positions 0..P-2 of the Bp prompts in one pass
+        prefill_batched(w, cache, prior_i[:, :P - 1])
+    rows, last = torch.arange(R, device=dev), (lens_dev.long() - 1).repeat_interleave(N)
+    pos = last.to(torch.int32).contiguous()               # every row resumes at its prompt's last token
+    tok = prior_i[torch.arange(Bp, device=dev), lens_dev.long() - 1].repeat_interleave(N).contiguous()
+    out_tokens = torch.full((R, total), model.pad_token, dtype=torch.int32, device=dev)
+    out_tokens[:, :P] = prior_i.repeat_interleave(N, 0)
+    probs_all = torch.zeros(R, total, V, dtype=torch.float32, device=dev) if return_probs else None
+    probs_step = torch.zeros(R, V, dtype=torch.float32, device=dev) if return_probs else None
+    hbuf, ctxbuf = (torch.empty(R, d, dtype=BF16, device=dev) for _ in range(2))
+    r = SubBatch(0, pos, tok, out_tokens, hbuf, ctxbuf, probs_step, cache,
+                 ops.rel_attn_decode_shared_workspace(Bp, N, Lpre, Lown, d, dev), torch.cuda.Stream())
+    allow = None
+    if grammar is not None:
+        allow = torch.as_tensor(np.ascontiguousarray(grammar).view(np.int32) if isinstance(grammar, np.ndarray) else grammar)
+        allow = allow.to(device=dev, dtype=torch.int32).contiguous()
+    sampler = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, allow_table=allow)
+    steps = max(length, 1)                                # length 0 still runs the last prompt token (its distribution)
+    eager = 1 if use_graph and not return_probs and steps - 1 > 2 else steps    # the first step also warms every kernel up
+    for s in range(eager):
+        decode_step(w, r, sampler, True, length > 0)
+        if return_probs:                                  # the distribution after position len_b - 1 + s
+            probs_all[rows, last + s] = probs_step
+    if eager < steps:
+        replay_graphs([r], steps - eager, lambda r_: decode_step(w, r_, sampler, True, True))
+    model.train(was_training)
+    return (out_tokens, probs_all) if return_probs else out_tokens
 
 
 # ---- beam search ------------------------------------------------------------------------------------------------------------

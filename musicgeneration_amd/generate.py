@@ -61,6 +61,10 @@ def get_options(argv=None):
     parser.add_option('--best-of', dest='best_of', type='int', default=1,
                       help='draw N candidates per sample (a batch of b * N rows, every prompt repeated N times), score every '
                            'continuation with the model at temperature 1 (MusicTransformer.score) and write the most likely one')
+    parser.add_option('--share-prompt', dest='share_prompt', action='store_true', default=False,
+                      help='KV-cache decode of the samples of one prompt over ONE copy of its K/V: with -c FILE (or --grammar) the '
+                           '-b x --best-of samples (16 at most) share the prompt, with --condition-files the --best-of N candidates '
+                           'of every file do (the prompt is prefilled once, not once per sample)')
     return parser.parse_args(argv)[0]
 
 
@@ -88,6 +92,24 @@ def _check_best_of(o):
         raise SystemExit(f'--best-of must be at least 1, got {o.best_of}')
     if o.best_of > 1 and o.beam_size:
         raise SystemExit('--best-of cannot be combined with -B/--beam-size (a search returns its best beam; --best-of ranks samples)')
+
+
+def _check_share_prompt(o):
+    """--share-prompt against what the shared prompt cache leaves out, before any model or device work"""
+    if not o.share_prompt:
+        return
+    for on, what, why in ((o.window, '--window', "a re-anchor would rebuild every sample's own window"),
+                          (o.kv_cache != 'bf16', '--kv-cache ' + o.kv_cache, 'the shared prompt cache is bf16'),
+                          (o.beam_size, '-B/--beam-size', 'a search reorders whole cache rows between its beams'),
+                          (o.reference_mask, '--reference-mask', 'the KV-cache decode is causal')):
+        if on:
+            raise SystemExit(f'--share-prompt cannot be combined with {what} ({why})')
+    if o.condition_files is None and o.condition_file is None and not o.grammar:
+        raise SystemExit('--share-prompt shares a prompt between its samples: add -c FILE, --condition-files or --grammar')
+    n = o.best_of if o.condition_files is not None else o.batch_size * o.best_of
+    if not 1 <= n <= 16:
+        raise SystemExit(f'--share-prompt decodes at most 16 samples per prompt, got {n}'
+                         + (' (--best-of)' if o.condition_files is not None else ' (-b x --best-of)'))
 
 
 def _best_of(o, mt, res, prompt_lens, grammar=None):
@@ -136,6 +158,7 @@ def main(argv=None):
     o = get_options(argv)
     _check_best_of(o)
     _check_beam_options(o)
+    _check_share_prompt(o)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
@@ -172,6 +195,12 @@ def main(argv=None):
         return res.cpu().numpy()
     if ragged is not None:
         prior, lens = ragged
+        if o.share_prompt:                                 # the N candidates of a file over one copy of its prompt
+            res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
+                                     prior_lengths=lens, samples_per_prompt=o.best_of).cpu().numpy()
+            res = _best_of(o, mt, res, [n for n in lens for _ in range(o.best_of)])
+            _write(o, [row[:n + o.max_len] for row, n in zip(res, lens)])
+            return
         if o.best_of > 1:                                  # every prompt N times, side by side
             prior, lens = prior.repeat_interleave(o.best_of, 0), [n for n in lens for _ in range(o.best_of)]
         if o.beam_size:
@@ -193,7 +222,7 @@ def main(argv=None):
         ids = EventSeq.from_note_seq(NoteSeq.from_midi_file(o.condition_file)).to_array()[:500]
         if len(ids) == 0:
             raise SystemExit(f'{o.condition_file}: no notes in the MIDI-like pitch range')
-        prior = torch.from_numpy(np.array([ids] * rows, dtype=np.int64)).to(device)
+        prior = torch.from_numpy(np.array([ids] * (1 if o.share_prompt else rows), dtype=np.int64)).to(device)
         print('Prompt: {} events from {}'.format(len(ids), o.condition_file))
     if o.grammar:
         if o.repr == 'remi':
@@ -203,7 +232,9 @@ def main(argv=None):
         else:
             raise SystemExit('--grammar is defined for --repr remi and --repr mumidi')
         bar = Codec.feat_ranges()['bar'][0]
-        prior = torch.full((rows, 1), bar, dtype=torch.long, device=device)
+        prior = torch.full((1 if o.share_prompt else rows, 1), bar, dtype=torch.long, device=device)
+        if o.share_prompt:                                 # the one-token prompt: nothing to share yet, every key is a row's own
+            cached = dict(samples_per_prompt=rows)
         if o.beam_size:
             _write(o, search(prior, grammar=Codec.next_token_table()))
             return
@@ -212,6 +243,9 @@ def main(argv=None):
         res = _best_of(o, mt, res, [1] * rows, Codec.next_token_table())
     elif o.beam_size:
         res = search(prior)
+    elif o.share_prompt:                                   # -c FILE: one prompt, -b x --best-of samples
+        res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
+                                 samples_per_prompt=rows).cpu().numpy()
     elif o.window:
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached).cpu().numpy()
     else:

@@ -336,7 +336,7 @@ class MusicTransformer(torch.nn.Module):
                         top_p: float = 1.0, seed: int = 0, use_graph: bool = True, return_probs: bool = False,
                         grammar=None, prefill: str = "auto", return_cache: bool = False, groups: Optional[int] = None,
                         masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
-                        hop: Optional[int] = None):
+                        hop: Optional[int] = None, samples_per_prompt: Optional[int] = None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq unless ``window`` is given, see below).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -388,9 +388,21 @@ class MusicTransformer(torch.nn.Module):
         row b carries the distributions after columns P_b-1 .. P_b+length-2 and zeros elsewhere (uniform prompts too); with
         ``return_cache`` the last window's caches, min(window, Pmax+length) rows, zero beyond the row of each row's last input
         token.  While no re-anchor happens (window >= Pmax + length) tokens, distributions and caches are bitwise those of the
-        call without ``window`` and with the batched prefill."""
+        call without ``window`` and with the batched prefill.
+
+        ``samples_per_prompt`` (N, 1 .. 16): N continuations of every prompt over ONE copy of its K/V.  ``prior`` [Bp, P] (with
+        ``prior_lengths``, or all of width P) gives int32 [Bp * N, Pmax+length], row b * N + n the n-th sample of prompt b, padded
+        as the ragged call pads; with ``return_probs`` the f32 [Bp * N, Pmax+length, V] distributions after positions
+        P_b-1 .. P_b+length-2 of every row.  One batched prefill of the Bp prompts fills a prompt cache that the decode never
+        writes; every row appends to a cache of its own of ``length`` rows, and the attention (mgx_rel_attn_decode_shared,
+        ABI 26) loads a prompt's keys once for the samples of that prompt.  Row r draws with (seed, position, r), as it does in
+        the call on ``prior.repeat_interleave(N, 0)``; the two calls run different kernels, so their distributions agree to
+        rounding and a draw near a CDF boundary may differ.  Prefill work and prompt-cache memory are 1/N of the repeated
+        call's.  Refused: ``window``, ``kv_cache="fp8"``, ``groups`` > 1, ``masked_groups``, ``prefill="token"``,
+        ``return_cache``, Pmax + length > max_seq.  None (default): the call as described above, untouched."""
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
-                                      prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop)
+                                      prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop,
+                                      samples_per_prompt)
 
     @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,

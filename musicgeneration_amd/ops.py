@@ -708,6 +708,56 @@ def rel_attn_decode(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace=None, *,
     return ctx
 
 
+# ---- N samples per prompt over a shared prompt cache (ABI 26; contract in include/mgx.h) -----------------------------
+SHARED_MAX_N = _lib.DEFINES["MGX_SHARED_MAX_N"]
+SHARED_NQ = _lib.DEFINES["MGX_SHARED_NQ"]                 # queries per workgroup of the kernel
+
+
+def rel_attn_decode_shared_splits(Bp, N, Lpre, Lown, d) -> int:
+    return int(_lib.load().mgx_rel_attn_decode_shared_splits(Bp, N, Lpre, Lown, d))
+
+
+def rel_attn_decode_shared_workspace(Bp, N, Lpre, Lown, d, device):
+    """scratch for the split-K partials of mgx_rel_attn_decode_shared (None for one split), as rel_attn_decode_workspace"""
+    n = _lib.load().mgx_rel_attn_decode_shared_workspace(Bp, N, Lpre, Lown, d)
+    return torch.empty(n, dtype=torch.uint8, device=device) if n else None
+
+
+def rel_attn_decode_shared(qkv_new, kpre, vpre, kown, vown, E, pos_rows, pre_rows, ctx, workspace, N):
+    """the decode attention of R = Bp * N rows, row b * N + n = sample n of prompt b: kpre / vpre bf16 [Bp, h, Lpre, 64] hold
+    every prompt's first pre_rows[b] keys once (never written), kown / vown bf16 [R, h, Lown, 64] what each row appended itself;
+    pos_rows int32 [R] (the N rows of a prompt hold one position), pre_rows int32 [Bp], both on the device and not checked"""
+    what = "rel_attn_decode_shared"
+    N = int(N)
+    if not 1 <= N <= SHARED_MAX_N:
+        raise ValueError(f"{what}: N must lie in 1 .. {SHARED_MAX_N}, got {N}")
+    for name, (k, v) in (("kpre / vpre", (kpre, vpre)), ("kown / vown", (kown, vown))):
+        if k.dim() != 4 or k.shape[-1] != 64 or v.shape != k.shape:
+            raise ValueError(f"{what}: {name} must be [rows, h, L, 64] of one shape, got {tuple(k.shape)} / {tuple(v.shape)}")
+        if k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16 or not (k.is_contiguous() and v.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be contiguous bf16, got {k.dtype} / {v.dtype}")
+    Bp, heads, Lpre, _ = kpre.shape
+    R, d = Bp * N, heads * 64
+    if kown.shape[0] != R or kown.shape[1] != heads:
+        raise ValueError(f"{what}: kown / vown must hold Bp * N = {R} rows of {heads} heads, got {tuple(kown.shape)}")
+    for name, t in (("qkv_new", qkv_new), ("ctx", ctx)):
+        cols = 3 * d if name == "qkv_new" else d
+        if t.dtype != torch.bfloat16 or tuple(t.shape) != (R, cols) or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous bf16 [{R}, {cols}], got {t.dtype} {tuple(t.shape)}")
+    if E.dtype != torch.bfloat16 or E.dim() != 2 or E.shape[1] != 64 or not E.is_contiguous():
+        raise ValueError(f"{what}: E must be contiguous bf16 [M, 64], got {E.dtype} {tuple(E.shape)}")
+    _check_pos_rows(pos_rows, R, True)
+    if pre_rows.dtype != torch.int32 or pre_rows.numel() != Bp or not pre_rows.is_contiguous():
+        raise ValueError(f"{what}: pre_rows must be a contiguous int32 tensor of {Bp} entries "
+                         f"(got {pre_rows.dtype}, {pre_rows.numel()} entries)")
+    _need_cuda(qkv_new, kpre, vpre, kown, vown, E, pos_rows, pre_rows, ctx, workspace)
+    check(_lib.load().mgx_rel_attn_decode_shared(ptr(qkv_new), ptr(kpre), ptr(vpre), ptr(kown), ptr(vown), ptr(E), ptr(pos_rows),
+                                                 ptr(pre_rows), ptr(ctx), ptr(workspace),
+                                                 0 if workspace is None else workspace.numel(), Bp, N, Lpre, kown.shape[2], d,
+                                                 E.shape[0], stream_ptr()), "mgx_rel_attn_decode_shared")
+    return ctx
+
+
 def _check_base(base, pos_dev, what):
     """the window's base (ABI 21) has the shape of the positions: one shared int32, or one per row"""
     if base.dtype != torch.int32 or pos_dev.dtype != torch.int32 or base.numel() != pos_dev.numel() or not base.is_contiguous():
