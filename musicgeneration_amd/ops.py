@@ -10,6 +10,7 @@ from typing import Tuple
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -765,6 +766,22 @@ def _check_base(base, pos_dev, what):
                          f"(got {base.dtype}, {base.numel()} entries)")
 
 
+def grammar_table(grammar, device):
+    """a grammar -- the [V, ceil(V/32)] bit table "token v may follow token t" (e.g. REMI_EventSeq.next_token_table()), a numpy
+    uint32 / int32 array or a tensor -- as the contiguous int32 device tensor the kernels' ``allow_table`` takes; None stays None"""
+    if grammar is None:
+        return None
+    table = torch.as_tensor(np.ascontiguousarray(grammar).view(np.int32) if isinstance(grammar, np.ndarray) else grammar)
+    return table.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _check_allow_table(allow_table, V):
+    if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
+                                    or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4
+                                    or not allow_table.is_contiguous()):
+        raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
+
+
 def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=None, temperature=1.0, top_k=0, top_p=1.0,
                      seed=0, advance=True, allow_table=None, row0=0, *, ragged=False, base=None):
     """allow_table: optional int32/uint32 [V, ceil(V/32)] grammar mask on the device (bit v of row t: v may follow t);
@@ -776,10 +793,7 @@ def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=No
     ld = logits.shape[-1]
     B = logits.numel() // ld
     sfx = _check_pos_rows(pos_dev, B, ragged)
-    if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
-                                    or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4
-                                    or not allow_table.is_contiguous()):
-        raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
+    _check_allow_table(allow_table, V)
     head = (ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed), ptr(pos_dev))
     tail = (ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[-1], ptr(probs_out), B, int(row0),
             1 if advance else 0, ptr(allow_table))
@@ -832,10 +846,7 @@ def beam_select(logits, V, score, tok, parent, pos_rows, hist_tok, hist_parent, 
     _check_int32_rows("beam_select", B * K, tok=tok, parent=parent, pos_rows=pos_rows, hist_tok=hist_tok, hist_parent=hist_parent)
     if tok.dim() != 1 or parent.dim() != 1 or pos_rows.dim() != 1 or hist_tok.dim() != 2 or hist_parent.shape != hist_tok.shape:
         raise ValueError("beam_select: tok, parent, pos_rows are [B*K]; hist_tok and hist_parent [B*K, out_ld] of one shape")
-    if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
-                                    or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4
-                                    or not allow_table.is_contiguous()):
-        raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
+    _check_allow_table(allow_table, V)
     check(_lib.load().mgx_beam_select(ptr(logits), int(V), ld, float(temperature), ptr(score), ptr(tok), ptr(parent), ptr(pos_rows),
                                       ptr(hist_tok), ptr(hist_parent), hist_tok.shape[1], B, K, 1 if advance else 0,
                                       ptr(allow_table), 1 if stochastic else 0, int(seed), stream_ptr()), "mgx_beam_select")
@@ -905,9 +916,7 @@ def token_logprob(logits, target, temperature=1.0, prev=None, allow_table=None, 
             raise ValueError(f"token_logprob: {name} must be int32 with one entry per row ({rows}), got {t.dtype} {tuple(t.shape)}")
     if (prev is None) != (allow_table is None):
         raise ValueError("token_logprob: prev and allow_table are given together or not at all")
-    if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
-                                    or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4):
-        raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
+    _check_allow_table(allow_table, V)
     logp, lse, hit = _score_outputs(rows, lg.device, want_lse)
     check(_lib.load().mgx_token_logprob(ptr(lg), V, int(ld), ptr(target), ptr(prev), ptr(allow_table), float(temperature), ptr(logp),
                                         ptr(lse), ptr(hit), rows, stream_ptr()), "mgx_token_logprob")

@@ -162,10 +162,7 @@ def score(model, x, lengths=None, from_pos=None, temperature=1.0, grammar=None, 
     path, W, stride, lens, fp = check_args(model.max_seq, model.embedding_dim, B, L, lengths, from_pos, temperature, grammar, logits,
                                            window, stride)
     dev = x.device
-    table = None
-    if grammar is not None:
-        table = torch.as_tensor(np.ascontiguousarray(grammar).view(np.int32) if isinstance(grammar, np.ndarray) else grammar)
-        table = table.to(device=dev, dtype=torch.int32).contiguous()
+    table = ops.grammar_table(grammar, dev)
     tok = x.to(torch.int32).contiguous()
     col = torch.arange(L, device=dev, dtype=torch.int32)[None, :]
     first = torch.tensor([max(1, v) for v in fp], dtype=torch.int32).to(dev)[:, None]
