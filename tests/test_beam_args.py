@@ -8,11 +8,7 @@ import pytest
 import torch
 
 import beam_ref
-
-
-def _model(L=96, V=337):
-    from musicgeneration_amd.network import MusicTransformer
-    return MusicTransformer(embedding_dim=128, vocab_size=V, num_layer=1, max_seq=L, dropout=0.0)
+from decode_fixtures import host_model
 
 
 @pytest.mark.parametrize("length,kw,msg", [
@@ -32,28 +28,28 @@ def _model(L=96, V=337):
 def test_generate_beam_refusals(length, kw, msg):
     x = torch.randint(0, 300, (3, 40))
     with pytest.raises(ValueError, match=msg):
-        _model().generate_beam(x, length, **kw)
+        host_model().generate_beam(x, length, **kw)
 
 
 def test_beam_size_is_limited_by_the_vocabulary():
     with pytest.raises(ValueError, match="beam_size"):
-        _model(V=8).generate_beam(torch.zeros(1, 4, dtype=torch.long), 4, beam_size=9)
+        host_model(V=8).generate_beam(torch.zeros(1, 4, dtype=torch.long), 4, beam_size=9)
 
 
 def test_prefill_that_pads_past_max_seq_is_refused():
     x = torch.randint(0, 300, (2, 90))                                              # 89 prefill rows pad to 96 > max_seq 92
     with pytest.raises(ValueError, match="max_seq=92"):
-        _model(L=92).generate_beam(x, 2, beam_size=2, prior_lengths=[90, 3])
+        host_model(L=92).generate_beam(x, 2, beam_size=2, prior_lengths=[90, 3])
     with pytest.raises(ValueError, match="max_seq=92"):
-        _model(L=92).generate_beam(x, 2, beam_size=2)
+        host_model(L=92).generate_beam(x, 2, beam_size=2)
 
 
 def test_check_beam_args_accepts_and_returns_the_prompt():
     from musicgeneration_amd import decode
     x = torch.randint(0, 300, (3, 40))
-    assert decode.check_beam_args(_model(), x, 56, 16, 0.5, None, "fp8") == (40, None)
-    assert decode.check_beam_args(_model(), x, 10, 1, 1.0, [3, 9, 5], "bf16") == (40, [3, 9, 5])
-    assert decode.check_beam_args(_model(), x, 10, 1, 1.0, [7, 7, 7], "bf16") == (7, None)
+    assert decode.check_beam_args(host_model(), x, 56, 16, 0.5, None, "fp8") == (40, None)
+    assert decode.check_beam_args(host_model(), x, 10, 1, 1.0, [3, 9, 5], "bf16") == (40, [3, 9, 5])
+    assert decode.check_beam_args(host_model(), x, 10, 1, 1.0, [7, 7, 7], "bf16") == (7, None)
 
 
 def test_beam_cli_refusals(tmp_path):

@@ -72,18 +72,19 @@ for that.  The product library only: no experiment build, no environment variabl
 ratio per output before it asserts (pytest -s; profiles/r18_attn_kernel_tests.txt has the figures).
 """
 import functools
-import os
 
 import pytest
 import torch
 
+import kernel_checks as KC
+from kernel_checks import BAND, Banded, Det, P, check_equal, nothing_more_after_a_gpu_error, operand, output  # noqa: F401 (the fixture is used by name)
 from oracle import train_ref as T
-from test_gpu_gemm_kernels import BAND, Banded, Det, P, _nothing_more_after_a_gpu_error, operand, output  # noqa: F401 (the fixture is used by name)
 
 pytestmark = pytest.mark.gpu
 
 BF, F32, F64 = torch.bfloat16, torch.float32, torch.float64
 SEEN = {}
+_report = KC.report_fixture(SEEN, "largest error / bound {:.3g}")
 PROD, DKV32, RECOMPUTE = 1 | 4 | 2 | 8, 1 | 64 | 2 | 8, 1 | 4 | 32 | 16
 PARTS_NAME = {PROD: "bwd", DKV32: "bwd[32-key dK/dV]", RECOMPUTE: "bwd[recompute dQ, dE]"}
 
@@ -92,52 +93,15 @@ SHAPES = ((2, 32, 1, 32), (1, 96, 3, 97), (3, 128, 2, 128), (2, 160, 1, 260), (1
 IDS = [f"L{s[1]}" for s in SHAPES]
 
 
-def _raw():
-    from musicgeneration_amd import _lib
-    assert "MGX_LIB_PATH" not in os.environ, "this module is about the product library"
-    return _lib.load(), _lib.check, _lib.stream_ptr
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    for (fam, kind), (r, case) in sorted(SEEN.items()):
-        print(f"\nMEASURED {fam} [{kind}]: largest error / bound {r:.3g} at {case}", end="")
-    print()
-
-
 class OnesBanded(Banded):
     """padbits: the bands have all bits set (a word taken from beyond the bitmap pads 32 keys)"""
 
     def __init__(self, t):
-        super().__init__(t, False)
-        b = self.buf.view(torch.uint8)
-        b[:BAND] = 0xFF
-        b[BAND + self.n * self.buf.element_size():] = 0xFF
+        super().__init__(t, BAND, b"\xff")
 
 
 def check_bound(fam, kind, got, ref, bound, case):
-    """|got - ref| <= bound, element by element (bound 0: equal); got finite"""
-    got = got.detach().cpu().to(F64)
-    assert torch.isfinite(got).all(), (fam, case, "non-finite output", torch.nonzero(~torch.isfinite(got))[:4].tolist())
-    assert torch.isfinite(ref).all() and torch.isfinite(bound).all() and (bound >= 0).all(), (fam, case, "the reference or its bound is not a number")
-    err = (got - ref).abs()
-    ratio = torch.where(bound > 0, err / bound.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    worst = ratio.max().item()
-    if worst > SEEN.get((fam, kind), (-1.0, None))[0]:
-        SEEN[(fam, kind)] = (worst, case)
-    print(f"[{fam}] {case}: error / bound {worst:.3g}")
-    if not worst <= 1.0:
-        i = tuple(int(v) for v in torch.nonzero(ratio == ratio.max())[0])
-        raise AssertionError(f"{fam} {case}: element {i} got {got[i].item()!r} ref {ref[i].item()!r} bound {bound[i].item():.3e} ratio {worst:.3f}")
-
-
-def check_equal(fam, got, want, case):
-    got = got.detach().cpu().to(F64)
-    bad = torch.nonzero(~(got == want))
-    assert bad.numel() == 0, (f"{fam} {case}: {bad.shape[0]} elements differ, first {bad[:4].tolist()} got "
-                              f"{[got[tuple(i)].item() for i in bad[:4]]} want {[torch.as_tensor(want).expand_as(got)[tuple(i)].item() for i in bad[:4]]}")
-    print(f"[{fam}] {case}: exact")
+    KC.check_bound(fam, got, ref, bound, case, seen=SEEN, key=(fam, kind))
 
 
 # ---- cases: inputs, reference and bounds, built once and shared ----------------------------------------------------------------------
@@ -193,7 +157,7 @@ def cases_of(kind, shape_index):
 # ---- forward ----------------------------------------------------------------------------------------------------------------------
 def launch_fwd(c, qkv=None, E=None, Lk=None):
     """mgx_rel_attn_fwd (Lk None) or mgx_rel_attn_fwd_nomask inside bands -> ctx bf16 [B, L, d], lse f32 [B, h, L] on the device"""
-    lib, chk, sp = _raw()
+    lib, chk, _, sp = KC.raw(product_only=True)
     B, L, d, M = c.B, c.L, c.d, c.M
     QKV, EE = operand(c.qkv if qkv is None else qkv), operand(c.E if E is None else E)
     PB = None if c.pm is None or Lk is not None else OnesBanded(T.pack_padbits(c.pm))
@@ -263,7 +227,7 @@ def test_weights(kind, shape_index):
     """mgx_rel_attn_weights on lse_in = fp32(reference lse): per element into a zero-filled buffer, masked entries exactly 0; into a
     buffer filled with a sentinel, every element of a tile above the diagonal (j >= 32 (i // 32 + 1)) comes back untouched and the
     masked entries of the visited tiles are written as 0"""
-    lib, chk, sp = _raw()
+    lib, chk, _, sp = KC.raw(product_only=True)
     SENTINEL = 7.25
     for c in cases_of(kind, shape_index)[:3]:
         B, L, d, M, h = c.B, c.L, c.d, c.M, c.heads
@@ -295,7 +259,7 @@ def test_weights(kind, shape_index):
 # ---- backward ---------------------------------------------------------------------------------------------------------------------
 def launch_bwd(c, ctx_in, lse_in, parts, det=False):
     """mgx_rel_attn_bwd_parts inside bands -> dqkv bf16 [B, L, 3d], dE f32 [M, 64] on the CPU"""
-    lib, chk, sp = _raw()
+    lib, chk, _, sp = KC.raw(product_only=True)
     B, L, d, M = c.B, c.L, c.d, c.M
     QKV, EE, CTX, DCTX, LSE = operand(c.qkv), operand(c.E), operand(ctx_in), operand(c.dctx), operand(lse_in)
     PB = None if c.pm is None else OnesBanded(T.pack_padbits(c.pm))

@@ -48,7 +48,7 @@ _CACHE = {}
 VIABLE, SPREAD, FC_SCALE, SEED = 4, 1.5, 0.5, 3
 
 
-def _model(V=V, nl=2, L=128, seed=None, viable=None, fc_scale=None, emb_scale=0.1):
+def _search_model(V=V, nl=2, L=128, seed=None, viable=None, fc_scale=None, emb_scale=0.1):
     """the fixture of test_gpu_decode.py (random init with tamed embeddings and relative terms), with an output bias that leaves
     VIABLE events likely (biases spread over +-SPREAD; -30 for the rest).  A search then weighs K * VIABLE candidates a few
     tenths apart instead of K * V a few hundredths apart: bf16 logits resolve the former (module docstring: the 90 % condition).
@@ -80,7 +80,7 @@ def _model(V=V, nl=2, L=128, seed=None, viable=None, fc_scale=None, emb_scale=0.
 def _plain_model():
     """no output bias, all 90 events in play, and embeddings and an output layer large enough that the context -- the cache a
     beam reads -- moves the log-probabilities by several EPS_PLAIN"""
-    return _model(viable=0, fc_scale=4.0, emb_scale=0.3)
+    return _search_model(viable=0, fc_scale=4.0, emb_scale=0.3)
 
 
 def _prompts(ragged):
@@ -169,7 +169,7 @@ def trajectory(mt, K, ragged, kv, eps, strangers=None):
 @pytest.mark.parametrize("K", [1, 4])
 def test_trajectory(K, ragged, kv):
     eps = EPS[kv]
-    bad, worst, gaps, full = trajectory(_model(), K, ragged, kv, eps)
+    bad, worst, gaps, full = trajectory(_search_model(), K, ragged, kv, eps)
     clear, pairs, B = int((gaps > 2 * eps).sum()), len(gaps), full[0].shape[0]
     SEEN[kv] = max(SEEN[kv], worst)
     print(f"\ntrajectory K={K} ragged={ragged} {kv}: largest |logp(search) - logp(reference)| {worst:.3e}, so far {SEEN[kv]:.3e} "
@@ -204,7 +204,7 @@ def test_a_beam_reads_its_parents_cache(kv):
 @pytest.mark.parametrize("kv", ["bf16", "fp8"])
 @pytest.mark.parametrize("ragged", [False, True], ids=["uniform", "ragged"])
 def test_one_beam_is_greedy(ragged, kv):
-    mt = _model()
+    mt = _search_model()
     prior, lens = _prompts(ragged)
     Ps = lens or [P] * prior.shape[0]
     toks, scores = mt.generate_beam(prior, LENGTH, 1, prior_lengths=lens, kv_cache=kv)
@@ -221,7 +221,7 @@ def test_one_beam_is_greedy(ragged, kv):
 
 @pytest.mark.parametrize("kv", ["bf16", "fp8"])
 def test_ragged_batch_equals_one_prompt_per_call(kv):
-    mt = _model()
+    mt = _search_model()
     prior, lens = _prompts(True)
     toks, scores = (t.cpu().numpy() for t in mt.generate_beam(prior, LENGTH, 4, prior_lengths=lens, kv_cache=kv))
     for b, n in enumerate(lens):
@@ -232,7 +232,7 @@ def test_ragged_batch_equals_one_prompt_per_call(kv):
 @pytest.mark.parametrize("length", [12, 11, 6])
 @pytest.mark.parametrize("kv", ["bf16", "fp8"])
 def test_graph_replay_equals_the_eager_run(kv, length):
-    mt = _model()
+    mt = _search_model()
     prior, lens = _prompts(True)
     for stochastic in (False, True):
         a = _search(mt, prior, lens, length, 4, kv, use_graph=True, stochastic=stochastic, seed=5)
@@ -242,7 +242,7 @@ def test_graph_replay_equals_the_eager_run(kv, length):
 
 
 def test_stochastic_search():
-    mt = _model()
+    mt = _search_model()
     prior, lens = _prompts(False)
     B, K = prior.shape[0], 4
     a = _search(mt, prior, lens, LENGTH, K, "bf16", stochastic=True, seed=11)
@@ -265,7 +265,7 @@ def test_grammar_is_obeyed():
     from musicgeneration_amd.REMI import REMI_EventSeq as Codec
     from musicgeneration_amd.train import vocab_of
     Vr = vocab_of("remi")
-    mt = _model(V=Vr, nl=1, viable=0, fc_scale=8.0)
+    mt = _search_model(V=Vr, nl=1, viable=0, fc_scale=8.0)
     table = Codec.next_token_table()
     bar = Codec.feat_ranges()["bar"][0]
     prior = torch.full((2, 1), bar, dtype=torch.long, device=DEV)

@@ -22,6 +22,8 @@ import pytest
 import torch
 
 import beam_ref
+import kernel_checks as KC
+from kernel_checks import nothing_more_after_a_gpu_error  # noqa: F401 (the fixture is used by name)
 
 pytestmark = pytest.mark.gpu
 
@@ -38,11 +40,6 @@ KINDS = ("gauss4", "shifted", "dominant")
 TEMPS = (0.7, 1.0, 1.5)
 STATES = ("first", "live", "dead")
 OUT_LD = 24
-
-
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
 
 
 def make_case(shape, kind, state, seed, identical=False):
@@ -90,7 +87,7 @@ def run_select(shape, logits, score, tok, t, temperature, allow=None, stochastic
              pos=torch.from_numpy(np.repeat(t, K)).to(DEV),
              ht=torch.full((B * K, OUT_LD), POISON, dtype=torch.int32, device=DEV),
              hp=torch.full((B * K, OUT_LD), POISON, dtype=torch.int32, device=DEV))
-    _ops().beam_select(d["logits"], V, d["score"], d["tok"], d["parent"], d["pos"], d["ht"], d["hp"], temperature=temperature,
+    KC.ops().beam_select(d["logits"], V, d["score"], d["tok"], d["parent"], d["pos"], d["ht"], d["hp"], temperature=temperature,
                        allow_table=None if allow is None else torch.from_numpy(allow.view(np.int32)).to(DEV),
                        stochastic=stochastic, seed=seed)
     torch.cuda.synchronize()
@@ -254,7 +251,7 @@ def test_reorder(shape, row_bytes):
         for kind in ("identity", "all-to-one", "permutation", "random"):
             parent = _parents(kind, R, K, rng)
             dst = poison.clone().view(view)
-            _ops().kv_beam_reorder(dst, src, torch.from_numpy(parent).to(DEV), torch.from_numpy(n.astype(np.int32)).to(DEV), K)
+            KC.ops().kv_beam_reorder(dst, src, torch.from_numpy(parent).to(DEV), torch.from_numpy(n.astype(np.int32)).to(DEV), K)
             got = dst.view(width).cpu().numpy()
             want = beam_ref.reorder(poison.cpu().numpy(), src_np, parent, n, K)
             assert np.array_equal(got, want), (shape, row_bytes, kind, n.tolist())
@@ -266,7 +263,7 @@ def test_reorder_refuses_one_buffer():
     x = torch.zeros(4, 1, 8, 64, dtype=BF, device=DEV)
     z = torch.zeros(4, dtype=torch.int32, device=DEV)
     with pytest.raises(MgxError, match="different buffers"):
-        _ops().kv_beam_reorder(x, x, z, z, 2)
+        KC.ops().kv_beam_reorder(x, x, z, z, 2)
 
 
 # =====================================================================================================================
@@ -281,7 +278,7 @@ def test_backtrack(R, K, steps):
     hp = rng.integers(0, K, (R, out_ld)).astype(np.int32)
     out = np.full((R, out_ld), POISON, dtype=np.int32)
     got = torch.from_numpy(out).to(DEV)
-    _ops().beam_backtrack(torch.from_numpy(ht).to(DEV), torch.from_numpy(hp).to(DEV), torch.from_numpy(c0).to(DEV), got, K, steps)
+    KC.ops().beam_backtrack(torch.from_numpy(ht).to(DEV), torch.from_numpy(hp).to(DEV), torch.from_numpy(c0).to(DEV), got, K, steps)
     want = beam_ref.backtrack(ht, hp, c0, steps, K, out)
     assert np.array_equal(got.cpu().numpy(), want)
     assert (want != POISON).sum() == R * steps                                      # the prompt columns are the caller's

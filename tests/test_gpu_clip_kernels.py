@@ -23,6 +23,8 @@ import pytest
 import torch
 
 import clip_ref
+import kernel_checks as KC
+from kernel_checks import bits, nothing_more_after_a_gpu_error  # noqa: F401 (the fixture is used by name)
 from oracle import train_ref as T
 
 pytestmark = pytest.mark.gpu
@@ -32,47 +34,23 @@ BF = torch.bfloat16
 F64 = torch.float64
 PARTS = 1024
 SIZES = (1, 3, 4, 5, 1023, 1025, 4 * 256 * 1024 + 4, 2 ** 21 + 3)
-C_ADAM = 16.0                                       # tests/test_gpu_rowwise_kernels.py: C["ADAM"]
 GUARD = 8                                           # elements on each side of every buffer
 GS = 0.37                                           # a gradient scale that is no power of two
-
-
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
-
-
-def _raw():
-    from musicgeneration_amd import _lib
-    return _lib.load(), _lib.ptr, _lib.stream_ptr
+SEEN = {}
 
 
 def blocks_of(n):
     return min(max((n // 4 + 255) // 256, 1), PARTS)
 
 
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int16) if t.dtype == BF else t.view(torch.int64) if t.dtype == F64 else t
-
-
-class Guarded:
+def guarded(data, dtype=None):
     """a device buffer of n elements with GUARD sentinel elements before and after it; .t is the view the kernels get (16-byte
-    aligned for fp32 and fp64, 8-byte for bf16: GUARD elements are a multiple of 16 bytes)"""
-
-    def __init__(self, data, dtype=None):
-        data = torch.from_numpy(data.copy()) if isinstance(data, np.ndarray) else torch.as_tensor(data)
-        dtype = dtype or data.dtype
-        n = data.numel()
-        self.full = torch.full((n + 2 * GUARD,), -12345.0 if dtype.is_floating_point else -12345, dtype=dtype, device=DEV)
-        self.t = self.full[GUARD:GUARD + n]
-        self.t.copy_(data.to(dtype))
-        assert self.t.data_ptr() % (16 if dtype != BF else 8) == 0
-        self.front, self.back = bits(self.full[:GUARD]).clone(), bits(self.full[GUARD + n:]).clone()
-
-    def guards_intact(self):
-        n = self.t.numel()
-        return bits(self.full[:GUARD]).equal(self.front) and bits(self.full[GUARD + n:]).equal(self.back)
+    aligned for fp32 and fp64, 8-byte for bf16: GUARD elements are a multiple of 16 bytes), .buf the whole allocation"""
+    data = torch.from_numpy(data.copy()) if isinstance(data, np.ndarray) else torch.as_tensor(data)
+    data = data.to(dtype or data.dtype)
+    b = KC.Banded(data, GUARD * data.element_size(), -12345.0 if data.dtype.is_floating_point else -12345)
+    assert b.t.data_ptr() % (16 if data.dtype != BF else 8) == 0
+    return b
 
 
 class Clip:
@@ -88,12 +66,12 @@ class Clip:
 
     def run(self, g, gscale, max_norm):
         n = g.numel()
-        _ops().grad_norm(g, gscale, max_norm, self.ws, self.state)
+        KC.ops().grad_norm(g, gscale, max_norm, self.ws, self.state)
         ws = self.ws_full.cpu()
         b = blocks_of(n)
         assert (ws[b:] == -777.0).all(), f"n={n}: workspace written beyond its {b} blocks"
         assert (self.st_full[4:].cpu() == 0x5A5A5A5A5A5A5A5A).all(), "memory behind the state written"
-        return _ops().read_clip_state(self.state)
+        return KC.ops().read_clip_state(self.state)
 
     def state_bytes(self):
         return self.state.cpu().numpy().tobytes()
@@ -125,13 +103,13 @@ def test_norm_against_fp64_for_ordinary_huge_and_tiny_gradients(n):
         g = gaussian(n) * np.float32(factor)
         ref = ref_norm(n, 0, factor)
         for gscale in (1.0, -0.5):
-            gd = Guarded(g)
+            gd = guarded(g)
             st = clip.run(gd.t, gscale, math.inf)
             want = ref * abs(gscale)
             err = abs(st["norm"] - want)
             print(f"[NORM] n={n} factor={factor:g} gscale={gscale}: got {st['norm']!r} ref {want!r} err/ref {err / want:.3e} bound {n * 2.0 ** -52:.3e}")
             assert err <= n * 2.0 ** -52 * want
-            assert gd.guards_intact() and bits(gd.t).equal(bits(torch.from_numpy(g)))
+            assert gd.bands_intact() and bits(gd.t).equal(bits(torch.from_numpy(g)))
             # max_norm = inf: measure only -- scale is gscale bit for bit, nothing is clipped or skipped
             assert clip.scale_bytes() == np.float32(gscale).tobytes() and st["skipped_last"] == 0 and st["clipped"] == 0 and st["skipped"] == 0
 
@@ -139,7 +117,7 @@ def test_norm_against_fp64_for_ordinary_huge_and_tiny_gradients(n):
 @pytest.mark.parametrize("n", SIZES)
 def test_all_zero_gradients_have_norm_zero_and_no_nan(n):
     clip = Clip()
-    gd = Guarded(torch.zeros(n))
+    gd = guarded(torch.zeros(n))
     for max_norm in (math.inf, 1.0):
         st = clip.run(gd.t, GS, max_norm)
         assert st["norm"] == 0.0 and clip.scale_bytes() == np.float32(GS).tobytes()
@@ -174,7 +152,7 @@ def test_scale_is_the_references_fp32_bit_for_bit_and_the_counter_counts_the_cli
     g, cases = scale_cases(n)
     assert [r["clipped"] for _, r in cases][0] and not cases[2][1]["clipped"] and not cases[3][1]["clipped"]
     clip = Clip()
-    gd = Guarded(g)
+    gd = guarded(g)
     clipped = 0
     for max_norm, ref in list(cases) + list(cases)[::-1]:
         st = clip.run(gd.t, GS, max_norm)
@@ -184,12 +162,12 @@ def test_scale_is_the_references_fp32_bit_for_bit_and_the_counter_counts_the_cli
         assert clip.scale_bytes() == ref["scale"].tobytes()
         assert abs(st["norm"] - ref["norm"]) <= n * 2.0 ** -52 * ref["norm"]
         assert st["clipped"] == clipped and st["skipped"] == 0 and st["skipped_last"] == 0
-    assert gd.guards_intact()
+    assert gd.bands_intact()
 
 
 def test_two_runs_give_the_same_state_bytes():
     n = 2 ** 21 + 3
-    g = Guarded(gaussian(n))
+    g = guarded(gaussian(n))
     a, b = Clip(), Clip()
     a.run(g.t, GS, 1.0)
     b.run(g.t, GS, 1.0)
@@ -203,20 +181,20 @@ def test_two_runs_give_the_same_state_bytes():
 class AdamState:
     def __init__(self, n, seed, with_shadow):
         gen = torch.Generator().manual_seed(seed)
-        self.p = Guarded(torch.randn(n, generator=gen))
-        self.m = Guarded(0.1 * torch.randn(n, generator=gen))
-        self.v = Guarded(torch.rand(n, generator=gen))
-        self.shadow = Guarded(self.p.t.cpu().to(BF)) if with_shadow else None
+        self.p = guarded(torch.randn(n, generator=gen))
+        self.m = guarded(0.1 * torch.randn(n, generator=gen))
+        self.v = guarded(torch.rand(n, generator=gen))
+        self.shadow = guarded(self.p.t.cpu().to(BF)) if with_shadow else None
         self.gen = gen
 
     def tensors(self):
         return [self.p, self.m, self.v] + ([self.shadow] if self.shadow else [])
 
     def snapshot(self):
-        return [bits(x.full).clone() for x in self.tensors()]
+        return [bits(x.buf).clone() for x in self.tensors()]
 
-    def guards_intact(self):
-        return all(x.guards_intact() for x in self.tensors())
+    def bands_intact(self):
+        return all(x.bands_intact() for x in self.tensors())
 
 
 HYPER = (1e-3, 0.9, 0.98, 1e-9)
@@ -226,44 +204,34 @@ HYPER = (1e-3, 0.9, 0.98, 1e-9)
 @pytest.mark.parametrize("with_shadow", (True, False))
 def test_without_a_clip_the_update_is_adam_steps_bit_for_bit(n, with_shadow):
     """max_norm = inf: scale == gscale, and the kernel is the same per-element code"""
-    ops = _ops()
+    ops = KC.ops()
     a, b = AdamState(n, n, with_shadow), AdamState(n, n, with_shadow)
     clip = Clip()
     for step in (1, 2, 1000):
-        g = Guarded(torch.randn(n, generator=a.gen))
+        g = guarded(torch.randn(n, generator=a.gen))
         st = clip.run(g.t, GS, math.inf)
         assert st["skipped_last"] == 0
         ops.adam_step_clipped(a.p.t, g.t, a.m.t, a.v.t, a.shadow.t if with_shadow else None, *HYPER, step, clip.state)
         ops.adam_step(b.p.t, g.t, b.m.t, b.v.t, b.shadow.t if with_shadow else None, *HYPER, step, GS)
         for x, y, name in zip(a.snapshot(), b.snapshot(), "pmvs"):
             assert x.equal(y), f"n={n} step={step}: {name} differs from mgx_adam_step"
-        assert a.guards_intact() and g.guards_intact()
+        assert a.bands_intact() and g.bands_intact()
 
 
 def check_f32(got, ref, F, case):
-    """the check of tests/test_gpu_rowwise_kernels.py: |got - ref| <= C_ADAM * F, element by element"""
     assert got.dtype == torch.float32
-    got = got.detach().cpu().to(F64).reshape(ref.shape)
-    assert torch.isfinite(got).all(), (case, "non-finite output")
-    F = torch.as_tensor(F, dtype=F64).expand(ref.shape)
-    assert (F > 0).all()
-    ratio = (got - ref).abs() / F
-    worst = ratio.max().item()
-    print(f"[ADAM] {case}: ratio {worst:.3f}")
-    if worst > C_ADAM:
-        i = int(ratio.argmax())
-        raise AssertionError(f"ADAM {case}: element {i} got {got[i].item()!r} ref {ref[i].item()!r} F {F[i].item():.3e} ratio {worst:.2f} > {C_ADAM}")
+    KC.check_floor("ADAM", got, ref, F, case, C=KC.C_ADAM, seen=SEEN)
 
 
 @pytest.mark.parametrize("n", (1031, 2 ** 21 + 3))
 @pytest.mark.parametrize("with_shadow", (True, False))
 def test_clipped_update_against_fp64_with_the_state_carried_across_steps(n, with_shadow):
-    ops = _ops()
+    ops = KC.ops()
     g_np, cases = scale_cases(n)
     max_norm, ref = cases[0]                                    # a quarter of the norm: clipped, scale decidable
     a = AdamState(n, n + 1, with_shadow)
     clip = Clip()
-    g = Guarded(g_np)
+    g = guarded(g_np)
     grad = torch.from_numpy(g_np.copy())
     for k, step in enumerate((1, 2, 3)):
         st = clip.run(g.t, GS, max_norm)
@@ -279,7 +247,7 @@ def test_clipped_update_against_fp64_with_the_state_carried_across_steps(n, with
         check_f32(a.v.t, r[2], F[2], case + " v")
         if with_shadow:
             assert bits(a.shadow.t).equal(bits(a.p.t.to(BF))), case + ": shadow is not the bf16 rounding of p"
-        assert a.guards_intact() and g.guards_intact()
+        assert a.bands_intact() and g.bands_intact()
 
 
 # =====================================================================================================================
@@ -287,7 +255,7 @@ def test_clipped_update_against_fp64_with_the_state_carried_across_steps(n, with
 # =====================================================================================================================
 @pytest.mark.parametrize("n", (7, 1027, 2 ** 21 + 3))
 def test_a_non_finite_gradient_skips_the_step_and_the_next_finite_one_updates(n):
-    ops = _ops()
+    ops = KC.ops()
     a = AdamState(n, n + 2, True)
     clip = Clip()
     clean = gaussian(n)
@@ -297,7 +265,7 @@ def test_a_non_finite_gradient_skips_the_step_and_the_next_finite_one_updates(n)
         for bad in (math.inf, -math.inf, math.nan):
             g_np = clean.copy()
             g_np[where] = bad
-            g = Guarded(g_np)
+            g = guarded(g_np)
             before = a.snapshot()
             st = clip.run(g.t, GS, 1.0)
             skipped += 1
@@ -306,9 +274,9 @@ def test_a_non_finite_gradient_skips_the_step_and_the_next_finite_one_updates(n)
             ops.adam_step_clipped(a.p.t, g.t, a.m.t, a.v.t, a.shadow.t, *HYPER, step, clip.state)
             for x, y, name in zip(a.snapshot(), before, "pmvs"):
                 assert x.equal(y), f"n={n} where={where} bad={bad}: {name} changed in a skipped step"
-            assert g.guards_intact()
+            assert g.bands_intact()
         # the next call with finite gradients clears the flag and updates
-        g = Guarded(clean)
+        g = guarded(clean)
         before = a.snapshot()
         st = clip.run(g.t, GS, 1.0)
         step += 1
@@ -317,20 +285,20 @@ def test_a_non_finite_gradient_skips_the_step_and_the_next_finite_one_updates(n)
         moved = [not x.equal(y) for x, y in zip(a.snapshot()[:3], before[:3])]
         assert all(moved), moved                                  # p, m and v; the shadow follows p
         assert bits(a.shadow.t).equal(bits(a.p.t.to(BF)))
-        assert a.guards_intact() and torch.isfinite(a.p.t).all()
+        assert a.bands_intact() and torch.isfinite(a.p.t).all()
 
 
 # =====================================================================================================================
 # 5. argument errors: the documented status, and no launch (the state keeps its bytes)
 # =====================================================================================================================
 def test_argument_errors_return_the_documented_status_without_launching():
-    lib, ptr, stream_ptr = _raw()
+    lib, _, ptr, stream_ptr = KC.raw()
     n = 1031
-    g, p, m, v = (Guarded(torch.randn(n)) for _ in range(4))
+    g, p, m, v = (guarded(torch.randn(n)) for _ in range(4))
     clip = Clip()
     clip.run(g.t, GS, 1.0)
     before_state, before_ws = clip.st_full.cpu().clone(), bits(clip.ws_full).clone()
-    before = [bits(x.full).clone() for x in (p, m, v)]
+    before = [bits(x.buf).clone() for x in (p, m, v)]
     G, W, S = ptr(g.t), ptr(clip.ws), ptr(clip.state)
     fl = ctypes.c_float
     NULL, SHAPE = -2, -1
@@ -360,8 +328,8 @@ def test_argument_errors_return_the_documented_status_without_launching():
     torch.cuda.synchronize()
     assert clip.st_full.cpu().equal(before_state) and bits(clip.ws_full).equal(before_ws)
     for x, y in zip((p, m, v), before):
-        assert bits(x.full).equal(y)
-    ops = _ops()
+        assert bits(x.buf).equal(y)
+    ops = KC.ops()
     with pytest.raises(ValueError):
         ops.grad_norm(g.t, 1.0, 1.0, clip.ws[:8], clip.state)                # workspace too small
     with pytest.raises(ValueError):

@@ -15,16 +15,18 @@ import pytest
 import torch
 
 import clip_ref
+import kernel_checks as KC
+from kernel_checks import bits
 from oracle import train_ref as T
 
 pytestmark = pytest.mark.gpu
 
 V, D, L, B = 90, 64, 32, 2
-C_ADAM = 16.0                                       # tests/test_gpu_rowwise_kernels.py: C["ADAM"]
+SEEN = {}
 F64 = torch.float64
 
 
-def _model(seed=0):
+def _net(seed=0):
     from musicgeneration_amd.network import MusicTransformer
     torch.manual_seed(seed)
     return MusicTransformer(embedding_dim=D, vocab_size=V, num_layer=1, max_seq=L, dropout=0.0).cuda().train()
@@ -44,27 +46,15 @@ def _backward(mt, seed):
     return loss.item()
 
 
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int16)
-
-
 def check_f32(got, ref, F, case):
-    """|got - ref| <= C_ADAM * F element by element (the check of tests/test_gpu_rowwise_kernels.py); F = 0 demands equality"""
+    """|got - ref| <= C_ADAM * F element by element; F = 0 demands equality"""
     assert got.dtype == torch.float32
-    got = got.detach().cpu().to(F64)
-    assert torch.isfinite(got).all(), (case, "non-finite output")
-    err, F = (got - ref).abs(), torch.as_tensor(F, dtype=F64)
-    bad = err > C_ADAM * F
-    print(f"[ADAM] {case}: largest ratio {(err[F > 0] / F[F > 0]).max().item():.3f}, {int((F == 0).sum())} elements with a zero floor")
-    if bad.any():
-        i = int(torch.nonzero(bad)[0])
-        raise AssertionError(f"{case}: element {i} got {got[i].item()!r} ref {ref[i].item()!r} F {F[i].item():.3e}")
+    KC.check_bound("ADAM", got, ref, KC.C_ADAM * torch.as_tensor(F, dtype=F64), case, seen=SEEN)
 
 
 def test_clipped_step_is_the_fp64_references_clipped_adam_on_the_flat_buffers():
     from musicgeneration_amd.optim import FusedAdam
-    mt = _model()
+    mt = _net()
     st = mt.store()
     _backward(mt, 1)
     grad = st.grad.detach().cpu()
@@ -101,7 +91,7 @@ def test_clipped_step_is_the_fp64_references_clipped_adam_on_the_flat_buffers():
 def _three_steps(max_norm):
     from musicgeneration_amd.criterion import CustomSchedule
     from musicgeneration_amd.optim import FusedAdam
-    mt = _model(seed=3)
+    mt = _net(seed=3)
     opt = FusedAdam(mt, lr=0.0, betas=(0.9, 0.98), eps=1e-9, max_norm=max_norm)
     sch = CustomSchedule(D, warmup_steps=20, optimizer=opt)
     opt.zero_grad()
@@ -130,7 +120,7 @@ def test_infinite_max_norm_trains_bit_for_bit_like_no_clipping():
 
 def test_a_poisoned_gradient_skips_the_step_and_training_recovers():
     from musicgeneration_amd.optim import FusedAdam
-    mt = _model(seed=4)
+    mt = _net(seed=4)
     st = mt.store()
     opt = FusedAdam(mt, lr=1e-3, betas=(0.9, 0.98), eps=1e-9, max_norm=1.0)
     opt.zero_grad()
@@ -159,7 +149,7 @@ def test_a_poisoned_gradient_skips_the_step_and_training_recovers():
 def test_max_norm_none_allocates_nothing_and_never_measures(monkeypatch):
     from musicgeneration_amd import ops
     from musicgeneration_amd.optim import FusedAdam
-    mt = _model(seed=5)
+    mt = _net(seed=5)
     st = mt.store()
     torch.cuda.synchronize()
     base = torch.cuda.memory_allocated()

@@ -5,27 +5,14 @@ import numpy as np
 import pytest
 import torch
 
+from decode_fixtures import tame_model
+
 pytestmark = pytest.mark.gpu
-
-
-def _model(d=128, nl=2, L=96, V=337, seed=0):
-    from musicgeneration_amd.network import MusicTransformer
-    from oracle import ref_cpu as R
-    p0 = R.init_params(V, d, nl, L, seed=seed)
-    # tame the random-init logits (N(0,1)*sqrt(d) embeddings give near one-hot attention, the worst case for
-    # bf16): decode-vs-forward parity is about the kernels, not about that fixture
-    p0["Decoder.embedding.weight"] = p0["Decoder.embedding.weight"] * 0.1
-    for k in list(p0):
-        if k.endswith("rga.E"):
-            p0[k] = p0[k] * 0.2
-    mt = MusicTransformer(embedding_dim=d, vocab_size=V, num_layer=nl, max_seq=L, dropout=0.0)
-    mt.load_state_dict(p0)
-    return mt.cuda().eval(), p0
 
 
 def test_cached_decode_matches_causal_forward_and_oracle():
     from oracle import ref_cpu as R
-    mt, p0 = _model()
+    mt, p0 = tame_model()
     V, L, B = 337, 96, 3
     g = torch.Generator().manual_seed(11)
     x = torch.randint(0, V - 1, (B, L), generator=g)
@@ -49,7 +36,7 @@ def test_split_key_cached_decode_matches_the_oracle_at_length_2048(d, nl, B):
     from oracle import ref_cpu as R
     V, L = 337, 2048
     assert ops.rel_attn_decode_splits(B, L, d) > 1
-    mt, p0 = _model(d=d, nl=nl, L=L, V=V, seed=21)
+    mt, p0 = tame_model(d=d, nl=nl, L=L, V=V, seed=21)
     g = torch.Generator().manual_seed(23)
     x = torch.randint(0, V - 1, (B, L), generator=g)
     toks, probs = mt.generate_cached(x.cuda(), 0, return_probs=True)
@@ -102,7 +89,7 @@ def test_sampler_distribution_and_filters():
 
 
 def test_graph_replay_equals_eager_decode():
-    mt, _ = _model(L=64)
+    mt, _ = tame_model(L=64)
     prior = torch.tensor([[24, 28, 31], [5, 6, 7]], device="cuda")
     a = mt.generate_cached(prior, 40, top_p=0.9, seed=123, use_graph=True).cpu()
     b = mt.generate_cached(prior, 40, top_p=0.9, seed=123, use_graph=False).cpu()
@@ -299,7 +286,7 @@ def test_cfg5_sized_cached_decode_matches_training_forward():
     """BASELINE cfg5's size (seq_len 8192, batch 32, cfg2-shaped model): the KV-cache decode path, teacher-forced over the
     whole sequence, gives the same next-token distributions as the training forward on the same prefix -- checked at
     positions 1, 4095 and 8191 (cache of 1, 4096 and 8192 rows) for every batch row."""
-    mt, _ = _model(d=512, nl=6, L=8192, V=337, seed=5)
+    mt, _ = tame_model(d=512, nl=6, L=8192, V=337, seed=5)
     V, L, B = 337, 8192, 32
     g = torch.Generator().manual_seed(55)
     x = torch.randint(0, V - 1, (B, L), generator=g).cuda()
@@ -380,7 +367,7 @@ def test_gru_train_packed_lengths_matches_torch_packed_gru():
 def test_batched_prefill_fills_the_same_caches_as_token_by_token(P):
     """A prompt goes through the full-sequence kernels in one pass (prefill='batched'): every layer's K/V cache rows and
     the first sampled distribution must agree with teacher-forcing the prompt one decode step at a time."""
-    mt, _ = _model(L=128)
+    mt, _ = tame_model(L=128)
     V, B = 337, 2
     g = torch.Generator().manual_seed(5)
     x = torch.randint(0, V - 1, (B, P), generator=g).cuda()
@@ -431,7 +418,7 @@ def test_cfg5_sized_graph_replay_equals_eager_greedy():
     (top_k = 1) continuation of a 7,900-token prompt for 64 tokens by graph replay equals the eager launches token for token
     -- the graph path at size is asserted, not only shape-checked.  (The prompt is prefilled in one batched pass both
     times, so the two runs start from identical caches.)"""
-    mt, _ = _model(d=512, nl=6, L=8192, V=337, seed=5)
+    mt, _ = tame_model(d=512, nl=6, L=8192, V=337, seed=5)
     V, B, P, n = 337, 32, 7900, 64
     g = torch.Generator().manual_seed(56)
     prompt = torch.randint(0, V - 1, (B, P), generator=g).cuda()
@@ -591,7 +578,7 @@ def test_decode_row_groups_on_streams_give_the_same_tokens(use_graph):
     never interact and the sampler draws by (seed, step, GLOBAL row), so every grouping returns the same tokens -- bitwise
     below the split-key length (the number of key splits depends on the sub-batch size, the per-row arithmetic otherwise
     not).  A ragged grouping (B=7 in 3 groups) is part of the sweep."""
-    mt, _ = _model(d=128, nl=2, L=160, V=337, seed=31)
+    mt, _ = tame_model(d=128, nl=2, L=160, V=337, seed=31)
     g = torch.Generator().manual_seed(5)
     for B, groups in ((8, (2, 4)), (7, (3,))):
         prior = torch.randint(0, 336, (B, 3), generator=g).cuda()

@@ -27,6 +27,8 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks as KC
+from kernel_checks import nothing_more_after_a_gpu_error  # noqa: F401 (the fixture is used by name)
 from oracle import decode_ref as D
 
 pytestmark = pytest.mark.gpu
@@ -38,11 +40,6 @@ NAN16 = 0x7FC0                                     # a bf16 NaN; as a byte patte
 C_ATTN = 16.0
 R_PROB = 2.0 ** -18
 SEEN = {"c": 0.0, "r": 0.0}                        # the largest ratios this process has seen, printed by the tests
-
-
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
 
 
 # =====================================================================================================================
@@ -112,7 +109,7 @@ class AttnData:
             self.kc, self.vc = K.to(BF), V.to(BF)
             self.cpu = [self.kc.cpu(), None, self.vc.cpu(), None]
         self.qkv_cpu, self.E_cpu = self.qkv.cpu(), self.E.cpu()
-        ops = _ops()
+        ops = KC.ops()
         assert ops.rel_attn_decode_splits(B, Lmax, d) == self.nsplit, (cfg, ops.rel_attn_decode_splits(B, Lmax, d))
         self.ws = ops.rel_attn_decode_workspace(B, Lmax, d, DEV)
         assert (self.ws is None) == (self.nsplit == 1)
@@ -140,7 +137,7 @@ class AttnData:
 
     def run(self, ts, ragged):
         """one call with every poison in place; returns ctx on the CPU after checking what the call wrote and left alone"""
-        ops = _ops()
+        ops = KC.ops()
         B, h, Lmax, d, M = self.B, self.h, self.Lmax, self.d, self.M
         t_rows = torch.tensor(ts if ragged else [ts] * B, device=DEV)
         stale = (torch.arange(Lmax, device=DEV)[None] >= t_rows[:, None])[:, None]             # [B, 1, Lmax]: rows >= t
@@ -287,7 +284,7 @@ def _randw(N, K, g):
 
 
 def _weight(w, frag):
-    ops = _ops()
+    ops = KC.ops()
     return ops.FragWeight(w.to(DEV)) if frag else w.to(DEV)
 
 
@@ -308,7 +305,7 @@ def check_rows(z, ref, what):
 
 
 def test_skinny_projection_against_fp64():
-    ops = _ops()
+    ops = KC.ops()
     g = torch.Generator().manual_seed(11)
     for M, N, K, act, has_bias, frag in shapes(KS):
         a, w = torch.randn(M, K, generator=g).to(BF), _randw(N, K, g)
@@ -337,7 +334,7 @@ def _coded_weight(N, K):
 @pytest.mark.parametrize("K", KS)
 def test_fragment_order_is_exact_on_unit_vectors(K):
     """row m of A is the unit vector e_k(m), W a small integer code of (n mod 16, k mod 16): C[m][n] = W[n][k(m)] exactly"""
-    ops = _ops()
+    ops = KC.ops()
     M = 32
     ks = _unit_rows(M, K)
     kq = K // 4
@@ -387,7 +384,7 @@ def test_layernorm_projection_against_fp64_with_rows_far_from_zero():
     """Z = LayerNorm(X + RES) and C = act(Z W^T + b): Z against the centred fp64 form, C against the fp64 product of the
     kernel's own Z (checked first, so no input error term is left).  On the rows far from zero Z also agrees with the
     training LayerNorm kernel within one bf16 ulp."""
-    ops = _ops()
+    ops = KC.ops()
     g = torch.Generator().manual_seed(12)
     seen = set()
     for M, N, K, act, has_bias, frag in shapes(KS[:-1]):
@@ -419,7 +416,7 @@ def test_layernorm_projection_against_fp64_with_rows_far_from_zero():
 
 
 def test_layernorm_projection_refuses_what_it_cannot_hold():
-    ops = _ops()
+    ops = KC.ops()
     from musicgeneration_amd._lib import MgxError
     g = torch.Generator().manual_seed(13)
     for M, K in ((33, 512), (4, 96), (4, 1088)):
@@ -444,7 +441,7 @@ def _embed_inputs(M, K, V, P, g):
 
 def test_fused_embedding_projection_against_fp64():
     """H = table[tok] sqrt(K) + pe[pos] and C = H W^T + b, shared and per-row positions, both weight layouts"""
-    ops = _ops()
+    ops = KC.ops()
     g = torch.Generator().manual_seed(14)
     V, P = 53, 41
     for i, (M, N, K, _, has_bias, frag) in enumerate(shapes(KS)):
@@ -464,7 +461,7 @@ def test_fused_embedding_projection_against_fp64():
 
 
 def test_decode_embed_against_fp64():
-    ops = _ops()
+    ops = KC.ops()
     g = torch.Generator().manual_seed(15)
     V, P = 53, 41
     for B in (1, 5, 37):
@@ -584,7 +581,7 @@ def sampler_reference(logits, V, temperature, top_k, top_p, seed, steps, row0, p
 
 def run_sampler(entry, logits, V, temperature, top_k, top_p, seed, pos, prev, table, row0=0, advance=True, out_ld=64):
     """one call on the device -> (tokens, out_tokens, probs_out, pos after the call), all on the CPU"""
-    ops = _ops()
+    ops = KC.ops()
     from musicgeneration_amd import _lib
     B = logits.shape[0]
     lg, pos_d, nt = logits.to(DEV), pos.to(DEV), prev.clone().to(DEV)
@@ -669,7 +666,7 @@ def test_sampler_draw_on_an_exact_cdf_boundary():
     no band applies.  For u >= 0.5 the sampler's u is a multiple of 2^-24 and can sit exactly ON a CDF boundary k 2^-10: the
     draw is then the id whose inclusive CDF equals u (the FIRST id that reaches it), not the next one.  The (step, row)
     pairs that give such a u are found with the hash's integer twin."""
-    ops = _ops()
+    ops = KC.ops()
     V, B, seed = 1024, 16, _case_seed(2000)
     steps = np.arange(400000)
     pos, want = [], []

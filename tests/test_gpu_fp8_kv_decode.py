@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from decode_fixtures import one, tame_model
 from oracle.decode_ref import dequant, quant_twin
 
 pytestmark = pytest.mark.gpu
@@ -16,24 +17,6 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 BF = torch.bfloat16
 SENTINEL = 0xA5
-
-
-def _model(d=128, nl=2, L=96, V=337, seed=0):
-    # the fixture of test_gpu_decode.py: random init with tamed embeddings and relative terms
-    from musicgeneration_amd.network import MusicTransformer
-    from oracle import ref_cpu as R
-    p0 = R.init_params(V, d, nl, L, seed=seed)
-    p0["Decoder.embedding.weight"] = p0["Decoder.embedding.weight"] * 0.1
-    for k in list(p0):
-        if k.endswith("rga.E"):
-            p0[k] = p0[k] * 0.2
-    mt = MusicTransformer(embedding_dim=d, vocab_size=V, num_layer=nl, max_seq=L, dropout=0.0)
-    mt.load_state_dict(p0)
-    return mt.cuda().eval(), p0
-
-
-def _one(t):
-    return torch.tensor([int(t)], dtype=torch.int32, device=DEV)
 
 
 def _special_rows(x, g):
@@ -151,7 +134,7 @@ def test_fp8_attention_is_attention_over_the_dequantized_rows(Lmax, B):
         assert (err <= 2 ** -8 * ref.abs() + 2e-3 * ref.abs().max()).all(), (b, t, err.max().item())
 
     for t in (0, 97, Lmax - 1):
-        ctx, kc, ks, vc, vs = run(_one(t), False)
+        ctx, kc, ks, vc, vs = run(one(t), False)
         for b in range(B):
             check_row(b, t, ctx, kc, ks, vc, vs)
     pos = torch.randint(0, Lmax, (B,), generator=g, dtype=torch.int32)
@@ -159,7 +142,7 @@ def test_fp8_attention_is_attention_over_the_dequantized_rows(Lmax, B):
     ctx, kc, ks, vc, vs = run(pos.to(DEV), True)
     for b in range(B):
         check_row(b, int(pos[b]), ctx, kc, ks, vc, vs)
-        c1, k1, s1, v1, t1 = run(_one(pos[b]), False)
+        c1, k1, s1, v1, t1 = run(one(pos[b]), False)
         assert torch.equal(ctx[b], c1[b]) and torch.equal(kc[b], k1[b]) and torch.equal(ks[b], s1[b]), b
         assert torch.equal(vc[b], v1[b]) and torch.equal(vs[b], t1[b]), b
 
@@ -197,7 +180,7 @@ def test_fp8_cache_decode_matches_an_fp8_emulating_fp32_model(d, nl, L, B):
     V = 337
     if L >= 1024:
         assert ops.rel_attn_decode_splits(B, L, d) > 1
-    mt, p0 = _model(d=d, nl=nl, L=L, V=V, seed=21)
+    mt, p0 = tame_model(d=d, nl=nl, L=L, V=V, seed=21)
     g = torch.Generator().manual_seed(23)
     x = torch.randint(0, V - 1, (B, L), generator=g)
     toks, probs = mt.generate_cached(x.cuda(), 0, return_probs=True, kv_cache="fp8")
@@ -230,7 +213,7 @@ def test_batched_and_token_prefill_fill_the_same_fp8_caches():
     test_gpu_decode.py): the dequantized caches agree to that rounding, plus one fp8 step (2^-3 of the element) where it
     moves an element across an fp8 rounding boundary.  Measured: 1.5 % of the elements of a layer moved by more than 2e-2 of
     the row maximum, the relative norm of the difference stays at bf16 level"""
-    mt, _ = _model(L=128)
+    mt, _ = tame_model(L=128)
     V, B, P = 337, 2, 70
     g = torch.Generator().manual_seed(5)
     x = torch.randint(0, V - 1, (B, P), generator=g).cuda()
@@ -258,7 +241,7 @@ def test_batched_and_token_prefill_fill_the_same_fp8_caches():
 def test_fp8_cfg5_sized_graph_replay_equals_eager_greedy():
     """batch 32, d 512, 6 layers, a 1500-event prompt (split-K attention + merge): greedy tokens by graph replay = eager"""
     from musicgeneration_amd import ops
-    mt, _ = _model(d=512, nl=6, L=2048, V=337, seed=5)
+    mt, _ = tame_model(d=512, nl=6, L=2048, V=337, seed=5)
     V, B, P, n = 337, 32, 1500, 48
     assert ops.rel_attn_decode_splits(B, P + n, 512) > 1
     g = torch.Generator().manual_seed(56)
@@ -272,7 +255,7 @@ def test_fp8_cfg5_sized_graph_replay_equals_eager_greedy():
 
 @pytest.mark.parametrize("use_graph", [False, True])
 def test_fp8_row_groups_give_the_same_tokens(use_graph):
-    mt, _ = _model(L=160)
+    mt, _ = tame_model(L=160)
     g = torch.Generator().manual_seed(8)
     x = torch.randint(0, 336, (7, 20), generator=g).cuda()
     ref = mt.generate_cached(x, 100, top_p=0.95, seed=77, use_graph=use_graph, kv_cache="fp8")
@@ -299,7 +282,7 @@ def test_fp8_grammar_is_respected():
 
 @pytest.mark.parametrize("prefill", ["batched", "auto"])
 def test_fp8_equal_prior_lengths_are_bitwise_the_uniform_call(prefill):
-    mt, _ = _model(L=128)
+    mt, _ = tame_model(L=128)
     V, B, P, n = 337, 3, 40, 30
     g = torch.Generator().manual_seed(3)
     x = torch.randint(0, V - 1, (B, P), generator=g).cuda()
@@ -322,7 +305,7 @@ def test_fp8_equal_prior_lengths_are_bitwise_the_uniform_call(prefill):
 
 
 def test_fp8_return_cache_shapes_and_ragged_prompts():
-    mt, _ = _model(L=160)
+    mt, _ = tame_model(L=160)
     V, n = 337, 40
     lens = [3, 1, 40, 17]
     g = torch.Generator().manual_seed(9)
@@ -353,7 +336,7 @@ def test_fp8_return_cache_shapes_and_ragged_prompts():
 # 6. the default is unchanged
 # ---------------------------------------------------------------------------------------------------------------------
 def test_kv_cache_bf16_is_bitwise_the_call_without_the_keyword():
-    mt, _ = _model(L=128)
+    mt, _ = tame_model(L=128)
     g = torch.Generator().manual_seed(13)
     x = torch.randint(0, 336, (3, 33), generator=g).cuda()
     (ta, pa), ka, va = mt.generate_cached(x, 40, top_p=0.9, seed=2, return_probs=True, return_cache=True)

@@ -4,17 +4,9 @@ the full bench batch: causality (bit-exact), linearity in V, row-normalisation, 
 import pytest
 import torch
 
+from kernel_checks import cos as _cos, rel as _rel
+
 pytestmark = pytest.mark.gpu
-
-
-def _rel(a, b):
-    a, b = a.float().flatten(), b.float().flatten()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def _cos(a, b):
-    a, b = a.float().flatten(), b.float().flatten()
-    return (a @ b / (a.norm() * b.norm() + 1e-30)).item()
 
 
 def test_cfg2_shape_forward_backward_vs_oracle():

@@ -32,140 +32,26 @@ The product library only: no experiment build, no environment variable.  Every t
 family before it asserts (pytest -s; profiles/r15_gemm_kernel_tests.txt has the figures).
 """
 import ctypes
-import os
+import functools
 
 import pytest
 import torch
 
+import kernel_checks as KC
+from kernel_checks import Det, P, Stream, check_equal, nothing_more_after_a_gpu_error, operand, output  # noqa: F401 (the fixture is used by name)
 from oracle import train_ref as T
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda:0")
 BF, F64 = torch.bfloat16, torch.float64
 SKINNY, TILE128, RING8, RING4 = 0, 1, 2, 3
-BAND = 512                                          # bytes before and after every buffer
-PATTERN = 0x5A
 SEEN = {}
-
-
-def _raw():
-    from musicgeneration_amd import _lib
-    assert "MGX_LIB_PATH" not in os.environ, "this module is about the product library"
-    return _lib.load(), _lib.check, _lib.ptr, _lib.stream_ptr
-
-
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    for fam, (r, case) in sorted(SEEN.items()):
-        print(f"\nMEASURED {fam}: largest error / bound {r:.3g} at {case}", end="")
-    print()
-
-
-@pytest.fixture(autouse=True)
-def _nothing_more_after_a_gpu_error():
-    """a HIP error is sticky and the device may be shared: the session ends instead of launching the remaining cases on it"""
-    yield
-    try:
-        torch.cuda.synchronize()
-    except RuntimeError as e:
-        pytest.exit(f"GPU error, nothing more is launched: {e}", returncode=3)
-
-
-class Stream:
-    """the stream a case launches on: the default stream (the whole device) or the CU-masked stream of `cus` CUs"""
-
-    def __init__(self, cus=0):
-        self.ms = _ops().masked_stream(cus) if cus else None
-
-    def __enter__(self):
-        torch.cuda.synchronize()
-        if self.ms is not None:
-            self.ctx = torch.cuda.stream(self.ms.stream)
-            self.ctx.__enter__()
-            assert _raw()[3]() == self.ms.ptr
-        return self
-
-    def __exit__(self, *exc):
-        if self.ms is not None:
-            self.ctx.__exit__(*exc)
-        torch.cuda.synchronize()
-
-
-# ---- guard bands ----------------------------------------------------------------------------------------------------------------
-class Banded:
-    """a CPU tensor placed on the GPU inside a larger allocation: BAND bytes of `fill` before and after it"""
-
-    def __init__(self, t, nan_bands):
-        t = t.contiguous()
-        es = t.element_size()
-        self.lead, self.n = BAND // es, t.numel()
-        self.buf = torch.empty(self.n + 2 * self.lead, dtype=t.dtype, device=DEV)
-        if nan_bands:
-            self.buf.fill_(float("nan"))
-        else:
-            self.buf.view(torch.uint8).fill_(PATTERN)
-        self.t = self.buf[self.lead:self.lead + self.n].view(t.shape)
-        self.t.copy_(t)
-        assert self.t.data_ptr() % 256 == self.buf.data_ptr() % 256
-
-    def bands_intact(self):
-        b = self.buf.view(torch.uint8)
-        es = self.buf.element_size()
-        return bool((b[:BAND] == PATTERN).all() and (b[BAND + self.n * es:] == PATTERN).all())
-
-
-def operand(t):
-    return None if t is None else Banded(t, True)
-
-
-def output(shape, dtype, init=None):
-    """an output inside pattern bands; its interior starts as `init` (gW / gb accumulate) or as the pattern (every element must be
-    written: 0x5A5A is 1.5e16 in bf16)"""
-    if init is not None:
-        return Banded(init.to(dtype), False)
-    o = Banded(torch.zeros(shape, dtype=dtype), False)
-    o.t.view(torch.uint8).fill_(PATTERN)
-    return o
-
-
-def P(b):
-    return None if b is None else b.t.data_ptr()
-
-
-# ---- checks ---------------------------------------------------------------------------------------------------------------------
-def _note(fam, worst, case):
-    if worst > SEEN.get(fam, (-1.0, None))[0]:
-        SEEN[fam] = (worst, case)
-    print(f"[{fam}] {case}: error / bound {worst:.3g}")
+_report = KC.report_fixture(SEEN, "largest error / bound {:.3g}")
+_raw = functools.partial(KC.raw, product_only=True)
 
 
 def check_bound(fam, got, ref, bound, case):
-    """|got - ref| <= bound, element by element; got finite"""
-    got = got.detach().cpu().to(F64)
-    assert torch.isfinite(got).all(), (fam, case, "non-finite output", torch.nonzero(~torch.isfinite(got))[:4].tolist())
-    err = (got - ref).abs()
-    ratio = torch.where(bound > 0, err / bound.clamp(min=1e-300), torch.where(err > 0, torch.full_like(err, float("inf")), torch.zeros_like(err)))
-    worst = ratio.max().item()
-    _note(fam, worst, case)
-    if worst > 1.0:
-        i = tuple(int(v) for v in torch.nonzero(ratio == ratio.max())[0])
-        raise AssertionError(f"{fam} {case}: element {i} got {got[i].item()!r} ref {ref[i].item()!r} bound {bound[i].item():.3e} ratio {worst:.3f}")
-
-
-def check_equal(fam, got, want, case):
-    """the values are equal (-0 == +0), element by element"""
-    got = got.detach().cpu().to(F64)
-    bad = torch.nonzero(~(got == want))
-    assert bad.numel() == 0, (f"{fam} {case}: {bad.shape[0]} elements differ, first {bad[:4].tolist()} got "
-                              f"{[got[tuple(i)].item() for i in bad[:4]]} want {[want[tuple(i)].item() for i in bad[:4]]}")
-    print(f"[{fam}] {case}: exact")
+    KC.check_bound(fam, got, ref, bound, case, seen=SEEN)
 
 
 def rounding_is_exercised(pre, case):
@@ -333,28 +219,12 @@ def test_ring_dx_on_the_whole_device(fam, R, epi):
 
 
 # ---- dW -------------------------------------------------------------------------------------------------------------------------
-class Det:
-    def __init__(self, on, ms=None):
-        self.on, self.ms = on, ms
-
-    def __enter__(self):
-        if self.on:
-            _ops().set_deterministic(True)
-            if self.ms is not None:
-                _ops()._det_register_stream(self.ms)
-
-    def __exit__(self, *exc):
-        if self.on:
-            torch.cuda.synchronize()
-            _ops().set_deterministic(False)
-
-
 def run_dw(M, shapes, kind, *, path, with_gb=True, det=False, cus=0, calls=1, seed=0):
     """path "tile": one mgx_linear_dw per weight (ops.linear_dw would reroute); "tile-grouped" / "ring": mgx_linear_dw_grouped (through
     ops.linear_dw_grouped: it owns the workspace), whose plan must be the 128 x 128 grouped kernel (workspace 0) / the ring kernel
     + fix-up (workspace > 0).  `calls` > 1: the same call again into the same slots (they accumulate)"""
     lib, chk, _, sp = _raw()
-    ops = _ops()
+    ops = KC.ops()
     case = f"dw {path} {kind} M={M} {shapes} gb={int(with_gb)} det={int(det)} cus={cus} calls={calls}"
     data, bufs = [], []
     for j, (N, K) in enumerate(shapes):

@@ -28,10 +28,11 @@ The constants absorb the summation order and the fast exp / tanh, nothing else. 
   C_SCAT  the row scatter (fp32 atomics)      2    measured 0.594 (n 5000, cols 64, V 300; 0.507 .. 0.594 over three runs)
 Every test prints its largest ratio before it asserts (pytest -s shows them).
 """
-import numpy as np
 import pytest
 import torch
 
+import kernel_checks as KC
+from kernel_checks import bits16, gen, nothing_more_after_a_gpu_error, weights  # noqa: F401 (the fixture is used by name)
 from oracle import train_ref as T
 
 pytestmark = pytest.mark.gpu
@@ -41,56 +42,11 @@ BF = torch.bfloat16
 F64 = torch.float64
 C = {"CELL": 4.0, "STEP": 0.25, "SCAT": 2.0}
 SEEN = {}
-
-
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
-
-
-def _raw():
-    from musicgeneration_amd import _lib
-    return _lib.load(), _lib.check, _lib.ptr, _lib.stream_ptr
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    for fam, (r, case) in sorted(SEEN.items()):
-        print(f"\nMEASURED {fam}: largest ratio {r:.3f} at {case}", end="")
-    print()
-
-
-def _b(F, ref):
-    F = torch.as_tensor(F, dtype=F64)
-    while F.dim() < ref.dim():
-        F = F.unsqueeze(-1)
-    return F.expand(ref.shape)
+_report = KC.report_fixture(SEEN, "largest ratio {:.3f}")
 
 
 def check(fam, got, ref, F, case, rounding, extra=None):
-    """|got - ref| <= rounding |ref| + extra + C[fam] F, element by element"""
-    got = got.detach().cpu().to(F64).reshape(ref.shape)
-    assert torch.isfinite(got).all(), (fam, case, "non-finite output")
-    F = _b(F, ref)
-    assert (F > 0).all()
-    ratio = ((got - ref).abs() - rounding * ref.abs() - (0.0 if extra is None else extra)) / F
-    worst = ratio.max().item()
-    if worst > SEEN.get(fam, (-1.0, None))[0]:
-        SEEN[fam] = (worst, case)
-    print(f"[{fam}] {case}: ratio {worst:.3f}")
-    if worst > C[fam]:
-        i = np.unravel_index(int(ratio.argmax()), ratio.shape)
-        raise AssertionError(f"{fam} {case}: element {tuple(int(v) for v in i)} got {got[i].item()!r} ref {ref[i].item()!r} "
-                             f"F {F[i].item():.3e} ratio {worst:.2f} > {C[fam]}")
-
-
-def bits16(t):
-    return t.detach().cpu().contiguous().view(torch.int16)
-
-
-def gen(*seed):
-    return torch.Generator().manual_seed(sum((i + 1) * 7919 * int(s) for i, s in enumerate(seed)))
+    KC.check_floor(fam, got, ref, F, case, C=C[fam], seen=SEEN, rounding=rounding, extra=extra)
 
 
 # =====================================================================================================================
@@ -124,7 +80,7 @@ def check_cell_bwd(gi, gh, h_prev, dh, dgi, dgh, dhp, case, extra=None):
 
 @pytest.mark.parametrize("B,H", CELL_SHAPES)
 def test_cell_forward_against_fp64(B, H):
-    ops = _ops()
+    ops = KC.ops()
     gi, gh, h_prev = cell_inputs(B, H)
     h_next, y = torch.empty(B, H, device=DEV), torch.empty(B, H, dtype=BF, device=DEV)
     ops.gru_cell_fwd(gi.to(DEV), gh.to(DEV), h_prev.to(DEV), h_next, y)
@@ -133,7 +89,7 @@ def test_cell_forward_against_fp64(B, H):
 
 @pytest.mark.parametrize("B,H", CELL_SHAPES)
 def test_cell_backward_against_fp64_for_every_combination_of_its_optional_inputs(B, H):
-    ops = _ops()
+    ops = KC.ops()
     gi, gh, h_prev = cell_inputs(B, H)
     g = gen(B, H, 1)
     parts = (torch.randn(B, H, generator=g), torch.randn(B, H, generator=g).to(BF), torch.randn(B, H, generator=g).to(BF))
@@ -151,7 +107,7 @@ def test_cell_backward_against_fp64_for_every_combination_of_its_optional_inputs
 @pytest.mark.parametrize("a", (30.0, 100.0))
 def test_cell_with_saturated_gates_is_finite_and_exact(a):
     """pre-activations of +-30 and +-100: sigmoid(+a) is exactly 1 in fp32, sigmoid(-100) exactly 0"""
-    ops = _ops()
+    ops = KC.ops()
     B, H = 4, 36
     g = gen(int(a))
     gi, gh, h_prev = cell_inputs(B, H, 1.0)
@@ -193,7 +149,7 @@ def test_cell_with_saturated_gates_is_finite_and_exact(a):
 @pytest.mark.parametrize("n", (8, 8 * 1000, 8 * (2 ** 16 + 5)))
 def test_dropout_is_the_integer_twin_bit_for_bit(n, p_drop):
     """n / 8 not a multiple of 256; kept elements are the bf16 rounding of value * scale in fp32, dropped ones 0"""
-    lib, chk, ptr, stream_ptr = _raw()
+    lib, chk, ptr, stream_ptr = KC.raw()
     seed = (1 << 40) + 12345
     x = torch.randn(n, generator=gen(n)).to(BF)
     xg, out = x.to(DEV), torch.full((n + 8,), 1.0, dtype=BF, device=DEV)
@@ -204,13 +160,13 @@ def test_dropout_is_the_integer_twin_bit_for_bit(n, p_drop):
     assert (out[n:].cpu().float() == 1.0).all()               # nothing past the end
     if p_drop > 0:
         assert (out[:n].cpu().float()[mult == 0] == 0).all() and (n < 8000 or ((mult == 0).any() and (mult != 0).any()))
-        assert _ops().dropout_bf16(xg, p_drop, seed).cpu().view(torch.int16).equal(bits16(want))
+        assert KC.ops().dropout_bf16(xg, p_drop, seed).cpu().view(torch.int16).equal(bits16(want))
 
 
 @pytest.mark.parametrize("n,ld,cols,V", ((7, 16, 12, 11), (1000, 72, 65, 9), (5000, 64, 64, 300)))
 def test_scatter_add_rows_against_fp64(n, ld, cols, V):
     """repeated indices, indices outside [0, V) (ignored), ld > cols, dst starting nonzero"""
-    ops = _ops()
+    ops = KC.ops()
     g = gen(n, V)
     idx = torch.randint(-2, V + 2, (n,), generator=g).to(torch.int32)
     idx[:3] = torch.tensor([3, 3, 3], dtype=torch.int32)
@@ -234,11 +190,6 @@ STEP_B = (1, 31, 32, 33, 100)
 STEP_KX = (64, 192, 320, 576, 1024)
 
 
-def weights(N, K, seed):
-    g = gen(N, K, seed)
-    return (torch.randn(N, K, generator=g) / K ** 0.5).to(BF), torch.randn(N, generator=g)
-
-
 def one_hot_rows(B, K):
     """row b is 1 at one column of k-step b % (K / 16), 0 elsewhere"""
     hot = torch.tensor([16 * (b % (K // 16)) + (5 * b + b // (K // 16)) % 16 for b in range(B)])
@@ -248,7 +199,7 @@ def one_hot_rows(B, K):
 
 
 def step_fwd(gi, h_prev, hp_bf, whh, bhh):
-    ops = _ops()
+    ops = KC.ops()
     B, H = h_prev.shape
     h_next, y = torch.full((B, H), float("nan"), device=DEV), torch.zeros(B, H, dtype=BF, device=DEV)
     gh_out = torch.zeros(B, 3 * H, dtype=BF, device=DEV)
@@ -292,7 +243,7 @@ def doubtful(v, F):
 @pytest.mark.parametrize("H,Kx,B", [(H, Kx, B) for H in (64, 320, 704) for Kx in STEP_KX for B in (1, 33)] +
                          [(H, Kx, 100) for H, Kx in ((128, 64), (192, 576), (512, 512), (1024, 1024), (1024, 320), (512, 1024))])
 def test_fused_sampling_step_against_fp64(H, Kx, B):
-    ops = _ops()
+    ops = KC.ops()
     wih, bih = weights(3 * H, Kx, 2)
     whh, bhh = weights(3 * H, H, 3)
     _, _, h_prev = cell_inputs(B, H)
@@ -318,7 +269,7 @@ def test_fused_sampling_step_against_fp64(H, Kx, B):
 
 @pytest.mark.parametrize("H,Kx", [(H, Kx) for H in (64, 704) for Kx in STEP_KX] + [(1024, 1024), (512, 576), (320, 64), (192, 192), (128, 320)])
 def test_fused_sampling_step_with_one_hot_rows_of_x_and_h_is_the_cell_on_exact_weight_columns(H, Kx):
-    ops = _ops()
+    ops = KC.ops()
     B = max(33, H // 16 + 3, Kx // 16 + 3)
     wih, bih = weights(3 * H, Kx, 5)
     whh, bhh = weights(3 * H, H, 6)
@@ -332,7 +283,7 @@ def test_fused_sampling_step_with_one_hot_rows_of_x_and_h_is_the_cell_on_exact_w
 
 
 def step_bwd(gi, gh, h_prev, dh_direct, dgh_next, whh, dy, final, B, H):
-    ops = _ops()
+    ops = KC.ops()
     dv = lambda t: None if t is None else t.to(DEV)                                                 # noqa: E731
     dgi, dgh = (torch.full((B, 3 * H), float("nan"), dtype=BF, device=DEV) for _ in range(2))
     dh_out = torch.full((B, H), float("nan"), device=DEV)

@@ -12,22 +12,14 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_checks import cos as _cos, rel as _relerr
+
 pytestmark = pytest.mark.gpu
 
 
 def _dev():
     assert torch.cuda.is_available(), "GPU tests need a HIP device"
     return torch.device("cuda:0")
-
-
-def _relerr(a, b):
-    a, b = a.float().flatten(), b.float().flatten()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
-
-
-def _cos(a, b):
-    a, b = a.float().flatten(), b.float().flatten()
-    return (a @ b / (a.norm() * b.norm() + 1e-30)).item()
 
 
 def _mask(tok, pad):

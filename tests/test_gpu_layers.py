@@ -9,17 +9,9 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_checks import cos as _cos, rel as _rel
+
 pytestmark = pytest.mark.gpu
-
-
-def _cos(a, b):
-    a, b = a.float().flatten().cpu(), b.float().flatten().cpu()
-    return (a @ b / (a.norm() * b.norm() + 1e-30)).item()
-
-
-def _rel(a, b):
-    a, b = a.float().flatten().cpu(), b.float().flatten().cpu()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
 
 
 @pytest.mark.parametrize("tag", ["c", "d"])

@@ -9,21 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+from kernel_checks import cos as _cos, rel as _rel
+
 pytestmark = pytest.mark.gpu
 
 
 def _load(golden_dir, name):
     return dict(np.load(os.path.join(golden_dir, name)))
-
-
-def _cos(a, b):
-    a, b = a.float().flatten(), b.float().flatten()
-    return (a @ b / (a.norm() * b.norm() + 1e-30)).item()
-
-
-def _rel(a, b):
-    a, b = a.float().flatten(), b.float().flatten()
-    return ((a - b).norm() / (b.norm() + 1e-30)).item()
 
 
 def _model_from(g, prefix, d, nl, L, dropout=0.0):

@@ -7,24 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+from decode_fixtures import check_rows, one, prompt_file, ragged_prior, tame_model
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 BF = torch.bfloat16
-
-
-def _model(d=128, nl=2, L=96, V=337, seed=0):
-    # the fixture of test_gpu_decode.py: random init with tamed embeddings and relative terms
-    from musicgeneration_amd.network import MusicTransformer
-    from oracle import ref_cpu as R
-    p0 = R.init_params(V, d, nl, L, seed=seed)
-    p0["Decoder.embedding.weight"] = p0["Decoder.embedding.weight"] * 0.1
-    for k in list(p0):
-        if k.endswith("rga.E"):
-            p0[k] = p0[k] * 0.2
-    mt = MusicTransformer(embedding_dim=d, vocab_size=V, num_layer=nl, max_seq=L, dropout=0.0)
-    mt.load_state_dict(p0)
-    return mt.cuda().eval(), p0
 
 
 def _positions(B, Lmax, g):
@@ -32,10 +20,6 @@ def _positions(B, Lmax, g):
     pos = torch.randint(0, Lmax, (B,), generator=g, dtype=torch.int32)
     pos[0], pos[1], pos[2], pos[3] = 0, 37, Lmax - 1, Lmax - 2
     return pos.to(DEV)
-
-
-def _one(t):
-    return torch.tensor([int(t)], dtype=torch.int32, device=DEV)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -56,10 +40,10 @@ def test_ragged_embed_and_embed_qkv_match_the_shared_position_kernels_rowwise():
     outs = {w_name: ops.decode_embed_linear(tok, table, pe, pos, w, bq, torch.empty(B, d, dtype=BF, device=DEV), ragged=True)
             for w_name, w in (("plain", wq), ("frag", wf))}
     for b in range(B):
-        h0 = ops.decode_embed(tok, table, pe, _one(pos[b]), torch.empty(B, d, dtype=BF, device=DEV))
+        h0 = ops.decode_embed(tok, table, pe, one(pos[b]), torch.empty(B, d, dtype=BF, device=DEV))
         assert torch.equal(h[b], h0[b]), b
         for w_name, w in (("plain", wq), ("frag", wf)):
-            q0, hh0 = ops.decode_embed_linear(tok, table, pe, _one(pos[b]), w, bq, torch.empty(B, d, dtype=BF, device=DEV))
+            q0, hh0 = ops.decode_embed_linear(tok, table, pe, one(pos[b]), w, bq, torch.empty(B, d, dtype=BF, device=DEV))
             q1, hh1 = outs[w_name]
             assert torch.equal(q1[b], q0[b]) and torch.equal(hh1[b], hh0[b]), (w_name, b)
     assert not torch.equal(h[0], h[2])                            # the rows did read different positions
@@ -86,7 +70,7 @@ def test_ragged_attention_matches_the_shared_position_kernel_rowwise(Lmax, B):
     ctx = ops.rel_attn_decode(qkv, kc, vc, E, pos, torch.empty(B, d, dtype=BF, device=DEV), ws, ragged=True)
     for b in range(B):
         k1, v1 = kc0.clone(), vc0.clone()
-        c1 = ops.rel_attn_decode(qkv, k1, v1, E, _one(pos[b]), torch.empty(B, d, dtype=BF, device=DEV), ws)
+        c1 = ops.rel_attn_decode(qkv, k1, v1, E, one(pos[b]), torch.empty(B, d, dtype=BF, device=DEV), ws)
         assert torch.equal(ctx[b], c1[b]), b
         assert torch.equal(kc[b], k1[b]) and torch.equal(vc[b], v1[b]), b
     assert torch.isfinite(ctx.float()).all()
@@ -111,7 +95,7 @@ def test_ragged_sampler_and_advance_match_the_shared_position_kernel_rowwise(gra
     nt, out, probs, p = prev.clone(), out0.clone(), torch.zeros(B, V, device=DEV), pos.clone()
     ops.sample_topk_topp(logits, V, p, nt, out, probs, 0.9, 50, 0.95, 1234, advance=True, allow_table=table, row0=3, ragged=True)
     for b in range(B):
-        nt1, out1, probs1, p1 = prev.clone(), out0.clone(), torch.zeros(B, V, device=DEV), _one(pos[b])
+        nt1, out1, probs1, p1 = prev.clone(), out0.clone(), torch.zeros(B, V, device=DEV), one(pos[b])
         ops.sample_topk_topp(logits, V, p1, nt1, out1, probs1, 0.9, 50, 0.95, 1234, advance=True, allow_table=table, row0=3)
         assert nt[b] == nt1[b] and torch.equal(out[b], out1[b]) and torch.equal(probs[b], probs1[b]), b
         assert out[b, pos[b] + 1] == nt[b]
@@ -124,18 +108,10 @@ def test_ragged_sampler_and_advance_match_the_shared_position_kernel_rowwise(gra
 # ---------------------------------------------------------------------------------------------------------------------
 # generate_cached(prior_lengths=...)
 # ---------------------------------------------------------------------------------------------------------------------
-def _ragged_prior(lens, V, g, fill=-7):
-    B, Pmax = len(lens), max(lens)
-    x = torch.randint(0, V - 1, (B, Pmax), generator=g)
-    for b, n in enumerate(lens):
-        x[b, n:] = fill                                           # ignored: anything may sit in the padding
-    return x
-
-
 @pytest.mark.parametrize("use_graph", [False, True])
 @pytest.mark.parametrize("prefill", ["batched", "auto"])
 def test_equal_prior_lengths_are_bitwise_the_uniform_call(prefill, use_graph):
-    mt, _ = _model(L=128)
+    mt, _ = tame_model(L=128)
     V, B, P, n = 337, 3, 40, 30
     g = torch.Generator().manual_seed(3)
     x = torch.randint(0, V - 1, (B, P), generator=g).cuda()
@@ -156,35 +132,15 @@ def test_equal_prior_lengths_are_bitwise_the_uniform_call(prefill, use_graph):
     assert all(torch.equal(c[:, :, :P + n], a) and not c[:, :, P + n:].any() for a, c in zip(ka + va, kc + vc))
 
 
-def _check_rows_against_forward_and_oracle(mt, p0, x, lens, n, toks, probs, V):
-    from oracle import ref_cpu as R
-    toks, probs = toks.cpu(), probs.cpu()
-    Pmax = x.shape[1]
-    assert toks.shape == (len(lens), Pmax + n) and probs.shape == (len(lens), Pmax + n, V)
-    for b, P in enumerate(lens):
-        assert torch.equal(toks[b, :P], x[b, :P].to(torch.int32)), b               # the prompt comes back unchanged
-        assert (toks[b, P + n:] == mt.pad_token).all(), b                          # then length samples, then padding
-        assert int(toks[b, P:P + n].max()) < V
-        seq = toks[b:b + 1, :P + n].long()
-        span = slice(P - 1, P + n - 1)                                             # the distributions after P-1 .. P+n-2
-        assert not probs[b, :P - 1].any() and not probs[b, P + n - 1:].any(), b
-        with torch.no_grad():
-            fwd = torch.softmax(mt(seq.to(torch.int32).cuda())[0].float(), -1).cpu()[0, span]
-            ref = torch.softmax(R.model_forward(p0, seq, V - 1)[0], -1)[0, span]
-        got = probs[b, span]
-        assert (got - fwd).abs().max().item() < 1e-2, b
-        assert (got - ref).abs().max().item() < 2e-2, b
-
-
 def test_ragged_prompts_match_the_forward_and_the_oracle_per_row():
-    mt, p0 = _model()
+    mt, p0 = tame_model()
     V, n = 337, 20
     lens = [1, 5, 33, 70]
     g = torch.Generator().manual_seed(17)
-    x = _ragged_prior(lens, V, g)
+    x = ragged_prior(lens, V, g)
     toks, probs = mt.generate_cached(x.cuda(), n, top_p=0.95, seed=9, return_probs=True, prior_lengths=lens)
     torch.cuda.synchronize()
-    _check_rows_against_forward_and_oracle(mt, p0, x, lens, n, toks, probs, V)
+    check_rows(mt, p0, x, lens, 1, n, toks, probs, V)
 
 
 @pytest.mark.parametrize("d,nl", [(128, 2), (512, 6)])
@@ -193,22 +149,22 @@ def test_ragged_prompts_on_the_split_key_path_match_the_oracle(d, nl):
     V, L, n = 337, 2048, 24
     lens = [1, 33, 700, 1500]
     assert ops.rel_attn_decode_splits(len(lens), max(lens) + n, d) > 1
-    mt, p0 = _model(d=d, nl=nl, L=L, V=V, seed=21)
+    mt, p0 = tame_model(d=d, nl=nl, L=L, V=V, seed=21)
     g = torch.Generator().manual_seed(29)
-    x = _ragged_prior(lens, V, g)
+    x = ragged_prior(lens, V, g)
     toks, probs = mt.generate_cached(x.cuda(), n, top_p=0.95, seed=4, return_probs=True, prior_lengths=lens)
     torch.cuda.synchronize()
-    _check_rows_against_forward_and_oracle(mt, p0, x, lens, n, toks, probs, V)
+    check_rows(mt, p0, x, lens, 1, n, toks, probs, V)
 
 
 def test_ragged_prompts_without_the_fused_step_match_the_forward():
     """B > 32: the step runs the unfused kernels (decode_embed, linear_fwd, add_ln_fwd) with per-row positions"""
-    mt, _ = _model(L=96)
+    mt, _ = tame_model(L=96)
     V, n, B = 337, 12, 34
     g = torch.Generator().manual_seed(41)
     lens = torch.randint(1, 60, (B,), generator=g).tolist()
     lens[0], lens[1] = 1, 60
-    x = _ragged_prior(lens, V, g)
+    x = ragged_prior(lens, V, g)
     toks, probs = mt.generate_cached(x.cuda(), n, top_k=20, seed=2, return_probs=True, prior_lengths=lens)
     toks, probs = toks.cpu(), probs.cpu()
     for b in (0, 1, 7, 33):
@@ -220,10 +176,10 @@ def test_ragged_prompts_without_the_fused_step_match_the_forward():
 
 
 def test_ragged_graph_replay_and_row_groups_are_bitwise_the_eager_single_group_run():
-    mt, _ = _model(d=128, nl=2, L=160, V=337, seed=31)
+    mt, _ = tame_model(d=128, nl=2, L=160, V=337, seed=31)
     g = torch.Generator().manual_seed(8)
     lens = [3, 1, 40, 17, 64, 2, 9]
-    x = _ragged_prior(lens, 337, g).cuda()
+    x = ragged_prior(lens, 337, g).cuda()
     ref = mt.generate_cached(x, 90, top_p=0.95, seed=77, use_graph=False, prior_lengths=lens)
     for use_graph in (False, True):
         for G in (1, 2, 3):
@@ -257,7 +213,7 @@ def test_ragged_prompts_with_a_grammar():
 
 
 def test_ragged_refusals_on_the_device():
-    mt, _ = _model(L=96)
+    mt, _ = tame_model(L=96)
     x = torch.randint(0, 300, (3, 40)).cuda()
     for lens, kw in (([0, 5, 40], {}), ([41, 5, 40], {}), ([1, 5, 40], dict(length=57)), ([1, 5, 40], dict(prefill="token"))):
         with pytest.raises(ValueError):
@@ -267,18 +223,11 @@ def test_ragged_refusals_on_the_device():
 # ---------------------------------------------------------------------------------------------------------------------
 # generate.py --condition-files
 # ---------------------------------------------------------------------------------------------------------------------
-def _prompt_file(path, n_notes, pitch0):
-    from musicgeneration_amd import smf
-    notes = [(80, pitch0 + (i % 12), 0.5 * i, 0.5 * i + 0.25) for i in range(n_notes)]
-    smf.write_notes(path, notes)
-    return notes
-
-
 def test_generate_cli_continues_each_condition_file_in_one_batch(tmp_path, capsys):
     from musicgeneration_amd import generate
     from musicgeneration_amd.sequence import NoteSeq
     a, b = str(tmp_path / "a.mid"), str(tmp_path / "b.mid")
-    notes = {a: _prompt_file(a, 3, 60), b: _prompt_file(b, 11, 48)}
+    notes = {a: prompt_file(a, 3, 60), b: prompt_file(b, 11, 48)}
     out = str(tmp_path / "gen") + "/"
     torch.manual_seed(0)
     generate.main(["-o", out, "-b", "5", "-l", "24", "--num-layers", "1", "--d-model", "128", "-M", "128", "-d", "",

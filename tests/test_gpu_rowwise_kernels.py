@@ -27,71 +27,26 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks as KC
+from kernel_checks import bits16, nothing_more_after_a_gpu_error  # noqa: F401 (the fixture is used by name)
 from oracle import train_ref as T
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 BF = torch.bfloat16
-F64 = torch.float64
-C = {"LNF": 8.0, "LNB": 4.0, "CE": 8.0, "ADAM": 16.0, "EMB": 4.0}
+C = {"LNF": 8.0, "LNB": 4.0, "CE": 8.0, "ADAM": KC.C_ADAM, "EMB": 4.0}
 SEEN = {}                                          # family -> (largest ratio this process has seen, its case)
-
-
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
-
-
-def _raw():
-    from musicgeneration_amd import _lib
-    return _lib.load(), _lib.check, _lib.ptr, _lib.stream_ptr
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    for fam, (r, case) in sorted(SEEN.items()):
-        print(f"\nMEASURED {fam}: largest ratio {r:.3f} at {case}", end="")
-    print()
-
-
-def _check(fam, got, ref, F, case, rounding):
-    """|got - ref| <= rounding * |ref| + C[fam] * F, element by element; records the largest (|err| - rounding |ref|) / F"""
-    got = got.detach().cpu().to(F64).reshape(ref.shape)
-    assert torch.isfinite(got).all(), (fam, case, "non-finite output")
-    F = torch.as_tensor(F, dtype=F64)
-    while F.dim() < ref.dim():                     # a floor per row
-        F = F.unsqueeze(-1)
-    F = F.expand(ref.shape)
-    assert (F > 0).all()
-    ratio = ((got - ref).abs() - rounding * ref.abs()) / F
-    worst = ratio.max().item()
-    if worst > SEEN.get(fam, (-1.0, None))[0]:
-        SEEN[fam] = (worst, case)
-    print(f"[{fam}] {case}: ratio {worst:.3f}")
-    if worst > C[fam]:
-        i = np.unravel_index(int(ratio.argmax()), ratio.shape)
-        raise AssertionError(f"{fam} {case}: element {tuple(int(v) for v in i)} got {got[i].item()!r} ref {ref[i].item()!r} "
-                             f"F {F[i].item():.3e} ratio {worst:.2f} > {C[fam]}")
+_report = KC.report_fixture(SEEN, "largest ratio {:.3f}")
 
 
 def check_bf16(fam, got, ref, F, case):
-    _check(fam, got, ref, F, case, 2.0 ** -8)
+    KC.check_floor(fam, got, ref, F, case, C=C[fam], seen=SEEN, rounding=2.0 ** -8)
 
 
 def check_f32(fam, got, ref, F, case):
     assert got.dtype == torch.float32
-    _check(fam, got, ref, F, case, 0.0)
-
-
-def bits16(t):
-    return t.detach().cpu().contiguous().view(torch.int16)
-
-
-def raw_bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == torch.float32 else t.view(torch.int16) if t.dtype == BF else t
+    KC.check_floor(fam, got, ref, F, case, C=C[fam], seen=SEEN)
 
 
 # =====================================================================================================================
@@ -102,7 +57,7 @@ LN_BIG = {8: 2049, 64: 4100, 504: 6151, 512: 2049, 520: 4100, 1024: 6151, 1032: 
 
 
 def ln_bwd_raw(dout, x, res, gamma, mean, rstd, dgamma, dbeta, dxsum, p_drop, seed, alias):
-    lib, check, ptr, stream_ptr = _raw()
+    lib, check, ptr, stream_ptr = KC.raw()
     rows, d = x.shape
     dres = torch.empty_like(x)
     dx = dres if alias else torch.empty_like(x)
@@ -115,7 +70,7 @@ def ln_bwd_raw(dout, x, res, gamma, mean, rstd, dgamma, dbeta, dxsum, p_drop, se
 
 def run_ln(kind, rows, d, p_drop=0.0, seed=0, init=False, alias=False, want_dxsum=True):
     case = f"{kind} rows={rows} d={d} p={p_drop} init={init} alias={alias}"
-    ops = _ops()
+    ops = KC.ops()
     x, res = T.ln_case(kind, rows, d, seed)
     g = torch.Generator().manual_seed(seed + d)
     gamma, beta = 1 + 0.5 * torch.randn(d, generator=g), torch.randn(d, generator=g)
@@ -198,7 +153,7 @@ def ce_lds(V):
 
 
 def ce_fwd_raw(logits, target, stats, V, ld, pad):
-    lib, check, ptr, stream_ptr = _raw()
+    lib, check, ptr, stream_ptr = KC.raw()
     rows = target.numel()
     argmax = torch.full((rows,), -7, dtype=torch.int32, device=DEV)
     lse = torch.full((rows,), float("nan"), dtype=torch.float32, device=DEV)
@@ -218,7 +173,7 @@ def on_device(t, off):
 
 def run_ce(kind, rows, V, ld, off=0, fill=float("nan"), init=False, gscale=1.0, gdev=None, all_pad=False, seed=0):
     case = f"{kind} rows={rows} V={V} ld={ld} off={off} fill={fill} init={init} g={gscale}/{gdev} all_pad={all_pad}"
-    ops = _ops()
+    ops = KC.ops()
     pad = V - 2 if V > 2 else 0
     logits = T.ce_logits(kind, rows, V, ld, seed, fill)
     target = torch.full((rows,), pad, dtype=torch.int32) if all_pad else T.ce_targets(rows, V, pad, seed)
@@ -272,7 +227,7 @@ def test_cross_entropy_ignores_the_padding_columns_bit_for_bit(V, ld):
         for fill in (float("nan"), float("inf")):
             other = run_ce("gauss", 17, V, ld, off, fill=fill)
             for a, b in zip(base, other):
-                assert raw_bits(a).equal(raw_bits(b)), (V, ld, off, fill)
+                assert KC.bits(a).equal(KC.bits(b)), (V, ld, off, fill)
 
 
 @pytest.mark.parametrize("V,ld", ((9, 16), (600, 600), (600, 640), (2049, 2049)))
@@ -291,7 +246,7 @@ def test_cross_entropy_accumulates_scales_and_handles_an_all_pad_batch(V, ld):
 @pytest.mark.parametrize("with_shadow", (True, False))
 def test_adam_against_fp64_with_the_state_carried_across_steps(n, with_shadow):
     """4 * 2^20 + 5 elements: more float4 groups than the 2048 * 256 threads, so the grid loops; n % 4 != 0: the tail"""
-    ops = _ops()
+    ops = KC.ops()
     lr, b1, b2, eps, gs = 1e-3, 0.9, 0.98, 1e-9, 0.5
     g = torch.Generator().manual_seed(n)
     p = torch.randn(n, generator=g).to(DEV)
@@ -318,7 +273,7 @@ def test_adam_against_fp64_with_the_state_carried_across_steps(n, with_shadow):
 
 
 def test_adam_without_gradient_scale_is_the_plain_update():
-    ops = _ops()
+    ops = KC.ops()
     for n in (3, 1031):
         g = torch.Generator().manual_seed(n)
         p0, grad, m0, v0 = torch.randn(n, generator=g), torch.randn(n, generator=g), 0.1 * torch.randn(n, generator=g), torch.rand(n, generator=g)
@@ -333,7 +288,7 @@ def test_adam_without_gradient_scale_is_the_plain_update():
 @pytest.mark.parametrize("n", (1, 7, 2 ** 19 + 13))
 def test_cast_bf16_is_torchs_rounding_bit_for_bit(n):
     """2^19 + 13 elements: more than the 2048 * 256 threads, so the grid loops"""
-    ops = _ops()
+    ops = KC.ops()
     g = torch.Generator().manual_seed(n)
     p = torch.randn(n, generator=g)
     special = torch.tensor([1 + 2.0 ** -8, 1 + 3 * 2.0 ** -8, -(1 + 2.0 ** -8), 1 + 2.0 ** -8 + 2.0 ** -20, 1e-40, -1e-40, 2.0 ** -133,
@@ -365,7 +320,7 @@ def pe_table(L, d):
 @pytest.mark.parametrize("B,L,d,V", ((3, 32, 8, 11), (2, 64, 520, 337), (4, 2048, 520, 337)))
 def test_embedding_forward_against_fp64(B, L, d, V, p_drop):
     """B > 1: row r reads pe[r % L]; 4 * 2048 rows of 65 groups: more than the 2048 * 256 threads, so the grid loops"""
-    ops = _ops()
+    ops = KC.ops()
     seed = (1 << 33) + 17
     g = torch.Generator().manual_seed(B * L + d)
     tok = torch.randint(0, V, (B, L), generator=g).to(torch.int32)
@@ -387,7 +342,7 @@ EMB_BWD = ((2, 96, 3, 64, False), (1, 4097, 3, 512, True), (4, 4096, 337, 520, F
 
 
 def run_embed_bwd(B, L, V, d, same, p_drop, det):
-    ops = _ops()
+    ops = KC.ops()
     seed, rows = 77, B * L
     g = torch.Generator().manual_seed(rows + V + d)
     tok = (torch.ones(B, L, dtype=torch.int64) if same else torch.randint(0, V - 1, (B, L), generator=g)).to(torch.int32)
@@ -419,7 +374,7 @@ def test_embedding_backward_against_fp64(B, L, V, d, same, p_drop):
 @pytest.mark.parametrize("p_drop", (0.0, 0.1))
 @pytest.mark.parametrize("B,L,V,d,same", EMB_BWD)
 def test_embedding_backward_against_fp64_in_deterministic_mode(B, L, V, d, same, p_drop):
-    ops = _ops()
+    ops = KC.ops()
     ops.set_deterministic(True, DEV)
     try:
         run_embed_bwd(B, L, V, d, same, p_drop, det=True)
@@ -430,7 +385,7 @@ def test_embedding_backward_against_fp64_in_deterministic_mode(B, L, V, d, same,
 @pytest.mark.parametrize("B,L", ((1, 32), (3, 32), (1, 96), (2049, 32), (3, 21856)))
 def test_pad_bitmap_words_are_exact(B, L):
     """B * L of 32, 96 and 64 k + 32 tokens: a wave whose upper half, or all but its first 32 lanes, lies past the end"""
-    ops = _ops()
+    ops = KC.ops()
     pad = 5
     g = torch.Generator().manual_seed(B * L)
     tok = torch.randint(0, 9, (B, L), generator=g).to(torch.int32)
@@ -444,7 +399,7 @@ def test_pad_bitmap_words_are_exact(B, L):
 
 
 def test_pad_bitmap_flag_is_raised_by_a_real_token_after_a_leading_pad_only():
-    ops = _ops()
+    ops = KC.ops()
     pad, L = 5, 64
     rows = {"trailing": [1] * 40 + [pad] * 24, "interior": [1, pad, pad, 1] * 16, "all-pad": [pad] * L,
             "leading": [pad] + [1] * 63, "leading-late": [pad] * 63 + [1]}

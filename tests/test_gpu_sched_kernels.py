@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks as KC
+from kernel_checks import bits16, gen, nothing_more_after_a_gpu_error, weights  # noqa: F401 (the fixture is used by name)
 from oracle import decode_ref as D
 from oracle import train_ref as T
 
@@ -23,35 +25,12 @@ F64 = torch.float64
 C_STEP = 0.25
 
 
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
-
-
-def _raw():
-    from musicgeneration_amd import _lib
-    return _lib.load(), _lib.check, _lib.ptr, _lib.stream_ptr
-
-
-def bits16(t):
-    return t.detach().cpu().contiguous().view(torch.int16)
-
-
-def gen(*seed):
-    return torch.Generator().manual_seed(sum((i + 1) * 7919 * int(s) for i, s in enumerate(seed)))
-
-
-def weights(N, K, seed):
-    g = gen(N, K, seed)
-    return (torch.randn(N, K, generator=g) / K ** 0.5).to(BF), torch.randn(N, generator=g)
-
-
 # =====================================================================================================================
 # 1. the step that saves its projections
 # =====================================================================================================================
 @pytest.mark.parametrize("B,H,Kx", [(1, 64, 64), (33, 64, 128), (5, 320, 64), (33, 704, 576)])     # the last: the K > 512 tail loop
 def test_save_step_is_the_sampling_step_plus_its_two_projections(B, H, Kx):
-    ops = _ops()
+    ops = KC.ops()
     wih, bih = weights(3 * H, Kx, 2)
     whh, bhh = weights(3 * H, H, 3)
     g = gen(B, H, Kx)
@@ -87,8 +66,8 @@ def test_save_step_is_the_sampling_step_plus_its_two_projections(B, H, Kx):
 # =====================================================================================================================
 @pytest.mark.parametrize("p_drop", (0.0, 0.1))
 def test_dropout_slices_tile_the_whole_buffer_call_bit_for_bit(p_drop):
-    lib, chk, ptr, stream_ptr = _raw()
-    ops = _ops()
+    lib, chk, ptr, stream_ptr = KC.raw()
+    ops = KC.ops()
     n = 8 * (2 ** 16 + 5)
     seed = (1 << 40) + 12345
     x = torch.randn(n, generator=gen(n)).to(BF).to(DEV)
@@ -121,7 +100,7 @@ HUGE = 3.0e38                                                # columns >= V hold
 
 def next_event(logits, V, flag, events, temperature, seed, step, emb):
     """-> tok, used_out int32 [B], x_out [B,Ep] (cpu), after checking the sentinels past every output"""
-    ops = _ops()
+    ops = KC.ops()
     B, Ep = logits.shape[0], emb.shape[1]
     PAD = 5
     tok = torch.full((B + PAD,), -9, dtype=torch.int32, device=DEV)

@@ -26,7 +26,9 @@ import numpy as np
 import pytest
 import torch
 
+import kernel_checks as KC
 import score_ref
+from kernel_checks import nothing_more_after_a_gpu_error  # noqa: F401 (the fixture is used by name)
 from oracle import train_ref as T
 
 pytestmark = pytest.mark.gpu
@@ -35,50 +37,18 @@ DEV = torch.device("cuda:0")
 BF = torch.bfloat16
 C = {"LP": 4.0, "FLP": 2.0}
 SEEN = {}
+_report = KC.report_fixture(SEEN, "largest ratio {:.3f}")
 CANARY = 8
 
 
-def _raw():
-    from musicgeneration_amd import _lib
-    return _lib.load(), _lib.check, _lib.ptr, _lib.stream_ptr
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _report():
-    yield
-    for fam, (r, case) in sorted(SEEN.items()):
-        print(f"\nMEASURED {fam}: largest ratio {r:.3f} at {case}", end="")
-    print()
-
-
 def _check(fam, got, ref, F, case):
-    """|got - ref| <= C[fam] * F on the finite entries of ref; -inf and NaN must match exactly"""
-    got, ref, F = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64), np.asarray(F, dtype=np.float64)
-    fin = np.isfinite(ref)
-    assert (np.isnan(got) == np.isnan(ref)).all(), (fam, case, "NaN rows differ")
-    assert (got[~fin & ~np.isnan(ref)] == ref[~fin & ~np.isnan(ref)]).all(), (fam, case, "infinite entries differ")
-    if not fin.any():
-        return
-    assert (F[fin] > 0).all()
-    ratio = np.abs(got[fin] - ref[fin]) / F[fin]
-    worst = float(ratio.max())
-    if worst > SEEN.get(fam, (-1.0, None))[0]:
-        SEEN[fam] = (worst, case)
-    print(f"[{fam}] {case}: ratio {worst:.3f}")
-    if worst > C[fam]:
-        i = int(np.flatnonzero(fin)[ratio.argmax()])
-        raise AssertionError(f"{fam} {case}: row {i} got {got[i]!r} ref {ref[i]!r} F {F[i]:.3e} ratio {worst:.2f} > {C[fam]}")
+    KC.check_floor_rows(fam, got, ref, F, case, C=C[fam], seen=SEEN)
 
 
-def _guarded(n, dtype, fill):
-    """an output of n elements between two canaries"""
-    buf = torch.full((n + 2 * CANARY,), fill, dtype=dtype, device=DEV)
-    return buf, buf[CANARY:CANARY + n]
-
-
-def _canaries_intact(buf, n, fill):
-    b = buf.cpu()
-    return bool((b[:CANARY] == fill).all() and (b[CANARY + n:] == fill).all())
+def canaried(n, dtype, fill):
+    """an output of n elements, all `fill`, between two canaries of CANARY elements of `fill`"""
+    t = torch.full((n,), fill, dtype=dtype)
+    return KC.Banded(t, CANARY * t.element_size(), fill)
 
 
 # =====================================================================================================================
@@ -87,7 +57,7 @@ def _canaries_intact(buf, n, fill):
 def run_token(logits, V, ld, target, temperature=1.0, table=None, prev=None, want_lse=True, fill=float("nan")):
     """logits: float array [rows, V] of bf16-representable values, laid out in a [rows, ld] buffer whose other columns hold
     ``fill``.  Returns (logp, lse, hit) as numpy"""
-    lib, check, ptr, stream_ptr = _raw()
+    lib, check, ptr, stream_ptr = KC.raw()
     rows = logits.shape[0]
     buf = torch.full((rows, ld), fill, dtype=BF)
     buf[:, :V] = torch.as_tensor(logits).to(BF)
@@ -95,13 +65,12 @@ def run_token(logits, V, ld, target, temperature=1.0, table=None, prev=None, wan
     tgt = torch.as_tensor(np.asarray(target), dtype=torch.int32).to(DEV)
     pv = None if prev is None else torch.as_tensor(np.asarray(prev), dtype=torch.int32).to(DEV)
     tb = None if table is None else torch.from_numpy(np.ascontiguousarray(table).view(np.int32)).to(DEV)
-    lp_buf, lp = _guarded(rows, torch.float32, 777.0)
-    ls_buf, ls = _guarded(rows, torch.float32, 777.0)
-    ht_buf, ht = _guarded(rows, torch.int32, 777)
+    LP, LS, HT = canaried(rows, torch.float32, 777.0), canaried(rows, torch.float32, 777.0), canaried(rows, torch.int32, 777)
+    lp, ls, ht = LP.t, LS.t, HT.t
     check(lib.mgx_token_logprob(ptr(buf), V, ld, ptr(tgt), ptr(pv), ptr(tb), float(temperature), lp.data_ptr(),
                                 ls.data_ptr() if want_lse else None, ht.data_ptr(), rows, stream_ptr()), "mgx_token_logprob")
     torch.cuda.synchronize()
-    assert _canaries_intact(lp_buf, rows, 777.0) and _canaries_intact(ls_buf, rows, 777.0) and _canaries_intact(ht_buf, rows, 777)
+    assert LP.bands_intact() and LS.bands_intact() and HT.bands_intact()
     if not want_lse:
         assert (ls.cpu() == 777.0).all()
     return lp.cpu().numpy(), ls.cpu().numpy(), ht.cpu().numpy()
@@ -222,7 +191,7 @@ def test_token_logprob_non_finite_rows():
 
 
 def test_token_logprob_refusals():
-    lib, *_ = _raw()
+    lib, *_ = KC.raw()
     one = ctypes.c_void_p(16)
     assert lib.mgx_token_logprob(one, 0, 4, one, None, None, 1.0, one, None, one, 4, None) == -1
     assert lib.mgx_token_logprob(one, 8, 4, one, None, None, 1.0, one, None, one, 4, None) == -1          # ld < V
@@ -236,7 +205,7 @@ def test_token_logprob_refusals():
 # =====================================================================================================================
 def run_linear(a, w, bias, target, temperature=1.0):
     """w [V, K] and bias [V] sit inside larger buffers whose following rows / elements are NaN"""
-    lib, check, ptr, stream_ptr = _raw()
+    lib, check, ptr, stream_ptr = KC.raw()
     M, K = a.shape
     V = w.shape[0]
     wbuf = torch.full((V + 5, K), float("nan"), dtype=BF)
@@ -249,13 +218,12 @@ def run_linear(a, w, bias, target, temperature=1.0):
         bbuf = bbuf.to(DEV)
     ad = torch.as_tensor(a).to(BF).to(DEV)
     tgt = torch.as_tensor(np.asarray(target), dtype=torch.int32).to(DEV)
-    lp_buf, lp = _guarded(M, torch.float32, 777.0)
-    ls_buf, ls = _guarded(M, torch.float32, 777.0)
-    ht_buf, ht = _guarded(M, torch.int32, 777)
+    LP, LS, HT = canaried(M, torch.float32, 777.0), canaried(M, torch.float32, 777.0), canaried(M, torch.int32, 777)
+    lp, ls, ht = LP.t, LS.t, HT.t
     check(lib.mgx_linear_logprob(ptr(ad), ptr(wbuf), ptr(bbuf), ptr(tgt), float(temperature), lp.data_ptr(), ls.data_ptr(),
                                  ht.data_ptr(), M, V, K, stream_ptr()), "mgx_linear_logprob")
     torch.cuda.synchronize()
-    assert _canaries_intact(lp_buf, M, 777.0) and _canaries_intact(ls_buf, M, 777.0) and _canaries_intact(ht_buf, M, 777)
+    assert LP.bands_intact() and LS.bands_intact() and HT.bands_intact()
     return lp.cpu().numpy(), ls.cpu().numpy(), ht.cpu().numpy()
 
 
@@ -338,7 +306,7 @@ def test_linear_logprob_non_finite_rows():
 
 
 def test_linear_logprob_refusals():
-    lib, *_ = _raw()
+    lib, *_ = KC.raw()
     one = ctypes.c_void_p(16)
     for M, V, K in ((4, 8, 1088), (4, 8, 96), (4, 0, 64), (0, 8, 64), (4, 8, 0)):
         assert lib.mgx_linear_logprob(one, one, None, one, 1.0, one, None, one, M, V, K, None) == -1, (M, V, K)

@@ -1,69 +1,26 @@
 """generate_cached(samples_per_prompt=N) and generate.py --share-prompt: N continuations of every prompt over one shared prompt
 K/V cache (ABI 26).  The model, its reference parameters and the per-row check against the training forward (1e-2) and the
-CPU oracle (2e-2) are those of tests/test_gpu_ragged_decode.py."""
+CPU oracle (2e-2) are those of tests/decode_fixtures.py."""
 import glob
 import os
 
 import pytest
 import torch
 
+from decode_fixtures import check_rows, prompt_file, ragged_prior, tame_model
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 
 
-def _model(d=128, nl=2, L=96, V=337, seed=0):
-    from musicgeneration_amd.network import MusicTransformer
-    from oracle import ref_cpu as R
-    p0 = R.init_params(V, d, nl, L, seed=seed)
-    p0["Decoder.embedding.weight"] = p0["Decoder.embedding.weight"] * 0.1
-    for k in list(p0):
-        if k.endswith("rga.E"):
-            p0[k] = p0[k] * 0.2
-    mt = MusicTransformer(embedding_dim=d, vocab_size=V, num_layer=nl, max_seq=L, dropout=0.0)
-    mt.load_state_dict(p0)
-    return mt.cuda().eval(), p0
-
-
-def _ragged_prior(lens, V, g, fill=-7):
-    B, Pmax = len(lens), max(lens)
-    x = torch.randint(0, V - 1, (B, Pmax), generator=g)
-    for b, n in enumerate(lens):
-        x[b, n:] = fill                                           # ignored: anything may sit in the padding
-    return x
-
-
-def _check_rows(mt, p0, x, lens, N, n, toks, probs, V, rows=None, oracle=True, forward=True):
-    """row b * N + k: its prompt, n samples, pad_token; its distributions against the forward and the oracle on its own tokens"""
-    from oracle import ref_cpu as R
-    toks, probs = toks.cpu(), probs.cpu()
-    Pmax = x.shape[1]
-    assert toks.shape == (len(lens) * N, Pmax + n) and probs.shape == (len(lens) * N, Pmax + n, V)
-    for r in (range(len(lens) * N) if rows is None else rows):
-        P = lens[r // N]
-        assert torch.equal(toks[r, :P], x[r // N, :P].to(torch.int32)), r          # the prompt comes back unchanged
-        assert (toks[r, P + n:] == mt.pad_token).all(), r                          # then n samples, then padding
-        assert int(toks[r, P:P + n].max()) < V
-        seq = toks[r:r + 1, :P + n].long()
-        span = slice(P - 1, P + n - 1)                                             # the distributions after P-1 .. P+n-2
-        assert not probs[r, :P - 1].any() and not probs[r, P + n - 1:].any(), r
-        got = probs[r, span]
-        with torch.no_grad():
-            if forward:
-                fwd = torch.softmax(mt(seq.to(torch.int32).cuda())[0].float(), -1).cpu()[0, span]
-                assert (got - fwd).abs().max().item() < 1e-2, r
-            if oracle:
-                ref = torch.softmax(R.model_forward(p0, seq, V - 1)[0], -1)[0, span]
-                assert (got - ref).abs().max().item() < 2e-2, r
-
-
 def test_ragged_prompts_match_the_forward_and_the_oracle_per_row():
-    mt, p0 = _model()
+    mt, p0 = tame_model()
     V, n, N, lens = 337, 20, 4, [1, 7, 33]
-    x = _ragged_prior(lens, V, torch.Generator().manual_seed(17))
+    x = ragged_prior(lens, V, torch.Generator().manual_seed(17))
     toks, probs = mt.generate_cached(x.cuda(), n, top_p=0.95, seed=9, return_probs=True, prior_lengths=lens, samples_per_prompt=N)
     torch.cuda.synchronize()
-    _check_rows(mt, p0, x, lens, N, n, toks, probs, V)
+    check_rows(mt, p0, x, lens, N, n, toks, probs, V)
     # the samples of a prompt are independent draws
     t = toks.cpu().view(len(lens), N, -1)
     for b in range(len(lens)):
@@ -71,12 +28,12 @@ def test_ragged_prompts_match_the_forward_and_the_oracle_per_row():
 
 
 def test_more_than_32_rows_take_the_unfused_chain():
-    mt, p0 = _model()
+    mt, p0 = tame_model()
     V, n, N, lens = 337, 12, 12, [1, 7, 33]                                        # R = 36 rows
-    x = _ragged_prior(lens, V, torch.Generator().manual_seed(41))
+    x = ragged_prior(lens, V, torch.Generator().manual_seed(41))
     toks, probs = mt.generate_cached(x.cuda(), n, top_k=20, seed=2, return_probs=True, prior_lengths=lens, samples_per_prompt=N)
     torch.cuda.synchronize()
-    _check_rows(mt, p0, x, lens, N, n, toks, probs, V, rows=(0, 11, 12, 17, 24, 35))
+    check_rows(mt, p0, x, lens, N, n, toks, probs, V, rows=(0, 11, 12, 17, 24, 35))
 
 
 def test_a_long_prompt_on_the_split_key_path_matches_the_oracle():
@@ -84,17 +41,17 @@ def test_a_long_prompt_on_the_split_key_path_matches_the_oracle():
     V, L, n, N, lens = 337, 1280, 8, 3, [1100, 40]
     d = 64
     assert ops.rel_attn_decode_shared_splits(len(lens), N, max(lens) - 1, n, d) > 1
-    mt, p0 = _model(d=d, nl=1, L=L, V=V, seed=21)
-    x = _ragged_prior(lens, V, torch.Generator().manual_seed(29))
+    mt, p0 = tame_model(d=d, nl=1, L=L, V=V, seed=21)
+    x = ragged_prior(lens, V, torch.Generator().manual_seed(29))
     toks, probs = mt.generate_cached(x.cuda(), n, top_p=0.95, seed=4, return_probs=True, prior_lengths=lens, samples_per_prompt=N)
     torch.cuda.synchronize()
-    _check_rows(mt, p0, x, lens, N, n, toks, probs, V, rows=(0, 2, 3, 5), forward=False)
+    check_rows(mt, p0, x, lens, N, n, toks, probs, V, rows=(0, 2, 3, 5), forward=False)
 
 
 def test_same_seed_same_tokens_and_graph_replay_is_bitwise_the_eager_run():
-    mt, _ = _model(d=128, nl=2, L=160, V=337, seed=31)
+    mt, _ = tame_model(d=128, nl=2, L=160, V=337, seed=31)
     lens, N = [3, 40, 17], 5
-    x = _ragged_prior(lens, 337, torch.Generator().manual_seed(8)).cuda()
+    x = ragged_prior(lens, 337, torch.Generator().manual_seed(8)).cuda()
     kw = dict(top_p=0.95, seed=77, prior_lengths=lens, samples_per_prompt=N)
     ref = mt.generate_cached(x, 60, use_graph=False, **kw)
     for use_graph in (False, True):
@@ -115,9 +72,9 @@ def test_first_step_agrees_with_the_call_on_repeated_prompts():
     """same seed, the prompts repeated N times through the ragged call: the first sampled step's distributions agree to 1e-2
     (different kernels: not bitwise).  The share of rows whose tokens are identical throughout is printed, not asserted: a
     last-bit difference may flip a draw"""
-    mt, _ = _model()
+    mt, _ = tame_model()
     V, n, N, lens = 337, 20, 4, [1, 7, 33]
-    x = _ragged_prior(lens, V, torch.Generator().manual_seed(17)).cuda()
+    x = ragged_prior(lens, V, torch.Generator().manual_seed(17)).cuda()
     kw = dict(top_p=0.95, seed=9, return_probs=True)
     ts, ps = mt.generate_cached(x, n, prior_lengths=lens, samples_per_prompt=N, **kw)
     tr, pr = mt.generate_cached(x.repeat_interleave(N, 0), n, prior_lengths=[v for v in lens for _ in range(N)], **kw)
@@ -130,9 +87,9 @@ def test_first_step_agrees_with_the_call_on_repeated_prompts():
 
 
 def test_without_the_keyword_nothing_changes():
-    mt, _ = _model()
+    mt, _ = tame_model()
     lens = [1, 7, 33]
-    x = _ragged_prior(lens, 337, torch.Generator().manual_seed(17)).cuda()
+    x = ragged_prior(lens, 337, torch.Generator().manual_seed(17)).cuda()
     for kw in (dict(prior_lengths=lens), dict()):
         xx = x if kw else x[2:]
         a = mt.generate_cached(xx, 20, top_p=0.95, seed=9, **kw)
@@ -162,7 +119,7 @@ def test_one_token_prompt_with_a_grammar(tmp_path):
 
 
 def test_refusals_on_the_device():
-    mt, _ = _model()
+    mt, _ = tame_model()
     x = torch.randint(0, 300, (3, 40)).cuda()
     for kw in (dict(samples_per_prompt=17), dict(samples_per_prompt=2, window=64), dict(samples_per_prompt=2, kv_cache="fp8"),
                dict(samples_per_prompt=2, return_cache=True), dict(samples_per_prompt=2, length=57)):
@@ -173,13 +130,6 @@ def test_refusals_on_the_device():
 # ---------------------------------------------------------------------------------------------------------------------
 # generate.py --share-prompt
 # ---------------------------------------------------------------------------------------------------------------------
-def _prompt_file(path, n_notes, pitch0):
-    from musicgeneration_amd import smf
-    notes = [(80, pitch0 + (i % 12), 0.5 * i, 0.5 * i + 0.25) for i in range(n_notes)]
-    smf.write_notes(path, notes)
-    return notes
-
-
 def _head(f, want):
     from musicgeneration_amd.sequence import NoteSeq
     got = sorted(NoteSeq.from_midi_file(f).notes, key=lambda n_: (n_.start, n_.pitch))
@@ -190,7 +140,7 @@ def _head(f, want):
 def test_generate_cli_shares_one_prompt_file_between_the_batch(tmp_path, capsys):
     from musicgeneration_amd import generate
     a = str(tmp_path / "a.mid")
-    notes = _prompt_file(a, 11, 48)
+    notes = prompt_file(a, 11, 48)
     out = str(tmp_path / "gen") + "/"
     torch.manual_seed(0)
     generate.main(["-o", out, "-b", "4", "-l", "24", "--num-layers", "1", "--d-model", "128", "-M", "128", "-d", "", "--top-p", "0.9",
@@ -206,7 +156,7 @@ def test_generate_cli_shares_one_prompt_file_between_the_batch(tmp_path, capsys)
 def test_generate_cli_shares_each_condition_file_between_its_candidates(tmp_path, capsys):
     from musicgeneration_amd import generate
     a, b = str(tmp_path / "a.mid"), str(tmp_path / "b.mid")
-    notes = {a: _prompt_file(a, 3, 60), b: _prompt_file(b, 11, 48)}
+    notes = {a: prompt_file(a, 3, 60), b: prompt_file(b, 11, 48)}
     out = str(tmp_path / "gen") + "/"
     torch.manual_seed(0)
     generate.main(["-o", out, "-b", "5", "-l", "16", "--num-layers", "1", "--d-model", "128", "-M", "128", "-d", "", "--top-p", "0.9",

@@ -17,6 +17,8 @@ write is compared bit for bit."""
 import pytest
 import torch
 
+import kernel_checks as KC
+from kernel_checks import nothing_more_after_a_gpu_error  # noqa: F401 (the fixture is used by name)
 from oracle import decode_ref as D
 
 pytestmark = pytest.mark.gpu
@@ -38,13 +40,8 @@ CONFIGS = {
 }
 
 
-def _ops():
-    from musicgeneration_amd import ops
-    return ops
-
-
 def sample_counts():
-    nq = _ops().SHARED_NQ
+    nq = KC.ops().SHARED_NQ
     return sorted({1, 2, 3, nq, nq + 1, 16})
 
 
@@ -126,7 +123,7 @@ class SharedData:
         self.kpre, self.vpre, self.kown, self.vown = Kp.to(BF), Vp.to(BF), Ko.to(BF), Vo.to(BF)
         self.cpu = [t.cpu() for t in (self.kpre, self.vpre, self.kown, self.vown)]
         self.qkv_cpu, self.E_cpu = self.qkv.cpu(), self.E.cpu()
-        ops = _ops()
+        ops = KC.ops()
         got = ops.rel_attn_decode_shared_splits(BP, N, Lpre, Lown, d)
         assert got == self.nsplit, (cfg, N, got)
         self.ws = ops.rel_attn_decode_shared_workspace(BP, N, Lpre, Lown, d, DEV)
@@ -145,7 +142,7 @@ class SharedData:
     def run(self, pts):
         """one call with every poison in place; ``pts``: (p, t) per prompt.  Returns ctx on the CPU after checking what the call
         wrote and what it left alone"""
-        ops = _ops()
+        ops = KC.ops()
         N, R, Lpre, Lown, d = self.N, self.R, self.Lpre, self.Lown, DM
         p_b = torch.tensor([p for p, _ in pts], device=DEV)
         t_b = torch.tensor([t for _, t in pts], device=DEV)
@@ -217,7 +214,7 @@ def test_shared_attention_value_cases(name, kind):
     and in the last split with the runner-up in split 0; every logit near -200"""
     cfg = CONFIGS[name]
     Lpre, Lown, _, n = cfg
-    nq = _ops().SHARED_NQ
+    nq = KC.ops().SHARED_NQ
     full = (Lpre, Lpre + Lown - 1)
     todo = [(3, (full, (1, Lown))), (nq + 1, ((65, 74), full)), (16, ((0, Lown - 1), (Lpre, Lpre + 1)))]
     for N, pts in todo:
@@ -256,7 +253,7 @@ def test_a_single_key_returns_its_value_for_every_sample_count():
 def test_positions_outside_the_contract_touch_nothing():
     """the positions cannot be checked on the host: a prompt whose (t, p) break the contract leaves both caches as they were
     (its ctx rows are unspecified), and the prompt beside it is computed as always"""
-    ops = _ops()
+    ops = KC.ops()
     N = 3
     data = SharedData(CONFIGS["two"], N, seed=3)
     Lpre, Lown, M, d = data.Lpre, data.Lown, data.M, DM
@@ -277,7 +274,7 @@ def test_shared_call_beside_the_ragged_call_on_repeated_caches():
     """information, not an assertion beyond the bound both meet: mgx_rel_attn_decode_ragged on R rows whose caches are the
     prompt rows followed by the own rows (the repeated call's layout) computes the same logical attention; whether the two
     agree bitwise is printed (their split counts differ where decode_splits and the shared policy do)"""
-    ops = _ops()
+    ops = KC.ops()
     for name, N, pts in (("one", 3, ((65, 74), (200, 263))), ("two", ops.SHARED_NQ + 1, ((1000, 1499), (0, 63))),
                          ("eight", 16, ((4000, 4199), (63, 70)))):
         data = SharedData(CONFIGS[name], N, seed=4)
@@ -299,7 +296,7 @@ def test_shared_call_beside_the_ragged_call_on_repeated_caches():
 
 
 def test_shape_violations_are_refused_with_a_message():
-    ops = _ops()
+    ops = KC.ops()
     from musicgeneration_amd._lib import MgxError
     data = SharedData(CONFIGS["one"], 2, seed=5)
     pos = torch.zeros(data.R, dtype=torch.int32, device=DEV)

@@ -3,10 +3,7 @@ run on the host before any device work, so they are tested without a GPU."""
 import pytest
 import torch
 
-
-def _model(L=96):
-    from musicgeneration_amd.network import MusicTransformer
-    return MusicTransformer(embedding_dim=128, vocab_size=337, num_layer=1, max_seq=L, dropout=0.0)
+from decode_fixtures import host_model
 
 
 @pytest.mark.parametrize("lens,length,kw,msg", [
@@ -20,13 +17,13 @@ def _model(L=96):
 def test_prior_lengths_are_refused(lens, length, kw, msg):
     x = torch.randint(0, 300, (3, 40))
     with pytest.raises(ValueError, match=msg):
-        _model().generate_cached(x, length, prior_lengths=lens, **kw)
+        host_model().generate_cached(x, length, prior_lengths=lens, **kw)
 
 
 def test_ragged_batched_prefill_that_pads_past_max_seq_is_refused():
     x = torch.randint(0, 300, (2, 90))                             # 89 prefill rows pad to 96 > max_seq 92
     with pytest.raises(ValueError, match="max_seq=92"):
-        _model(L=92).generate_cached(x, 2, prior_lengths=[90, 3])
+        host_model(L=92).generate_cached(x, 2, prior_lengths=[90, 3])
 
 
 def _midi(path, n):

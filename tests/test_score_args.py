@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import score_ref
+from decode_fixtures import host_model
 
 WINDOWS = (2, 3, 5, 32, 33)
 
@@ -87,11 +88,6 @@ def test_reference_ties_and_non_finite_rows():
     assert s.tolist() == [-1.0, -np.inf] and c.tolist() == [2, 2] and h.tolist() == [1, 1] and m[0] == 3.0
 
 
-def _model(L=64, V=40, d=64):
-    from musicgeneration_amd.network import MusicTransformer
-    return MusicTransformer(embedding_dim=d, vocab_size=V, num_layer=1, max_seq=L, dropout=0.0)
-
-
 @pytest.mark.parametrize("kw,msg", [
     (dict(grammar=np.zeros((40, 2), np.uint32), logits="fp32"), "grammar"),
     (dict(logits="fp16"), "logits"),
@@ -109,7 +105,7 @@ def _model(L=64, V=40, d=64):
 def test_score_refusals_need_no_device(kw, msg):
     x = torch.randint(0, 39, (3, 50))                          # a CPU tensor: a refusal that came later would be MgxError
     with pytest.raises(ValueError, match=msg):
-        _model().score(x, **kw)
+        host_model(L=64, V=40, d=64).score(x, **kw)
     from musicgeneration_amd import scoring
     kw = dict(kw)
     with pytest.raises(ValueError, match=msg):
@@ -124,7 +120,7 @@ def test_check_args_resolves_the_logit_path_and_restores_the_mode():
     with pytest.raises(ValueError, match="1024"):
         scoring.check_args(64, 1088, 2, 50, logits="fp32")
     assert scoring.check_args(64, 64, 2, 50, window=33, from_pos=4, lengths=[50, 0])[1:] == (33, 16, [50, 0], [4, 4])
-    mt = _model()
+    mt = host_model(L=64, V=40, d=64)
     mt.train()
     with pytest.raises(ValueError):
         mt.score(torch.zeros(1, 4, dtype=torch.long), window=1)

@@ -3,10 +3,7 @@ decode.window_schedule plans, which the driver follows, and the refusals, which 
 import pytest
 import torch
 
-
-def _model(L=96):
-    from musicgeneration_amd.network import MusicTransformer
-    return MusicTransformer(embedding_dim=128, vocab_size=337, num_layer=1, max_seq=L, dropout=0.0)
+from decode_fixtures import host_model
 
 
 # lens, length, window, hop, the steps before which a re-anchor happens, the last step's base, the last step's t per row
@@ -81,11 +78,11 @@ def _check(model, x, length, **kw):
 def test_window_arguments_are_refused(shape, length, kw, L, msg):
     x = torch.randint(0, 300, shape)
     with pytest.raises(ValueError, match=msg):
-        _model(L).generate_cached(x, length, **kw)
+        host_model(L).generate_cached(x, length, **kw)
 
 
 def test_window_lifts_the_length_limit_and_nothing_else():
-    m = _model()
+    m = host_model()
     x = torch.randint(0, 300, (3, 40))
     # accepted: (P, lens, batched prefill, hop); the default hop is max(1, W // 8)
     assert _check(m, x[:, :5], 100, window=40) == (5, None, True, 5)
