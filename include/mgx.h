@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace */
-#define MGX_ABI_VERSION 26
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account */
+#define MGX_ABI_VERSION 27
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -500,6 +500,36 @@ int mgx_rel_attn_decode_shared(const uint16_t* qkv_new, const uint16_t* kpre, co
                                uint16_t* vown, const uint16_t* E, const int32_t* pos_rows, const int32_t* pre_rows,
                                uint16_t* ctx, void* workspace, size_t ws_bytes, int Bp, int N, int Lpre, int Lown, int d, int M,
                                void* stream);
+
+/* ---- Length budgets (ABI 27): every row of the KV-cache decode generates to a budget of its own -- seconds, bars, anything a
+ * table over the vocabulary can price -- and ends on its own.  The state lives on the device, so both calls are captured with the
+ * step:  cost int32 [V] (>= 0: what every id costs),  remaining int32 [B] (what row b may still spend; INT32_MAX = no budget),
+ * done int32 [B] (0 = live),  count int32 [B] (the events row b has kept).  A row is LIVE while done[b] == 0, and the two calls keep
+ * live => remaining[b] > 0.  A step is: logits, mgx_budget_mask, the sampler with advance != 0, mgx_budget_account.
+ * mgx_budget_mask, in place on the step's logits bf16 [B,ld] before the sampler: for a live row, logits[b,v] = -inf (0xFF80) for
+ *   every v < V with cost[v] > remaining[b].  Rows with done[b] != 0, columns >= V and every other id are left bit for bit.  The
+ *   mask is in the logits themselves, so it holds under top-k / top-p and under the sampler's grammar -- also when a grammar row
+ *   leaves no finite logit and is ignored.  (An id of cost 0 is never masked.)  One workgroup per row.
+ * mgx_budget_account, after the sampler and its advance.  The sampler has just written next_tok[b] to column
+ *   col = base + pos of out_tokens int32 [B,out_ld], with pos = pos_dev[b] (per_row != 0) or pos_dev[0] as it stands AFTER the
+ *   advance and base = base_dev[b] / base_dev[0] (NULL: 0; the window's base, ABI 21).  For a live row, with
+ *   c = cost[next_tok[b]]:  remaining[b] -= c, then
+ *     remaining[b] > 0:   count[b] += 1, the row stays live;
+ *     remaining[b] <= 0:  done[b] = 1 (after the mask this is remaining[b] == 0, and c > 0).  inclusive != 0: the token stays
+ *                         and count[b] += 1 -- the row lands exactly on its budget (seconds).  inclusive == 0: the token is
+ *                         dropped, out_tokens[b,col] = next_tok[b] = pad_token -- it closes what the budget counts and is not
+ *                         part of it (the N-th new `bar`).
+ *   For a row with done[b] != 0 on entry: out_tokens[b,col] = next_tok[b] = pad_token; its state is not touched.
+ *   Neither call moves a position: an ended row keeps stepping on pad tokens beside the others, so the shared counter, the
+ *   ragged step and mgx_decode_reanchor's t' >= 0 hold as they do without budgets.  Plain loads and stores, no atomics: the host
+ *   reads `done` between replays.  One thread per row.
+ * Contract (not checked: the values live on the device): 0 <= next_tok[b] < the entries of cost (a negative id costs 0);
+ *   a column outside 0..out_ld-1 is not written.                                                                           */
+int mgx_budget_mask(uint16_t* logits, int V, int ld, const int32_t* cost, const int32_t* remaining, const int32_t* done, int B,
+                    void* stream);
+int mgx_budget_account(int32_t* next_tok, int32_t* out_tokens, int out_ld, const int32_t* pos_dev, const int32_t* base_dev,
+                       int per_row, const int32_t* cost, int32_t* remaining, int32_t* done, int32_t* count, int pad_token,
+                       int inclusive, int B, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

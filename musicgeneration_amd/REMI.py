@@ -152,6 +152,17 @@ class REMI_EventSeq:
         return table
 
     @staticmethod
+    def bar_cost(vocab_size=None):
+        """what every id costs in bars, int32 [vocab_size]: 1 on ``bar``, 0 elsewhere (also on a model's pad id beyond dim()).
+        The cost table of ``MusicTransformer.generate_timed(..., inclusive=False)`` for a budget in bars"""
+        V = REMI_EventSeq.dim() if vocab_size is None else int(vocab_size)
+        if V < REMI_EventSeq.dim():
+            raise ValueError(f"vocab_size ({V}) is below the codec's {REMI_EventSeq.dim()} ids")
+        cost = np.zeros(V, dtype=np.int32)
+        cost[list(REMI_EventSeq.feat_ranges()['bar'])] = 1
+        return cost
+
+    @staticmethod
     def get_velocity_bins():
         n = REMI_EventSeq.velocity_range.stop - REMI_EventSeq.velocity_range.start
         return np.arange(REMI_EventSeq.velocity_range.start, REMI_EventSeq.velocity_range.stop,

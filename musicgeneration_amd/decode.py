@@ -9,7 +9,9 @@ matrix and every row's resume token and position on the device; ``KVCache`` is t
 (``SharedKVCache``: two of them, the prompts' and the rows' own); ``SubBatch`` holds the rows of one step with their buffers and
 is where a row's position lives (``pos``, on the device: one shared counter, or one per row when prompts differ in length);
 ``run_steps`` is the step loop, eager or captured (``replay_graphs``).  ``window_schedule`` is the host-side plan of the
-re-anchored window (``window=``, ``decode_window``), the one way to generate past max_seq with the cache."""
+re-anchored window (``window=``, ``decode_window``), the one way to generate past max_seq with the cache.  ``generate_timed`` is
+``generate_cached`` with a ``Budget``: every row's clock on the device (``decode_step_budget`` brackets the sampler with
+ops.budget_mask / ops.budget_account) and a step loop that reads the rows' ``done`` flags every ``poll`` steps and stops early."""
 from __future__ import annotations
 
 import dataclasses
@@ -381,10 +383,88 @@ def decode_step(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_int
                          row0=r.b0, ragged=ragged, base=r.base, **sampler)
 
 
-def replay_graphs(subs, steps: int, step_rows, before=None) -> None:
-    """one graph of ``step_rows(r)`` per sub-batch, each replayed ``steps`` times on its own stream: the sub-batches meet at the
-    end only, so their chains of launches overlap freely (parallel branches INSIDE one graph were measured to run in turn).
-    ``before(i, r)``: eager work on r's stream ahead of its replay i (the window's re-anchor)"""
+class Budget:
+    """the per-row length budgets of generate_timed (include/mgx.h, ABI 27).  On the host: ``budgets``, one int per row
+    (ops.NO_BUDGET: none), ``cost`` int32 [V] (numpy), ``inclusive``, ``poll``.  ``stage`` puts the clock on the device: ``cost``,
+    ``remaining`` [B], ``done`` [B] (set from the start for a budget of 0: the row generates nothing) and ``count`` [B].  The
+    step loop files ``steps_run``"""
+
+    def __init__(self, budgets, cost, pad_token: int, inclusive: bool, poll: int):
+        self.budgets, self.cost_host, self.pad_token, self.inclusive, self.poll = budgets, cost, pad_token, inclusive, poll
+        self.steps_run = 0
+
+    def stage(self, dev) -> "Budget":
+        self.cost = torch.from_numpy(self.cost_host).to(dev)
+        self.remaining = torch.tensor(self.budgets, dtype=torch.int32, device=dev)
+        self.done = (self.remaining == 0).to(torch.int32)
+        self.count = torch.zeros_like(self.remaining)
+        return self
+
+    def finished(self) -> bool:
+        """has every row ended?  One read of ``done``: the loop's only host synchronisation"""
+        return bool(self.done.min().item())
+
+    def until_poll(self, made: int) -> int:
+        """after ``made`` steps: the steps up to and including the next one whose number is a multiple of ``poll``"""
+        return self.poll - made % self.poll
+
+
+def check_budget_args(model, B: int, budget, cost, max_length: int, poll: int, refused: dict):
+    """every refusal of generate_timed that generate_cached does not make (ValueError), on the host.  Returns (one int32 budget
+    per row, ops.NO_BUDGET for None; cost as a numpy int32 [vocab_size])"""
+    import numpy as np
+    why = {"samples_per_prompt": "the shared prompt cache is another driver (generate_cached(samples_per_prompt=))",
+           "groups": "the budget clock covers the batch as one group",
+           "masked_groups": "the budget clock covers the batch as one group",
+           "return_cache": "an ended row's cache rows hold pad-token steps",
+           "beam_size": "beam search is another driver (generate_beam): a beam has no clock of its own"}
+    for name, value in refused.items():
+        if name not in why:
+            raise TypeError(f"generate_timed() got an unexpected keyword argument {name!r}")
+        if value and not (name == "groups" and int(value) == 1):
+            raise ValueError(f"generate_timed is not combined with {name} ({why[name]})")
+    if int(poll) < 1:
+        raise ValueError(f"poll must be >= 1 (the steps between two reads of the rows' done flags), got {poll}")
+    if int(max_length) < 1:
+        raise ValueError(f"max_length must be >= 1 (the cap on every row's events), got {max_length}")
+    V = model.vocab_size
+    arr = np.asarray(cost.detach().cpu() if isinstance(cost, torch.Tensor) else cost)
+    if arr.shape != (V,):
+        raise ValueError(f"cost must have one entry per id, [vocab_size] = [{V}], got shape {tuple(arr.shape)}")
+    if arr.dtype.kind not in "iu":
+        if arr.dtype.kind != "f" or not np.isfinite(arr).all() or (arr != np.rint(arr)).any():
+            raise ValueError(f"cost must hold integers (int32), got {arr.dtype}")
+    if (arr < 0).any():
+        raise ValueError(f"cost must be >= 0, got {arr.min()} at id {int(arr.argmin())}")
+    if (arr > ops.NO_BUDGET).any():
+        raise ValueError(f"cost must fit int32, got {arr.max()}")
+    if arr[model.pad_token] != 0:
+        raise ValueError(f"cost[pad_token] must be 0 (an ended row steps on pad tokens), got {arr[model.pad_token]}")
+    if isinstance(budget, (torch.Tensor, np.ndarray)):
+        budget = budget.tolist()
+    rows = list(budget) if isinstance(budget, (list, tuple)) else [budget] * B
+    if len(rows) != B:
+        raise ValueError(f"budget has {len(rows)} entries for a batch of {B} prompts")
+    rows = [ops.NO_BUDGET if v is None else v for v in rows]
+    for v in rows:
+        if v != int(v) or int(v) < 0:
+            raise ValueError(f"budget must be an integer >= 0 (or None: no budget), got {v}")
+        if int(v) > ops.NO_BUDGET:
+            raise ValueError(f"budget must fit int32, got {v}")
+    return [int(v) for v in rows], np.ascontiguousarray(arr.astype(np.int32))
+
+
+def decode_step_budget(w: Weights, r: SubBatch, sampler: dict, ragged: bool, bud: Budget) -> None:
+    """decode_step under the rows' budgets: the logits are masked before the sampler sees them and the draw is charged after it"""
+    logits = step_logits(w, r, ragged)
+    ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
+    ops.sample_topk_topp(logits, w.V, r.pos, r.tok, r.out, r.probs, advance=True, row0=r.b0, ragged=ragged, base=r.base, **sampler)
+    ops.budget_account(r.tok, r.out, r.pos, bud.cost, bud.remaining, bud.done, bud.count, bud.pad_token, bud.inclusive,
+                       ragged=ragged, base=r.base)
+
+
+def capture_graphs(subs, step_rows) -> None:
+    """one graph of ``step_rows(r)`` per sub-batch, captured on the sub-batch's own stream (the capture itself does not execute)"""
     cur = torch.cuda.current_stream()
     torch.cuda.synchronize()
     for r in subs:
@@ -392,27 +472,59 @@ def replay_graphs(subs, steps: int, step_rows, before=None) -> None:
         with torch.cuda.stream(r.stream):
             r.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(r.graph, stream=r.stream):
-                step_rows(r)                              # the capture itself does not execute
-    for i in range(steps):
+                step_rows(r)
+
+
+def replay_captured(subs, first: int, steps: int, before=None) -> None:
+    """replays ``first`` .. ``first + steps - 1`` of every sub-batch's captured graph, each on its own stream.  ``before(i, r)``:
+    eager work on r's stream ahead of replay i"""
+    for i in range(first, first + steps):
         for r in subs:
             with torch.cuda.stream(r.stream):
                 if before is not None:
                     before(i, r)
                 r.graph.replay()
+
+
+def replay_graphs(subs, steps: int, step_rows, before=None, budget=None, made_before: int = 0) -> int:
+    """one graph of ``step_rows(r)`` per sub-batch, each replayed ``steps`` times on its own stream: the sub-batches meet at the
+    end only, so their chains of launches overlap freely (parallel branches INSIDE one graph were measured to run in turn).
+    ``before(i, r)``: eager work on r's stream ahead of its replay i (the window's re-anchor).  ``budget`` (a staged Budget):
+    the replays go in runs that end on every budget.poll-th step of the call (``made_before`` steps ran ahead of the replays),
+    and after each the host reads ``done`` once -- the only synchronisation, made on the first sub-batch's stream once the
+    others have drained, so the current stream stays out of the loop -- and stops when every row has ended.  Returns the
+    replays made"""
+    capture_graphs(subs, step_rows)
+    made = 0
+    while made < steps:
+        run = steps - made if budget is None else min(steps - made, budget.until_poll(made_before + made))
+        replay_captured(subs, made, run, before)
+        made += run
+        if budget is not None and made < steps:
+            for r in subs[1:]:
+                r.stream.synchronize()
+            with torch.cuda.stream(subs[0].stream):
+                if budget.finished():
+                    break
+    cur = torch.cuda.current_stream()
     for r in subs:
         cur.wait_stream(r.stream)
     # the graphs, their private pools and the side streams must outlive the replays still in flight
     for r in subs:
         r.stream.synchronize()
+    return made
 
 
-def run_steps(subs, n_steps: int, step_rows, *, graph: bool, on_step=None, before=None) -> None:
+def run_steps(subs, n_steps: int, step_rows, *, graph: bool, on_step=None, before=None, budget=None) -> None:
     """``n_steps`` steps of ``step_rows(r)`` for every sub-batch.  The first runs eagerly on the current stream, the sub-batches
     one after the other, which also warms every kernel up before capture; the rest are captured once and replayed
     (replay_graphs) if ``graph`` is wanted, more than two remain and no step needs the host in between (``on_step``), else
     they run eagerly too.  ``on_step(s)``: host work after step s (filing its distribution); ``before(s)``: eager work ahead of
-    step s on the stream the step runs on (the window's re-anchor; one sub-batch only)"""
+    step s on the stream the step runs on (the window's re-anchor; one sub-batch only).  ``budget`` (a staged Budget): after
+    every ``budget.poll``-th step, eager or replayed, the host reads ``done`` and the loop stops once every row has ended;
+    ``budget.steps_run`` receives the steps made"""
     eager = 1 if graph and on_step is None and n_steps - 1 > 2 else n_steps
+    made = 0
     for s in range(eager):
         if before is not None:
             before(s)
@@ -420,8 +532,15 @@ def run_steps(subs, n_steps: int, step_rows, *, graph: bool, on_step=None, befor
             step_rows(r)
         if on_step is not None:
             on_step(s)
-    if eager < n_steps:
-        replay_graphs(subs, n_steps - eager, step_rows, before=None if before is None else lambda i, r: before(i + eager))
+        made = s + 1
+        if budget is not None and made < n_steps and made % budget.poll == 0 and budget.finished():
+            break
+    else:
+        if eager < n_steps:
+            made += replay_graphs(subs, n_steps - eager, step_rows, budget=budget, made_before=eager,
+                                  before=None if before is None else lambda i, r: before(i + eager))
+    if budget is not None:
+        budget.steps_run = made
 
 
 def probs_filer(subs, total: int, V: int, col0):
@@ -437,13 +556,14 @@ def probs_filer(subs, total: int, V: int, col0):
 
 
 def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length: int, window: int, hop: int, ragged: bool,
-                  step_rows, use_graph: bool, on_step, pad_token: int):
+                  step_rows, use_graph: bool, on_step, pad_token: int, budget=None):
     """the steps of generate_cached(window=): the cache holds window positions 0..window-1 only, and every time the longest
     row has filled it the window is re-anchored -- ops.decode_reanchor drops the oldest ``hop`` tokens of every row (pos -= hop,
     base += hop) and gathers the remaining ones, which one batched causal pass turns back into cache rows 0.. .  The schedule is
     window_schedule's, known on the host, so nothing is read back; the step graph is captured once and replayed across the
-    re-anchors, which run eagerly on the graph's stream.  ``lens``: every row's prompt length; ``r``: the whole batch.  Returns
-    the window position of every row's last input token"""
+    re-anchors, which run eagerly on the graph's stream.  ``lens``: every row's prompt length; ``r``: the whole batch;
+    ``budget``: run_steps's (the schedule is indexed by step, so stopping early needs nothing here).  Returns the window position
+    of every row's last input token"""
     dev, B = prior_i.device, prior_i.shape[0]
     base0, t0 = window_start(lens, window)
     _, ts, anchors = window_schedule(lens, length, window, hop)
@@ -464,13 +584,15 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
         if s in anchors:
             ops.decode_reanchor(r.pos, r.base, r.out, seq, hop, pad_token, ragged=ragged)
             prefill_batched(w, cache, seq, n)
-    run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=on_step, before=reanchor)
+    run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=on_step, before=reanchor, budget=budget)
     return ts[-1] if ts else t0
 
 
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
-                    return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None):
-    """MusicTransformer.generate_cached (documented there)"""
+                    return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None,
+                    bud: Optional[Budget] = None):
+    """MusicTransformer.generate_cached (documented there).  ``bud``: generate_timed's budgets, not yet staged -- the steps run
+    decode_step_budget and the loop stops once every row has ended"""
     P, lens, batched, hop = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache, window, hop, groups,
                                        masked_groups, samples_per_prompt, return_cache)
     sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
@@ -511,11 +633,17 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
         w = Weights(model, st, fused=B <= 32 and d <= 1024)
         probs_all, file = probs_filer(subs, total, V, pos_rows.long()) if return_probs else (None, None)
 
+        if bud is not None:
+            bud.stage(dev)
+
         def step_rows(r):                                     # length 0 still runs the last prompt token (its distribution)
-            decode_step(w, r, sampler, ragged, length > 0)
+            if bud is not None:
+                decode_step_budget(w, r, sampler, ragged, bud)
+            else:
+                decode_step(w, r, sampler, ragged, length > 0)
         if window is not None:
             final_t = decode_window(w, subs[0], cache, prior_i, lens or [P] * B, length, window, hop, ragged, step_rows,
-                                    use_graph, file, model.pad_token)
+                                    use_graph, file, model.pad_token, bud)
         else:
             if first > 0:                                     # positions 0..P-2 in one pass; token P-1 takes the first step below
                 prefill_batched(w, cache, prior_i[:, :first])
@@ -527,7 +655,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
                 if return_probs:
                     file(p - (P - 1))                         # the distribution after column p
                 tok.copy_(prior_i[:, p + 1])
-            run_steps(subs, max(length, 1), step_rows, graph=use_graph, on_step=file)
+            run_steps(subs, max(length, 1), step_rows, graph=use_graph, on_step=file, budget=bud)
     if return_cache and window is not None:               # what earlier windows and the prefill left beyond the last step's row
         cache.zero_rows_from(torch.tensor(final_t, dtype=torch.int32, device=dev) + 1)
     elif return_cache and ragged:                         # prefill rows a short row's decode never reached
@@ -563,6 +691,27 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
         # length 0 still runs the last prompt token (its distribution)
         run_steps([r], max(length, 1), lambda r_: decode_step(w, r_, sampler, True, length > 0), graph=use_graph, on_step=file)
     return (out, probs_all) if return_probs else out
+
+
+def generate_timed(model, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,
+                   prior_lengths, kv_cache, window, hop, return_probs, refused):
+    """MusicTransformer.generate_timed (documented there): generate_cached's driver with a Budget"""
+    B = prior.shape[0]
+    budgets, cost_i = check_budget_args(model, B, budget, cost, max_length, poll, refused)
+    check_args(model, prior, max_length, return_probs, "auto", prior_lengths, kv_cache, window, hop)     # before any device work
+    bud = Budget(budgets, cost_i, model.pad_token, bool(inclusive), int(poll))
+    res = generate_cached(model, prior, max_length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, "auto",
+                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud)
+    tokens, probs = res if return_probs else (res, None)
+    # what every row spent: the cost of the events it kept, columns P_b .. P_b + count_b - 1
+    start = torch.tensor(_prompt_lengths(prior, prior_lengths) or [prior.shape[1]] * B, device=tokens.device)[:, None]
+    cols = torch.arange(tokens.shape[1], device=tokens.device)[None, :]
+    kept = (cols >= start) & (cols < start + bud.count[:, None])
+    spent = torch.where(kept, bud.cost[tokens.long()], 0).sum(1)
+    info = dict(steps_run=bud.steps_run, spent=spent, remaining=bud.remaining, done=bud.done.bool())
+    if return_probs:
+        info["probs"] = probs
+    return tokens, bud.count, info
 
 
 # ---- beam search ------------------------------------------------------------------------------------------------------------

@@ -65,6 +65,12 @@ def get_options(argv=None):
                       help='KV-cache decode of the samples of one prompt over ONE copy of its K/V: with -c FILE (or --grammar) the '
                            '-b x --best-of samples (16 at most) share the prompt, with --condition-files the --best-of N candidates '
                            'of every file do (the prompt is prefilled once, not once per sample)')
+    parser.add_option('--seconds', dest='seconds', type='float', default=None,
+                      help='generate S seconds of music after the prompt (--repr midi_like; KV-cache decode with a per-sample clock '
+                           'on the device): every sample ends exactly on S, in 0.01 s units, and -l becomes the cap on its events')
+    parser.add_option('--bars', dest='bars', type='int', default=None,
+                      help='generate N bars (--repr remi): every sample ends where its N-th new bar token would begin, and -l '
+                           'becomes the cap on its events.  With --grammar: exactly N bars after the one-bar prompt')
     return parser.parse_args(argv)[0]
 
 
@@ -110,6 +116,49 @@ def _check_share_prompt(o):
     if not 1 <= n <= 16:
         raise SystemExit(f'--share-prompt decodes at most 16 samples per prompt, got {n}'
                          + (' (--best-of)' if o.condition_files is not None else ' (-b x --best-of)'))
+
+
+def _check_timed(o):
+    """--seconds / --bars against the options a length budget does not offer, before any model or device work.  Returns the
+    keyword arguments of generate_timed that the flag sets (None without either)"""
+    if o.seconds is None and o.bars is None:
+        return None
+    if o.seconds is not None and o.bars is not None:
+        raise SystemExit('--seconds and --bars are two budgets for one clock: give one')
+    flag, need = ('--seconds', 'midi_like') if o.seconds is not None else ('--bars', 'remi')
+    if o.repr != need:
+        raise SystemExit(f'{flag} prices the events of --repr {need}, got --repr {o.repr}')
+    for on, what, why in ((o.beam_size, '-B/--beam-size', 'a beam has no clock of its own'),
+                          (o.share_prompt, '--share-prompt', 'the shared prompt cache is another decode driver'),
+                          (o.best_of > 1, '--best-of', 'candidates of different lengths are not ranked against each other'),
+                          (o.reference_mask, '--reference-mask', 'the KV-cache decode is causal')):
+        if on:
+            raise SystemExit(f'{flag} cannot be combined with {what} ({why})')
+    from .sequence import TIME_UNITS_PER_SECOND
+    budget = int(round(TIME_UNITS_PER_SECOND * o.seconds)) if o.seconds is not None else o.bars
+    if budget < 0:
+        raise SystemExit(f'{flag} must be >= 0, got {o.seconds if o.seconds is not None else o.bars}')
+    return dict(budget=budget, inclusive=o.seconds is not None)
+
+
+def _timed(o, mt, timed, prior, lens=None, **kw):
+    """--seconds / --bars: the samples through generate_timed, each trimmed to its prompt and the events it kept"""
+    if o.seconds is not None:
+        from .sequence import EventSeq
+        cost, unit = EventSeq.time_cost(mt.vocab_size), 'x 0.01 s'
+    else:
+        from .REMI import REMI_EventSeq
+        cost, unit = REMI_EventSeq.bar_cost(mt.vocab_size), 'bars'
+    tokens, lengths, info = mt.generate_timed(prior, timed['budget'], cost, o.max_len, inclusive=timed['inclusive'],
+                                              temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, prior_lengths=lens,
+                                              kv_cache=o.kv_cache, window=o.window or None, hop=o.hop or None, **kw)
+    tokens, lengths, done, spent = tokens.cpu().numpy(), lengths.tolist(), info['done'].tolist(), info['spent'].tolist()
+    lens = lens or [prior.shape[1]] * len(lengths)
+    print('Budget {} {}: {} steps for at most {} events'.format(timed['budget'], unit, info['steps_run'], o.max_len))
+    for i, (n, ended) in enumerate(zip(lengths, done)):
+        if not ended:
+            print('Sample {}: reached -l {} events first ({} of {} {})'.format(i, o.max_len, spent[i], timed['budget'], unit))
+    return [row[:p + n] for row, p, n in zip(tokens, lens, lengths)]
 
 
 def _best_of(o, mt, res, prompt_lens, grammar=None):
@@ -159,11 +208,12 @@ def main(argv=None):
     _check_best_of(o)
     _check_beam_options(o)
     _check_share_prompt(o)
+    timed = _check_timed(o)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
         raise SystemExit('--reference-mask cannot be combined with --window (the KV-cache decode is causal)')
-    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size):
+    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size or timed):
         raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
                          '(or -B K; the default sampler recomputes the window and keeps no cache)')
     # with --window every branch below samples through the KV-cache decode and its re-anchored window
@@ -195,6 +245,9 @@ def main(argv=None):
         return res.cpu().numpy()
     if ragged is not None:
         prior, lens = ragged
+        if timed:
+            _write(o, _timed(o, mt, timed, prior.to(device), lens))
+            return
         if o.share_prompt:                                 # the N candidates of a file over one copy of its prompt
             res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                      prior_lengths=lens, samples_per_prompt=o.best_of).cpu().numpy()
@@ -238,11 +291,17 @@ def main(argv=None):
         if o.beam_size:
             _write(o, search(prior, grammar=Codec.next_token_table()))
             return
+        if timed:
+            _write(o, _timed(o, mt, timed, prior, grammar=Codec.next_token_table()))
+            return
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  grammar=Codec.next_token_table(), **cached).cpu().numpy()
         res = _best_of(o, mt, res, [1] * rows, Codec.next_token_table())
     elif o.beam_size:
         res = search(prior)
+    elif timed:
+        _write(o, _timed(o, mt, timed, prior))
+        return
     elif o.share_prompt:                                   # -c FILE: one prompt, -b x --best-of samples
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  samples_per_prompt=rows).cpu().numpy()

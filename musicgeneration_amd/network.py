@@ -405,6 +405,33 @@ class MusicTransformer(torch.nn.Module):
                                       samples_per_prompt)
 
     @torch.no_grad()
+    def generate_timed(self, prior: torch.Tensor, budget, cost, max_length: int, *, inclusive: bool = True, poll: int = 32,
+                       temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, use_graph: bool = True,
+                       grammar=None, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
+                       hop: Optional[int] = None, return_probs: bool = False, **refused):
+        """Generate to a musical length: ``generate_cached`` where every row stops at a budget of its own instead of after a
+        number of events.  ``cost`` (int32-representable [vocab_size], >= 0, 0 at pad_token) prices every id --
+        ``EventSeq.time_cost`` in centiseconds, ``REMI_EventSeq.bar_cost`` in bars -- and ``budget`` (an int, or one per row;
+        None = no budget) is what a row's CONTINUATION may cost; ``max_length`` caps its events.  A budget of 0 generates
+        nothing.  Each row keeps its clock on the device (include/mgx.h, ABI 27): before the sampler every id that costs more
+        than the row has left is masked out of the logits (mgx_budget_mask), so no row overshoots -- also under top-k / top-p
+        and ``grammar`` -- and after it the draw is charged (mgx_budget_account) and a row whose budget is spent ends.
+        ``inclusive=True``: the token that spends the last unit stays, so the row lands exactly on its budget (seconds);
+        ``inclusive=False``: that token is dropped -- the N-th new ``bar`` closes bar N and is not part of it.  An ended row
+        goes on stepping on pad tokens beside the others (positions never stop), and after every ``poll`` steps the host reads
+        the rows' flags once -- the only synchronisation -- and stops when all have ended, so the call costs the steps of its
+        longest row rounded up to ``poll``, not ``max_length``.  (A row with only a few units left waits for an id cheap
+        enough -- a short time shift -- and may reach ``max_length`` first: it then has spent less than its budget.)  The other arguments are ``generate_cached``'s (prefill "auto").
+        Returns (tokens int32 [B, Pmax+max_length]: prompt, kept events, then pad_token;  lengths int32 [B]: the events every
+        row kept;  info: ``steps_run``, ``spent`` int64 [B] (the cost of the kept events), ``remaining`` and ``done`` [B] as the
+        device left them, and ``probs`` f32 [B, Pmax+max_length, V] with ``return_probs`` -- the distributions the sampler saw,
+        0 at every masked id).  Refused (ValueError, before any device work): ``samples_per_prompt``, ``groups`` > 1,
+        ``masked_groups``, ``return_cache``, ``beam_size`` (other drivers), a malformed ``cost``, ``poll`` < 1, ``budget`` < 0,
+        ``max_length`` < 1, and what ``generate_cached`` refuses."""
+        return decode.generate_timed(self, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed,
+                                     use_graph, grammar, prior_lengths, kv_cache, window, hop, return_probs, refused)
+
+    @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,
                       seed: int = 0, grammar=None, prior_lengths=None, kv_cache: str = "bf16", use_graph: bool = True,
                       return_beams: bool = False):

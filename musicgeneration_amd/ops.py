@@ -825,6 +825,58 @@ def decode_reanchor(pos_dev, base, out_tokens, seq, hop, pad_token, *, ragged=Fa
     return seq
 
 
+# ---- length budgets on the decode path (ABI 27; contracts in include/mgx.h) ------------------------------------------
+NO_BUDGET = 2 ** 31 - 1                                   # remaining = INT32_MAX: the row has no budget
+
+
+def _check_budget_state(what, B, cost, **rows):
+    """the budget state: cost int32 [V], remaining / done / count int32 [B], all contiguous"""
+    if cost.dtype != torch.int32 or cost.dim() != 1 or not cost.is_contiguous():
+        raise ValueError(f"{what}: cost must be a contiguous int32 tensor [V], got {cost.dtype} {tuple(cost.shape)}")
+    for name, t in rows.items():
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
+
+
+def budget_mask(logits, V, cost, remaining, done):
+    """in place, before the sampler: logits bf16 [B, ld] of a live row (done[b] == 0) get -inf at every id v < V with
+    cost[v] > remaining[b]; done rows, columns >= V and every other id stay bit for bit"""
+    _need_cuda(logits, cost, remaining, done)
+    B = remaining.numel()
+    ld = logits.shape[-1]
+    if logits.dtype != torch.bfloat16 or logits.numel() != B * ld:
+        raise ValueError(f"budget_mask: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    _check_budget_state("budget_mask", B, cost, remaining=remaining, done=done)
+    if not 0 < int(V) <= min(ld, cost.numel()):
+        raise ValueError(f"budget_mask: V must lie in 1 .. min(ld, the entries of cost) = {min(ld, cost.numel())}, got {V}")
+    check(_lib.load().mgx_budget_mask(ptr(logits), int(V), ld, ptr(cost), ptr(remaining), ptr(done), B, stream_ptr()),
+          "mgx_budget_mask")
+    return logits
+
+
+def budget_account(next_tok, out_tokens, pos_dev, cost, remaining, done, count, pad_token, inclusive=True, *, ragged=False,
+                   base=None):
+    """after the sampler and its advance: charges cost[next_tok[b]] to every live row, ends the rows whose budget is spent
+    (``inclusive``: the last token stays; else it becomes pad_token) and writes pad_token over what an ended row sampled --
+    next_tok[b] and out_tokens[b, base + pos], the column the sampler has just written.  ``ragged`` / ``base`` as in
+    sample_topk_topp"""
+    _need_cuda(next_tok, out_tokens, pos_dev, base, cost, remaining, done, count)
+    B = remaining.numel()
+    _check_pos_rows(pos_dev, B, ragged)
+    if base is not None:
+        _check_base(base, pos_dev, "budget_account")
+    _check_budget_state("budget_account", B, cost, next_tok=next_tok, remaining=remaining, done=done, count=count)
+    if pos_dev.dtype != torch.int32 or pos_dev.numel() < 1:
+        raise ValueError(f"budget_account: the positions must be int32, got {pos_dev.dtype} with {pos_dev.numel()} entries")
+    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B:
+        raise ValueError(f"budget_account: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
+                         f"{tuple(out_tokens.shape)}")
+    check(_lib.load().mgx_budget_account(ptr(next_tok), ptr(out_tokens), out_tokens.shape[1], ptr(pos_dev), ptr(base),
+                                         1 if ragged else 0, ptr(cost), ptr(remaining), ptr(done), ptr(count), int(pad_token),
+                                         1 if inclusive else 0, B, stream_ptr()), "mgx_budget_account")
+    return next_tok
+
+
 # ---- beam search on the decode path (ABI 22; contracts in include/mgx.h) ---------------------------------------------
 def _check_int32_rows(what, R, **ts):
     for name, t in ts.items():

@@ -26,6 +26,7 @@ DEFAULT_NORMALIZATION_BASELINE = 60
 USE_VELOCITY = True
 BEAT_LENGTH = 60 / DEFAULT_TEMPO
 DEFAULT_TIME_SHIFT_BINS = 0.01 * np.arange(1, 101)
+TIME_UNITS_PER_SECOND = 100                 # EventSeq.time_cost counts centiseconds: every time_shift bin is a whole number of them
 DEFAULT_VELOCITY_STEPS = 32
 DEFAULT_NOTE_LENGTH = BEAT_LENGTH * 2
 MIN_NOTE_LENGTH = BEAT_LENGTH / 2
@@ -128,6 +129,19 @@ class EventSeq:
         n = EventSeq.velocity_range.stop - EventSeq.velocity_range.start
         return np.arange(EventSeq.velocity_range.start, EventSeq.velocity_range.stop,
                          n / (EventSeq.velocity_steps - 1))
+
+    @staticmethod
+    def time_cost(vocab_size=None):
+        """what every id costs in time, int32 [vocab_size] in units of 1 / TIME_UNITS_PER_SECOND s: rint(100 * bin) on the
+        time_shift ids, 0 elsewhere -- also on the ids a model adds beyond dim() (its pad id).  The cost table of
+        ``MusicTransformer.generate_timed`` for a budget in seconds"""
+        V = EventSeq.dim() if vocab_size is None else int(vocab_size)
+        if V < EventSeq.dim():
+            raise ValueError(f"vocab_size ({V}) is below the codec's {EventSeq.dim()} ids")
+        cost = np.zeros(V, dtype=np.int32)
+        ts = EventSeq.feat_ranges()['time_shift']
+        cost[ts.start:ts.stop] = np.rint(TIME_UNITS_PER_SECOND * np.asarray(EventSeq.time_shift_bins)).astype(np.int32)
+        return cost
 
     # ---- index array <-> events --------------------------------------------------------------------
     @staticmethod
