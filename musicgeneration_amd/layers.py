@@ -24,6 +24,14 @@ from . import ops
 ALIGN = 64  # elements; keeps every fp32/bf16 view 128-byte aligned
 
 
+def seed_stride(num_layers: int) -> int:
+    """How far the dropout seed of a training forward lies from the previous forward's.  One forward uses seed (embedding),
+    seed + 4 i + 1 (layer i, LayerNorm 1) and seed + 4 i + 2 (LayerNorm 2), 4 * num_layers - 2 at the most: 64 up to 16 layers
+    (the seeds those models always had), 4 per layer beyond, where 64 would hand layer 16 the seeds of the next forward's
+    layer 0."""
+    return max(64, 4 * num_layers)
+
+
 def sinusoid(max_seq: int, embedding_dim: int) -> np.ndarray:
     """float64 [1, max_seq, d] table; same values as the reference's nested loops (layers.py:9-19)."""
     pos = np.arange(max_seq, dtype=np.float64)[:, None]
@@ -175,13 +183,16 @@ class EncoderLayer(torch.nn.Module):
         self.dropout2 = torch.nn.Dropout(rate)
         self._seed_ctr = 0
 
-    def forward(self, x, mask=None, **kwargs):
-        """layers.py:152-161 on its own (see RelativeGlobalAttention.forward): -> (out2, attention weights)"""
+    def forward(self, x, mask=None, seed=None, **kwargs):
+        """layers.py:152-161 on its own (see RelativeGlobalAttention.forward): -> (out2, attention weights).
+        ``seed``: the dropout seed of this call (LayerNorm 1 uses seed + 1, LayerNorm 2 seed + 2).  Encoder.forward hands every
+        layer its own; a layer called on its own counts its calls."""
         attn_out, w = self.rga([x, x, x], mask)
         bf = torch.bfloat16
         p = self.rate if self.training else 0.0
-        self._seed_ctr += 1
-        seed = (torch.initial_seed() * 1000003 + self._seed_ctr * 64) & 0x7FFFFFFFFFFFFFFF
+        if seed is None:
+            self._seed_ctr += 1
+            seed = (torch.initial_seed() * 1000003 + self._seed_ctr * 64) & 0x7FFFFFFFFFFFFFFF
         # dropout is fused into the residual + LayerNorm kernel (mask = pure function of (seed, element index))
         out1 = ops.add_ln_std(attn_out.to(bf).contiguous(), x.to(bf).contiguous(), self.layernorm1.weight, self.layernorm1.bias,
                               self.layernorm1.eps, p, seed + 1)
@@ -331,10 +342,12 @@ class Encoder(torch.nn.Module):
         tok = x.to(torch.int32).contiguous()
         p = self.rate if self.training else 0.0
         self._seed_ctr += 1
-        seed = (torch.initial_seed() * 1000003 + self._seed_ctr * 64) & 0x7FFFFFFFFFFFFFFF
+        seed = (torch.initial_seed() * 1000003 + self._seed_ctr * seed_stride(self.num_layers)) & 0x7FFFFFFFFFFFFFFF
         h = _EmbedStd.apply(tok, self.embedding.weight, self.pos_encoding.table()[: tok.shape[1]].contiguous(), p, seed)
-        for layer in self.enc_layers:
-            h, w = layer(h, mask)
+        for i, layer in enumerate(self.enc_layers):
+            # the seed plan of the flat path (network._hidden): left to themselves the layers, which all count the same calls, would
+            # all drop the same elements
+            h, w = layer(h, mask, seed=seed + 4 * i)
             weights.append(w)
         return h.float(), weights
 

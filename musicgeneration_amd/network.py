@@ -14,7 +14,7 @@ from typing import Optional
 import torch
 
 from . import config, decode, ops
-from .layers import Encoder, EncoderLayer, FlatStore
+from .layers import Encoder, EncoderLayer, FlatStore, seed_stride
 
 
 class MusicTransformer(torch.nn.Module):
@@ -96,10 +96,12 @@ class MusicTransformer(torch.nn.Module):
 
     def _next_seed(self) -> int:
         # under data parallelism every rank usually calls torch.manual_seed with the same value: the rank enters the seed, or
-        # all ranks would draw the same dropout masks for their (different) rows
+        # all ranks would draw the same dropout masks for their (different) rows.  One call uses seed .. seed + 4 * num_layer - 2
+        # (_hidden), so consecutive calls lie seed_stride apart: 64 up to 16 layers, more beyond
         self._seed_ctr += 1
         rank = self._dp.rank if self._dp is not None else 0
-        return ((torch.initial_seed() + 0x9E3779B9 * rank) * 1000003 + self._seed_ctr * 64) & 0x7FFFFFFFFFFFFFFF
+        return ((torch.initial_seed() + 0x9E3779B9 * rank) * 1000003
+                + self._seed_ctr * seed_stride(self.num_layer)) & 0x7FFFFFFFFFFFFFFF
 
     # ------------------------------------------------------------------------------------------
     # the hot path: tokens -> logits                 network.py:37-39 + layers.py:223-233,152-161

@@ -38,6 +38,65 @@ def _lin(x, w, b):
 
 
 # --------------------------------------------------------------------------------------
+# dropout with injected masks
+# --------------------------------------------------------------------------------------
+# The kernels' dropout mask is a pure function of (seed, element index) (oracle/train_ref.py: make_drop / hash32 / drop_mult), so
+# a test can hand the oracle the very multipliers (0 or the keep scale) a training step applied.  ``drop`` maps a site to its
+# multiplier tensor: "emb" -> [B,L,d]; ("ln1", i) and ("ln2", i) -> [B,L,d] of layer i; ("gru", l) -> [T,B,H] on the output of GRU
+# layer l.  A site that is missing is not dropped.  A value (m_fwd, m_bwd) multiplies by m_fwd forward and by m_bwd backward
+# (SplitMult): an oracle that is wrong on purpose, for the tests that show that a bound notices a backward under another mask.
+# Where the multiplier goes is where the kernel applies it (include/mgx.h K1, K6, mgx_dropout_bf16): the embedding inside its
+# single bf16 rounding; a LayerNorm site in fp32 on the already-rounded branch output, before the residual add; the GRU output
+# followed by one bf16 rounding.
+class SplitMult(torch.autograd.Function):
+    """y = x * m_fwd, dx = dy * m_bwd"""
+
+    @staticmethod
+    def forward(ctx, x, m_fwd, m_bwd):
+        ctx.save_for_backward(m_bwd)
+        return x * m_fwd
+
+    @staticmethod
+    def backward(ctx, dy):
+        (m_bwd,) = ctx.saved_tensors
+        return dy * m_bwd, None, None
+
+
+def _mul(t: torch.Tensor, m) -> torch.Tensor:
+    if m is None:
+        return t
+    if isinstance(m, tuple):
+        return SplitMult.apply(t, m[0].to(t.dtype), m[1].to(t.dtype))
+    return t * m.to(t.dtype)
+
+
+def site_mult(p_drop: float, seed: int, B: int, L: int, d: int, Lp: Optional[int] = None) -> torch.Tensor:
+    """the multipliers [B,L,d] of one dropout site of the model: the twin's mask over the rows the KERNEL runs on, [B * Lp, d]
+    with Lp = L rounded up to the attention's 32-key tile (MusicTransformer pads the tokens; pass Lp = L for the stand-alone
+    Encoder, whose row-wise kernels see the unpadded rows), cut to the real rows.  The keep scale is the twin's
+    fp32(1 / (1 - thr / 65536)), not 1 / (1 - p)."""
+    from . import train_ref
+    Lp = (L + 31) // 32 * 32 if Lp is None else Lp
+    return train_ref.drop_mult(p_drop, seed, B * Lp * d).view(B, Lp, d)[:, :L]
+
+
+def model_drop(p_drop: float, seed: int, nl: int, B: int, L: int, d: int, Lp: Optional[int] = None) -> dict:
+    """``drop`` of one training forward that drew ``seed``: embedding seed, layer i LN1 seed + 4 i + 1, LN2 seed + 4 i + 2"""
+    drop = {"emb": site_mult(p_drop, seed, B, L, d, Lp)}
+    for i in range(nl):
+        drop["ln1", i] = site_mult(p_drop, seed + 4 * i + 1, B, L, d, Lp)
+        drop["ln2", i] = site_mult(p_drop, seed + 4 * i + 2, B, L, d, Lp)
+    return drop
+
+
+def gru_drop(p_drop: float, seed: int, nl: int, T: int, B: int, H: int) -> dict:
+    """``drop`` of Event_Melody_RNN.Train over T steps (the primary step included): nn.GRU's inter-layer dropout, on the output
+    [T * B, H] of every layer but the last, layer l with seed + l"""
+    from . import train_ref
+    return {("gru", l): train_ref.drop_mult(p_drop, seed + l, T * B * H).view(T, B, H) for l in range(nl - 1)}
+
+
+# --------------------------------------------------------------------------------------
 # masks / positional table
 # --------------------------------------------------------------------------------------
 def look_ahead_mask(x: torch.Tensor, pad: int) -> torch.Tensor:
@@ -95,10 +154,13 @@ def attn_core(qkv: torch.Tensor, E: torch.Tensor, mask: Optional[torch.Tensor], 
     return _r((w @ v).permute(0, 2, 1, 3).reshape(B, L, d)), w, logits
 
 
-def rga_forward(p: Params, prefix: str, x: torch.Tensor, mask: Optional[torch.Tensor], h: int
+def rga_forward(p: Params, prefix: str, x: torch.Tensor, mask: Optional[torch.Tensor], h: int, round_p: bool = False
                 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """RelativeGlobalAttention.forward with q=k=v=x.           layers.py:64-109
-    returns (out [B,L,d], attention_weights [B,h,L,L])"""
+    returns (out [B,L,d], attention_weights [B,h,L,L])
+    round_p (with EMULATE_BF16): the softmax enters the P V product rounded to bf16.  The attention kernel feeds exp(s - m), m its
+    softmax reference, to that product as bf16 -- a rounding the emulation cannot reproduce; this is one of the same size, and the
+    distance between the two emulations says how far a correct kernel may lie from the emulated oracle."""
     B, L, d = x.shape
     dh = d // h
 
@@ -113,22 +175,23 @@ def rga_forward(p: Params, prefix: str, x: torch.Tensor, mask: Optional[torch.Te
     if mask is not None:
         logits = logits + (mask.to(torch.int64) * -1e9).to(logits.dtype)   # layers.py:99-100
     w = torch.softmax(logits, -1)
-    ctx = _r((w @ v).permute(0, 2, 1, 3).reshape(B, L, d))
+    ctx = _r(((_r(w) if round_p else w) @ v).permute(0, 2, 1, 3).reshape(B, L, d))
     return _lin(ctx, p[prefix + "fc.weight"], p[prefix + "fc.bias"]), w
 
 
 # --------------------------------------------------------------------------------------
 # encoder layer / model
 # --------------------------------------------------------------------------------------
-def encoder_layer(p: Params, pre: str, x: torch.Tensor, mask, h: int, rate: float, training: bool):
-    """EncoderLayer.forward (post-LN, eps 1e-6, FFN d -> d/2 -> d, ReLU).   layers.py:152-161"""
+def encoder_layer(p: Params, pre: str, x: torch.Tensor, mask, h: int, rate: float, training: bool, drop=None):
+    """EncoderLayer.forward (post-LN, eps 1e-6, FFN d -> d/2 -> d, ReLU).   layers.py:152-161
+    drop = (LN1 multipliers, LN2 multipliers) replaces F.dropout (rate / training are then unused); None: as before"""
     d = x.shape[-1]
     a, w = rga_forward(p, pre + "rga.", x, mask, h)
-    a = F.dropout(a, rate, training)
+    a = F.dropout(a, rate, training) if drop is None else _mul(a, drop[0])
     o1 = _r(F.layer_norm(a + x, (d,), p[pre + "layernorm1.weight"], p[pre + "layernorm1.bias"], 1e-6))
     f = F.relu(_lin(o1, p[pre + "FFN_pre.weight"], p[pre + "FFN_pre.bias"]))
     f = _lin(f, p[pre + "FFN_suf.weight"], p[pre + "FFN_suf.bias"])
-    f = F.dropout(f, rate, training)
+    f = F.dropout(f, rate, training) if drop is None else _mul(f, drop[1])
     o2 = _r(F.layer_norm(o1 + f, (d,), p[pre + "layernorm2.weight"], p[pre + "layernorm2.bias"], 1e-6))
     return o2, w
 
@@ -140,28 +203,30 @@ def num_layers_of(p: Params) -> int:
     return n
 
 
-def decoder_stack(p: Params, x: torch.Tensor, mask, rate: float = 0.0, training: bool = False):
-    """Encoder.forward: emb*sqrt(d) + PE, dropout, N layers.      layers.py:223-233"""
+def decoder_stack(p: Params, x: torch.Tensor, mask, rate: float = 0.0, training: bool = False, drop=None):
+    """Encoder.forward: emb*sqrt(d) + PE, dropout, N layers.      layers.py:223-233
+    drop: injected multipliers per site (see above) in place of F.dropout; None: as before"""
     emb = p["Decoder.embedding.weight"]
     d = emb.shape[1]
     h = d // 64                                             # layers.py:219
     L = x.shape[1]
     hcur = emb[x.long()] * math.sqrt(d)
-    hcur = _r(hcur + sinusoid_table(L, d).to(hcur.dtype)[None])
-    hcur = F.dropout(hcur, rate, training)
+    hcur = hcur + sinusoid_table(L, d).to(hcur.dtype)[None]
+    hcur = F.dropout(_r(hcur), rate, training) if drop is None else _r(_mul(hcur, drop.get("emb")))
     ws = []
     for li in range(num_layers_of(p)):
-        hcur, w = encoder_layer(p, f"Decoder.enc_layers.{li}.", hcur, mask, h, rate, training)
+        hcur, w = encoder_layer(p, f"Decoder.enc_layers.{li}.", hcur, mask, h, rate, training,
+                                None if drop is None else (drop.get(("ln1", li)), drop.get(("ln2", li))))
         ws.append(w)
     return hcur, ws
 
 
 def model_forward(p: Params, x: torch.Tensor, pad: int, rate: float = 0.0, training: bool = False,
-                  causal: bool = True):
+                  causal: bool = True, drop=None):
     """MusicTransformer.forward (train/eval branch).          network.py:35-40
-    causal=False restates generate()'s mask=None call (network.py:60-62)."""
+    causal=False restates generate()'s mask=None call (network.py:60-62).  drop: see decoder_stack."""
     mask = look_ahead_mask(x, pad) if causal else None
-    hcur, ws = decoder_stack(p, x, mask, rate, training)
+    hcur, ws = decoder_stack(p, x, mask, rate, training, drop)
     return _lin(hcur, p["fc.weight"], p["fc.bias"]), ws
 
 
@@ -260,8 +325,9 @@ def gru_init_hidden(p: Params, init: torch.Tensor, layers: int, hidden: int) -> 
     return out.view(layers, init.shape[0], hidden)
 
 
-def gru_step(p: Params, event: torch.Tensor, hid: torch.Tensor):
-    """event int64 [1,B], hid [layers,B,H] -> (logits [1,B,V], hid').  Gate order r,z,n (torch GRU)."""
+def gru_step(p: Params, event: torch.Tensor, hid: torch.Tensor, drop=None):
+    """event int64 [1,B], hid [layers,B,H] -> (logits [1,B,V], hid').  Gate order r,z,n (torch GRU).
+    drop: per layer, the multipliers [B,H] on what the layer hands to the NEXT one (its own hidden state stays whole) or None"""
     x = p["event_embedding.weight"][event[0]]
     new = []
     for l in range(hid.shape[0]):
@@ -274,22 +340,31 @@ def gru_step(p: Params, event: torch.Tensor, hid: torch.Tensor):
         n = torch.tanh(inn + r * hn)
         x = (1 - z) * n + z * hid[l]
         new.append(x)
+        if drop is not None and drop[l] is not None:
+            x = _r(_mul(x, drop[l]))
     return F.linear(x, p["output_fc.weight"], p["output_fc.bias"])[None], torch.stack(new)
 
 
 def gru_train_logits(p: Params, init: torch.Tensor, events: torch.Tensor, layers: int, hidden: int,
-                     primary_event: int) -> torch.Tensor:
+                     primary_event: int, drop=None) -> torch.Tensor:
     """Event_Melody_RNN.Train (network.py:109-116 -> SeqForward :63-84): the primary event as step 0, then the
     teacher-forced ``events`` int64 [T,B], through the GRU from ``init_to_hidden(init)``; logits [T+1,B,V].
-    Dropout between layers is off (eval / dropout=0), as in the golden fixture G8."""
+    Dropout between layers is off (eval / dropout=0), as in the golden fixture G8, unless ``drop`` injects it: ("gru", l) ->
+    multipliers [T+1,B,H] on layer l's output (gru_drop)."""
     hid = gru_init_hidden(p, init, layers, hidden)
     B = init.shape[0]
     ev = torch.full((1, B), primary_event, dtype=torch.long)
+
+    def at(t):
+        if drop is None:
+            return None
+        ms = [drop.get(("gru", l)) for l in range(layers)]
+        return [None if m is None else tuple(k[t] for k in m) if isinstance(m, tuple) else m[t] for m in ms]
     outs = []
-    o, hid = gru_step(p, ev, hid)
+    o, hid = gru_step(p, ev, hid, at(0))
     outs.append(o)
     for t in range(events.shape[0]):
-        o, hid = gru_step(p, events[t:t + 1].long(), hid)
+        o, hid = gru_step(p, events[t:t + 1].long(), hid, at(t + 1))
         outs.append(o)
     return torch.cat(outs, 0)
 

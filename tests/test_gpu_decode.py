@@ -169,8 +169,10 @@ def test_gru_train_backward_matches_oracle_autograd(B, T, H, nl):
 
 
 def test_gru_train_dropout_is_consistent():
-    """nn.GRU's inter-layer dropout in training mode: the backward uses the forward's mask (finite-difference check of
-    one weight through the dropped path) and eval mode ignores it."""
+    """nn.GRU's inter-layer dropout: eval mode ignores it (two calls agree bit for bit), training mode applies it, a pinned
+    ``dropout_seed`` repeats the mask and another seed draws another, and the gradients through the dropped path are finite.
+    That the backward uses the forward's mask is checked where the masks are known, against the oracle under the same masks:
+    tests/test_gpu_dropout_model.py::test_gru_training_with_inter_layer_dropout_matches_the_masked_oracle."""
     from musicgeneration_amd.melody_rnn import Event_Melody_RNN
     torch.manual_seed(5)
     net = Event_Melody_RNN(init_dim=8, event_dim=40, hidden_dim=64, rnn_layers=2, dropout=0.5).cuda()
@@ -183,6 +185,9 @@ def test_gru_train_dropout_is_consistent():
     assert not torch.allclose(c, a, atol=1e-3)                       # dropout active
     c.float().pow(2).sum().backward()
     assert all(torch.isfinite(q.grad).all() for q in net.parameters())
+    with torch.no_grad():
+        d, e, f = (net.Train(init, events, dropout_seed=s) for s in (11, 11, 12))
+    assert torch.equal(d, e) and not torch.allclose(d, f, atol=1e-3)
 
 
 
