@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account */
-#define MGX_ABI_VERSION 27
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS */
+#define MGX_ABI_VERSION 28
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -530,6 +530,45 @@ int mgx_budget_mask(uint16_t* logits, int V, int ld, const int32_t* cost, const 
 int mgx_budget_account(int32_t* next_tok, int32_t* out_tokens, int out_ld, const int32_t* pos_dev, const int32_t* base_dev,
                        int per_row, const int32_t* cost, int32_t* remaining, int32_t* done, int32_t* count, int pad_token,
                        int inclusive, int B, void* stream);
+
+/* ---- Held-note state (ABI 28): every row of the KV-cache decode carries the set of notes it holds, so the sampler can be kept
+ * to well-formed streams -- no note_off of a silent pitch, no note_on of a sounding one -- and to a cap on polyphony.  The state
+ * lives on the device, so both calls are captured with the step:  rule int32 [V]: rule[v] = +(k+1): id v SETS bit k (a note_on
+ * of key k), -(k+1): id v CLEARS bit k (its note_off), 0: id v touches no bit; 0 <= k < 32 * MGX_NOTE_WORDS, and a value outside
+ * -128 .. 128 counts as 0 in both calls.  state int32 [B, MGX_NOTE_WORDS]: bit k of row b lives in word k >> 5 at bit k & 31.
+ * A step is: logits, (mgx_budget_mask,) the sampler's first draw, mgx_notes_mask, the sampler, mgx_notes_keep, (mgx_budget_account,)
+ * mgx_notes_account.
+ * mgx_notes_mask, in place on the step's logits bf16 [B,ld] before the sampler, with n_b = popcount(state[b]) as the call finds it:
+ *   for every v < V with a set-rule:    logits[b,v] = -inf (0xFF80) if the bit is set or n_b >= max_on;
+ *   for every v < V with a clear-rule:  logits[b,v] = -inf if the bit is clear.
+ *   Ids with rule 0, columns >= V, rule and state are left bit for bit.  1 <= max_on <= 128; 128 is no cap (a set-rule id of a
+ *   clear bit is then always allowed).  The mask is in the logits themselves, so it holds under top-k / top-p.  Where every bit
+ *   with a set-rule has a clear-rule and the reverse, the mask never empties a row that had a finite logit on those ids: a set
+ *   bit's clear id stays, with no bit set every set id stays (max_on >= 1), and rule-0 ids always stay.  One workgroup per row.
+ * mgx_notes_account, after the sampler (and after mgx_budget_account, whose pad_token then freezes an ended row: its rule is 0):
+ *   tok = next_tok[b]; for 0 <= tok < V, rule[tok] = +(k+1) sets bit k of state[b] and -(k+1) clears it, whatever the bit was --
+ *   no validity check, so the state is the fold of the rules over the tokens behind an unmasked sampler too: a bit is set iff the
+ *   last token that touched it set it.  Any other tok and rule 0 leave the row as it is.  Writes nothing but state.  Plain loads
+ *   and stores, no atomics.  One thread per row.
+ * mgx_notes_keep makes a constrained row the unconstrained row of the same seed for as long as that one is legal.  The sampler
+ *   draws by inverse CDF, so a draw from the masked logits differs from the unmasked draw of the same random number even where
+ *   the latter was legal.  The step therefore draws twice: FIRST from the logits as they stand before mgx_notes_mask, with the
+ *   call's seed, into first_tok int32 [B] (no advance, no column written); then mgx_notes_mask; then from the masked logits with
+ *   ANOTHER seed, into next_tok and its column, with the advance.  mgx_notes_keep then, for every row whose first_tok[b] = t is
+ *   legal -- 0 <= t < V and mgx_notes_mask, as called with this state and max_on, does not ban t -- writes next_tok[b] = t and
+ *   out_tokens[b, col] = t, col = base + pos as in mgx_budget_account (the column the second draw was written to; out_tokens
+ *   NULL or a column outside 0..out_ld-1: not written).  Other rows keep the second draw.  With independent random numbers the
+ *   token has exactly the masked distribution when neither top_k nor top_p cuts: p(t) + p(banned) p(t) / (1 - p(banned)).
+ *   Under top-k / top-p the first draw is filtered from the unmasked, the second from the masked logits; the token is legal
+ *   either way.  Reads state, writes next_tok and that column only.  One thread per row.
+ * MGX_ERR_NULL for a NULL pointer, MGX_ERR_SHAPE unless B > 0, V > 0 (mask: ld >= V; mask, keep: 1 <= max_on <= 128).
+ * Contract (not checked: the values live on the device): rule has at least V entries.                                      */
+#define MGX_NOTE_WORDS 4
+int mgx_notes_mask(uint16_t* logits, int V, int ld, const int32_t* rule, const int32_t* state, int max_on, int B, void* stream);
+int mgx_notes_account(const int32_t* next_tok, const int32_t* rule, int32_t* state, int V, int B, void* stream);
+int mgx_notes_keep(const int32_t* first_tok, int32_t* next_tok, int32_t* out_tokens, int out_ld, const int32_t* pos_dev,
+                   const int32_t* base_dev, int per_row, const int32_t* rule, const int32_t* state, int max_on, int V, int B,
+                   void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

@@ -10,8 +10,10 @@ matrix and every row's resume token and position on the device; ``KVCache`` is t
 is where a row's position lives (``pos``, on the device: one shared counter, or one per row when prompts differ in length);
 ``run_steps`` is the step loop, eager or captured (``replay_graphs``).  ``window_schedule`` is the host-side plan of the
 re-anchored window (``window=``, ``decode_window``), the one way to generate past max_seq with the cache.  ``generate_timed`` is
-``generate_cached`` with a ``Budget``: every row's clock on the device (``decode_step_budget`` brackets the sampler with
-ops.budget_mask / ops.budget_account) and a step loop that reads the rows' ``done`` flags every ``poll`` steps and stops early."""
+``generate_cached`` with a ``Budget``: every row's clock on the device (``decode_step_constrained`` brackets the sampler with
+ops.budget_mask / ops.budget_account) and a step loop that reads the rows' ``done`` flags every ``poll`` steps and stops early.
+``NoteState`` (``note_rules=``, ``max_polyphony=``) is the second per-row state bracketing the sampler the same way: the set of
+notes every row holds (ops.notes_mask / ops.notes_account), which keeps a MIDI-like stream well-formed."""
 from __future__ import annotations
 
 import dataclasses
@@ -19,10 +21,12 @@ from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import ops
 from .ops import BF16
+from .sequence import held_bits
 
 
 class KVCache:
@@ -412,7 +416,6 @@ class Budget:
 def check_budget_args(model, B: int, budget, cost, max_length: int, poll: int, refused: dict):
     """every refusal of generate_timed that generate_cached does not make (ValueError), on the host.  Returns (one int32 budget
     per row, ops.NO_BUDGET for None; cost as a numpy int32 [vocab_size])"""
-    import numpy as np
     why = {"samples_per_prompt": "the shared prompt cache is another driver (generate_cached(samples_per_prompt=))",
            "groups": "the budget clock covers the batch as one group",
            "masked_groups": "the budget clock covers the batch as one group",
@@ -454,13 +457,90 @@ def check_budget_args(model, B: int, budget, cost, max_length: int, poll: int, r
     return [int(v) for v in rows], np.ascontiguousarray(arr.astype(np.int32))
 
 
-def decode_step_budget(w: Weights, r: SubBatch, sampler: dict, ragged: bool, bud: Budget) -> None:
-    """decode_step under the rows' budgets: the logits are masked before the sampler sees them and the draw is charged after it"""
+class NoteState:
+    """the per-row held-note state of generate_cached(note_rules=) (include/mgx.h, ABI 28).  On the host: ``rule`` int32 [V]
+    (numpy; check_note_args) and ``max_on``, the cap on the notes a row holds (ops.NOTE_BITS: none).  ``stage`` puts ``rule``
+    and ``state`` int32 [rows, ops.NOTE_WORDS] on the device, with ``first`` int32 [rows], where a step keeps its first draw"""
+
+    SECOND_SEED = 0x9E3779B97F4A7C15                      # added to the call's seed (mod 2^64) for a step's second draw
+
+    def __init__(self, rule, max_polyphony=None):
+        self.rule_host, self.max_on = rule, ops.NOTE_BITS if max_polyphony is None else int(max_polyphony)
+
+    @staticmethod
+    def fold(rule, ids):
+        """the state words (numpy uint32 [ops.NOTE_WORDS]) after ``ids``: the bits whose last toucher set them"""
+        words = np.zeros(ops.NOTE_WORDS, dtype=np.uint32)
+        for k in held_bits(rule, ids):
+            words[k >> 5] |= np.uint32(1) << np.uint32(k & 31)
+        return words
+
+    def stage(self, dev, prior, lens, repeat: int = 1) -> "NoteState":
+        """``prior`` [B, P] with the prompts' lengths ``lens`` (a list): every row starts from what its OWN prompt leaves held,
+        folded once on the host -- well-formed or not, above the cap or not; row b * repeat + n belongs to prompt b"""
+        rows = np.asarray(prior.detach().cpu())
+        state = np.stack([self.fold(self.rule_host, rows[b, :n]) for b, n in enumerate(lens)]).view(np.int32)
+        self.rule = torch.from_numpy(self.rule_host).to(dev)
+        self.state = torch.from_numpy(state).to(dev).repeat_interleave(repeat, 0).contiguous()
+        self.first = torch.zeros(self.state.shape[0], dtype=torch.int32, device=dev)      # every row's first draw of a step
+        return self
+
+
+def check_note_args(model, note_rules, max_polyphony, *, grammar=None, groups=None, masked_groups=False, return_cache=False):
+    """every refusal of note_rules / max_polyphony (ValueError), on the host.  Returns a NoteState, or None without note_rules"""
+    if note_rules is None:
+        if max_polyphony is not None:
+            raise ValueError("max_polyphony caps the notes that note_rules counts: it needs note_rules")
+        return None
+    for on, name, why in ((grammar is not None, "grammar", "the two masks together can leave a row no id, and no codec needs both"),
+                          ((groups or 1) > 1 or masked_groups, "groups / masked_groups", "the note state covers the batch as one group"),
+                          (return_cache, "return_cache", "the caller of return_cache continues a decode whose note state is not returned")):
+        if on:
+            raise ValueError(f"note_rules is not combined with {name} ({why})")
+    if max_polyphony is not None and (max_polyphony != int(max_polyphony) or not 1 <= int(max_polyphony) <= ops.NOTE_BITS):
+        raise ValueError(f"max_polyphony must be an integer in 1 .. {ops.NOTE_BITS} (None: no cap), got {max_polyphony}")
+    V = model.vocab_size
+    arr = np.asarray(note_rules.detach().cpu() if isinstance(note_rules, torch.Tensor) else note_rules)
+    if arr.shape != (V,) or arr.dtype.kind not in "iu":
+        raise ValueError(f"note_rules must be integers, one per id, [vocab_size] = [{V}], got {arr.dtype} {tuple(arr.shape)}")
+    arr = arr.astype(np.int64)
+    if arr[model.pad_token] != 0:
+        raise ValueError(f"note_rules[pad_token] must be 0 (an ended row steps on pad tokens), got {arr[model.pad_token]}")
+    if (np.abs(arr) > ops.NOTE_BITS).any():
+        v = int(np.abs(arr).argmax())
+        raise ValueError(f"note_rules must lie in -{ops.NOTE_BITS} .. {ops.NOTE_BITS} (bit k is +-(k + 1)), got {arr[v]} at id {v}")
+    sets, clears = set((arr[arr > 0] - 1).tolist()), set((-arr[arr < 0] - 1).tolist())
+    if sets != clears:
+        raise ValueError(f"every bit of note_rules needs an id that sets it and one that clears it (else the mask could leave a "
+                         f"row no id): bits {sorted(sets ^ clears)[:8]} have only one of the two")
+    return NoteState(np.ascontiguousarray(arr.astype(np.int32)), max_polyphony)
+
+
+def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_into_out: bool, bud: Optional[Budget],
+                            notes: Optional[NoteState]) -> None:
+    """decode_step under the rows' budgets and / or held notes: the logits are masked before the sampler sees them, and the draw
+    is charged to the clock and applied to the notes after it.  With ``notes`` the step draws twice (below)"""
     logits = step_logits(w, r, ragged)
-    ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
-    ops.sample_topk_topp(logits, w.V, r.pos, r.tok, r.out, r.probs, advance=True, row0=r.b0, ragged=ragged, base=r.base, **sampler)
-    ops.budget_account(r.tok, r.out, r.pos, bud.cost, bud.remaining, bud.done, bud.count, bud.pad_token, bud.inclusive,
-                       ragged=ragged, base=r.base)
+    if bud is not None:
+        ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
+    out = r.out if sample_into_out else None
+    if notes is not None:
+        # the sampler draws by inverse CDF, so a draw from the masked logits is another token even where the unmasked draw of
+        # the same random number was legal.  Hence two draws: the first from the logits as they stand, with the call's seed and
+        # nothing written but notes.first; the second, below, from the masked logits with a seed of its own; notes_keep then
+        # puts a legal first draw in the second's place, and the row is the unconstrained row until that one breaks a rule
+        ops.sample_topk_topp(logits, w.V, r.pos, notes.first, None, None, advance=False, row0=r.b0, ragged=ragged, base=r.base,
+                             **sampler)
+        ops.notes_mask(logits, w.V, notes.rule, notes.state, notes.max_on)
+        sampler = dict(sampler, seed=(int(sampler["seed"]) + NoteState.SECOND_SEED) % 2 ** 64)
+    ops.sample_topk_topp(logits, w.V, r.pos, r.tok, out, r.probs, advance=True, row0=r.b0, ragged=ragged, base=r.base, **sampler)
+    if notes is not None:
+        ops.notes_keep(notes.first, r.tok, out, r.pos, notes.rule, notes.state, notes.max_on, w.V, ragged=ragged, base=r.base)
+    if bud is not None:
+        ops.budget_account(r.tok, r.out, r.pos, bud.cost, bud.remaining, bud.done, bud.count, bud.pad_token, bud.inclusive,
+                           ragged=ragged, base=r.base)
+    if notes is not None:
+        ops.notes_account(r.tok, notes.rule, notes.state, w.V)
 
 
 def capture_graphs(subs, step_rows) -> None:
@@ -590,14 +670,17 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
 
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
                     return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None,
-                    bud: Optional[Budget] = None):
+                    bud: Optional[Budget] = None, note_rules=None, max_polyphony=None):
     """MusicTransformer.generate_cached (documented there).  ``bud``: generate_timed's budgets, not yet staged -- the steps run
-    decode_step_budget and the loop stops once every row has ended"""
+    decode_step_constrained and the loop stops once every row has ended"""
+    notes = check_note_args(model, note_rules, max_polyphony, grammar=grammar, groups=groups, masked_groups=masked_groups,
+                            return_cache=return_cache)
     P, lens, batched, hop = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache, window, hop, groups,
                                        masked_groups, samples_per_prompt, return_cache)
     sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     if samples_per_prompt is not None:
-        return generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs)
+        return generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs,
+                               notes)
     extra, prior, ragged = prior.shape[1] - P, prior[:, :P], lens is not None      # extra > 0: equal prior_lengths below the width
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -635,10 +718,12 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
 
         if bud is not None:
             bud.stage(dev)
+        if notes is not None:                                 # what every prompt leaves held; the prefill below stays unconstrained
+            notes.stage(dev, prior, lens or [P] * B)
 
         def step_rows(r):                                     # length 0 still runs the last prompt token (its distribution)
-            if bud is not None:
-                decode_step_budget(w, r, sampler, ragged, bud)
+            if bud is not None or notes is not None:
+                decode_step_constrained(w, r, sampler, ragged, bud is not None or length > 0, bud, notes)
             else:
                 decode_step(w, r, sampler, ragged, length > 0)
         if window is not None:
@@ -668,12 +753,13 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     return (res, *(cache.grow(extra) if extra else cache).result()) if return_cache else res
 
 
-def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, grammar, use_graph: bool, return_probs: bool):
+def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, grammar, use_graph: bool, return_probs: bool,
+                    notes: Optional[NoteState] = None):
     """generate_cached(samples_per_prompt=N), its arguments checked: rows r = b * N + n, sample n of prompt b.  One batched
     prefill of the Bp prompts fills the prompt cache (pre_rows = len_b - 1 rows each); every row then resumes at its prompt's
     last token and runs the ragged step on R = Bp * N rows, whose attention reads the prompt's rows once for the samples of a
     prompt and appends to the row's own cache.  Row r draws with (seed, t, r), as it does in the call on the prompts repeated N
-    times"""
+    times.  ``notes``: a NoteState, not yet staged -- every row starts from its prompt's held notes"""
     with decode_session(model) as st:
         (Bp, P), dev = prior.shape, st.param.device
         R, total, d, V = Bp * N, P + length, model.embedding_dim, model.vocab_size
@@ -688,20 +774,27 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
                            V if return_probs else None)
         sampler = dict(sampling, allow_table=ops.grammar_table(grammar, dev))
         probs_all, file = probs_filer([r], total, V, pos.long()) if return_probs else (None, None)
-        # length 0 still runs the last prompt token (its distribution)
-        run_steps([r], max(length, 1), lambda r_: decode_step(w, r_, sampler, True, length > 0), graph=use_graph, on_step=file)
+        if notes is not None:
+            notes.stage(dev, prior, lens, repeat=N)
+
+        def step_rows(r_):                                    # length 0 still runs the last prompt token (its distribution)
+            if notes is not None:
+                decode_step_constrained(w, r_, sampler, True, length > 0, None, notes)
+            else:
+                decode_step(w, r_, sampler, True, length > 0)
+        run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=file)
     return (out, probs_all) if return_probs else out
 
 
 def generate_timed(model, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,
-                   prior_lengths, kv_cache, window, hop, return_probs, refused):
+                   prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules=None, max_polyphony=None):
     """MusicTransformer.generate_timed (documented there): generate_cached's driver with a Budget"""
     B = prior.shape[0]
     budgets, cost_i = check_budget_args(model, B, budget, cost, max_length, poll, refused)
     check_args(model, prior, max_length, return_probs, "auto", prior_lengths, kv_cache, window, hop)     # before any device work
     bud = Budget(budgets, cost_i, model.pad_token, bool(inclusive), int(poll))
     res = generate_cached(model, prior, max_length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, "auto",
-                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud)
+                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud, note_rules, max_polyphony)
     tokens, probs = res if return_probs else (res, None)
     # what every row spent: the cost of the events it kept, columns P_b .. P_b + count_b - 1
     start = torch.tensor(_prompt_lengths(prior, prior_lengths) or [prior.shape[1]] * B, device=tokens.device)[:, None]

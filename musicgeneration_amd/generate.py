@@ -71,6 +71,15 @@ def get_options(argv=None):
     parser.add_option('--bars', dest='bars', type='int', default=None,
                       help='generate N bars (--repr remi): every sample ends where its N-th new bar token would begin, and -l '
                            'becomes the cap on its events.  With --grammar: exactly N bars after the one-bar prompt')
+    parser.add_option('--well-formed', dest='well_formed', action='store_true', default=False,
+                      help='keep every sample a well-formed note stream (--repr midi_like; KV-cache decode with the set of held '
+                           'notes per sample on the device): no note_off of a silent pitch, no note_on of a sounding one, '
+                           'counted from what the prompt leaves sounding')
+    parser.add_option('--max-polyphony', dest='max_polyphony', type='int', default=None,
+                      help='at most K notes sounding at once (1 .. 128): no note_on while K are held.  Implies --well-formed')
+    parser.add_option('--release', dest='release', action='store_true', default=False,
+                      help='close the notes a sample still holds where it ends: their note_off events are appended before the '
+                           'MIDI file is written (--repr midi_like; with --seconds: after the events the sample kept)')
     return parser.parse_args(argv)[0]
 
 
@@ -141,6 +150,31 @@ def _check_timed(o):
     return dict(budget=budget, inclusive=o.seconds is not None)
 
 
+def _check_notes(o):
+    """--well-formed / --max-polyphony / --release against the options they do not go with, before any model or device work.
+    Returns whether sampling is constrained (--max-polyphony implies --well-formed)"""
+    well = o.well_formed or o.max_polyphony is not None
+    if not well and not o.release:
+        return False
+    flag = '--max-polyphony' if o.max_polyphony is not None else '--well-formed' if o.well_formed else '--release'
+    if o.repr != 'midi_like':
+        raise SystemExit(f'{flag} follows the note_on / note_off events of --repr midi_like, got --repr {o.repr}')
+    for on, what, why in ((o.beam_size, '-B/--beam-size', "a beam's held notes would have to follow its parent: not built"),
+                          (o.grammar, '--grammar', 'the two masks together can leave a sample no event'),
+                          (well and o.reference_mask, '--reference-mask', 'the KV-cache decode is causal')):
+        if on:
+            raise SystemExit(f'{flag} cannot be combined with {what} ({why})')
+    if o.max_polyphony is not None and not 1 <= o.max_polyphony <= 128:
+        raise SystemExit(f'--max-polyphony must lie in 1 .. 128, got {o.max_polyphony}')
+    return well
+
+
+def _note_args(o, mt):
+    """the keyword arguments of generate_cached / generate_timed that --well-formed / --max-polyphony set"""
+    from .sequence import EventSeq
+    return dict(note_rules=EventSeq.note_rules(mt.vocab_size), max_polyphony=o.max_polyphony)
+
+
 def _timed(o, mt, timed, prior, lens=None, **kw):
     """--seconds / --bars: the samples through generate_timed, each trimmed to its prompt and the events it kept"""
     if o.seconds is not None:
@@ -209,11 +243,12 @@ def main(argv=None):
     _check_beam_options(o)
     _check_share_prompt(o)
     timed = _check_timed(o)
+    well = _check_notes(o)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
         raise SystemExit('--reference-mask cannot be combined with --window (the KV-cache decode is causal)')
-    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size or timed):
+    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size or timed or well):
         raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
                          '(or -B K; the default sampler recomputes the window and keeps no cache)')
     # with --window every branch below samples through the KV-cache decode and its re-anchored window
@@ -237,6 +272,7 @@ def main(argv=None):
                 m = ms(pred, torch.from_numpy(y).to(device, dtype=torch.int))
             print('Test >>>> Loss: {:6.6}, Accuracy: {}'.format(m['loss'], m['accuracy']))
     mt.test()
+    notes = _note_args(o, mt) if well else {}             # --well-formed: every sampling call below is the KV-cache decode
 
     def search(prior, **kw):                              # -B: the best beam of every sample
         res, scores = mt.generate_beam(prior, o.max_len, o.beam_size, temperature=o.temperature, stochastic=o.stochastic_beam_search,
@@ -246,11 +282,11 @@ def main(argv=None):
     if ragged is not None:
         prior, lens = ragged
         if timed:
-            _write(o, _timed(o, mt, timed, prior.to(device), lens))
+            _write(o, _timed(o, mt, timed, prior.to(device), lens, **notes))
             return
         if o.share_prompt:                                 # the N candidates of a file over one copy of its prompt
             res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                     prior_lengths=lens, samples_per_prompt=o.best_of).cpu().numpy()
+                                     prior_lengths=lens, samples_per_prompt=o.best_of, **notes).cpu().numpy()
             res = _best_of(o, mt, res, [n for n in lens for _ in range(o.best_of)])
             _write(o, [row[:n + o.max_len] for row, n in zip(res, lens)])
             return
@@ -260,7 +296,7 @@ def main(argv=None):
             _write(o, [row[:n + o.max_len] for row, n in zip(search(prior.to(device), prior_lengths=lens), lens)])
             return
         res = mt.generate_cached(prior.to(device), o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                 prior_lengths=lens, **cached).cpu().numpy()
+                                 prior_lengths=lens, **cached, **notes).cpu().numpy()
         res, lens = _best_of(o, mt, res, lens), lens[::o.best_of]
         res = [row[:n + o.max_len] for row, n in zip(res, lens)]             # without the pad tail
         _write(o, res)
@@ -300,13 +336,14 @@ def main(argv=None):
     elif o.beam_size:
         res = search(prior)
     elif timed:
-        _write(o, _timed(o, mt, timed, prior))
+        _write(o, _timed(o, mt, timed, prior, **notes))
         return
     elif o.share_prompt:                                   # -c FILE: one prompt, -b x --best-of samples
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                 samples_per_prompt=rows).cpu().numpy()
-    elif o.window:
-        res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached).cpu().numpy()
+                                 samples_per_prompt=rows, **notes).cpu().numpy()
+    elif o.window or well:
+        res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached,
+                                 **notes).cpu().numpy()
     else:
         res = mt.generate(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                           reference_mask=o.reference_mask).cpu().numpy()
@@ -320,6 +357,9 @@ def _write(o, res):
     for i, seq in enumerate(res):
         name = os.path.join(o.output_dir, f'gen-{i:03d}')
         if o.repr == 'midi_like':
+            if o.release:                                 # the note_off of every note the sample still holds
+                from .sequence import EventSeq
+                seq = EventSeq.release(seq)
             n = utils.event_indeces_to_midi_file(seq, name + '.mid')
             print('===> {} ({} notes)'.format(name + '.mid', n))
         elif o.repr == 'remi':

@@ -338,7 +338,8 @@ class MusicTransformer(torch.nn.Module):
                         top_p: float = 1.0, seed: int = 0, use_graph: bool = True, return_probs: bool = False,
                         grammar=None, prefill: str = "auto", return_cache: bool = False, groups: Optional[int] = None,
                         masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
-                        hop: Optional[int] = None, samples_per_prompt: Optional[int] = None):
+                        hop: Optional[int] = None, samples_per_prompt: Optional[int] = None, note_rules=None,
+                        max_polyphony: Optional[int] = None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq unless ``window`` is given, see below).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -401,16 +402,35 @@ class MusicTransformer(torch.nn.Module):
         the call on ``prior.repeat_interleave(N, 0)``; the two calls run different kernels, so their distributions agree to
         rounding and a draw near a CDF boundary may differ.  Prefill work and prompt-cache memory are 1/N of the repeated
         call's.  Refused: ``window``, ``kv_cache="fp8"``, ``groups`` > 1, ``masked_groups``, ``prefill="token"``,
-        ``return_cache``, Pmax + length > max_seq.  None (default): the call as described above, untouched."""
+        ``return_cache``, Pmax + length > max_seq.  None (default): the call as described above, untouched.
+
+        ``note_rules`` (integers [vocab_size], ``EventSeq.note_rules(vocab_size)`` for the MIDI-like codec) and
+        ``max_polyphony`` (1 .. 128, None: no cap): well-formed note streams.  rule[v] = +(k+1): id v turns key k on,
+        -(k+1): it turns key k off, 0: neither.  Every row keeps on the device the set of keys it holds (include/mgx.h, ABI
+        28), starting from what its own prompt leaves held (folded on the host: a key is held iff the last prompt id that
+        touched it turned it on -- the prompt may be ill-formed or above the cap).  Before the sampler every note_on of a held
+        key, every note_off of a silent key and, once ``max_polyphony`` keys are held, every note_on is masked out of the logits
+        (mgx_notes_mask; so also out of ``return_probs`` and under top-k / top-p), and after it the draw is applied to the
+        row's set (mgx_notes_account); the launches are captured with the step.  A row is the unconstrained row of the same
+        seed up to the first step at which that one breaks a rule: the step also draws once BEFORE the mask, with ``seed``,
+        and a legal first draw stands (mgx_notes_keep); the masked draw uses a seed of its own, so without top-k / top-p the
+        token has exactly the masked distribution.  Works with ``prior_lengths``, ``kv_cache``, ``window``,
+        ``return_probs``, ``use_graph``, ``prefill`` ("token": the teacher-forced prompt steps are not constrained) and
+        ``samples_per_prompt``; the return values do not change (``EventSeq.held_after(row)`` gives a row's final held keys).
+        Refused (ValueError, before any device work): ``max_polyphony`` without ``note_rules`` or outside 1 .. 128; rules that
+        are not integers [vocab_size], exceed +-128, are not 0 at pad_token, or name a key with only one of its two ids (with
+        these the mask can never leave a row without an allowed id); ``grammar`` (the two masks together could), ``groups`` > 1,
+        ``masked_groups``, ``return_cache``.  None (default): the call as described above, untouched."""
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
                                       prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop,
-                                      samples_per_prompt)
+                                      samples_per_prompt, None, note_rules, max_polyphony)
 
     @torch.no_grad()
     def generate_timed(self, prior: torch.Tensor, budget, cost, max_length: int, *, inclusive: bool = True, poll: int = 32,
                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, use_graph: bool = True,
                        grammar=None, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
-                       hop: Optional[int] = None, return_probs: bool = False, **refused):
+                       hop: Optional[int] = None, return_probs: bool = False, note_rules=None,
+                       max_polyphony: Optional[int] = None, **refused):
         """Generate to a musical length: ``generate_cached`` where every row stops at a budget of its own instead of after a
         number of events.  ``cost`` (int32-representable [vocab_size], >= 0, 0 at pad_token) prices every id --
         ``EventSeq.time_cost`` in centiseconds, ``REMI_EventSeq.bar_cost`` in bars -- and ``budget`` (an int, or one per row;
@@ -429,14 +449,17 @@ class MusicTransformer(torch.nn.Module):
         device left them, and ``probs`` f32 [B, Pmax+max_length, V] with ``return_probs`` -- the distributions the sampler saw,
         0 at every masked id).  Refused (ValueError, before any device work): ``samples_per_prompt``, ``groups`` > 1,
         ``masked_groups``, ``return_cache``, ``beam_size`` (other drivers), a malformed ``cost``, ``poll`` < 1, ``budget`` < 0,
-        ``max_length`` < 1, and what ``generate_cached`` refuses."""
+        ``max_length`` < 1, and what ``generate_cached`` refuses.  ``note_rules`` / ``max_polyphony``: as in
+        ``generate_cached`` -- the budget's mask and account run first, the notes' second; an ended row steps on pad_token,
+        whose rule is 0, so its held set stays what it was when the row ended."""
         return decode.generate_timed(self, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed,
-                                     use_graph, grammar, prior_lengths, kv_cache, window, hop, return_probs, refused)
+                                     use_graph, grammar, prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules,
+                                     max_polyphony)
 
     @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,
                       seed: int = 0, grammar=None, prior_lengths=None, kv_cache: str = "bf16", use_graph: bool = True,
-                      return_beams: bool = False):
+                      return_beams: bool = False, note_rules=None, max_polyphony: Optional[int] = None):
         """Beam search over the KV-cache decode: the ``beam_size`` (K, 1 .. min(16, V)) best continuations of ``length`` events
         of every prompt of ``prior`` [B,P], each prompt searched with its own beam.  A beam's score is the sum of its events'
         log softmax(logits / temperature) (under ``grammar``: over the allowed events, the sampler's rule).  The search starts
@@ -451,7 +474,11 @@ class MusicTransformer(torch.nn.Module):
         Returns (tokens int32 [B, Pmax+length] of the best beam of every prompt, padded as ``generate_cached`` pads ragged
         rows; scores f32 [B]).  ``return_beams`` appends all beams int32 [B, K, Pmax+length], their scores f32 [B, K] and the
         two history tables int32 [B, K, Pmax+length]: column c of slot j holds the token chosen for that slot at column c and
-        the slot (0..K-1) of the previous column that it extends."""
+        the slot (0..K-1) of the previous column that it extends.  ``note_rules`` / ``max_polyphony`` are refused (ValueError): a
+        beam's held notes would have to follow its parent through the reorder, which is not built."""
+        if note_rules is not None or max_polyphony is not None:
+            raise ValueError("generate_beam is not combined with note_rules / max_polyphony (a beam's held notes would have to "
+                             "follow its parent through the reorder: not built)")
         return decode.generate_beam(self, prior, length, beam_size, temperature, stochastic, seed, grammar, prior_lengths, kv_cache,
                                     use_graph, return_beams)
 

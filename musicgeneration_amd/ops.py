@@ -877,6 +877,81 @@ def budget_account(next_tok, out_tokens, pos_dev, cost, remaining, done, count, 
     return next_tok
 
 
+# ---- held-note state on the decode path (ABI 28; contracts in include/mgx.h) -----------------------------------------
+NOTE_WORDS = _lib.DEFINES["MGX_NOTE_WORDS"]               # int32 words of a row's state
+NOTE_BITS = 32 * NOTE_WORDS                               # the bits a rule may name; max_on = NOTE_BITS is no cap
+
+
+def _check_note_state(what, rule, state):
+    """the held-note state: rule int32 [V], state int32 [B, NOTE_WORDS], both contiguous.  Returns B"""
+    if rule.dtype != torch.int32 or rule.dim() != 1 or not rule.is_contiguous():
+        raise ValueError(f"{what}: rule must be a contiguous int32 tensor [V], got {rule.dtype} {tuple(rule.shape)}")
+    if state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != NOTE_WORDS or not state.is_contiguous():
+        raise ValueError(f"{what}: state must be a contiguous int32 tensor [B, {NOTE_WORDS}], got {state.dtype} {tuple(state.shape)}")
+    return state.shape[0]
+
+
+def notes_mask(logits, V, rule, state, max_on=NOTE_BITS):
+    """in place, before the sampler: logits bf16 [B, ld] get -inf at every id v < V whose rule sets a bit that state[b] holds
+    already -- or any bit, once the row holds ``max_on`` -- and at every id whose rule clears a bit the row does not hold;
+    rule-0 ids and columns >= V stay bit for bit"""
+    _need_cuda(logits, rule, state)
+    B = _check_note_state("notes_mask", rule, state)
+    ld = logits.shape[-1]
+    if logits.dtype != torch.bfloat16 or logits.numel() != B * ld or not logits.is_contiguous():
+        raise ValueError(f"notes_mask: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    if not 0 < int(V) <= min(ld, rule.numel()):
+        raise ValueError(f"notes_mask: V must lie in 1 .. min(ld, the entries of rule) = {min(ld, rule.numel())}, got {V}")
+    if not 1 <= int(max_on) <= NOTE_BITS:
+        raise ValueError(f"notes_mask: max_on must lie in 1 .. {NOTE_BITS} ({NOTE_BITS}: no cap), got {max_on}")
+    check(_lib.load().mgx_notes_mask(ptr(logits), int(V), ld, ptr(rule), ptr(state), int(max_on), B, stream_ptr()), "mgx_notes_mask")
+    return logits
+
+
+def notes_account(next_tok, rule, state, V=None):
+    """after the sampler: applies rule[next_tok[b]] to state[b] -- sets or clears the bit, whatever it was; a token outside
+    0 .. V-1 (``V`` None: the entries of rule) and rule 0 leave the row alone"""
+    _need_cuda(next_tok, rule, state)
+    B = _check_note_state("notes_account", rule, state)
+    if next_tok.dtype != torch.int32 or next_tok.dim() != 1 or next_tok.numel() != B or not next_tok.is_contiguous():
+        raise ValueError(f"notes_account: next_tok must be a contiguous int32 tensor of {B} entries, got {next_tok.dtype} "
+                         f"{tuple(next_tok.shape)}")
+    V = rule.numel() if V is None else int(V)
+    if not 0 < V <= rule.numel():
+        raise ValueError(f"notes_account: V must lie in 1 .. the entries of rule = {rule.numel()}, got {V}")
+    check(_lib.load().mgx_notes_account(ptr(next_tok), ptr(rule), ptr(state), V, B, stream_ptr()), "mgx_notes_account")
+    return state
+
+
+def notes_keep(first_tok, next_tok, out_tokens, pos_dev, rule, state, max_on=NOTE_BITS, V=None, *, ragged=False, base=None):
+    """between the step's two draws and the accounts: a row whose first draw first_tok[b] -- made before notes_mask -- is legal
+    under state[b] and ``max_on`` keeps it: next_tok[b] and out_tokens[b, base + pos] (the column the second draw was written
+    to; ``out_tokens`` None: no column) receive it.  ``ragged`` / ``base`` as in sample_topk_topp"""
+    _need_cuda(first_tok, next_tok, out_tokens, pos_dev, base, rule, state)
+    B = _check_note_state("notes_keep", rule, state)
+    _check_pos_rows(pos_dev, B, ragged)
+    if base is not None:
+        _check_base(base, pos_dev, "notes_keep")
+    for name, t in (("first_tok", first_tok), ("next_tok", next_tok)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
+            raise ValueError(f"notes_keep: {name} must be a contiguous int32 tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
+    if pos_dev.dtype != torch.int32 or pos_dev.numel() < 1:
+        raise ValueError(f"notes_keep: the positions must be int32, got {pos_dev.dtype} with {pos_dev.numel()} entries")
+    if out_tokens is not None and (out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B
+                                   or out_tokens.stride(1) != 1 or out_tokens.stride(0) != out_tokens.shape[1]):
+        raise ValueError(f"notes_keep: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
+                         f"{tuple(out_tokens.shape)}")
+    V = rule.numel() if V is None else int(V)
+    if not 0 < V <= rule.numel():
+        raise ValueError(f"notes_keep: V must lie in 1 .. the entries of rule = {rule.numel()}, got {V}")
+    if not 1 <= int(max_on) <= NOTE_BITS:
+        raise ValueError(f"notes_keep: max_on must lie in 1 .. {NOTE_BITS} ({NOTE_BITS}: no cap), got {max_on}")
+    check(_lib.load().mgx_notes_keep(ptr(first_tok), ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[1],
+                                     ptr(pos_dev), ptr(base), 1 if ragged else 0, ptr(rule), ptr(state), int(max_on), V, B,
+                                     stream_ptr()), "mgx_notes_keep")
+    return next_tok
+
+
 # ---- beam search on the decode path (ABI 22; contracts in include/mgx.h) ---------------------------------------------
 def _check_int32_rows(what, R, **ts):
     for name, t in ts.items():

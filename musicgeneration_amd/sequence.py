@@ -32,6 +32,18 @@ DEFAULT_NOTE_LENGTH = BEAT_LENGTH * 2
 MIN_NOTE_LENGTH = BEAT_LENGTH / 2
 
 
+def held_bits(rule, ids):
+    """the fold of a rule table (EventSeq.note_rules: +(k + 1) sets bit k, -(k + 1) clears it, 0 touches none) over ``ids``: the
+    sorted bits left set, int64.  A set of a set bit and a clear of a clear bit change nothing, so a bit is set iff the last id
+    that touched it set it; ids outside the table touch nothing"""
+    rule = np.asarray(rule).astype(np.int64)
+    idx = np.asarray(ids).astype(np.int64).reshape(-1)
+    r = rule[idx[(idx >= 0) & (idx < len(rule))]]
+    r = r[r != 0][::-1]                                   # the touching ids, last first
+    bits, last = np.unique(np.abs(r) - 1, return_index=True)
+    return bits[r[last] > 0]
+
+
 class Note:
     """Minimal stand-in for pretty_midi.Note (velocity, pitch, start, end)."""
 
@@ -142,6 +154,37 @@ class EventSeq:
         ts = EventSeq.feat_ranges()['time_shift']
         cost[ts.start:ts.stop] = np.rint(TIME_UNITS_PER_SECOND * np.asarray(EventSeq.time_shift_bins)).astype(np.int32)
         return cost
+
+    @staticmethod
+    def note_rules(vocab_size=None):
+        """what every id does to the set of held notes, int32 [vocab_size]: +(k + 1) on the note_on of key k (the id sets bit
+        k), -(k + 1) on its note_off (the id clears bit k), 0 elsewhere -- velocity, time_shift and the ids a model adds beyond
+        dim() (its pad id).  The rule table of ``MusicTransformer.generate_cached(note_rules=)``"""
+        V = EventSeq.dim() if vocab_size is None else int(vocab_size)
+        if V < EventSeq.dim():
+            raise ValueError(f"vocab_size ({V}) is below the codec's {EventSeq.dim()} ids")
+        rule = np.zeros(V, dtype=np.int32)
+        ranges = EventSeq.feat_ranges()
+        on, off = ranges['note_on'], ranges['note_off']
+        rule[on.start:on.stop] = np.arange(1, len(on) + 1)
+        rule[off.start:off.stop] = -np.arange(1, len(off) + 1)
+        return rule
+
+    @staticmethod
+    def held_after(ids):
+        """the keys (0-based, sorted) still sounding after the ids: the fold of note_rules over them -- a note_on of a sounding
+        key leaves it sounding, a note_off of a silent key leaves it silent -- so a key is held iff the last id that touched it
+        was its note_on"""
+        return held_bits(EventSeq.note_rules(), ids)
+
+    @staticmethod
+    def release(ids):
+        """the ids followed by the note_off of every key they leave sounding (held_after), in ascending key order; dtype as
+        to_array's"""
+        idx = np.asarray(ids).reshape(-1)
+        off = EventSeq.feat_ranges()['note_off'].start + EventSeq.held_after(idx)
+        dtype = np.uint8 if EventSeq.dim() <= 256 else np.uint16
+        return np.concatenate([idx, off]).astype(dtype)
 
     # ---- index array <-> events --------------------------------------------------------------------
     @staticmethod
