@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS */
-#define MGX_ABI_VERSION 28
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment */
+#define MGX_ABI_VERSION 29
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -689,6 +689,46 @@ int mgx_linear_logprob(const uint16_t* A, const uint16_t* W, const float* bias, 
  *   order (two calls give the same bits); a counted -inf or NaN propagates.  One workgroup per row b.                       */
 int mgx_score_reduce(const float* logp, const int32_t* hit, double* sum, int32_t* count, int32_t* hits, int B, int L,
                      void* stream);
+
+/* ---- Train-time augmentation on the device (ABI 29): the crop of data.py:96-107, the transposition of utils/shared.py:36-68 as
+ * PerformanceRNN/train.py:220-222 applies it, and a time stretch, in one launch.  Per row the kernel cuts a crop out of a corpus
+ * that lives in device memory, stretches its time, transposes it and writes the model's x and y; no token crosses the host.
+ * One workgroup per row; the source is walked in tiles, for any n >= 1.
+ *
+ *   corpus uint16 [corpus_len]: the pieces, one after the other.  start int64 [B], avail int32 [B]: where row b's crop begins
+ *   and how many tokens lie between start[b] and the end of its piece.
+ * Source.  Row b reads src[i] = corpus[start[b] + i] for i < n_src, with
+ *     n_src = min(n, avail[b], corpus_len - start[b])      without a stretch (stretch_q NULL),
+ *     n_src = min(2n, avail[b], corpus_len - start[b])     with one.
+ *   A negative start[b] or avail[b], or start[b] >= corpus_len, gives an empty source.  No value in device memory turns into an
+ *   access outside corpus[0 .. corpus_len), perm[0 .. S*V) or the elements of x / y named under "Output".
+ * Stretch.  stretch_q int32 [B] in per-mille, or NULL: none.  q = stretch_q[b] if 500 <= stretch_q[b] <= 2000, else 1000.  The
+ *   codec's time ids are the run ts0 .. ts0 + n_ts - 1, id ts0 + j lasting j + 1 units (ts0 >= 0, n_ts >= 1, ts0 + n_ts <= 65536;
+ *   both ignored without a stretch).
+ *     u_i = src[i] - ts0 + 1 if src[i] lies in the run, else 0;   T_i = u_0 + ... + u_i (64 bits);
+ *     S_i = floor((T_i q + 500) / 1000),  S_{-1} = 0.
+ *   A token with u_i = 0 is emitted as it is.  A time token emits delta_i = S_i - S_{i-1} units: floor(delta_i / n_ts) ids
+ *   ts0 + n_ts - 1, then id ts0 + (delta_i mod n_ts) - 1 if the remainder is above 0; nothing when delta_i = 0.  The cumulative
+ *   time is rounded, never the single shift: the ids emitted for src[0 .. i] last exactly S_i units, drift does not accumulate.
+ *   q = 1000 emits the source.  (Six 100-unit shifts at q = 1005, n_ts = 100: S = 101 201 302 402 503 603, deltas 101 100 101 100 101 100,
+ *   emitted units 100 1 100 100 1 100 100 1 100.)
+ * Transposition.  perm int32 [S,V] and shift_row int32 [B], both given or both NULL (none).  Every emitted id v with 0 <= v < V
+ *   becomes perm[shift_row[b] * V + v]; with shift_row[b] outside 0 .. S-1, or v >= V, the id stays as it is.
+ * Output.  out[0 ..) is the emitted stream; its first n ids count.
+ *     x[b*stride_b + j*stride_t] = out[j]           for j < n - 1 (y given) or j < n (y NULL)
+ *     y[b*stride_b + (j-1)*stride_t] = out[j]       for 1 <= j < n
+ *   x, y int32; strides (L, 1) give the transformer's [B, L] pair with L = n - 1, strides (1, B) a time-major [T, B].  Where the
+ *   row emitted fewer than n ids the rest is pad_token, as it is (not transposed).  n_out int32 [B] or NULL:
+ *   n_out[b] = min(emitted, n).  Nothing else is written; no input is written.
+ * Length.  With q >= 500 any two consecutive source tokens emit at least one id (two time tokens of u units in all give
+ *   floor or ceil of u q / 1000 >= 1 units between them), so 2n source tokens always give n ids; with q >= 1000 every source
+ *   token emits at least one.  A row comes up short only where its piece ends: within n tokens of it, or within 2n for q < 1000.
+ * B > 0, n > 0, V > 0, stride_b > 0, stride_t > 0, S > 0 with a table; otherwise MGX_ERR_SHAPE / MGX_ERR_NULL.  Plain loads and
+ * stores, no atomics; the result is a pure function of the inputs, and every per-row value is read when the kernel runs, so a
+ * captured launch follows the arrays.                                                                                       */
+int mgx_crop_augment(const uint16_t* corpus, size_t corpus_len, const int64_t* start, const int32_t* avail, const int32_t* perm,
+                     int S, int V, const int32_t* shift_row, const int32_t* stretch_q, int ts0, int n_ts, int32_t* x, int32_t* y,
+                     int stride_b, int stride_t, int32_t* n_out, int pad_token, int B, int n, void* stream);
 
 #ifdef __cplusplus
 }

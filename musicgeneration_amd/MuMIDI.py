@@ -155,6 +155,17 @@ class MuMIDI_EventSeq:
         return table
 
     @staticmethod
+    def transpose_table(offsets, vocab_size=None):
+        """what every id becomes under a transposition, int32 [len(offsets), vocab_size]: row s moves the PITCH half of
+        note_on (its first len(pitch_range) slots) by offsets[s] semitones (|offset| <= 11; a pitch that would leave the range
+        comes back by an octave, as in ``EventSeq.transpose_table``) and rotates chord roots as ``REMI_EventSeq.transpose_table``
+        does; the drum half of note_on, N:N and every other id (also a model's pad id beyond dim()) map to themselves"""
+        r = MuMIDI_EventSeq.feat_ranges()
+        on = r['note_on']
+        pitches = range(on.start, on.start + len(MuMIDI_EventSeq.pitch_range))
+        return _vocab.transpose_table(MuMIDI_EventSeq.dim(), offsets, vocab_size, pitch_runs=(pitches,), chord_run=r['chord'])
+
+    @staticmethod
     def write_midi(events, output_path):
         """utils/MuMIDI.py:576-704: 'bar' advances the bar, 'position' (1-based) and a track token set the cursor,
         (note_velocity, note_on, note_duration) triples become notes of the current track (drum pitches live in the upper

@@ -163,6 +163,15 @@ class REMI_EventSeq:
         return cost
 
     @staticmethod
+    def transpose_table(offsets, vocab_size=None):
+        """what every id becomes under a transposition, int32 [len(offsets), vocab_size]: row s moves note_on pitch p to
+        p + offsets[s] (|offset| <= 11; a pitch that would leave the range comes back by an octave, as in
+        ``EventSeq.transpose_table``) and a chord quality * 12 + root to quality * 12 + (root + offset) mod 12; N:N and every
+        other id (also a model's pad id beyond dim()) map to themselves.  The table of ``data.DeviceData(transpose=)``"""
+        r = REMI_EventSeq.feat_ranges()
+        return _vocab.transpose_table(REMI_EventSeq.dim(), offsets, vocab_size, pitch_runs=(r['note_on'],), chord_run=r['chord'])
+
+    @staticmethod
     def get_velocity_bins():
         n = REMI_EventSeq.velocity_range.stop - REMI_EventSeq.velocity_range.start
         return np.arange(REMI_EventSeq.velocity_range.start, REMI_EventSeq.velocity_range.stop,

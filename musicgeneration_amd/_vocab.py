@@ -42,3 +42,34 @@ def encode(pairs: Sequence[Tuple[range, int]], vocab_size: int) -> np.ndarray:
     """[(feature id range, value)] -> id array.  ``range.__getitem__`` raises IndexError for a value the feature has no
     slot for -- the reference's behaviour (e.g. REMI note_velocity >= 4), kept on purpose."""
     return np.array([ids[v] for ids, v in pairs], dtype=word_dtype(vocab_size))
+
+
+# ---- transposition tables (train-time augmentation: data.DeviceData, ops.crop_augment) -----------------------------------------
+MAX_TRANSPOSE = 11                                         # semitones: beyond an octave the wrap below is no transposition
+
+
+def transpose_table(dim: int, offsets, vocab_size=None, pitch_runs=(), chord_run: Optional[range] = None) -> np.ndarray:
+    """int32 [len(offsets), V]: row s maps every id to its id under a transposition by offsets[s] semitones.
+
+    ``pitch_runs``: id ranges whose slot k is a pitch -- slot k goes to k + offset, and a slot that would leave the run comes
+    back by an octave (-12 above, +12 below: utils/shared.py:36-68 of the reference).  ``chord_run``: ids quality * 12 + root
+    followed by one 'no chord' id -- the root goes to (root + offset) mod 12, the last id stays.  Every other id, and the ids a
+    model adds beyond ``dim`` (its pad id), map to themselves."""
+    V = dim if vocab_size is None else int(vocab_size)
+    if V < dim:
+        raise ValueError(f"vocab_size ({V}) is below the codec's {dim} ids")
+    offsets = [int(o) for o in offsets]
+    if not offsets or any(abs(o) > MAX_TRANSPOSE for o in offsets):
+        raise ValueError(f"transposition offsets must be a non-empty list of semitones in -{MAX_TRANSPOSE} .. {MAX_TRANSPOSE}, got {offsets}")
+    table = np.tile(np.arange(V, dtype=np.int32), (len(offsets), 1))
+    for s, off in enumerate(offsets):
+        for run in pitch_runs:
+            if len(run) < 2 * 12:
+                raise ValueError("a pitch run shorter than two octaves cannot wrap by one")
+            k = np.arange(len(run)) + off
+            k = np.where(k >= len(run), k - 12, np.where(k < 0, k + 12, k))
+            table[s, run.start:run.stop] = run.start + k
+        if chord_run is not None:
+            c = np.arange(len(chord_run) - 1)
+            table[s, chord_run.start:chord_run.stop - 1] = chord_run.start + (c // 12) * 12 + (c % 12 + off) % 12
+    return table

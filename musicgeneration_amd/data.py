@@ -109,6 +109,114 @@ class Data:
         return data[:, :-1], data[:, 1:]
 
 
+def check_stretch(stretch):
+    """a list of time-stretch factors in 0.5 .. 2.0 -> their rounded per-mille; ValueError otherwise"""
+    try:
+        qs = [int(round(1000 * float(f))) for f in stretch]
+    except (TypeError, ValueError):
+        raise ValueError(f"stretch must be a list of factors in 0.5 .. 2.0, got {stretch!r}") from None
+    if not qs or any(not 500 <= q <= 2000 for q in qs):
+        raise ValueError(f"stretch must be a non-empty list of factors in 0.5 .. 2.0, got {list(stretch)}")
+    return qs
+
+
+class DeviceData:
+    """The feeder of ``Data.slide_seq2seq_batch`` with the tokens on the device: the kept files of one split of ``data`` are
+    uploaded ONCE as one flat 16-bit corpus, and a batch is one small staged copy (four per-row numbers) and one kernel
+    (ops.crop_augment) that cuts the crops, stretches their time, transposes them and writes x and y.
+
+    Which files and which starts: drawn from ``data``'s own random stream exactly as ``Data.batch`` draws them (``plan``), so
+    without augmentation a batch holds the tokens the host feeder returns for the same seed.  The augmentation draws come from
+    ``aug_rng``, a second stream: turning augmentation on never moves the crops.
+      transpose: a list of semitone offsets (|offset| <= 11); per row one of them, uniformly; the codec's table is built once.
+      stretch:   a list of factors in 0.5 .. 2.0, kept as rounded per-mille; per row one of them, uniformly.  Needs a codec whose
+                 time ids are one linear run (``codec.stretch_ids``): the MIDI-like one.
+      corpus (uint16), offsets and lengths (int64, per file of the split, also as ``offsets_host`` / ``lengths_host``): on the device.
+      codec:     the event codec of the files (default ``sequence.EventSeq``); vocab_size: the model's (default: pad_token + 1
+                 or the codec's ids, whichever is larger)."""
+
+    def __init__(self, data: Data, device, pad_token, mode='train', transpose=None, stretch=None, aug_rng=None, codec=None,
+                 vocab_size=None):
+        if codec is None:
+            from .sequence import EventSeq as codec
+        if mode not in data.file_dict:
+            raise ValueError(f"mode must be one of {sorted(data.file_dict)}, got {mode!r}")
+        self.data, self.mode, self.device, self.pad_token = data, mode, torch.device(device), int(pad_token)
+        V = max(codec.dim(), self.pad_token + 1) if vocab_size is None else int(vocab_size)
+        self.offsets_semitones = None if transpose is None else [int(o) for o in transpose]
+        table = None if transpose is None else codec.transpose_table(self.offsets_semitones, V)      # refuses |offset| > 11
+        self.stretch_q, self.ts0, self.n_ts = None, 0, 0
+        if stretch is not None:
+            self.stretch_q = check_stretch(stretch)
+            if not hasattr(codec, 'stretch_ids'):
+                raise ValueError(f"{codec.__name__} carries time in bar, position and tempo tokens, not in a run of time-shift "
+                                 "ids: a time stretch needs the MIDI-like codec")
+            self.ts0, self.n_ts = codec.stretch_ids(V)
+        self.aug_rng = aug_rng if aug_rng is not None else random.Random(0)
+        self.files = list(data.file_dict[mode])
+        arrays = [np.asarray(data.array(f)).reshape(-1) for f in self.files]
+        for f, a in zip(self.files, arrays):
+            if len(a) and (int(a.max()) > 65535 or int(a.min()) < 0):
+                raise ValueError(f"{f}: token ids outside 0 .. 65535 do not fit the 16-bit corpus")
+        self.lengths_host = np.array([len(a) for a in arrays], dtype=np.int64)
+        self.offsets_host = np.concatenate([[0], np.cumsum(self.lengths_host)[:-1]]).astype(np.int64) if arrays else np.zeros(0, np.int64)
+        flat = np.concatenate(arrays).astype(np.uint16) if arrays else np.zeros(0, np.uint16)
+        self.corpus = torch.from_numpy(flat).to(self.device)
+        self.offsets = torch.from_numpy(self.offsets_host).to(self.device)
+        self.lengths = torch.from_numpy(self.lengths_host).to(self.device)
+        self.perm = None if table is None else torch.from_numpy(table).to(self.device)
+
+    def plan(self, batch_size, length):
+        """host only: the crops of the next batch, (file indices into the split, starts inside the files), int64 [batch_size]
+        each -- ``Data.batch``'s draws from ``data``'s random stream: one ``sample`` of the files, then per file in order one
+        ``randrange(0, len - (length + 1))``.  A file shorter than length + 1 raises IndexError, one of exactly length + 1
+        ValueError, as there (and as there, the draws made before it are spent)"""
+        rng = self.data._rng
+        files = rng.sample(range(len(self.files)), k=batch_size)
+        need = length + 1
+        starts = []
+        for f in files:
+            n = int(self.lengths_host[f])
+            if need > n:
+                raise IndexError
+            starts.append(rng.randrange(0, n - need))
+        return np.array(files, dtype=np.int64), np.array(starts, dtype=np.int64)
+
+    def draw_augmentation(self, batch_size):
+        """host only: per row the table row of its transposition and its stretch in per-mille, from ``aug_rng`` (row after
+        row: the shift, then the factor); None for an augmentation that is off"""
+        shift = [] if self.perm is not None else None
+        q = [] if self.stretch_q is not None else None
+        for _ in range(batch_size):
+            if shift is not None:
+                shift.append(self.aug_rng.randrange(len(self.offsets_semitones)))
+            if q is not None:
+                q.append(self.stretch_q[self.aug_rng.randrange(len(self.stretch_q))])
+        return shift, q
+
+    def slide_seq2seq_batch(self, batch_size, length, crops=None):
+        """-> (x, y) int32 [batch_size, length] on the device: ``Data.slide_seq2seq_batch`` of the split, augmented.
+        ``crops``: what ``plan(batch_size, length)`` returned, for a caller that handles a failed draw apart from the launch"""
+        from . import ops
+        files, starts = self.plan(batch_size, length) if crops is None else crops
+        shift, q = self.draw_augmentation(batch_size)
+        B = batch_size
+        # the four per-row arrays in one pinned buffer (int32 words: start as int64 first) and one copy
+        stage = torch.empty(5 * B, dtype=torch.int32, pin_memory=self.device.type == 'cuda')
+        host = stage.numpy()
+        host[:2 * B].view(np.int64)[:] = self.offsets_host[files] + starts
+        host[2 * B:3 * B] = self.lengths_host[files] - starts
+        host[3 * B:4 * B] = 0 if shift is None else shift
+        host[4 * B:] = 1000 if q is None else q
+        dev = stage.to(self.device, non_blocking=True)
+        x = torch.empty(B, length, dtype=torch.int32, device=self.device)
+        y = torch.empty_like(x)
+        ops.crop_augment(self.corpus, dev[:2 * B].view(torch.int64), dev[2 * B:3 * B], x, y, self.pad_token, perm=self.perm,
+                         shift_row=None if shift is None else dev[3 * B:4 * B],
+                         stretch_q=None if q is None else dev[4 * B:], ts0=self.ts0, n_ts=self.n_ts)
+        return x, y
+
+
 # --------------------------------------------------------------------------------------------------
 # GRU feeder: mirror of mg/model/utils/data.py:23-47 (SeqBatchify, MyDataset) and :49-123 (Event_Dataset)
 # --------------------------------------------------------------------------------------------------

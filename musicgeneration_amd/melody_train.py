@@ -8,11 +8,16 @@ the next input is the ground-truth event or the model's own arg-max); the coins 
 ``sequence`` mode (train.py:263-287): whole variable-length
 sequences, ``SeqBatchify`` collate (sorted, zero-padded ``X [B,Tmax]``, concatenated labels ``X[i,1:len_i]``),
 ``Train(init, X, lengths)`` and the loss over ``flatten_padded_sequences`` -- the computation the reference's loop is
-written for (its own ``SeqForward`` mixes the batch and time axes and cannot run)."""
+written for (its own ``SeqForward`` mixes the batch and time axes and cannot run).
+
+``-t`` (the reference parses it and never reads it): every row of a ``segment`` / ``window`` batch is transposed by its own
+offset from -6 .. 5 semitones (the range of PerformanceRNN/train.py:221) on the device, by ops.crop_augment over the uploaded
+batch."""
 from __future__ import annotations
 
 import optparse
 import os
+import random
 import time
 
 import numpy as np
@@ -55,12 +60,40 @@ def get_options(argv=None):
     return parser.parse_args(argv)[0]
 
 
+class Transposer:
+    """-t: a collated batch np [T, B] -> events int64 [T, B] on the device, every row transposed by an offset of its own from
+    TRANSPOSE_OFFSETS.  The uploaded batch itself is the corpus of ops.crop_augment (row b starts at b * T), written time-major"""
+    TRANSPOSE_OFFSETS = range(-6, 6)                           # np.random.randint(-6, 6): PerformanceRNN/train.py:221
+
+    def __init__(self, event_dim, device, rng=None):
+        self.device = device
+        self.rng = rng if rng is not None else random.Random(1234)
+        self.perm = torch.from_numpy(EventSeq.transpose_table(self.TRANSPOSE_OFFSETS, event_dim)).to(device)
+        self.shape, self.start, self.avail = None, None, None
+
+    def __call__(self, batch):
+        from . import ops
+        T, B = batch.shape
+        if self.shape != (T, B):
+            self.shape = (T, B)
+            self.start = (torch.arange(B, dtype=torch.int64) * T).to(self.device)
+            self.avail = torch.full((B,), T, dtype=torch.int32, device=self.device)
+        corpus = torch.from_numpy(np.ascontiguousarray(batch.T).astype(np.uint16).reshape(-1)).to(self.device)
+        shift = torch.tensor([self.rng.randrange(len(self.TRANSPOSE_OFFSETS)) for _ in range(B)], dtype=torch.int32).to(self.device)
+        x = torch.empty(T, B, dtype=torch.int32, device=self.device)
+        ops.crop_augment(corpus, self.start, self.avail, x, None, 0, perm=self.perm, shift_row=shift, time_major=True)
+        return x.long()
+
+
 def main(argv=None):
     o = get_options(argv)
     if o.mode not in ('segment', 'window', 'sequence'):
         raise ValueError("--mode must be segment, window or sequence")
     if not 0.0 <= o.teacher_forcing_ratio <= 1.0:
         raise ValueError("--teacher-forcing-ratio must lie in [0, 1]")
+    if o.use_transposition and o.mode == 'sequence':
+        raise ValueError("-t/--use-transposition works on the fixed-length batches of --mode segment and --mode window; a "
+                         "--mode sequence batch is packed and sorted by length, its labels cut on the host")
     model_config = dict(MODEL)
     for k, v in utils.params2dict(o.model_params).items():
         model_config[k] = type(MODEL.get(k, v))(v)
@@ -93,6 +126,7 @@ def main(argv=None):
         print(f'Iteration={len(windows) // o.batch_size}')
         loader = torch.utils.data.DataLoader(MyDataset(windows), o.batch_size, collate_fn=dataset.SegBatchify, shuffle=True,
                                              drop_last=True, num_workers=0)
+    transposer = Transposer(event_dim, device) if o.use_transposition else None
     loss_function = nn.CrossEntropyLoss()
     os.makedirs(o.save_path, exist_ok=True)
 
@@ -118,7 +152,10 @@ def main(argv=None):
                     # step t+1 has consumed X[i, 0..t] and predicts X[i, t+1]: rows 1..len-1 of each sample carry a label
                     loss = loss_function(flatten_padded_sequences(outputs[:, 1:], lengths), label)
                 else:
-                    events = torch.from_numpy(np.ascontiguousarray(batch).astype(np.int64)).to(device)     # [T, B]
+                    if transposer is not None:
+                        events = transposer(batch)
+                    else:
+                        events = torch.from_numpy(np.ascontiguousarray(batch).astype(np.int64)).to(device)     # [T, B]
                     if o.mode == 'window':                                                                 # train.py:231-232
                         outputs = model.generate(init, events.shape[0], events=events[:-1], output_type='logit',
                                                  teacher_forcing_ratio=o.teacher_forcing_ratio, seed=n_iter)

@@ -952,6 +952,50 @@ def notes_keep(first_tok, next_tok, out_tokens, pos_dev, rule, state, max_on=NOT
     return next_tok
 
 
+# ---- train-time augmentation on the device (ABI 29; contract in include/mgx.h) ---------------------------------------
+def _check_crop_rows(B, **rows):
+    for name, (t, dtype) in rows.items():
+        if t is not None and (t.dtype != dtype or t.dim() != 1 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"crop_augment: {name} must be a contiguous {dtype} tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
+
+
+def crop_augment(corpus, start, avail, x, y, pad_token, *, perm=None, shift_row=None, stretch_q=None, ts0=0, n_ts=0, n_out=None,
+                 time_major=False):
+    """one crop per row out of ``corpus`` (16-bit ids, 1-D, on the device), stretched in time and transposed, written as the
+    model's pair: with n = the ids that count per row, ``x`` and ``y`` int32 [B, n - 1] (the stream and the stream moved on by
+    one), or ``x`` [B, n] alone with ``y`` None; ``time_major``: [n - 1, B] / [n, B] instead.  start int64 [B] and avail int32
+    [B]: where a row's crop begins and how far its piece goes on from there.  perm int32 [S, V] with shift_row int32 [B] (the
+    table's row per crop), stretch_q int32 [B] in per-mille with the codec's time run (ts0, n_ts): each optional.  Rows that run
+    out of source end in pad_token; n_out int32 [B] (optional) receives the ids written per row.  Returns (x, y)"""
+    _need_cuda(corpus, start, avail, x, y, perm, shift_row, stretch_q, n_out)
+    if corpus.dtype not in (torch.uint16, torch.int16) or corpus.dim() != 1 or corpus.numel() < 1:
+        raise ValueError(f"crop_augment: the corpus must be a non-empty 1-D uint16 tensor, got {corpus.dtype} {tuple(corpus.shape)}")
+    if x.dtype != torch.int32 or x.dim() != 2:
+        raise ValueError(f"crop_augment: x must be a contiguous int32 matrix, got {x.dtype} {tuple(x.shape)}")
+    if y is not None and (y.dtype != torch.int32 or y.shape != x.shape):
+        raise ValueError(f"crop_augment: y must be int32 of x's shape {tuple(x.shape)}, got {y.dtype} {tuple(y.shape)}")
+    T, B = (x.shape[0], x.shape[1]) if time_major else (x.shape[1], x.shape[0])
+    n = T + (1 if y is not None else 0)
+    if B < 1 or T < 1:
+        raise ValueError(f"crop_augment: x must hold at least one row and one column, got {tuple(x.shape)}")
+    _check_crop_rows(B, start=(start, torch.int64), avail=(avail, torch.int32), shift_row=(shift_row, torch.int32),
+                     stretch_q=(stretch_q, torch.int32), n_out=(n_out, torch.int32))
+    if (perm is None) != (shift_row is None):
+        raise ValueError("crop_augment: perm and shift_row go together: give both or neither")
+    S, V = 0, 1
+    if perm is not None:
+        if perm.dtype != torch.int32 or perm.dim() != 2 or perm.numel() < 1:
+            raise ValueError(f"crop_augment: perm must be a contiguous int32 table [S, V], got {perm.dtype} {tuple(perm.shape)}")
+        S, V = perm.shape
+    if stretch_q is not None and not (int(ts0) >= 0 and int(n_ts) >= 1 and int(ts0) + int(n_ts) <= 65536):
+        raise ValueError(f"crop_augment: a stretch needs the codec's time run inside the 16-bit ids, got ts0={ts0}, n_ts={n_ts}")
+    stride_b, stride_t = (1, B) if time_major else (T, 1)
+    check(_lib.load().mgx_crop_augment(ptr(corpus), corpus.numel(), ptr(start), ptr(avail), ptr(perm), S, V, ptr(shift_row),
+                                       ptr(stretch_q), int(ts0), int(n_ts), ptr(x), ptr(y), stride_b, stride_t, ptr(n_out),
+                                       int(pad_token), B, n, stream_ptr()), "mgx_crop_augment")
+    return x, y
+
+
 # ---- beam search on the decode path (ABI 22; contracts in include/mgx.h) ---------------------------------------------
 def _check_int32_rows(what, R, **ts):
     for name, t in ts.items():

@@ -171,6 +171,28 @@ class EventSeq:
         return rule
 
     @staticmethod
+    def transpose_table(offsets, vocab_size=None):
+        """what every id becomes under a transposition, int32 [len(offsets), vocab_size]: row s moves the note_on and the
+        note_off of key k to key k + offsets[s] (|offset| <= 11), a key that would leave the range coming back by an octave --
+        the reference's rule (utils/shared.py:36-68); velocity, time_shift and the ids a model adds beyond dim() map to
+        themselves.  The wrap can send two keys to one (86 and 74 at +3).  The table of ``data.DeviceData(transpose=)``"""
+        r = EventSeq.feat_ranges()
+        return _vocab.transpose_table(EventSeq.dim(), offsets, vocab_size, pitch_runs=(r['note_on'], r['note_off']))
+
+    @staticmethod
+    def stretch_ids(vocab_size=None):
+        """(ts0, n_ts): the time ids are the run ts0 .. ts0 + n_ts - 1 and id ts0 + j lasts j + 1 units of time_cost -- what a
+        time stretch on the device needs of a codec (``data.DeviceData(stretch=)``).  ValueError when the bins are not linear"""
+        cost = EventSeq.time_cost(vocab_size)
+        ts = EventSeq.feat_ranges()['time_shift']
+        timed = np.flatnonzero(cost)
+        if len(ts) == 0 or not np.array_equal(timed, np.arange(ts.start, ts.stop)) \
+                or not np.array_equal(cost[ts.start:ts.stop], np.arange(1, len(ts) + 1)):
+            raise ValueError("a time stretch needs linear time_shift bins: id ts0 + j lasting j + 1 units of "
+                             f"1/{TIME_UNITS_PER_SECOND} s; these bins cost {cost[ts.start:ts.stop].tolist()[:8]}...")
+        return ts.start, len(ts)
+
+    @staticmethod
     def held_after(ids):
         """the keys (0-based, sorted) still sounding after the ids: the fold of note_rules over them -- a note_on of a sounding
         key leaves it sounding, a note_off of a silent key leaves it silent -- so a key is held iff the last id that touched it

@@ -3,7 +3,8 @@ same prints, same checkpoint dict {'net','optimizer','epoch'} and file name, sam
 (train.py:252-329: per-epoch batches, loss/accum_grad, Noam schedule step every accum_grad
 micro-batches, 2-sample eval per epoch, save every 50 epochs and on Ctrl-C) -- running on the MI355X
 kernels.  Extras that do not change the defaults: --num-layers --d-model --repr --dropout --dp, --clip-norm
-(global gradient-norm clipping on the device; a non-finite step is skipped) and the
+(global gradient-norm clipping on the device; a non-finite step is skipped), the device feeder and its
+train-time augmentation --device-feeder --transpose --stretch (data.DeviceData) and the
 data-parallel co-residency knobs --rccl-cus --nccl-channels --buckets.
 
 The reference parses -b/-e/-l/-w/-S/-i/-g but its loop reads config.* instead; here the
@@ -52,6 +53,13 @@ def get_options(argv=None):
     parser.add_option('--max-batches', dest='max_batches', type='int', default=0, help='stop after N micro-batches')
     parser.add_option('--clip-norm', dest='clip_norm', type='float', default=0.0,
                       help='clip the global gradient norm to X and skip non-finite steps; inf = guard only; 0 = off')
+    # the training batches cut, stretched and transposed on the device (data.DeviceData); any of the three selects that feeder
+    parser.add_option('--device-feeder', dest='device_feeder', action='store_true', default=False,
+                      help='training crops are cut on the device from a corpus uploaded once')
+    parser.add_option('--transpose', dest='transpose', type='int', default=0,
+                      help='per crop a transposition by -N .. N semitones, 0 <= N <= 11; 0 = off')
+    parser.add_option('--stretch', dest='stretch', type='string', default=None,
+                      help='f1,f2,...: per crop one of these time-stretch factors (0.5 .. 2.0); --repr midi_like only')
     # data-parallel co-residency knobs (the same three as bench.py): CUs kept free of the compute stream for
     # RCCL's kernels, the number of RCCL channels, per-layer gradient buckets merged into K groups
     parser.add_option('--rccl-cus', dest='rccl_cus', type='int', default=0, help='multiple of 8; 0 = the compute stream uses the whole chip')
@@ -73,8 +81,44 @@ def vocab_of(repr_name):
     raise ValueError(repr_name)
 
 
+def codec_of(repr_name):
+    if repr_name == 'midi_like':
+        from .sequence import EventSeq
+        return EventSeq
+    if repr_name == 'remi':
+        from .REMI import REMI_EventSeq
+        return REMI_EventSeq
+    if repr_name == 'mumidi':
+        from .MuMIDI import MuMIDI_EventSeq
+        return MuMIDI_EventSeq
+    raise ValueError(repr_name)
+
+
+def augment_args(options):
+    """--device-feeder / --transpose / --stretch -> None (the host feeder) or the keywords of data.DeviceData; ValueError for
+    what cannot be done.  Host only: runs before anything touches the device"""
+    from .data import check_stretch
+    if not 0 <= options.transpose <= 11:
+        raise ValueError(f"--transpose takes the largest shift in semitones, 0 .. 11 (0 = off), got {options.transpose}")
+    stretch = None
+    if options.stretch is not None:
+        if options.repr != 'midi_like':
+            raise ValueError(f"--stretch needs --repr midi_like: the {options.repr} codec carries time in bar, position and tempo "
+                             "tokens (tempo is a class / value pair of tokens), not in a run of time-shift ids that a stretch can re-bin")
+        try:
+            stretch = [float(f) for f in options.stretch.split(',')]
+        except ValueError:
+            raise ValueError(f"--stretch takes factors separated by commas, e.g. 0.95,1.0,1.05; got {options.stretch!r}") from None
+        check_stretch(stretch)
+    if not (options.device_feeder or options.transpose or stretch):
+        return None
+    n = options.transpose
+    return {'transpose': list(range(-n, n + 1)) if n else None, 'stretch': stretch, 'codec': codec_of(options.repr)}
+
+
 def main(argv=None):
     options = get_options(argv)
+    augment_args(options)                                  # refusals first: before the device, the dataset and the model
     prev = torch.cuda.current_stream() if torch.cuda.is_available() else None
     try:
         return _run(options)
@@ -138,6 +182,15 @@ def _run(options):
                    min_length=options.max_seq + 2 if multi_gpu else None)
     log(dataset)
     dataset.check_vocab(vocab)        # out-of-vocabulary ids raise here (the kernels do not range-check per step)
+    aug = augment_args(options)
+    feeder = dataset
+    if aug is not None:
+        # training batches only: evaluation stays on the host feeder, unaugmented.  The augmentation draws get a stream of their
+        # own, seeded with the rank like the crops'
+        from .data import DeviceData
+        feeder = DeviceData(dataset, device, pad, vocab_size=vocab, aug_rng=random.Random(4321 + rank), **aug)
+        log('Device feeder: {} events on the device, transpose {}, stretch {}'.format(
+            feeder.corpus.numel(), aug['transpose'] or 'off', aug['stretch'] or 'off'))
 
     log('Loading model')
     mt = MusicTransformer(**model_config)
@@ -199,7 +252,10 @@ def _run(options):
             b = 0
             for b in range(nb):
                 try:
-                    batch_x, batch_y = dataset.slide_seq2seq_batch(options.batch_size, options.max_seq)
+                    if feeder is dataset:
+                        batch_x, batch_y = dataset.slide_seq2seq_batch(options.batch_size, options.max_seq)
+                    else:                                  # only the draw may fail like this: the launch stays outside the try
+                        crops = feeder.plan(options.batch_size, options.max_seq)
                 except (IndexError, ValueError):
                     # the reference swallows IndexError (train.py:261-262); a file of exactly max_seq+1 events raises
                     # ValueError from randrange instead.  Single process: skip like the reference.
@@ -209,8 +265,11 @@ def _run(options):
                     continue
                 # host-side, before the H2D copy, and OUTSIDE the try above: its ValueError (which rows, why) must reach the user
                 # instead of being taken for a failed draw (skipped silently / reported as a rank mismatch under DP)
-                utils.check_no_leading_pads(batch_x, pad)
-                batch_x, batch_y = to_dev(batch_x), to_dev(batch_y)
+                if feeder is dataset:
+                    utils.check_no_leading_pads(batch_x, pad)
+                    batch_x, batch_y = to_dev(batch_x), to_dev(batch_y)
+                else:                                      # never on the host: mt.check_no_leading_pads() after the epoch covers it
+                    batch_x, batch_y = feeder.slide_seq2seq_batch(options.batch_size, options.max_seq, crops)
                 mt.train()
                 last_micro = (b + 1) % options.accum_grad == 0
                 ctx = dp.no_sync() if (dp is not None and not last_micro) else _null()
