@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: mgx_sample_topk_topp_rows; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts): mgx_decode_embed_ragged, mgx_decode_embed_linear_ragged, mgx_decode_embed_linear_frag_ragged, mgx_rel_attn_decode_ragged, mgx_sample_topk_topp_ragged; 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8, mgx_rel_attn_decode_fp8_ragged; 21: re-anchored decode window: mgx_sample_topk_topp_window, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment */
-#define MGX_ABI_VERSION 29
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters) */
+#define MGX_ABI_VERSION 30
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -256,8 +256,9 @@ int mgx_linear_ln_fwd(const uint16_t* X, const uint16_t* RES, const float* gamma
                       void* stream);
 
 /* Decode-step fusion (ABI 12; M <= 32 rows): H bf16 [M,K] = table[tok]*sqrt(K) + pe[t] (layers.py:226-229) and
- * C bf16 [M,N] = H W^T + bias in one launch (the embedding rides in the first QKV projection of a decode step).          */
-int mgx_decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
+ * C bf16 [M,N] = H W^T + bias in one launch (the embedding rides in the first QKV projection of a decode step).
+ * pos_dev, per_row: "Step positions" under K12 below, for the M rows.                                                   */
+int mgx_decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, int per_row,
                             const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V,
                             void* stream);
 /* The three decode-size projections with the weight in MFMA FRAGMENT ORDER (see the fused GRU step below for the layout; rows
@@ -268,7 +269,7 @@ int mgx_skinny_fwd_frag(const uint16_t* A, const uint16_t* Wf, const float* bias
 int mgx_linear_ln_fwd_frag(const uint16_t* X, const uint16_t* RES, const float* gamma, const float* beta, float eps,
                            const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* Z, int M, int N, int K, int act,
                            void* stream);
-int mgx_decode_embed_linear_frag(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
+int mgx_decode_embed_linear_frag(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, int per_row,
                                  const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V,
                                  void* stream);
 
@@ -317,22 +318,38 @@ int mgx_linear_dw_grouped(const mgx_dw_problem* problems, int count, int M, void
                           void* stream);
 
 /* ---- K12: autoregressive decode with a KV cache (replaces the per-token full-window recompute of
- * network.py:52-77; causal semantics).  The current position t lives in device memory
- * (pos_dev[0]) so that one captured graph of a whole step can be replayed for every token.
+ * network.py:52-77; causal semantics).  The step's position lives in device memory so that one captured
+ * graph of a whole step can be replayed for every token.
+ *
+ * Step positions -- the one convention of every decode call that reads a position (ABI 30):
+ *   pos_dev   device int32: t, the position of the step's input token.  per_row == 0: ONE counter, pos_dev[0], shared by the
+ *             call's rows.  per_row != 0: int32 [B], one position per row (B = the call's rows; M for the fused embedding), so
+ *             one batch continues prompts of different lengths; row b computes exactly what the shared call computes with
+ *             pos_dev[0] = pos_dev[b].
+ *   base_dev  where the call takes one: device int32 of pos_dev's shape, or NULL for 0.  Past max_seq a row's cache holds a
+ *             WINDOW of its sequence (mgx_decode_reanchor): t is the position inside the window and base the column of
+ *             out_tokens that holds window position 0.  base + t is the ABSOLUTE step and, where tokens are written, the output
+ *             column.  A base of zeros gives the result of NULL bit for bit.  Embedding and attention work inside the window
+ *             and take no base.
+ *   The arguments come in one order: pos_dev, base_dev, per_row (pos_dev, per_row without a base).
+ *   Contract (not checked: the values live on the device): 0 <= t < Lmax <= M for the attention, t < the rows of pe for the
+ *   embedding, 0 <= base + t and base + t + 1 < out_ld for the sampler when out_tokens is given.
+ *
  * mgx_decode_embed: out bf16 [B,d] = table[tok]*sqrt(d) + pe[t]            (layers.py:226-229)          */
-int mgx_decode_embed(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
+int mgx_decode_embed(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, int per_row,
                      uint16_t* out, int B, int d, int V, void* stream);
 /* qkv_new bf16 [B,3d] (projection of the token at position t): k_t, v_t are appended to
  * kcache/vcache bf16 [B,h,Lmax,64] (head-major: the workgroup of (b,h) streams one contiguous run of 128-byte rows)
  * at row t, then ctx bf16 [B,d] = softmax_j((q.k_j + q.E[M-1-(t-j)])/8) v_j
  * over j = 0..t.  t < Lmax <= M.                                                                      */
 /* Long caches are split over several workgroups per (b,h) whose partial results a second kernel merges: workspace =
- * caller scratch >= mgx_rel_attn_decode_workspace(B, Lmax, d) bytes (0 for short caches: NULL is accepted then).      */
+ * caller scratch >= mgx_rel_attn_decode_workspace(B, Lmax, d) bytes (0 for short caches: NULL is accepted then).  The splits
+ * are a function of the shapes; with per-row positions a short row may leave whole splits empty (the merge skips them).  */
 size_t mgx_rel_attn_decode_workspace(int B, int Lmax, int d);
 /* key splits per (b,h) for this cache length (1 = no workspace, no merge launch).                                    */
 int mgx_rel_attn_decode_splits(int B, int Lmax, int d);
 int mgx_rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
-                        const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes,
+                        const int32_t* pos_dev, int per_row, uint16_t* ctx, void* workspace, size_t ws_bytes,
                         int B, int Lmax, int d, int M, void* stream);
 /* logits bf16 [B,ld] -> next_tok int32 [B] drawn from softmax(logits/temperature) restricted to the top_k
  * most likely ids (0 = all) and then to the smallest set whose mass reaches top_p (1 = all).
@@ -340,46 +357,18 @@ int mgx_rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vca
  * top-p then the largest tau with mass(p >= tau) >= top_p * (the mass top-k kept) -- so ids whose probabilities are EQUAL
  * are kept or dropped together: a tie across the k-th value keeps more than top_k ids.  The draw is the first kept id, in id
  * order, whose inclusive CDF reaches u * (kept mass).
- * out_tokens int32 [B,out_ld] (or NULL): column t+1 receives the token; probs_out f32 [B,V] (or NULL)
- * receives the unfiltered softmax.  The draw is a pure function of (seed, t, row).
- * advance != 0: pos_dev[0] += 1 after sampling.  V <= 1024.
+ * With s = base + t, the absolute step: out_tokens int32 [B,out_ld] (or NULL): column s+1 receives the token; probs_out
+ * f32 [B,V] (or NULL) receives the unfiltered softmax.  The draw is a pure function of (seed, s, row0 + row): the call's rows
+ * are rows [row0, row0+B) of a larger batch (every pointer addresses the sub-batch's first row), so a batch sampled in several
+ * independent sub-batches (KV-cache decode runs them on separate streams, each with its own pos_dev) gets the tokens the whole
+ * batch would get.  advance != 0: every entry of pos_dev += 1 after sampling (base_dev is never written).  V <= 1024.
  * allow_table (optional, NULL = none): uint32 [V, ceil(V/32)] grammar mask -- bit v of row t set iff token v may follow
  * token t (t = the token next_tok holds on entry); disallowed logits are -inf before temperature/top-k/top-p.  A grammar row
  * that leaves no finite logit (it allows nothing, or only ids whose logit is -inf) is ignored for that draw.     */
 int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                         uint64_t seed, int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld,
-                         float* probs_out, int B, int advance, const uint32_t* allow_table, void* stream);
-/* The same for rows [row0, row0+B) of a larger batch (every pointer addresses the sub-batch's first row): the draw is a
- * function of (seed, t, row0 + row), so a batch sampled in several independent sub-batches (KV-cache decode runs them on
- * separate streams, each with its own pos_dev) gets the tokens the whole batch would get.                              */
-int mgx_sample_topk_topp_rows(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                              uint64_t seed, int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld,
-                              float* probs_out, int B, int row0, int advance, const uint32_t* allow_table, void* stream);
-
-/* ---- Ragged decode (ABI 19): one position per batch row, so one batch continues prompts of different lengths.
- * Each *_ragged call is its namesake with `pos_dev` replaced by pos_rows, device int32[B] (B = the call's rows; M rows for
- * the fused embedding), and row b computes exactly what the namesake computes with pos_dev[0] = pos_rows[b]:
- *   - the embedding adds pe[pos_rows[b]];
- *   - the attention appends row b's k/v at cache row t = pos_rows[b] and attends over row b's keys 0..t; the key splits are
- *     the ones the namesake would use at that t, so a short row may leave whole splits empty (the merge skips them);
- *   - the sampler draws with (seed, pos_rows[b], row0 + b), writes out_tokens[b, pos_rows[b] + 1], and with advance != 0
- *     adds 1 to every pos_rows[b].
- * Contract (not checked: the positions live on the device): 0 <= pos_rows[b] < Lmax <= M for the attention, pos_rows[b] < the
- * rows of pe for the embedding, pos_rows[b] + 1 < out_ld when out_tokens is given.                                        */
-int mgx_decode_embed_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
-                            uint16_t* out, int B, int d, int V, void* stream);
-int mgx_decode_embed_linear_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
-                                   const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V,
-                                   void* stream);
-int mgx_decode_embed_linear_frag_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
-                                        const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K,
-                                        int V, void* stream);
-int mgx_rel_attn_decode_ragged(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
-                               const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes,
-                               int B, int Lmax, int d, int M, void* stream);
-int mgx_sample_topk_topp_ragged(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                                uint64_t seed, int32_t* pos_rows, int32_t* next_tok, int32_t* out_tokens, int out_ld,
-                                float* probs_out, int B, int row0, int advance, const uint32_t* allow_table, void* stream);
+                         uint64_t seed, int32_t* pos_dev, const int32_t* base_dev, int per_row, int32_t* next_tok,
+                         int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
+                         const uint32_t* allow_table, void* stream);
 
 /* ---- 8-bit K/V cache (ABI 20): the decode attention over caches that hold OCP fp8 e4m3fn codes (not the fnuz variant).
  * kcache, vcache: uint8 [B,h,Lmax,64] codes; kscale, vscale: float [B,h,Lmax], one scale per (b,h,row).  An element is
@@ -395,37 +384,26 @@ int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* kcache, uin
 /* mgx_rel_attn_decode over the 8-bit cache: k_t, v_t of qkv_new are quantized as above and appended at row t, and row t enters
  * this call already quantized, so ctx is exactly softmax_j((q.k~_j + q.E[M-1-(t-j)])/8) v~_j over the dequantized rows
  * k~_j, v~_j, j = 0..t.  q, E and ctx stay bf16.  The key splits, workspace and partials are those of mgx_rel_attn_decode
- * (mgx_rel_attn_decode_workspace / _splits cover both).  The _ragged form reads pos_rows int32[B] as the ragged calls above. */
+ * (mgx_rel_attn_decode_workspace / _splits cover both).                                                                 */
 int mgx_rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
-                            const uint16_t* E, const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes,
-                            int B, int Lmax, int d, int M, void* stream);
-int mgx_rel_attn_decode_fp8_ragged(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
-                                   const uint16_t* E, const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes,
-                                   int B, int Lmax, int d, int M, void* stream);
+                            const uint16_t* E, const int32_t* pos_dev, int per_row, uint16_t* ctx, void* workspace,
+                            size_t ws_bytes, int B, int Lmax, int d, int M, void* stream);
 
-/* ---- Re-anchored decode window (ABI 21): the KV-cache decode past max_seq.  A row's cache holds a window of its sequence:
- * window position t (the `pos` every decode call reads) is column base + t of out_tokens, and every `hop` tokens the window
- * drops its oldest hop tokens, renumbers the rest from 0 and rebuilds their K/V in one full-sequence pass.  pos_dev and base_dev
- * have one shape: int32[1] shared by the rows (per_row = 0) or int32[B] (per_row != 0).
- * mgx_sample_topk_topp_window is mgx_sample_topk_topp_rows (per_row = 0) / _ragged (per_row != 0) with the absolute step
- * base + t in place of t: the draw is a function of (seed, base + t, row0 + row), out_tokens column base + t + 1 receives the
- * token, and advance != 0 adds 1 to pos_dev only.  base_dev == 0 gives the namesake's result bit for bit.
- * Contract (not checked: both live on the device): base + t + 1 < out_ld when out_tokens is given.                     */
-int mgx_sample_topk_topp_window(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                                uint64_t seed, int32_t* pos_dev, const int32_t* base_dev, int32_t* next_tok,
-                                int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
-                                const uint32_t* allow_table, int per_row, void* stream);
-/* The re-anchor, in stream order: t' = pos_dev - hop and base' = base_dev + hop replace pos_dev and base_dev (every entry),
+/* ---- Re-anchored decode window (ABI 21): the KV-cache decode past max_seq.  A row's cache holds a window of its sequence
+ * ("Step positions" above: pos_dev and base_dev of one shape), and every `hop` tokens the window drops its oldest hop tokens,
+ * renumbers the rest from 0 and rebuilds their K/V in one full-sequence pass.
+ * mgx_decode_reanchor, in stream order: t' = pos_dev - hop and base' = base_dev + hop replace pos_dev and base_dev (every entry),
  * then the prefill's token matrix seq int32 [B,n_pad] is filled from the moved window: seq[b,i] = out_tokens[b, base'_b + i]
- * for i < t'_b and pad_token elsewhere (out_tokens int32 [B,out_ld]).  The counters move in a launch of their own before
- * seq is filled, so no workgroup reads a position another has already moved.  hop >= 0 (0 only fills seq).
+ * for i < t'_b and pad_token elsewhere (out_tokens int32 [B,out_ld]; base_dev is required).  The counters move in a launch of
+ * their own before seq is filled, so no workgroup reads a position another has already moved.  hop >= 0 (0 only fills seq).
  * Contract (not checked: the counters live on the device): t'_b >= 0 and base'_b + t'_b < out_ld; a column outside
  * out_tokens is not read (seq gets pad_token there).                                                                    */
-int mgx_decode_reanchor(int32_t* pos_dev, int32_t* base_dev, const int32_t* out_tokens, int out_ld, int32_t* seq,
-                        int n_pad, int hop, int pad_token, int B, int per_row, void* stream);
+int mgx_decode_reanchor(int32_t* pos_dev, int32_t* base_dev, int per_row, const int32_t* out_tokens, int out_ld, int32_t* seq,
+                        int n_pad, int hop, int pad_token, int B, void* stream);
 
 /* ---- Beam search on the KV-cache decode (ABI 22).  R = B * K rows: row r = b * K + k is beam k (0 <= k < K <= 16) of prompt b.
- * A step runs the ragged decode chain on all R rows (pos_rows int32 [R]; the K beams of a prompt always hold one position), then
+ * A step runs the decode chain with per-row positions on all R rows (pos_rows int32 [R]; the K beams of a prompt always hold one
+ * position), then
  * mgx_beam_select in place of the sampler, then mgx_kv_beam_reorder once per cache tensor; mgx_beam_backtrack ends the search.
  *
  * mgx_beam_select: the K best of the K * V one-token expansions of every prompt's beams.
@@ -475,11 +453,11 @@ int mgx_beam_backtrack(const int32_t* hist_tok, const int32_t* hist_parent, cons
  *   kpre, vpre [Bp,h,Lpre,64]: the prompt cache, one per prompt, written by the prefill only -- this call never writes it;
  *   kown, vown [R,h,Lown,64]:  what every row has appended itself, from row 0 on.
  * pre_rows int32 [Bp]: p_b, the prompt-cache rows of prompt b.  Logical key j of row r is kpre[b,h,j] for j < p_b and
- * kown[r,h,j - p_b] for j >= p_b.  pos_rows int32 [R] as in the ragged calls; the N rows of a prompt hold ONE position (the
+ * kown[r,h,j - p_b] for j >= p_b.  pos_rows int32 [R], one position per row (per_row != 0 above); the N rows of a prompt hold ONE position (the
  * kernel reads row b * N), as the K beams of mgx_beam_select do.
  * mgx_rel_attn_decode_shared: with t = pos_rows[b * N] and p = pre_rows[b], row r's k_t, v_t (qkv_new bf16 [R,3d]) are stored at
  *   kown / vown[r,h,t - p], and ctx bf16 [R,d] = softmax_j((q_r.k_j + q_r.E[M-1-(t-j)])/8) v_j over the logical keys j = 0..t
- *   (key t is read from qkv_new).  It is what mgx_rel_attn_decode_ragged computes on R rows whose caches are the prompt rows
+ *   (key t is read from qkv_new).  It is what mgx_rel_attn_decode with per_row != 0 computes on R rows whose caches are the prompt rows
  *   followed by the own rows, with a prompt's key, value and E row loaded once for MGX_SHARED_NQ queries at a time.
  * Contract: 0 <= p <= min(t, Lpre), t - p < Lown, t < M; Lpre >= 1 and Lown >= 1 (p = 0: everything lives in the own cache;
  *   p = t: the own cache holds the new key only).  t and p live on the device and are not checked on the host; the kernel
@@ -511,8 +489,7 @@ int mgx_rel_attn_decode_shared(const uint16_t* qkv_new, const uint16_t* kpre, co
  *   mask is in the logits themselves, so it holds under top-k / top-p and under the sampler's grammar -- also when a grammar row
  *   leaves no finite logit and is ignored.  (An id of cost 0 is never masked.)  One workgroup per row.
  * mgx_budget_account, after the sampler and its advance.  The sampler has just written next_tok[b] to column
- *   col = base + pos of out_tokens int32 [B,out_ld], with pos = pos_dev[b] (per_row != 0) or pos_dev[0] as it stands AFTER the
- *   advance and base = base_dev[b] / base_dev[0] (NULL: 0; the window's base, ABI 21).  For a live row, with
+ *   col = base + t of out_tokens int32 [B,out_ld] ("Step positions", K12), t as it stands AFTER the advance.  For a live row, with
  *   c = cost[next_tok[b]]:  remaining[b] -= c, then
  *     remaining[b] > 0:   count[b] += 1, the row stays live;
  *     remaining[b] <= 0:  done[b] = 1 (after the mask this is remaining[b] == 0, and c > 0).  inclusive != 0: the token stays
@@ -521,7 +498,7 @@ int mgx_rel_attn_decode_shared(const uint16_t* qkv_new, const uint16_t* kpre, co
  *                         part of it (the N-th new `bar`).
  *   For a row with done[b] != 0 on entry: out_tokens[b,col] = next_tok[b] = pad_token; its state is not touched.
  *   Neither call moves a position: an ended row keeps stepping on pad tokens beside the others, so the shared counter, the
- *   ragged step and mgx_decode_reanchor's t' >= 0 hold as they do without budgets.  Plain loads and stores, no atomics: the host
+ *   per-row step and mgx_decode_reanchor's t' >= 0 hold as they do without budgets.  Plain loads and stores, no atomics: the host
  *   reads `done` between replays.  One thread per row.
  * Contract (not checked: the values live on the device): 0 <= next_tok[b] < the entries of cost (a negative id costs 0);
  *   a column outside 0..out_ld-1 is not written.                                                                           */

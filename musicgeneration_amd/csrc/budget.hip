@@ -29,15 +29,13 @@ __global__ __launch_bounds__(MASK_THREADS) void budget_mask_kernel(uint16_t* __r
 }
 
 __global__ __launch_bounds__(256) void budget_account_kernel(int32_t* __restrict__ next_tok, int32_t* __restrict__ out_tokens,
-                                                             int out_ld, const int32_t* __restrict__ pos_dev,
-                                                             const int32_t* __restrict__ base_dev, int per_row,
-                                                             const int32_t* __restrict__ cost, int32_t* __restrict__ remaining,
+                                                             int out_ld, StepPos stp, const int32_t* __restrict__ cost,
+                                                             int32_t* __restrict__ remaining,
                                                              int32_t* __restrict__ done, int32_t* __restrict__ count,
                                                              int pad_token, int inclusive, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int at = per_row ? b : 0;
-    const int col = (base_dev ? base_dev[at] : 0) + pos_dev[at];      // the column the sampler has just written
+    const int col = stp.step(b);                          // the column the sampler has just written
     bool drop = true;                                     // an ended row: whatever it sampled is pad_token
     if (done[b] == 0) {
         const int tok = next_tok[b];
@@ -75,7 +73,7 @@ extern "C" int mgx_budget_account(int32_t* next_tok, int32_t* out_tokens, int ou
                 "mgx_budget_account: NULL pointer");
     MGX_REQUIRE(B > 0 && out_ld > 0, MGX_ERR_SHAPE, "mgx_budget_account: need B>0, out_ld>0 (B=%d out_ld=%d)", B, out_ld);
     hipLaunchKernelGGL(budget_account_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, next_tok, out_tokens, out_ld,
-                       pos_dev, base_dev, per_row, cost, remaining, done, count, pad_token, inclusive, B);
+                       StepPos{pos_dev, base_dev, per_row}, cost, remaining, done, count, pad_token, inclusive, B);
     MGX_CHECK_LAUNCH("mgx_budget_account");
     return MGX_OK;
 }

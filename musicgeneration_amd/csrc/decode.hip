@@ -12,12 +12,12 @@
 //                         top_k = 0 and top_p = 1 reproduce the reference's full-softmax categorical
 //                         (network.py:73-74).  Thresholds are exact (bisection on the float bit pattern).
 //
-// Every kernel that reads the position has a PER_ROW instantiation (the *_ragged entry points, ABI 19): pos_dev then holds
-// one position per batch row, so a batch can continue prompts of different lengths in lockstep.  Nothing else in a step
-// depends on the position (the relative term E[M-1-(t-j)] only on the row's own t); PER_ROW = false is the shared counter.
-// Past max_seq (ABI 21) the cache holds a window of the sequence: pos_dev is the position inside the window, a second counter
-// of the same shape, base_dev, the output column of window position 0.  Only the sampler reads it
-// (mgx_sample_topk_topp_window); mgx_decode_reanchor moves both when the host re-anchors the window.
+// Every kernel that reads the position takes a StepPos (mgx_common.hpp; the header's "Step positions"): one counter shared by
+// the rows, or one position per batch row, so that a batch can continue prompts of different lengths in lockstep.  Nothing else
+// in a step depends on the position (the relative term E[M-1-(t-j)] only on the row's own t).
+// Past max_seq the cache holds a window of the sequence: the position is the one inside the window, and a second counter of
+// the same shape, the base, is the output column of window position 0.  Only the sampler reads it (embedding and attention
+// get a StepPos without one); mgx_decode_reanchor moves both when the host re-anchors the window.
 // mgx_rel_attn_decode_shared (ABI 26) is the per-row attention for N samples per prompt: the prompt's keys are held once per prompt
 // and loaded once for several of its samples' queries (rel_attn_decode_shared_kernel, below the merge kernel).
 #include "mgx_common.hpp"
@@ -26,17 +26,16 @@ namespace {
 constexpr float LOG2E = 1.4426950408889634f;
 }
 
-template <bool PER_ROW>
 __global__ __launch_bounds__(256) void decode_embed_kernel(const int32_t* __restrict__ tok, const float* __restrict__ table,
-                                                           const float* __restrict__ pe, const int32_t* __restrict__ pos_dev,
-                                                           uint16_t* __restrict__ out, int B, int d, int V, float scale) {
+                                                           const float* __restrict__ pe, StepPos stp, uint16_t* __restrict__ out,
+                                                           int B, int d, int V, float scale) {
     const int gpr = d >> 3;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= B * gpr) return;
     const int r = g / gpr, c = (g % gpr) * 8;
     int t = tok[r];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    const int pos = pos_dev[PER_ROW ? r : 0];
+    const int pos = stp.at(r);
     const f32x4* tp = (const f32x4*)(table + (size_t)t * d + c);
     const f32x4* pp = (const f32x4*)(pe + (size_t)pos * d + c);
     const f32x4 a0 = tp[0], a1 = tp[1], p0 = pp[0], p1 = pp[1];
@@ -105,17 +104,15 @@ MGX_DEV void dec_finish(float m, float l, float* acc, uint16_t* __restrict__ ctx
     }
 }
 
-template <bool PER_ROW>
 __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
     const uint16_t* __restrict__ qkv_new, uint16_t* __restrict__ kcache, uint16_t* __restrict__ vcache,
-    const uint16_t* __restrict__ E, const int32_t* __restrict__ pos_dev, uint16_t* __restrict__ ctx,
-    float* __restrict__ partial, int Lmax, int d, int M) {
+    const uint16_t* __restrict__ E, StepPos stp, uint16_t* __restrict__ ctx, float* __restrict__ partial, int Lmax, int d, int M) {
     const int heads = d >> 6;
     const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
     const int nsplit = gridDim.y, sp = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int ks = lane >> 3, dg = lane & 7;
-    const int t = pos_dev[PER_ROW ? b : 0];                     // current position; keys 0..t (per row: a short row may leave
+    const int t = stp.at(b);                                    // current position; keys 0..t (per row: a short row may leave
                                                                 // whole splits empty, which write m = -inf, l = 0)
     const uint16_t* qrow = qkv_new + (size_t)b * 3 * d + hd * 64;
     // caches are head-major [B, h, Lmax, 64]: a workgroup streams one contiguous run of 128-byte rows
@@ -385,17 +382,16 @@ MGX_DEV void unpack16(const uint16_t* p, float* f) {            // 16 bf16 -> f3
 // s_j = scale_k[j] (q.code_k[j]) + q.E_row, and p_j scale_v[j] weights the V codes.  Row t enters its own step already
 // quantized: the key slot that covers j == t quantizes k_t / v_t from qkv_new in registers with the appender's arithmetic, so
 // the call is exactly attention over the dequantized rows 0..t.
-template <bool PER_ROW>
 __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_fp8_kernel(
     const uint16_t* __restrict__ qkv_new, uint8_t* __restrict__ kcache, uint8_t* __restrict__ vcache, float* __restrict__ kscale,
-    float* __restrict__ vscale, const uint16_t* __restrict__ E, const int32_t* __restrict__ pos_dev, uint16_t* __restrict__ ctx,
-    float* __restrict__ partial, int Lmax, int d, int M) {
+    float* __restrict__ vscale, const uint16_t* __restrict__ E, StepPos stp, uint16_t* __restrict__ ctx, float* __restrict__ partial,
+    int Lmax, int d, int M) {
     const int heads = d >> 6;
     const int b = blockIdx.x / heads, hd = blockIdx.x % heads;
     const int nsplit = gridDim.y, sp = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int ks = lane >> 2, dg = lane & 3;
-    const int t = pos_dev[PER_ROW ? b : 0];
+    const int t = stp.at(b);
     const uint16_t* qrow = qkv_new + (size_t)b * 3 * d + hd * 64;
     const size_t row0 = ((size_t)b * heads + hd) * Lmax;
     uint8_t* kc = kcache + row0 * 64;
@@ -485,13 +481,11 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(const uint16_t* __res
 // ---------------------------------------------------------------------------------------------------
 constexpr int SMP_PER_LANE = 16;                         // the uniform: u01 (mgx_common.hpp)
 
-template <bool PER_ROW>
 __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__ logits, int V, int ld, float inv_temp,
-                                                    int top_k, float top_p, uint64_t seed, int32_t* __restrict__ pos_dev,
+                                                    int top_k, float top_p, uint64_t seed, StepPos stp,
                                                     int32_t* __restrict__ next_tok, int32_t* __restrict__ out_tokens,
                                                     int out_ld, float* __restrict__ probs_out, int row0,
-                                                    const uint32_t* __restrict__ allow_table,
-                                                    const int32_t* __restrict__ base_dev) {
+                                                    const uint32_t* __restrict__ allow_table) {
     const int row = blockIdx.x, lane = threadIdx.x;
     const uint16_t* lp = logits + (size_t)row * ld;
     float p[SMP_PER_LANE];
@@ -576,8 +570,7 @@ __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__
 #pragma unroll
     for (int i = 0; i < SMP_PER_LANE; ++i) { if (!(p[i] >= tau)) p[i] = 0.f; kept += p[i]; }
     const float total = wave_sum(kept);
-    // the absolute step: the position itself, or (mgx_sample_topk_topp_window) the window position plus the window's base
-    const int step = pos_dev[PER_ROW ? row : 0] + (base_dev ? base_dev[PER_ROW ? row : 0] : 0);
+    const int step = stp.step(row);                      // the absolute step: the position, plus the window's base if there is one
     const float target = u01(seed, (uint32_t)step, (uint32_t)(row0 + row)) * total;
     int choice = -1;
     float base = 0.f;
@@ -608,50 +601,38 @@ __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__
         if (out_tokens) out_tokens[(size_t)row * out_ld + step + 1] = choice;
     }
 }
-__global__ void advance_pos_kernel(int32_t* pos_dev) { pos_dev[0] += 1; }
-__global__ __launch_bounds__(256) void advance_pos_rows_kernel(int32_t* __restrict__ pos_rows, int B) {
+// the sampler's advance over the n counters (n = B per row, 1 shared)
+__global__ __launch_bounds__(256) void advance_pos_kernel(int32_t* __restrict__ pos_dev, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < B) pos_rows[i] += 1;
+    if (i < n) pos_dev[i] += 1;
 }
 // mgx_decode_reanchor, in two launches so that no workgroup reads a position another has already moved: the n counters first
-// (n = B per row, 1 shared), then the prefill's token matrix from the moved window
+// (as above), then the prefill's token matrix from the moved window
 __global__ __launch_bounds__(256) void reanchor_move_kernel(int32_t* __restrict__ pos_dev, int32_t* __restrict__ base_dev, int n,
                                                             int hop) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { pos_dev[i] -= hop; base_dev[i] += hop; }
 }
-template <bool PER_ROW>
-__global__ __launch_bounds__(256) void reanchor_fill_kernel(const int32_t* __restrict__ pos_dev, const int32_t* __restrict__ base_dev,
-                                                            const int32_t* __restrict__ out_tokens, int out_ld,
+__global__ __launch_bounds__(256) void reanchor_fill_kernel(StepPos stp, const int32_t* __restrict__ out_tokens, int out_ld,
                                                             int32_t* __restrict__ seq, int n_pad, int pad_token, int B) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= B * n_pad) return;
     const int b = g / n_pad, i = g % n_pad;
-    const int t = pos_dev[PER_ROW ? b : 0], col = base_dev[PER_ROW ? b : 0] + i;
+    const int t = stp.at(b), col = stp.base_at(b) + i;
     // the contract keeps col inside the row for i < t; a row that breaks it reads pad_token, never past out_tokens
     seq[g] = (i < t && col >= 0 && col < out_ld) ? out_tokens[(size_t)b * out_ld + col] : pad_token;
 }
 
-template <bool PER_ROW>
-static int decode_embed(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, uint16_t* out, int B,
-                        int d, int V, void* stream, const char* name) {
+extern "C" int mgx_decode_embed(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, int per_row,
+                                uint16_t* out, int B, int d, int V, void* stream) {
+    const char* name = "mgx_decode_embed";
     MGX_REQUIRE(tok && table && pe && pos_dev && out, MGX_ERR_NULL, "%s: NULL pointer", name);
     MGX_REQUIRE(B > 0 && d > 0 && d % 8 == 0 && V > 0, MGX_ERR_SHAPE, "%s: need d%%8==0 (B=%d d=%d)", name, B, d);
     const int total = B * (d / 8);
-    hipLaunchKernelGGL(decode_embed_kernel<PER_ROW>, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
-                       pos_dev, out, B, d, V, sqrtf((float)d));
+    hipLaunchKernelGGL(decode_embed_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, tok, table, pe,
+                       StepPos{pos_dev, nullptr, per_row}, out, B, d, V, sqrtf((float)d));
     MGX_CHECK_LAUNCH(name);
     return MGX_OK;
-}
-
-extern "C" int mgx_decode_embed(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev,
-                                uint16_t* out, int B, int d, int V, void* stream) {
-    return decode_embed<false>(tok, table, pe, pos_dev, out, B, d, V, stream, "mgx_decode_embed");
-}
-
-extern "C" int mgx_decode_embed_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
-                                       uint16_t* out, int B, int d, int V, void* stream) {
-    return decode_embed<true>(tok, table, pe, pos_rows, out, B, d, V, stream, "mgx_decode_embed_ragged");
 }
 
 // key splits per (b,h): enough workgroups to keep ~4 per CU (32 waves) streaming once the cache is long; short caches
@@ -674,12 +655,12 @@ extern "C" size_t mgx_rel_attn_decode_workspace(int B, int Lmax, int d) {
     return s == 1 ? 0 : (size_t)B * (d / 64) * s * DEC_PART * sizeof(float);
 }
 
-// the four attention entry points.  FP8: the caches are e4m3fn codes with their two scale arrays; it takes the bf16 cache's key
+// the two attention entry points.  FP8: the caches are e4m3fn codes with their two scale arrays; it takes the bf16 cache's key
 // splits, so mgx_rel_attn_decode_workspace / _splits cover both
-template <bool FP8, bool PER_ROW>
+template <bool FP8>
 static int rel_attn_decode(const uint16_t* qkv_new, void* kcache, void* vcache, float* kscale, float* vscale, const uint16_t* E,
-                           const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M,
-                           void* stream, const char* name) {
+                           const int32_t* pos_dev, int per_row, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax,
+                           int d, int M, void* stream, const char* name) {
     MGX_REQUIRE(qkv_new && kcache && vcache && (!FP8 || (kscale && vscale)) && E && pos_dev && ctx, MGX_ERR_NULL, "%s: NULL pointer",
                 name);
     MGX_REQUIRE(B > 0 && d > 0 && d % 64 == 0 && Lmax > 0 && M >= Lmax, MGX_ERR_SHAPE,
@@ -689,12 +670,13 @@ static int rel_attn_decode(const uint16_t* qkv_new, void* kcache, void* vcache, 
                 "%s: workspace must hold mgx_rel_attn_decode_workspace() = %zu bytes (got %zu)", name,
                 mgx_rel_attn_decode_workspace(B, Lmax, d), ws_bytes);
     const dim3 grid(B * (d / 64), ns), block(64 * DEC_WAVES);
+    const StepPos stp{pos_dev, nullptr, per_row};
     if constexpr (FP8)
-        hipLaunchKernelGGL(rel_attn_decode_fp8_kernel<PER_ROW>, grid, block, 0, (hipStream_t)stream, qkv_new, (uint8_t*)kcache,
-                           (uint8_t*)vcache, kscale, vscale, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
+        hipLaunchKernelGGL(rel_attn_decode_fp8_kernel, grid, block, 0, (hipStream_t)stream, qkv_new, (uint8_t*)kcache,
+                           (uint8_t*)vcache, kscale, vscale, E, stp, ctx, (float*)workspace, Lmax, d, M);
     else
-        hipLaunchKernelGGL(rel_attn_decode_kernel<PER_ROW>, grid, block, 0, (hipStream_t)stream, qkv_new, (uint16_t*)kcache,
-                           (uint16_t*)vcache, E, pos_dev, ctx, (float*)workspace, Lmax, d, M);
+        hipLaunchKernelGGL(rel_attn_decode_kernel, grid, block, 0, (hipStream_t)stream, qkv_new, (uint16_t*)kcache,
+                           (uint16_t*)vcache, E, stp, ctx, (float*)workspace, Lmax, d, M);
     if (ns > 1)
         hipLaunchKernelGGL(rel_attn_decode_merge_kernel, dim3(B * (d / 64)), dim3(64), 0, (hipStream_t)stream,
                            (const float*)workspace, ctx, ns, d);
@@ -703,31 +685,17 @@ static int rel_attn_decode(const uint16_t* qkv_new, void* kcache, void* vcache, 
 }
 
 extern "C" int mgx_rel_attn_decode(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
-                                   const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax, int d,
-                                   int M, void* stream) {
-    return rel_attn_decode<false, false>(qkv_new, kcache, vcache, nullptr, nullptr, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax,
-                                         d, M, stream, "mgx_rel_attn_decode");
-}
-
-extern "C" int mgx_rel_attn_decode_ragged(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
-                                          const int32_t* pos_rows, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int Lmax,
-                                          int d, int M, void* stream) {
-    return rel_attn_decode<false, true>(qkv_new, kcache, vcache, nullptr, nullptr, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax,
-                                        d, M, stream, "mgx_rel_attn_decode_ragged");
+                                   const int32_t* pos_dev, int per_row, uint16_t* ctx, void* workspace, size_t ws_bytes, int B,
+                                   int Lmax, int d, int M, void* stream) {
+    return rel_attn_decode<false>(qkv_new, kcache, vcache, nullptr, nullptr, E, pos_dev, per_row, ctx, workspace, ws_bytes, B, Lmax,
+                                  d, M, stream, "mgx_rel_attn_decode");
 }
 
 extern "C" int mgx_rel_attn_decode_fp8(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale, float* vscale,
-                                       const uint16_t* E, const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes,
-                                       int B, int Lmax, int d, int M, void* stream) {
-    return rel_attn_decode<true, false>(qkv_new, kcache, vcache, kscale, vscale, E, pos_dev, ctx, workspace, ws_bytes, B, Lmax, d,
-                                        M, stream, "mgx_rel_attn_decode_fp8");
-}
-
-extern "C" int mgx_rel_attn_decode_fp8_ragged(const uint16_t* qkv_new, uint8_t* kcache, uint8_t* vcache, float* kscale,
-                                              float* vscale, const uint16_t* E, const int32_t* pos_rows, uint16_t* ctx,
-                                              void* workspace, size_t ws_bytes, int B, int Lmax, int d, int M, void* stream) {
-    return rel_attn_decode<true, true>(qkv_new, kcache, vcache, kscale, vscale, E, pos_rows, ctx, workspace, ws_bytes, B, Lmax, d,
-                                       M, stream, "mgx_rel_attn_decode_fp8_ragged");
+                                       const uint16_t* E, const int32_t* pos_dev, int per_row, uint16_t* ctx, void* workspace,
+                                       size_t ws_bytes, int B, int Lmax, int d, int M, void* stream) {
+    return rel_attn_decode<true>(qkv_new, kcache, vcache, kscale, vscale, E, pos_dev, per_row, ctx, workspace, ws_bytes, B, Lmax, d,
+                                 M, stream, "mgx_rel_attn_decode_fp8");
 }
 
 // key splits of the shared-prompt attention, from the shapes alone.  A call has Bp * h * ceil(N / NQ) workgroups per split where
@@ -789,74 +757,35 @@ extern "C" int mgx_kv_store_fp8(const uint16_t* qkv, int Lrows, int n, uint8_t* 
     return MGX_OK;
 }
 
-// the four sampler entry points; advance: one more launch moves the position(s) on.  base_dev: the window's base(s), or NULL
-template <bool PER_ROW>
-static int sample(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p, uint64_t seed, int32_t* pos_dev,
-                  int32_t* next_tok, int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
-                  const uint32_t* allow_table, void* stream, const char* name, const int32_t* base_dev = nullptr) {
+// advance: one more launch moves the position(s) on.  base_dev: the window's base(s), or NULL
+extern "C" int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p, uint64_t seed,
+                                    int32_t* pos_dev, const int32_t* base_dev, int per_row, int32_t* next_tok, int32_t* out_tokens,
+                                    int out_ld, float* probs_out, int B, int row0, int advance, const uint32_t* allow_table,
+                                    void* stream) {
+    const char* name = "mgx_sample_topk_topp";
     MGX_REQUIRE(logits && pos_dev && next_tok, MGX_ERR_NULL, "%s: NULL pointer", name);
     MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && top_p > 0.f && row0 >= 0, MGX_ERR_SHAPE,
                 "%s: need 0<V<=%d, ld>=V, temperature>0, top_p>0, row0>=0 (V=%d ld=%d)", name, 64 * SMP_PER_LANE, V, ld);
-    hipLaunchKernelGGL(sample_kernel<PER_ROW>, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k,
-                       top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, row0, allow_table, base_dev);
-    if (advance && PER_ROW)
-        hipLaunchKernelGGL(advance_pos_rows_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_dev, B);
-    else if (advance)
-        hipLaunchKernelGGL(advance_pos_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, pos_dev);
+    hipLaunchKernelGGL(sample_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature, top_k, top_p, seed,
+                       StepPos{pos_dev, base_dev, per_row}, next_tok, out_tokens, out_ld, probs_out, row0, allow_table);
+    if (advance) {
+        const int n = per_row ? B : 1;
+        hipLaunchKernelGGL(advance_pos_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_dev, n);
+    }
     MGX_CHECK_LAUNCH(name);
     return MGX_OK;
 }
 
-extern "C" int mgx_sample_topk_topp_rows(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                                         uint64_t seed, int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld,
-                                         float* probs_out, int B, int row0, int advance, const uint32_t* allow_table,
-                                         void* stream) {
-    return sample<false>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B, row0,
-                         advance, allow_table, stream, "mgx_sample_topk_topp_rows");
-}
-
-extern "C" int mgx_sample_topk_topp_ragged(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                                           uint64_t seed, int32_t* pos_rows, int32_t* next_tok, int32_t* out_tokens, int out_ld,
-                                           float* probs_out, int B, int row0, int advance, const uint32_t* allow_table,
-                                           void* stream) {
-    return sample<true>(logits, V, ld, temperature, top_k, top_p, seed, pos_rows, next_tok, out_tokens, out_ld, probs_out, B, row0,
-                        advance, allow_table, stream, "mgx_sample_topk_topp_ragged");
-}
-
-extern "C" int mgx_sample_topk_topp(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p, uint64_t seed,
-                                    int32_t* pos_dev, int32_t* next_tok, int32_t* out_tokens, int out_ld, float* probs_out, int B,
-                                    int advance, const uint32_t* allow_table, void* stream) {
-    return sample<false>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B, 0,
-                         advance, allow_table, stream, "mgx_sample_topk_topp");
-}
-
-extern "C" int mgx_sample_topk_topp_window(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p,
-                                           uint64_t seed, int32_t* pos_dev, const int32_t* base_dev, int32_t* next_tok,
-                                           int32_t* out_tokens, int out_ld, float* probs_out, int B, int row0, int advance,
-                                           const uint32_t* allow_table, int per_row, void* stream) {
-    const char* name = "mgx_sample_topk_topp_window";
-    MGX_REQUIRE(base_dev, MGX_ERR_NULL, "%s: NULL pointer", name);
-    return per_row ? sample<true>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B,
-                                  row0, advance, allow_table, stream, name, base_dev)
-                   : sample<false>(logits, V, ld, temperature, top_k, top_p, seed, pos_dev, next_tok, out_tokens, out_ld, probs_out, B,
-                                   row0, advance, allow_table, stream, name, base_dev);
-}
-
-extern "C" int mgx_decode_reanchor(int32_t* pos_dev, int32_t* base_dev, const int32_t* out_tokens, int out_ld, int32_t* seq,
-                                   int n_pad, int hop, int pad_token, int B, int per_row, void* stream) {
+extern "C" int mgx_decode_reanchor(int32_t* pos_dev, int32_t* base_dev, int per_row, const int32_t* out_tokens, int out_ld,
+                                   int32_t* seq, int n_pad, int hop, int pad_token, int B, void* stream) {
     MGX_REQUIRE(pos_dev && base_dev && out_tokens && seq, MGX_ERR_NULL, "mgx_decode_reanchor: NULL pointer");
     MGX_REQUIRE(B > 0 && n_pad > 0 && out_ld > 0 && hop >= 0 && (size_t)B * n_pad <= 0x7fffffff, MGX_ERR_SHAPE,
                 "mgx_decode_reanchor: need B>0, n_pad>0, out_ld>0, hop>=0, B*n_pad<2^31 (B=%d n_pad=%d out_ld=%d hop=%d)", B, n_pad,
                 out_ld, hop);
     const int n = per_row ? B : 1;
     hipLaunchKernelGGL(reanchor_move_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, pos_dev, base_dev, n, hop);
-    const dim3 grid((B * n_pad + 255) / 256), block(256);
-    if (per_row)
-        hipLaunchKernelGGL(reanchor_fill_kernel<true>, grid, block, 0, (hipStream_t)stream, pos_dev, base_dev, out_tokens, out_ld, seq,
-                           n_pad, pad_token, B);
-    else
-        hipLaunchKernelGGL(reanchor_fill_kernel<false>, grid, block, 0, (hipStream_t)stream, pos_dev, base_dev, out_tokens, out_ld, seq,
-                           n_pad, pad_token, B);
+    hipLaunchKernelGGL(reanchor_fill_kernel, dim3((B * n_pad + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       StepPos{pos_dev, base_dev, per_row}, out_tokens, out_ld, seq, n_pad, pad_token, B);
     MGX_CHECK_LAUNCH("mgx_decode_reanchor");
     return MGX_OK;
 }

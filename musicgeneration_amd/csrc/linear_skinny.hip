@@ -172,10 +172,10 @@ __global__ __launch_bounds__(256) void linear_skinny_ln_kernel(const uint16_t* _
 // workgroup (47 us against 9.4 + 5.2: 16 workgroups each stream all of W1 behind a 32-row operand with ~8 KB in flight per
 // wave -- the chain is bound by dependent L2 round trips, and recomputation multiplies them).
 // =================================================================================================
-// PER_ROW (ABI 19, *_ragged): pos_dev holds one position per row instead of one shared counter.
-template <bool FRAG, bool PER_ROW>
+// stp: the rows' position(s), one shared counter or one per row (StepPos, mgx_common.hpp).
+template <bool FRAG>
 __global__ __launch_bounds__(256) void linear_skinny_embed_kernel(const int32_t* __restrict__ tok, const float* __restrict__ table,
-                                                                  const float* __restrict__ pe, const int32_t* __restrict__ pos_dev,
+                                                                  const float* __restrict__ pe, StepPos stp,
                                                                   const uint16_t* __restrict__ W, const float* __restrict__ bias,
                                                                   uint16_t* __restrict__ C, uint16_t* __restrict__ H, int M, int N,
                                                                   int K, int V, float scale) {
@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void linear_skinny_embed_kernel(const int32_t*
     const bool nv = s.nv, mv = s.mv;
     int t = tok[mv ? mrow : 0];
     t = t < 0 ? 0 : (t >= V ? V - 1 : t);
-    const int pos = pos_dev[PER_ROW ? (mv ? mrow : 0) : 0];
+    const int pos = stp.at(mv ? mrow : 0);
     const float* tp = table + (size_t)t * K + w * kq + hh * 8;
     const float* pp = pe + (size_t)pos * K + w * kq + hh * 8;
     const uint16_t* wp = skinny_wptr<FRAG>(W, s, K);
@@ -244,29 +244,21 @@ extern "C" int mgx_linear_ln_fwd_frag(const uint16_t* X, const uint16_t* RES, co
     return linear_ln_fwd<true>(X, RES, gamma, beta, eps, Wf, bias, C, Z, M, N, K, act, stream, "mgx_linear_ln_fwd_frag");
 }
 
-// the four fused-embedding entry points: W row-major or (FRAG) in MFMA fragment order, one position or (PER_ROW) one per row
-template <bool FRAG, bool PER_ROW>
-static int decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, const uint16_t* W,
+// the two fused-embedding entry points: W row-major or (FRAG) in MFMA fragment order
+template <bool FRAG>
+static int decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, int per_row, const uint16_t* W,
                                const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V, void* stream, const char* name) {
     if (int rc = skinny_check(name, tok && table && pe && pos_dev && W && C && H, M, N, K, 0)) return rc;
     MGX_REQUIRE(V > 0, MGX_ERR_SHAPE, "%s: need V>0 (got %d)", name, V);
-    return skinny_launch(name, linear_skinny_embed_kernel<FRAG, PER_ROW>, N, stream, tok, table, pe, pos_dev, W, bias, C, H, M, N, K, V,
-                         sqrtf((float)K));
+    return skinny_launch(name, linear_skinny_embed_kernel<FRAG>, N, stream, tok, table, pe, StepPos{pos_dev, nullptr, per_row}, W, bias, C, H,
+                         M, N, K, V, sqrtf((float)K));
 }
-extern "C" int mgx_decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, const uint16_t* W,
-                                       const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V, void* stream) {
-    return decode_embed_linear<false, false>(tok, table, pe, pos_dev, W, bias, C, H, M, N, K, V, stream, "mgx_decode_embed_linear");
+extern "C" int mgx_decode_embed_linear(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, int per_row,
+                                       const uint16_t* W, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V, void* stream) {
+    return decode_embed_linear<false>(tok, table, pe, pos_dev, per_row, W, bias, C, H, M, N, K, V, stream, "mgx_decode_embed_linear");
 }
-extern "C" int mgx_decode_embed_linear_frag(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, const uint16_t* Wf,
-                                            const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V, void* stream) {
-    return decode_embed_linear<true, false>(tok, table, pe, pos_dev, Wf, bias, C, H, M, N, K, V, stream, "mgx_decode_embed_linear_frag");
-}
-extern "C" int mgx_decode_embed_linear_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows, const uint16_t* W,
-                                              const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V, void* stream) {
-    return decode_embed_linear<false, true>(tok, table, pe, pos_rows, W, bias, C, H, M, N, K, V, stream, "mgx_decode_embed_linear_ragged");
-}
-extern "C" int mgx_decode_embed_linear_frag_ragged(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_rows,
-                                                   const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V,
-                                                   void* stream) {
-    return decode_embed_linear<true, true>(tok, table, pe, pos_rows, Wf, bias, C, H, M, N, K, V, stream, "mgx_decode_embed_linear_frag_ragged");
+extern "C" int mgx_decode_embed_linear_frag(const int32_t* tok, const float* table, const float* pe, const int32_t* pos_dev, int per_row,
+                                            const uint16_t* Wf, const float* bias, uint16_t* C, uint16_t* H, int M, int N, int K, int V,
+                                            void* stream) {
+    return decode_embed_linear<true>(tok, table, pe, pos_dev, per_row, Wf, bias, C, H, M, N, K, V, stream, "mgx_decode_embed_linear_frag");
 }

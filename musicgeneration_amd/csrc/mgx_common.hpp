@@ -54,6 +54,17 @@ MGX_DEV float u01(uint64_t seed, uint32_t step, uint32_t row) {
                         hash32((uint32_t)(seed >> 32) + 0xc2b2ae35u));
     return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f);
 }
+// Where a decode step stands (mgx.h, "Step positions"): `pos` is one counter shared by the rows or (per_row) one per row; `base`,
+// of the same shape or NULL, is the output column of window position 0.  Every decode kernel that reads a position takes one
+// by value; the kernels that are per-row by contract (shared prompt cache, beam) keep their plain pos_rows.
+struct StepPos {
+    const int32_t* pos;
+    const int32_t* base;
+    int per_row;
+    MGX_DEV int at(int row) const { return pos[per_row ? row : 0]; }                       // the row's position
+    MGX_DEV int base_at(int row) const { return base ? base[per_row ? row : 0] : 0; }      // 0 without a window
+    MGX_DEV int step(int row) const { return at(row) + base_at(row); }                     // the absolute step = the output column
+};
 struct DropCfg {
     uint32_t thr16;   // drop iff 16-bit random < thr16
     uint32_t mix;     // seed mix

@@ -54,10 +54,9 @@ __global__ __launch_bounds__(256) void notes_account_kernel(const int32_t* __res
 }
 
 __global__ __launch_bounds__(256) void notes_keep_kernel(const int32_t* __restrict__ first_tok, int32_t* __restrict__ next_tok,
-                                                         int32_t* __restrict__ out_tokens, int out_ld,
-                                                         const int32_t* __restrict__ pos_dev, const int32_t* __restrict__ base_dev,
-                                                         int per_row, const int32_t* __restrict__ rule,
-                                                         const int32_t* __restrict__ state, int max_on, int V, int B) {
+                                                         int32_t* __restrict__ out_tokens, int out_ld, StepPos stp,
+                                                         const int32_t* __restrict__ rule, const int32_t* __restrict__ state,
+                                                         int max_on, int V, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const int tok = first_tok[b];
@@ -73,8 +72,7 @@ __global__ __launch_bounds__(256) void notes_keep_kernel(const int32_t* __restri
     }
     next_tok[b] = tok;
     if (out_tokens) {
-        const int at = per_row ? b : 0;
-        const int col = (base_dev ? base_dev[at] : 0) + pos_dev[at];      // the column the sampler has just written
+        const int col = stp.step(b);                                      // the column the sampler has just written
         if (col >= 0 && col < out_ld) out_tokens[(size_t)b * out_ld + col] = tok;
     }
 }
@@ -108,7 +106,7 @@ extern "C" int mgx_notes_keep(const int32_t* first_tok, int32_t* next_tok, int32
     MGX_REQUIRE(max_on >= 1 && max_on <= NOTE_BITS, MGX_ERR_SHAPE, "mgx_notes_keep: need 1 <= max_on <= %d (max_on=%d)", NOTE_BITS,
                 max_on);
     hipLaunchKernelGGL(notes_keep_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, first_tok, next_tok, out_tokens,
-                       out_ld, pos_dev, base_dev, per_row, rule, state, max_on, V, B);
+                       out_ld, StepPos{pos_dev, base_dev, per_row}, rule, state, max_on, V, B);
     MGX_CHECK_LAUNCH("mgx_notes_keep");
     return MGX_OK;
 }

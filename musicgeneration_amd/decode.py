@@ -7,7 +7,7 @@ has one name each: ``check_args`` (with ``check_shared_args`` / ``check_beam_arg
 device work; ``decode_session`` is the only place that touches ``model.training``; ``stage_prompt`` puts the prompt, the output
 matrix and every row's resume token and position on the device; ``KVCache`` is the only place that knows the two cache formats
 (``SharedKVCache``: two of them, the prompts' and the rows' own); ``SubBatch`` holds the rows of one step with their buffers and
-is where a row's position lives (``pos``, on the device: one shared counter, or one per row when prompts differ in length);
+is where a row's position lives (``pos`` on the device with ``ragged`` and ``base``: one shared counter, or one per row);
 ``run_steps`` is the step loop, eager or captured (``replay_graphs``).  ``window_schedule`` is the host-side plan of the
 re-anchored window (``window=``, ``decode_window``), the one way to generate past max_seq with the cache.  ``generate_timed`` is
 ``generate_cached`` with a ``Budget``: every row's clock on the device (``decode_step_constrained`` brackets the sampler with
@@ -68,11 +68,11 @@ class KVCache:
         self.k[layer][:, :, :n] = qkv[:, :n, d:2 * d].view(B, n, heads, 64).permute(0, 2, 1, 3)
         self.v[layer][:, :, :n] = qkv[:, :n, 2 * d:].view(B, n, heads, 64).permute(0, 2, 1, 3)
 
-    def attend(self, layer: int, qkv_new, E, pos, ctx, workspace, ragged: bool):
-        """append the step's k, v at the position(s) ``pos`` and attend over rows 0..pos: ctx bf16 [B, d]"""
-        return ops.rel_attn_decode(qkv_new, self.k[layer], self.v[layer], E, pos, ctx, workspace, ragged=ragged,
+    def attend(self, layer: int, qkv_new, E, at: dict, ctx, workspace):
+        """append the step's k, v at the rows' position(s) ``at`` (SubBatch.at) and attend over rows 0..pos: ctx bf16 [B, d]"""
+        return ops.rel_attn_decode(qkv_new, self.k[layer], self.v[layer], E, ctx=ctx, workspace=workspace,
                                    kscale=self.kscale[layer] if self.fp8 else None,
-                                   vscale=self.vscale[layer] if self.fp8 else None)
+                                   vscale=self.vscale[layer] if self.fp8 else None, **at)
 
     def zero_rows_from(self, bound: torch.Tensor) -> None:
         """zero the cache rows at or beyond bound[b] of every batch row b"""
@@ -242,11 +242,12 @@ class SharedKVCache:
         self.pre_rows = torch.zeros(Bp, dtype=torch.int32, device=device)
         self.store_prefill = self.pre.store_prefill       # the batched pass over the Bp prompts fills the prompt cache
 
-    def attend(self, layer: int, qkv_new, E, pos, ctx, workspace, ragged: bool):
-        """append every row's k, v to its own cache and attend over the prompt's rows, then the row's own: ctx bf16 [Bp * N, d]"""
+    def attend(self, layer: int, qkv_new, E, at: dict, ctx, workspace):
+        """append every row's k, v to its own cache and attend over the prompt's rows, then the row's own: ctx bf16 [Bp * N, d];
+        ``at`` (SubBatch.at): one position per row, by the kernel's contract"""
         pre, own = self.pre, self.own
-        return ops.rel_attn_decode_shared(qkv_new, pre.k[layer], pre.v[layer], own.k[layer], own.v[layer], E, pos, self.pre_rows,
-                                          ctx, workspace, self.N)
+        return ops.rel_attn_decode_shared(qkv_new, pre.k[layer], pre.v[layer], own.k[layer], own.v[layer], E, at["pos_dev"],
+                                          self.pre_rows, ctx, workspace, self.N)
 
 
 class Weights:
@@ -280,6 +281,7 @@ class SubBatch:
     """views of rows [b0, b1) of every per-row buffer, and what runs them"""
     b0: int
     pos: torch.Tensor             # int32 [1] (shared counter) or [b1 - b0] (ragged): the position of the token in ``tok``
+    ragged: bool                  # one position per row (a ragged batch of one row exists: not told from pos.numel())
     tok: torch.Tensor             # int32 [b1 - b0]: the step's input token, replaced by the sampled one
     out: torch.Tensor             # int32 [b1 - b0, total]
     h: torch.Tensor               # bf16 [b1 - b0, d]: the embedding output (a buffer the captured step owns)
@@ -292,14 +294,25 @@ class SubBatch:
     base: Optional[torch.Tensor] = None   # int32 of pos's shape with ``window``: the column of ``out`` that holds window position 0
 
     @classmethod
-    def alloc(cls, b0: int, b1: int, pos, tok, out, cache, ws, d: int, V: Optional[int] = None, stream=None, base=None):
+    def alloc(cls, b0: int, b1: int, pos, ragged: bool, tok, out, cache, ws, d: int, V: Optional[int] = None, stream=None, base=None):
         """rows [b0, b1) of the whole batch's ``tok`` and ``out`` with step buffers of their own (``probs`` with ``V`` given:
         return_probs) and, unless one is handed in, a stream of their own; ``pos`` / ``base`` / ``cache`` are those rows' already"""
         n, dev = b1 - b0, tok.device
         h, ctx = (torch.empty(n, d, dtype=BF16, device=dev) for _ in range(2))
         probs = torch.zeros(n, V, dtype=torch.float32, device=dev) if V else None
-        return cls(b0, pos, tok[b0:b1], out[b0:b1], h, ctx, probs, cache, ws, torch.cuda.Stream() if stream is None else stream,
-                   base=base)
+        return cls(b0, pos, ragged, tok[b0:b1], out[b0:b1], h, ctx, probs, cache, ws,
+                   torch.cuda.Stream() if stream is None else stream, base=base)
+
+    @property
+    def at(self) -> dict:
+        """where the rows stand in the cache: the position arguments of the embedding and attention ops"""
+        return dict(pos_dev=self.pos, ragged=self.ragged)
+
+    @property
+    def step(self) -> dict:
+        """the rows' absolute step, position plus the window's base: the position arguments of every op that draws a token
+        or writes a column of ``out``"""
+        return dict(self.at, base=self.base)
 
 
 def stage_prompt(prior, lens, pad_token: int, total: int, dev, repeat: int = 1):
@@ -356,7 +369,7 @@ def prefill_batched(w: Weights, cache: KVCache, tokens: torch.Tensor, n: Optiona
         hh = ops.add_ln_fwd(f, o1, ly["g2"], ly["b2"], 1e-6)[0]
 
 
-def step_logits(w: Weights, r: SubBatch, ragged: bool) -> torch.Tensor:
+def step_logits(w: Weights, r: SubBatch) -> torch.Tensor:
     """the step of the rows of ``r`` up to the logits, bf16 [rows, vocab_padded].  In the fused chain (decode-size
     batches) every LayerNorm rides in the projection that consumes it (mgx_linear_ln_fwd) and the embedding in the first QKV
     projection (mgx_decode_embed_linear): 39 launches per token instead of 46"""
@@ -367,12 +380,12 @@ def step_logits(w: Weights, r: SubBatch, ragged: bool) -> torch.Tensor:
         return ops.linear_fwd(z, wt, bias, act), z
     L = w.step
     if w.fused:
-        qkv, h = ops.decode_embed_linear(r.tok, w.emb, w.pe, r.pos, L[0]["wqkv"], L[0]["bqkv"], r.h, ragged=ragged)
+        qkv, h = ops.decode_embed_linear(r.tok, w.emb, w.pe, w=L[0]["wqkv"], bias=L[0]["bqkv"], hout=r.h, **r.at)
     else:
-        h = ops.decode_embed(r.tok, w.emb, w.pe, r.pos, r.h, ragged=ragged)
+        h = ops.decode_embed(r.tok, w.emb, w.pe, out=r.h, **r.at)
         qkv = ops.linear_fwd(h, L[0]["wqkv"], L[0]["bqkv"], 0)
     for i, ly in enumerate(L):
-        r.cache.attend(i, qkv, ly["E"], r.pos, r.ctx, r.ws, ragged)
+        r.cache.attend(i, qkv, ly["E"], r.at, r.ctx, r.ws)
         a = ops.linear_fwd(r.ctx, ly["wfc"], ly["bfc"], 0)
         f, o1 = ln_linear(a, h, ly["g1"], ly["b1"], ly["w1"], ly["bb1"], 1)
         f = ops.linear_fwd(f, ly["w2"], ly["bb2"], 0)
@@ -381,10 +394,10 @@ def step_logits(w: Weights, r: SubBatch, ragged: bool) -> torch.Tensor:
     return qkv
 
 
-def decode_step(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_into_out: bool) -> None:
+def decode_step(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool) -> None:
     """one token for the rows of ``r``; ``sampler``: keyword arguments of ops.sample_topk_topp"""
-    ops.sample_topk_topp(step_logits(w, r, ragged), w.V, r.pos, r.tok, r.out if sample_into_out else None, r.probs, advance=True,
-                         row0=r.b0, ragged=ragged, base=r.base, **sampler)
+    ops.sample_topk_topp(step_logits(w, r), w.V, next_tok=r.tok, out_tokens=r.out if sample_into_out else None, probs_out=r.probs,
+                         advance=True, row0=r.b0, **r.step, **sampler)
 
 
 class Budget:
@@ -516,11 +529,11 @@ def check_note_args(model, note_rules, max_polyphony, *, grammar=None, groups=No
     return NoteState(np.ascontiguousarray(arr.astype(np.int32)), max_polyphony)
 
 
-def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, ragged: bool, sample_into_out: bool, bud: Optional[Budget],
+def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool, bud: Optional[Budget],
                             notes: Optional[NoteState]) -> None:
     """decode_step under the rows' budgets and / or held notes: the logits are masked before the sampler sees them, and the draw
     is charged to the clock and applied to the notes after it.  With ``notes`` the step draws twice (below)"""
-    logits = step_logits(w, r, ragged)
+    logits = step_logits(w, r)
     if bud is not None:
         ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
     out = r.out if sample_into_out else None
@@ -529,16 +542,15 @@ def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, ragged: bool
         # the same random number was legal.  Hence two draws: the first from the logits as they stand, with the call's seed and
         # nothing written but notes.first; the second, below, from the masked logits with a seed of its own; notes_keep then
         # puts a legal first draw in the second's place, and the row is the unconstrained row until that one breaks a rule
-        ops.sample_topk_topp(logits, w.V, r.pos, notes.first, None, None, advance=False, row0=r.b0, ragged=ragged, base=r.base,
-                             **sampler)
+        ops.sample_topk_topp(logits, w.V, next_tok=notes.first, advance=False, row0=r.b0, **r.step, **sampler)
         ops.notes_mask(logits, w.V, notes.rule, notes.state, notes.max_on)
         sampler = dict(sampler, seed=(int(sampler["seed"]) + NoteState.SECOND_SEED) % 2 ** 64)
-    ops.sample_topk_topp(logits, w.V, r.pos, r.tok, out, r.probs, advance=True, row0=r.b0, ragged=ragged, base=r.base, **sampler)
+    ops.sample_topk_topp(logits, w.V, next_tok=r.tok, out_tokens=out, probs_out=r.probs, advance=True, row0=r.b0, **r.step, **sampler)
     if notes is not None:
-        ops.notes_keep(notes.first, r.tok, out, r.pos, notes.rule, notes.state, notes.max_on, w.V, ragged=ragged, base=r.base)
+        ops.notes_keep(notes.first, r.tok, out, rule=notes.rule, state=notes.state, max_on=notes.max_on, V=w.V, **r.step)
     if bud is not None:
-        ops.budget_account(r.tok, r.out, r.pos, bud.cost, bud.remaining, bud.done, bud.count, bud.pad_token, bud.inclusive,
-                           ragged=ragged, base=r.base)
+        ops.budget_account(r.tok, r.out, cost=bud.cost, remaining=bud.remaining, done=bud.done, count=bud.count,
+                           pad_token=bud.pad_token, inclusive=bud.inclusive, **r.step)
     if notes is not None:
         ops.notes_account(r.tok, notes.rule, notes.state, w.V)
 
@@ -635,8 +647,8 @@ def probs_filer(subs, total: int, V: int, col0):
     return probs_all, file
 
 
-def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length: int, window: int, hop: int, ragged: bool,
-                  step_rows, use_graph: bool, on_step, pad_token: int, budget=None):
+def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length: int, window: int, hop: int, step_rows,
+                  use_graph: bool, on_step, pad_token: int, budget=None):
     """the steps of generate_cached(window=): the cache holds window positions 0..window-1 only, and every time the longest
     row has filled it the window is re-anchored -- ops.decode_reanchor drops the oldest ``hop`` tokens of every row (pos -= hop,
     base += hop) and gathers the remaining ones, which one batched causal pass turns back into cache rows 0.. .  The schedule is
@@ -651,8 +663,8 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
     def as_dev(v):
         return torch.tensor(v, dtype=torch.int32, device=dev)
     rows, base_rows, t_rows = torch.arange(B, device=dev), as_dev(base0).long(), as_dev(t0).long()
-    r.pos.copy_(as_dev(t0 if ragged else t0[:1]))
-    r.base.copy_(as_dev(base0 if ragged else base0[:1]))
+    r.pos.copy_(as_dev(t0 if r.ragged else t0[:1]))
+    r.base.copy_(as_dev(base0 if r.ragged else base0[:1]))
     n = max(t0)
     if n > 0:                                             # window positions 0..n-1 of every row, the ragged start's one pass
         prefill_batched(w, cache, prior_i.gather(1, base_rows[:, None] + torch.arange(n, device=dev)[None, :]))
@@ -662,7 +674,7 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
 
     def reanchor(s):
         if s in anchors:
-            ops.decode_reanchor(r.pos, r.base, r.out, seq, hop, pad_token, ragged=ragged)
+            ops.decode_reanchor(out_tokens=r.out, seq=seq, hop=hop, pad_token=pad_token, **r.step)
             prefill_batched(w, cache, seq, n)
     run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=on_step, before=reanchor, budget=budget)
     return ts[-1] if ts else t0
@@ -708,7 +720,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
                 per = torch.cuda.get_device_properties(dev).multi_processor_count // G // 8 * 8
                 stream = ops.masked_stream(per, g * per, dev).stream
             cut = slice(b0, b1) if ragged else slice(g, g + 1)
-            subs.append(SubBatch.alloc(b0, b1, pos_all[cut], tok, out, cache.rows(b0, b1),
+            subs.append(SubBatch.alloc(b0, b1, pos_all[cut], ragged, tok, out, cache.rows(b0, b1),
                                        ops.rel_attn_decode_workspace(b1 - b0, cache_rows, d, dev), d, V if return_probs else None,
                                        stream, base=None if window is None else base_all[cut]))
         # grammar: applied inside the sampling kernel, so the constrained step stays graph-captured
@@ -723,12 +735,12 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
 
         def step_rows(r):                                     # length 0 still runs the last prompt token (its distribution)
             if bud is not None or notes is not None:
-                decode_step_constrained(w, r, sampler, ragged, bud is not None or length > 0, bud, notes)
+                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes)
             else:
-                decode_step(w, r, sampler, ragged, length > 0)
+                decode_step(w, r, sampler, length > 0)
         if window is not None:
-            final_t = decode_window(w, subs[0], cache, prior_i, lens or [P] * B, length, window, hop, ragged, step_rows,
-                                    use_graph, file, model.pad_token, bud)
+            final_t = decode_window(w, subs[0], cache, prior_i, lens or [P] * B, length, window, hop, step_rows, use_graph, file,
+                                    model.pad_token, bud)
         else:
             if first > 0:                                     # positions 0..P-2 in one pass; token P-1 takes the first step below
                 prefill_batched(w, cache, prior_i[:, :first])
@@ -736,7 +748,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
                 tok.copy_(prior_i[:, 0])
             for p in range(first, P - 1):                     # prefill="token": the prior is teacher-forced token by token
                 for r in subs:
-                    decode_step(w, r, sampler, ragged, False)
+                    decode_step(w, r, sampler, False)
                 if return_probs:
                     file(p - (P - 1))                         # the distribution after column p
                 tok.copy_(prior_i[:, p + 1])
@@ -770,7 +782,7 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
         w = Weights(model, st, fused=R <= 32 and d <= 1024)
         if P > 1:                                             # positions 0..P-2 of the Bp prompts in one pass
             prefill_batched(w, cache, prior_i[:, :P - 1])
-        r = SubBatch.alloc(0, R, pos, tok, out, cache, ops.rel_attn_decode_shared_workspace(Bp, N, Lpre, Lown, d, dev), d,
+        r = SubBatch.alloc(0, R, pos, True, tok, out, cache, ops.rel_attn_decode_shared_workspace(Bp, N, Lpre, Lown, d, dev), d,
                            V if return_probs else None)
         sampler = dict(sampling, allow_table=ops.grammar_table(grammar, dev))
         probs_all, file = probs_filer([r], total, V, pos.long()) if return_probs else (None, None)
@@ -779,9 +791,9 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
 
         def step_rows(r_):                                    # length 0 still runs the last prompt token (its distribution)
             if notes is not None:
-                decode_step_constrained(w, r_, sampler, True, length > 0, None, notes)
+                decode_step_constrained(w, r_, sampler, length > 0, None, notes)
             else:
-                decode_step(w, r_, sampler, True, length > 0)
+                decode_step(w, r_, sampler, length > 0)
         run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=file)
     return (out, probs_all) if return_probs else out
 
@@ -846,12 +858,12 @@ def generate_beam(model, prior, length, beam_size, temperature, stochastic, seed
         score = torch.full((B, K), float("-inf"), dtype=torch.float32, device=dev)
         score[:, 0] = 0.0                                     # ONE live beam: duplicates of the first expansion cannot fill the beam
         hist_tok, hist_parent = (torch.zeros(R, total, dtype=torch.int32, device=dev) for _ in range(2))
-        onX = SubBatch.alloc(0, R, pos, tok, out, X, ops.rel_attn_decode_workspace(R, total, d, dev), d)
+        onX = SubBatch.alloc(0, R, pos, True, tok, out, X, ops.rel_attn_decode_workspace(R, total, d, dev), d)
         onY = dataclasses.replace(onX, cache=Y)               # the same rows, buffers and stream on the other cache
         allow = ops.grammar_table(grammar, dev)
 
         def step(r: SubBatch, into: KVCache):                 # attend on r's cache, select, gather the parents' rows into ``into``
-            ops.beam_select(step_logits(w, r, True), V, score, tok, parent, pos, hist_tok, hist_parent, temperature=temperature,
+            ops.beam_select(step_logits(w, r), V, score, tok, parent, pos, hist_tok, hist_parent, temperature=temperature,
                             allow_table=allow, stochastic=stochastic, seed=seed)
             for dst, src in zip(into.tensors(), r.cache.tensors()):
                 ops.kv_beam_reorder(dst, src, parent, pos, K)

@@ -358,7 +358,7 @@ class MusicTransformer(torch.nn.Module):
         ``prior_lengths`` (length-B ints): prompts of different lengths P_b, right-padded into ``prior`` [B, Pmax] (entries at or
         beyond P_b are ignored).  One batched causal prefill covers prior[:, :Pmax-1] (a row's cache rows past P_b-2 are
         overwritten by its own decode steps before they are read), then every row decodes ``length`` tokens in lockstep from
-        its own position P_b-1 (per-row positions on the device, *_ragged kernels; graph capture, ``groups`` and ``grammar``
+        its own position P_b-1 (per-row positions on the device, the kernels' per_row; graph capture, ``groups`` and ``grammar``
         as above).  Returns int32 [B, Pmax+length]: row b holds its prompt, its ``length`` sampled tokens, then ``pad_token``.
         Unequal lengths need the batched prefill ("token" is refused; "auto" means "batched").  With ``return_probs`` row b
         carries the distributions after positions P_b-1 .. P_b+length-2 and zeros elsewhere -- unlike the uniform case, which

@@ -613,19 +613,29 @@ def linear_dw_grouped(problems):
 
 
 # ---- decode path (no autograd) ----------------------------------------------------------------------
-def _check_pos_rows(pos_dev, B, ragged):
-    """``ragged=True`` (ABI 19): pos_dev is int32 [B], one position per row, instead of the shared counter pos_dev[0]"""
-    if ragged and (pos_dev.dtype != torch.int32 or pos_dev.numel() != B or not pos_dev.is_contiguous()):
-        raise ValueError(f"ragged decode: the positions must be a contiguous int32 tensor of {B} entries "
-                         f"(got {pos_dev.dtype}, {pos_dev.numel()} entries)")
-    return "_ragged" if ragged else ""
+def _step_pos(what, pos_dev, B, ragged, base=None, with_base=False):
+    """the step-position arguments of a decode call (include/mgx.h, "Step positions"), checked on the host (ValueError):
+    ``pos_dev`` contiguous int32, one shared counter or -- ``ragged`` -- one position per row, B entries; ``base``, the window's
+    base, of the positions' shape or None.  Returns (pos_dev, per_row) as the C arguments, (pos_dev, base_dev, per_row) with
+    ``with_base``"""
+    n = B if ragged else 1
+    if pos_dev.dtype != torch.int32 or pos_dev.numel() != n or not pos_dev.is_contiguous():
+        kind = f"ragged decode: the positions must be a contiguous int32 tensor of {B} entries" if ragged else \
+            "a shared position is one contiguous int32"
+        raise ValueError(f"{what}: {kind} (got {pos_dev.dtype}, {pos_dev.numel()} entries)")
+    if base is not None and (base.dtype != torch.int32 or base.numel() != n or not base.is_contiguous()):
+        raise ValueError(f"{what}: base must be a contiguous int32 tensor of the positions' {n} entries "
+                         f"(got {base.dtype}, {base.numel()} entries)")
+    per_row = 1 if ragged else 0
+    return (ptr(pos_dev), ptr(base), per_row) if with_base else (ptr(pos_dev), per_row)
 
 
 def decode_embed(tok, table, pe, pos_dev, out, *, ragged=False):
+    pos = _step_pos("decode_embed", pos_dev, tok.numel(), ragged)
     _need_cuda(tok, table, pe, pos_dev, out)
     V, d = table.shape
-    name = "mgx_decode_embed" + _check_pos_rows(pos_dev, tok.numel(), ragged)
-    check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(out), tok.numel(), d, V, stream_ptr()), name)
+    check(_lib.load().mgx_decode_embed(ptr(tok), ptr(table), ptr(pe), *pos, ptr(out), tok.numel(), d, V, stream_ptr()),
+          "mgx_decode_embed")
     return out
 
 
@@ -635,12 +645,14 @@ def decode_embed_linear(tok, table, pe, pos_dev, w, bias, hout, *, ragged=False)
     V, d = table.shape
     N = w.shape[0]
     c = torch.empty(tok.numel(), N, dtype=torch.bfloat16, device=hout.device)
+    pos = _step_pos("decode_embed_linear", pos_dev, tok.numel(), ragged)
     frag = isinstance(w, FragWeight)                    # the weight in MFMA fragment order
-    name = "mgx_decode_embed_linear" + ("_frag" if frag else "") + _check_pos_rows(pos_dev, tok.numel(), ragged)
     wd = w.data if frag else w
     _need_cuda(tok, table, pe, pos_dev, wd, bias, hout)
-    check(getattr(_lib.load(), name)(ptr(tok), ptr(table), ptr(pe), ptr(pos_dev), ptr(wd), ptr(bias), ptr(c), ptr(hout),
-                                     tok.numel(), N, d, V, stream_ptr()), name)
+    lib = _lib.load()
+    fn, name = (lib.mgx_decode_embed_linear_frag, "mgx_decode_embed_linear_frag") if frag else \
+        (lib.mgx_decode_embed_linear, "mgx_decode_embed_linear")
+    check(fn(ptr(tok), ptr(table), ptr(pe), *pos, ptr(wd), ptr(bias), ptr(c), ptr(hout), tok.numel(), N, d, V, stream_ptr()), name)
     return c, hout
 
 
@@ -699,13 +711,16 @@ def rel_attn_decode(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace=None, *,
     ``ragged``: row b's position is pos_dev[b] (each < Lmax: not checked, the positions live on the device).
     uint8 / float8_e4m3fn caches are the 8-bit cache (ABI 20) and need ``kscale`` / ``vscale`` f32 [B, h, Lmax]."""
     fp8 = _check_kv_cache(kcache, vcache, kscale, vscale, "rel_attn_decode")
-    _need_cuda(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace, kscale, vscale)
     B, heads, Lmax, _ = kcache.shape
-    name = "mgx_rel_attn_decode" + ("_fp8" if fp8 else "") + _check_pos_rows(pos_dev, B, ragged)
-    scales = (ptr(kscale), ptr(vscale)) if fp8 else ()
-    check(getattr(_lib.load(), name)(ptr(qkv_new), ptr(kcache), ptr(vcache), *scales, ptr(E), ptr(pos_dev), ptr(ctx), ptr(workspace),
-                                     0 if workspace is None else workspace.numel(), B, Lmax, heads * 64, E.shape[0],
-                                     stream_ptr()), name)
+    pos = _step_pos("rel_attn_decode", pos_dev, B, ragged)
+    _need_cuda(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace, kscale, vscale)
+    tail = (ptr(E), *pos, ptr(ctx), ptr(workspace), 0 if workspace is None else workspace.numel(), B, Lmax, heads * 64, E.shape[0],
+            stream_ptr())
+    if fp8:
+        check(_lib.load().mgx_rel_attn_decode_fp8(ptr(qkv_new), ptr(kcache), ptr(vcache), ptr(kscale), ptr(vscale), *tail),
+              "mgx_rel_attn_decode_fp8")
+    else:
+        check(_lib.load().mgx_rel_attn_decode(ptr(qkv_new), ptr(kcache), ptr(vcache), *tail), "mgx_rel_attn_decode")
     return ctx
 
 
@@ -747,7 +762,7 @@ def rel_attn_decode_shared(qkv_new, kpre, vpre, kown, vown, E, pos_rows, pre_row
             raise ValueError(f"{what}: {name} must be contiguous bf16 [{R}, {cols}], got {t.dtype} {tuple(t.shape)}")
     if E.dtype != torch.bfloat16 or E.dim() != 2 or E.shape[1] != 64 or not E.is_contiguous():
         raise ValueError(f"{what}: E must be contiguous bf16 [M, 64], got {E.dtype} {tuple(E.shape)}")
-    _check_pos_rows(pos_rows, R, True)
+    _step_pos(what, pos_rows, R, True)
     if pre_rows.dtype != torch.int32 or pre_rows.numel() != Bp or not pre_rows.is_contiguous():
         raise ValueError(f"{what}: pre_rows must be a contiguous int32 tensor of {Bp} entries "
                          f"(got {pre_rows.dtype}, {pre_rows.numel()} entries)")
@@ -757,13 +772,6 @@ def rel_attn_decode_shared(qkv_new, kpre, vpre, kown, vown, E, pos_rows, pre_row
                                                  0 if workspace is None else workspace.numel(), Bp, N, Lpre, kown.shape[2], d,
                                                  E.shape[0], stream_ptr()), "mgx_rel_attn_decode_shared")
     return ctx
-
-
-def _check_base(base, pos_dev, what):
-    """the window's base (ABI 21) has the shape of the positions: one shared int32, or one per row"""
-    if base.dtype != torch.int32 or pos_dev.dtype != torch.int32 or base.numel() != pos_dev.numel() or not base.is_contiguous():
-        raise ValueError(f"{what}: base must be a contiguous int32 tensor of the positions' {pos_dev.numel()} entries "
-                         f"(got {base.dtype}, {base.numel()} entries)")
 
 
 def grammar_table(grammar, device):
@@ -789,39 +797,30 @@ def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=No
     ragged: row b's position is pos_dev[b] (draw, out_tokens column pos_dev[b] + 1, and every entry advanced);
     base (ABI 21): int32 of pos_dev's shape, the out_tokens column of window position 0 -- the draw and the column written
     take base + pos_dev in place of pos_dev; advance moves pos_dev only"""
-    _need_cuda(logits, pos_dev, next_tok, out_tokens, probs_out, allow_table, base)
     ld = logits.shape[-1]
     B = logits.numel() // ld
-    sfx = _check_pos_rows(pos_dev, B, ragged)
+    pos = _step_pos("sample_topk_topp", pos_dev, B, ragged, base, with_base=True)
+    _need_cuda(logits, pos_dev, next_tok, out_tokens, probs_out, allow_table, base)
     _check_allow_table(allow_table, V)
-    head = (ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed), ptr(pos_dev))
-    tail = (ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[-1], ptr(probs_out), B, int(row0),
-            1 if advance else 0, ptr(allow_table))
-    if base is not None:
-        _check_base(base, pos_dev, "sample_topk_topp")
-        check(_lib.load().mgx_sample_topk_topp_window(*head, ptr(base), *tail, 1 if ragged else 0, stream_ptr()),
-              "mgx_sample_topk_topp_window")
-        return next_tok
-    name = "mgx_sample_topk_topp" + (sfx or "_rows")
-    check(getattr(_lib.load(), name)(*head, *tail, stream_ptr()), "mgx_sample_topk_topp" + sfx)
+    check(_lib.load().mgx_sample_topk_topp(ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed), *pos,
+                                           ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[-1],
+                                           ptr(probs_out), B, int(row0), 1 if advance else 0, ptr(allow_table), stream_ptr()),
+          "mgx_sample_topk_topp")
     return next_tok
 
 
 def decode_reanchor(pos_dev, base, out_tokens, seq, hop, pad_token, *, ragged=False):
     """the re-anchor of the decode window (ABI 21): pos_dev -= hop and base += hop (int32 [1] shared, or [B] with ``ragged``),
     then seq int32 [B, n_pad] = the window's tokens out_tokens[b, base_b : base_b + pos_b], right-padded with pad_token"""
-    _need_cuda(pos_dev, base, out_tokens, seq)
     B, n_pad = seq.shape
-    _check_pos_rows(pos_dev, B, ragged)
-    _check_base(base, pos_dev, "decode_reanchor")
-    if not ragged and pos_dev.numel() != 1:
-        raise ValueError(f"decode_reanchor: a shared position is one int32, got {pos_dev.numel()} entries")
+    pos = _step_pos("decode_reanchor", pos_dev, B, ragged, base, with_base=True)
+    _need_cuda(pos_dev, base, out_tokens, seq)
     if (out_tokens.dtype != torch.int32 or seq.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B
             or not out_tokens.is_contiguous() or not seq.is_contiguous()):
         raise ValueError(f"decode_reanchor: out_tokens and seq must be contiguous int32 [{B}, ...], got {out_tokens.dtype} "
                          f"{tuple(out_tokens.shape)} and {seq.dtype} {tuple(seq.shape)}")
-    check(_lib.load().mgx_decode_reanchor(ptr(pos_dev), ptr(base), ptr(out_tokens), out_tokens.shape[1], ptr(seq), n_pad, int(hop),
-                                          int(pad_token), B, 1 if ragged else 0, stream_ptr()), "mgx_decode_reanchor")
+    check(_lib.load().mgx_decode_reanchor(*pos, ptr(out_tokens), out_tokens.shape[1], ptr(seq), n_pad, int(hop), int(pad_token), B,
+                                          stream_ptr()), "mgx_decode_reanchor")
     return seq
 
 
@@ -860,20 +859,16 @@ def budget_account(next_tok, out_tokens, pos_dev, cost, remaining, done, count, 
     (``inclusive``: the last token stays; else it becomes pad_token) and writes pad_token over what an ended row sampled --
     next_tok[b] and out_tokens[b, base + pos], the column the sampler has just written.  ``ragged`` / ``base`` as in
     sample_topk_topp"""
-    _need_cuda(next_tok, out_tokens, pos_dev, base, cost, remaining, done, count)
     B = remaining.numel()
-    _check_pos_rows(pos_dev, B, ragged)
-    if base is not None:
-        _check_base(base, pos_dev, "budget_account")
+    pos = _step_pos("budget_account", pos_dev, B, ragged, base, with_base=True)
+    _need_cuda(next_tok, out_tokens, pos_dev, base, cost, remaining, done, count)
     _check_budget_state("budget_account", B, cost, next_tok=next_tok, remaining=remaining, done=done, count=count)
-    if pos_dev.dtype != torch.int32 or pos_dev.numel() < 1:
-        raise ValueError(f"budget_account: the positions must be int32, got {pos_dev.dtype} with {pos_dev.numel()} entries")
     if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B:
         raise ValueError(f"budget_account: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
                          f"{tuple(out_tokens.shape)}")
-    check(_lib.load().mgx_budget_account(ptr(next_tok), ptr(out_tokens), out_tokens.shape[1], ptr(pos_dev), ptr(base),
-                                         1 if ragged else 0, ptr(cost), ptr(remaining), ptr(done), ptr(count), int(pad_token),
-                                         1 if inclusive else 0, B, stream_ptr()), "mgx_budget_account")
+    check(_lib.load().mgx_budget_account(ptr(next_tok), ptr(out_tokens), out_tokens.shape[1], *pos, ptr(cost), ptr(remaining),
+                                         ptr(done), ptr(count), int(pad_token), 1 if inclusive else 0, B, stream_ptr()),
+          "mgx_budget_account")
     return next_tok
 
 
@@ -927,16 +922,12 @@ def notes_keep(first_tok, next_tok, out_tokens, pos_dev, rule, state, max_on=NOT
     """between the step's two draws and the accounts: a row whose first draw first_tok[b] -- made before notes_mask -- is legal
     under state[b] and ``max_on`` keeps it: next_tok[b] and out_tokens[b, base + pos] (the column the second draw was written
     to; ``out_tokens`` None: no column) receive it.  ``ragged`` / ``base`` as in sample_topk_topp"""
-    _need_cuda(first_tok, next_tok, out_tokens, pos_dev, base, rule, state)
     B = _check_note_state("notes_keep", rule, state)
-    _check_pos_rows(pos_dev, B, ragged)
-    if base is not None:
-        _check_base(base, pos_dev, "notes_keep")
+    pos = _step_pos("notes_keep", pos_dev, B, ragged, base, with_base=True)
+    _need_cuda(first_tok, next_tok, out_tokens, pos_dev, base, rule, state)
     for name, t in (("first_tok", first_tok), ("next_tok", next_tok)):
         if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
             raise ValueError(f"notes_keep: {name} must be a contiguous int32 tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
-    if pos_dev.dtype != torch.int32 or pos_dev.numel() < 1:
-        raise ValueError(f"notes_keep: the positions must be int32, got {pos_dev.dtype} with {pos_dev.numel()} entries")
     if out_tokens is not None and (out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B
                                    or out_tokens.stride(1) != 1 or out_tokens.stride(0) != out_tokens.shape[1]):
         raise ValueError(f"notes_keep: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
@@ -947,8 +938,7 @@ def notes_keep(first_tok, next_tok, out_tokens, pos_dev, rule, state, max_on=NOT
     if not 1 <= int(max_on) <= NOTE_BITS:
         raise ValueError(f"notes_keep: max_on must lie in 1 .. {NOTE_BITS} ({NOTE_BITS}: no cap), got {max_on}")
     check(_lib.load().mgx_notes_keep(ptr(first_tok), ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[1],
-                                     ptr(pos_dev), ptr(base), 1 if ragged else 0, ptr(rule), ptr(state), int(max_on), V, B,
-                                     stream_ptr()), "mgx_notes_keep")
+                                     *pos, ptr(rule), ptr(state), int(max_on), V, B, stream_ptr()), "mgx_notes_keep")
     return next_tok
 
 

@@ -26,7 +26,7 @@ def _d(t) -> torch.Tensor:
 # embedding, projection, LayerNorm
 # ---------------------------------------------------------------------------------------------------------------------
 def embed(tok, table, pe, pos) -> torch.Tensor:
-    """mgx_decode_embed(_ragged): table[tok] * sqrt(d) + pe[pos], fp64 [rows, d].  ``pos``: one int or one per row."""
+    """mgx_decode_embed: table[tok] * sqrt(d) + pe[pos], fp64 [rows, d].  ``pos``: one int or one per row."""
     tok = torch.as_tensor(tok).long().reshape(-1)
     pos = torch.as_tensor(pos).long().reshape(-1).expand(tok.numel()) if torch.as_tensor(pos).numel() == 1 \
         else torch.as_tensor(pos).long().reshape(-1)

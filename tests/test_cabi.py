@@ -200,11 +200,11 @@ def test_binding_matches_pinned_signatures():
         "mgx_adam_step": (i, [vp, vp, vp, vp, vp, sz, f, f, f, f, i, f, vp]),
         "mgx_dropout_bf16_at": (i, [vp, vp, sz, sz, f, vp, vp]),                             # const uint64_t*
         "mgx_gru_next_event": (i, [vp, i, i, vp, vp, f, vp, u32, vp, i, vp, vp, vp, i, vp]),
-        "mgx_sample_topk_topp_window": (i, [vp, i, i, f, i, f, u64, vp, vp, vp, vp, i, vp, i, i, i, vp, i, vp]),
+        "mgx_sample_topk_topp": (i, [vp, i, i, f, i, f, u64, vp, vp, i, vp, vp, i, vp, i, i, i, vp, vp]),
         "mgx_linear_dw_grouped": (i, [vp, i, i, vp, sz, vp]),                                # const mgx_dw_problem*
         "mgx_grad_norm": (i, [vp, sz, f, f, vp, vp, vp]),                                    # double*, mgx_clip_state*
     }
-    assert len(pinned["mgx_sample_topk_topp_window"][1]) == 19
+    assert len(pinned["mgx_sample_topk_topp"][1]) == 19
     for name, (res, args) in pinned.items():
         fn = getattr(lib, name)
         assert fn.restype is res, name

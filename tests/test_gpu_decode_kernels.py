@@ -588,11 +588,11 @@ def run_sampler(entry, logits, V, temperature, top_k, top_p, seed, pos, prev, ta
     out = torch.full((B, out_ld), -1, dtype=torch.int32, device=DEV)
     probs = torch.full((B, V), float("nan"), device=DEV)
     tab = None if table is None else torch.from_numpy(table.view(np.int32).copy()).to(DEV)
-    if entry == "plain":
+    if entry == "plain":                                   # the C entry itself: a shared counter, no base, row0 = 0
         assert row0 == 0
         _lib.check(_lib.load().mgx_sample_topk_topp(lg.data_ptr(), V, lg.shape[1], float(temperature), int(top_k), float(top_p),
-                                                    int(seed), pos_d.data_ptr(), nt.data_ptr(), out.data_ptr(), out_ld,
-                                                    probs.data_ptr(), B, 1 if advance else 0,
+                                                    int(seed), pos_d.data_ptr(), None, 0, nt.data_ptr(), out.data_ptr(), out_ld,
+                                                    probs.data_ptr(), B, 0, 1 if advance else 0,
                                                     None if tab is None else tab.data_ptr(), _lib.stream_ptr()),
                    "mgx_sample_topk_topp")
     else:

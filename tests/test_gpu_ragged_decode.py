@@ -1,4 +1,4 @@
-"""KV-cache decode over prompts of different lengths (ABI 19): the *_ragged kernels read one position per batch row, and
+"""KV-cache decode over prompts of different lengths (ABI 19): with per_row set the decode kernels read one position per batch row, and
 generate_cached(prior_lengths=...) continues right-padded prompts of different lengths in one lockstep batch."""
 import glob
 import os

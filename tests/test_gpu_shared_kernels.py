@@ -271,7 +271,7 @@ def test_positions_outside_the_contract_touch_nothing():
 
 
 def test_shared_call_beside_the_ragged_call_on_repeated_caches():
-    """information, not an assertion beyond the bound both meet: mgx_rel_attn_decode_ragged on R rows whose caches are the
+    """information, not an assertion beyond the bound both meet: mgx_rel_attn_decode with per-row positions on R rows whose caches are the
     prompt rows followed by the own rows (the repeated call's layout) computes the same logical attention; whether the two
     agree bitwise is printed (their split counts differ where decode_splits and the shared policy do)"""
     ops = KC.ops()

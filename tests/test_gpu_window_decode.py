@@ -1,6 +1,6 @@
 """KV-cache decode past max_seq (ABI 21): generate_cached(window=, hop=) keeps a window of every row's sequence in the cache
 and re-anchors it every ``hop`` tokens -- the oldest tokens dropped, the rest renumbered from position 0 and their K/V rebuilt
-by one batched causal pass.  mgx_sample_topk_topp_window and mgx_decode_reanchor are the two kernels entries it adds."""
+by one batched causal pass.  The sampler's base (mgx_sample_topk_topp's base_dev) and mgx_decode_reanchor are what it adds to the C ABI."""
 import glob
 import os
 
@@ -51,7 +51,8 @@ def _same(a, b):
 @pytest.mark.parametrize("grammar", [False, True])
 @pytest.mark.parametrize("per_row", [False, True])
 def test_window_sampler_is_the_sampler_at_the_absolute_step(per_row, grammar):
-    """pos = t and base = c give, bit for bit, what the existing sampler gives at position c + t; advance moves pos only"""
+    """pos = t and base = c give, bit for bit, what the sampler without a base gives at position c + t (c = 0: a base of zeros
+    is no base, the header's sentence, for the shared counter and for per-row positions); advance moves pos only"""
     from musicgeneration_amd import ops
     g = torch.Generator().manual_seed(11)
     B, out_ld = 6, 1100

@@ -45,3 +45,87 @@ def test_condition_files_cli_refusals(tmp_path):
     from musicgeneration_amd.sequence import EventSeq, NoteSeq
     longest = len(EventSeq.from_note_seq(NoteSeq.from_midi_file(b)).to_array())
     assert f"({longest} events)" in msg and "-l 100" in msg and "-M 128" in msg
+
+
+# ---- the step-position arguments of the ops wrappers (ops._step_pos): refused on the host, before any device work --------
+_B, _D, _V = 3, 64, 20
+_BF = torch.bfloat16
+
+
+def _i32(*shape):
+    return torch.zeros(*shape, dtype=torch.int32)
+
+
+def _wrappers():
+    """name -> (call(pos, ragged, base), takes a base): every ops wrapper that takes a position, on CPU tensors that are
+    otherwise well-formed, so that the position check is the only one that can refuse"""
+    from musicgeneration_amd import ops
+    tok, table, pe = _i32(_B), torch.zeros(_V, _D), torch.zeros(8, _D)
+    hid, out = torch.zeros(_B, _D, dtype=_BF), _i32(_B, 16)
+    cache, E = torch.zeros(_B, 1, 8, 64, dtype=_BF), torch.zeros(8, 64, dtype=_BF)
+    rule, state = _i32(_V), _i32(_B, ops.NOTE_WORDS)
+    return {
+        "decode_embed": (lambda p, r, b: ops.decode_embed(tok, table, pe, p, hid, ragged=r), False),
+        "decode_embed_linear": (lambda p, r, b: ops.decode_embed_linear(tok, table, pe, p, torch.zeros(32, _D, dtype=_BF), None, hid,
+                                                                        ragged=r), False),
+        "rel_attn_decode": (lambda p, r, b: ops.rel_attn_decode(torch.zeros(_B, 3 * _D, dtype=_BF), cache, cache.clone(), E, p, hid,
+                                                                ragged=r), False),
+        "sample_topk_topp": (lambda p, r, b: ops.sample_topk_topp(torch.zeros(_B, 32, dtype=_BF), _V, p, _i32(_B), out, ragged=r,
+                                                                  base=b), True),
+        "decode_reanchor": (lambda p, r, b: ops.decode_reanchor(p, _i32(p.numel()) if b is None else b, out, _i32(_B, 32), 2, 0,
+                                                                ragged=r), True),
+        "budget_account": (lambda p, r, b: ops.budget_account(_i32(_B), out, p, _i32(_V), _i32(_B), _i32(_B), _i32(_B), 0, ragged=r,
+                                                              base=b), True),
+        "notes_keep": (lambda p, r, b: ops.notes_keep(_i32(_B), _i32(_B), out, p, rule, state, ragged=r, base=b), True),
+    }
+
+
+WRAPPERS = ["decode_embed", "decode_embed_linear", "rel_attn_decode", "sample_topk_topp", "decode_reanchor", "budget_account",
+            "notes_keep"]
+WITH_BASE = ["sample_topk_topp", "decode_reanchor", "budget_account", "notes_keep"]
+
+
+def test_the_wrapper_lists_cover_every_wrapper():
+    table = _wrappers()
+    assert sorted(table) == sorted(WRAPPERS) and sorted(n for n, (_, b) in table.items() if b) == sorted(WITH_BASE)
+
+
+@pytest.mark.parametrize("name", WRAPPERS)
+def test_positions_of_the_wrong_kind_are_refused(name):
+    call, _ = _wrappers()[name]
+    for ragged, n in ((False, 1), (True, _B)):
+        with pytest.raises(ValueError, match="int32"):                     # wrong dtype
+            call(torch.zeros(n, dtype=torch.int64), ragged, None)
+        with pytest.raises(ValueError, match="int32"):
+            call(torch.zeros(n, dtype=torch.float32), ragged, None)
+    with pytest.raises(ValueError, match="contiguous"):                    # a strided view (one entry is always contiguous)
+        call(_i32(2 * _B)[::2], True, None)
+    for n in (1, _B - 1, _B + 1):                                          # ragged: one entry per row
+        with pytest.raises(ValueError, match=f"{_B} entries"):
+            call(_i32(n), True, None)
+    for n in (0, 2, _B):                                                   # a shared counter is one entry
+        with pytest.raises(ValueError, match="shared position"):
+            call(_i32(n), False, None)
+
+
+@pytest.mark.parametrize("name", WITH_BASE)
+def test_a_base_of_another_shape_is_refused(name):
+    call, _ = _wrappers()[name]
+    for ragged, n, bad in ((False, 1, (0, 2, _B)), (True, _B, (1, _B - 1, _B + 1))):
+        for m in bad:
+            with pytest.raises(ValueError, match="base"):
+                call(_i32(n), ragged, _i32(m))
+        with pytest.raises(ValueError, match="base"):
+            call(_i32(n), ragged, torch.zeros(n, dtype=torch.int64))
+
+
+@pytest.mark.parametrize("name", WRAPPERS)
+def test_well_formed_positions_pass_the_host_check(name):
+    """what the helper lets through reaches the next check, which on CPU tensors is the one for device memory -- also for a
+    ragged batch of one row, which a check on the entry count alone could not tell from a shared counter"""
+    from musicgeneration_amd._lib import MgxError
+    call, has_base = _wrappers()[name]
+    for ragged, n in ((False, 1), (True, _B)):
+        for base in ([None, _i32(n)] if has_base else [None]):
+            with pytest.raises(MgxError, match="CUDA/HIP tensors"):
+                call(_i32(n), ragged, base)

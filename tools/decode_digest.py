@@ -1,7 +1,8 @@
-"""Digests of the KV-cache decode: a fixed, seeded list of small generate_cached calls, one SHA-256 per case over the tokens
-and, where the case asks for them, the probabilities and every returned cache tensor (bytes of the contiguous CPU copy).
-Two checkouts (or two libraries, MGX_LIB_PATH) compute the same thing bit for bit when their lists agree line for line.
-Only the public generate_cached is used, so this file copied into an older checkout digests that checkout."""
+"""Digests of the KV-cache decode: a fixed, seeded list of small generate_cached calls -- and, for every other driver that passes
+a position, of generate_cached(window= / samples_per_prompt= / note_rules=), generate_timed and generate_beam -- one SHA-256 per
+case over the tokens and, where the case asks for them, the probabilities and every returned tensor (bytes of the contiguous
+CPU copy).  Two checkouts (or two libraries, MGX_LIB_PATH) compute the same thing bit for bit when their lists agree line for line.
+Only the model's public methods are used, so this file copied into an older checkout digests that checkout."""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -50,5 +51,38 @@ CASES = [
 for name, mt, prior, n, kw in CASES:
     for kv in ("bf16", "fp8"):
         res = mt.generate_cached(prior, n, seed=11, kv_cache=kv, **kw)
+        torch.cuda.synchronize()
+        print(f"{name:20s} {kv:4s} {digest(res)}", flush=True)
+
+# every other driver that passes a position: the re-anchored window, N samples per prompt, budgets, held notes, beam search
+pad = small.pad_token
+cost = torch.arange(V) % 5
+cost[pad] = 0
+rules = torch.zeros(V, dtype=torch.int32)                  # ids 0..39 set bits 0..39, ids 40..79 clear them
+rules[:40], rules[40:80] = torch.arange(1, 41, dtype=torch.int32), -torch.arange(1, 41, dtype=torch.int32)
+rules[pad] = 0
+p30, lens30 = tokens(4, 30, 8), [30, 3, 17, 1]
+timed = lambda mt, prior, n, kv, **kw: [(t, c, i["spent"], i["remaining"], i["done"]) for t, c, i in
+                                        [mt.generate_timed(prior, kw.pop("budget"), cost, n, seed=11, kv_cache=kv, **kw)]]
+beam = lambda mt, prior, n, kv, **kw: mt.generate_beam(prior, n, seed=11, kv_cache=kv, return_beams=True, **kw)
+cached = lambda mt, prior, n, kv, **kw: mt.generate_cached(prior, n, seed=11, kv_cache=kv, **kw)
+# name, call, prior, new tokens, caches, options
+MORE = [
+    ("window_ragged", cached, p70, 40, ("bf16", "fp8"), dict(prior_lengths=[70, 40, 33, 30], window=48, hop=8, top_p=0.9,
+                                                             return_cache=True)),
+    ("window_shared", cached, tokens(3, 20, 9), 40, ("bf16", "fp8"), dict(window=32, hop=8, top_k=20, return_probs=True)),
+    ("samples3_ragged", cached, p30, 24, ("bf16",), dict(prior_lengths=lens30, samples_per_prompt=3, top_p=0.9)),
+    ("timed_ragged", timed, p30, 40, ("bf16", "fp8"), dict(budget=[20, 35, None, 0], prior_lengths=lens30, poll=4, top_p=0.9)),
+    ("timed_window", timed, tokens(2, 20, 10), 40, ("bf16",), dict(budget=[30, 70], inclusive=False, window=32, hop=8, poll=8)),
+    ("notes_ragged", cached, p30, 40, ("bf16", "fp8"), dict(prior_lengths=lens30, note_rules=rules, max_polyphony=3, top_k=30)),
+    ("notes_shared", cached, tokens(5, 12, 11), 30, ("bf16",), dict(note_rules=rules)),
+    ("notes_samples2", cached, p30, 24, ("bf16",), dict(prior_lengths=lens30, samples_per_prompt=2, note_rules=rules)),
+    ("beam4", beam, tokens(3, 12, 12), 20, ("bf16", "fp8"), dict(beam_size=4)),
+    ("beam3_ragged_stoch", beam, p30[:2], 21, ("bf16", "fp8"), dict(beam_size=3, prior_lengths=[30, 5], stochastic=True,
+                                                                    temperature=0.9)),
+]
+for name, call, prior, n, kvs, kw in MORE:
+    for kv in kvs:
+        res = call(small, prior, n, kv, **dict(kw))
         torch.cuda.synchronize()
         print(f"{name:20s} {kv:4s} {digest(res)}", flush=True)
