@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters) */
-#define MGX_ABI_VERSION 30
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM */
+#define MGX_ABI_VERSION 31
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -546,6 +546,42 @@ int mgx_notes_account(const int32_t* next_tok, const int32_t* rule, int32_t* sta
 int mgx_notes_keep(const int32_t* first_tok, int32_t* next_tok, int32_t* out_tokens, int out_ld, const int32_t* pos_dev,
                    const int32_t* base_dev, int per_row, const int32_t* rule, const int32_t* state, int max_on, int V, int B,
                    void* stream);
+
+/* ---- Repetition control (ABI 31): a presence / frequency penalty over the row's recent tokens and a no-repeat-n-gram rule, in
+ * one stateless call.  The row's history is what the decode holds on the device already: out_tokens int32 [B,out_ld], the prompt
+ * and every token the sampler has written, in absolute columns whatever the window does.  So there is no state to keep, stage or
+ * gather, and the call is captured with the step.  Every amount is FINITE (a "banned" id gets `ban` subtracted, not -inf), so the
+ * call never changes which logits of a row are finite: the sampler still ignores a grammar row that leaves no finite logit,
+ * mgx_budget_mask still never masks a cost-0 id, mgx_notes_mask still never empties a row -- and where every other id is masked
+ * away the banned id is what is left and is drawn.
+ * A step is: logits, (mgx_budget_mask,) mgx_repeat_penalty, (the sampler's first draw, mgx_notes_mask,) the sampler,
+ * (mgx_notes_keep,) (mgx_budget_account,) (mgx_notes_account) -- before the first draw, because mgx_notes_keep lets a legal first
+ * draw stand: drawn from unpenalised logits it would carry most samples past the penalty.
+ * mgx_repeat_penalty, in place on the step's logits bf16 [B,ld] before the sampler.  For row b, with c = base + t ("Step
+ *   positions", K12), the column of the step's input token -- the row's last token: the prompt's last on the first step, afterwards
+ *   the one the sampler wrote.  A row with c < 0 or c >= out_ld is left bit for bit.
+ *   Counts (window > 0):  cnt[v] = the number of columns j, max(0, c - window + 1) <= j <= c, with out_tokens[b,j] == v, for
+ *     0 <= v < V.  History ids outside 0..V-1 (a pad id, a negative filler) count for nothing.
+ *   N-gram (ngram = n >= 2):  k = n - 1, lo = span ? max(0, c - span + 1) : 0.  If c - k + 1 >= lo, the context is
+ *     out_tokens[b, c-k+1 .. c], and for every e, lo + k - 1 <= e <= c - 1, whose k columns e-k+1 .. e equal the context element
+ *     by element, the follower f = out_tokens[b, e+1] is BANNED if 0 <= f < V.  The comparison is on raw int32 values, out-of-range
+ *     ids included; occurrences may overlap the context (e + 1 <= c); one that begins before lo does not count.
+ *   Amount, for v < V:  a[v] = ban if v is banned;  else pen[cnt[v]] if window > 0, subject[v] != 0 and cnt[v] > 0;  else none.  A
+ *     banned id that is also counted gets ban, not the sum.  Where there is one, logits[b,v] = bf16(f32(logits[b,v]) - a[v]): ONE
+ *     f32 subtraction rounded to nearest, then one rounding to bf16, nearest-even.  -inf stays -inf; a NaN becomes a NaN of
+ *     unspecified payload.  Ids without an amount, columns >= V, out_tokens, pos_dev, base_dev, subject and pen are not written.
+ *   pen float [window + 1] (pen[0] is never read) and subject int32 [V] may be NULL if and only if window == 0.
+ * MGX_ERR_NULL for a NULL logits, out_tokens or pos_dev, or subject / pen missing with window > 0.  MGX_ERR_SHAPE unless B > 0,
+ *   0 < V <= 1024, ld >= V, out_ld > 0;  0 <= window <= MGX_REPEAT_MAX_WINDOW;  ngram == 0 or 2 <= ngram <= MGX_REPEAT_MAX_NGRAM;
+ *   span == 0 or span >= ngram;  not both window == 0 and ngram == 0;  with ngram != 0, ban finite and > 0.
+ * Contract (not checked: the values live on the device): pen finite, the positions as under "Step positions".
+ * One workgroup of 256 threads per row; the grid is a function of B only (no host read, no allocation).  LDS atomics on the counts
+ * and the ban bitmap, no global atomics.                                                                                   */
+#define MGX_REPEAT_MAX_WINDOW 4096
+#define MGX_REPEAT_MAX_NGRAM  64
+int mgx_repeat_penalty(uint16_t* logits, int V, int ld, const int32_t* out_tokens, int out_ld, const int32_t* pos_dev,
+                       const int32_t* base_dev, int per_row, const int32_t* subject, const float* pen, int window, int ngram,
+                       int span, float ban, int B, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

@@ -96,6 +96,13 @@ class MuMIDI_EventSeq:
         return c.idxs_feats
 
     @staticmethod
+    def repeat_subject(vocab_size=None):
+        """the ids whose repetition ``decode.Repetition`` penalises by default, int32 [vocab_size]: 1 on the note_on ids (the drum hits included), 0
+        elsewhere -- also on the ids a model adds beyond dim() (its pad id).  Only pitches: a frequency penalty on position or duration
+        ids would distort the rhythm"""
+        return _vocab.repeat_subject(MuMIDI_EventSeq.dim(), MuMIDI_EventSeq.feat_ranges()['note_on'], vocab_size)
+
+    @staticmethod
     def get_track_id(track_name):
         return MuMIDI_EventSeq.feat_ranges()['track'][0] + tracks_idx[track_name]
 

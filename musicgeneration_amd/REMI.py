@@ -163,6 +163,13 @@ class REMI_EventSeq:
         return cost
 
     @staticmethod
+    def repeat_subject(vocab_size=None):
+        """the ids whose repetition ``decode.Repetition`` penalises by default, int32 [vocab_size]: 1 on the note_on ids, 0
+        elsewhere -- also on the ids a model adds beyond dim() (its pad id).  Only pitches: a frequency penalty on position or duration
+        ids would distort the rhythm"""
+        return _vocab.repeat_subject(REMI_EventSeq.dim(), REMI_EventSeq.feat_ranges()['note_on'], vocab_size)
+
+    @staticmethod
     def transpose_table(offsets, vocab_size=None):
         """what every id becomes under a transposition, int32 [len(offsets), vocab_size]: row s moves note_on pitch p to
         p + offsets[s] (|offset| <= 11; a pitch that would leave the range comes back by an octave, as in

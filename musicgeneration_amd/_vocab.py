@@ -73,3 +73,14 @@ def transpose_table(dim: int, offsets, vocab_size=None, pitch_runs=(), chord_run
             c = np.arange(len(chord_run) - 1)
             table[s, chord_run.start:chord_run.stop - 1] = chord_run.start + (c // 12) * 12 + (c % 12 + off) % 12
     return table
+
+
+def repeat_subject(dim, note_on, vocab_size=None):
+    """the ids that repetition control counts, int32 [vocab_size]: 1 on the run ``note_on``, 0 elsewhere and on the ids a model
+    adds beyond ``dim`` (its pad id)"""
+    V = dim if vocab_size is None else int(vocab_size)
+    if V < dim:
+        raise ValueError(f"vocab_size ({V}) is below the codec's {dim} ids")
+    subject = np.zeros(V, dtype=np.int32)
+    subject[note_on.start:note_on.stop] = 1
+    return subject

@@ -13,7 +13,9 @@ re-anchored window (``window=``, ``decode_window``), the one way to generate pas
 ``generate_cached`` with a ``Budget``: every row's clock on the device (``decode_step_constrained`` brackets the sampler with
 ops.budget_mask / ops.budget_account) and a step loop that reads the rows' ``done`` flags every ``poll`` steps and stops early.
 ``NoteState`` (``note_rules=``, ``max_polyphony=``) is the second per-row state bracketing the sampler the same way: the set of
-notes every row holds (ops.notes_mask / ops.notes_account), which keeps a MIDI-like stream well-formed."""
+notes every row holds (ops.notes_mask / ops.notes_account), which keeps a MIDI-like stream well-formed.  ``Repetition``
+(``repetition=``) is not a state: one launch before the sampler (ops.repeat_penalty) reads the row's own columns of the output
+matrix and penalises repeated ids and n-grams by finite amounts."""
 from __future__ import annotations
 
 import dataclasses
@@ -529,13 +531,105 @@ def check_note_args(model, note_rules, max_polyphony, *, grammar=None, groups=No
     return NoteState(np.ascontiguousarray(arr.astype(np.int32)), max_polyphony)
 
 
+REPEAT_MAX_AMOUNT = 1e4                                   # the largest amount a logit loses: exp(-1e4 / T) is 0 in f32
+
+
+class Repetition:
+    """repetition control of generate_cached / generate_timed (include/mgx.h, ABI 31): a presence / frequency penalty over the
+    last ``window`` tokens of every row and a no-repeat-``ngram`` rule over its last ``span`` tokens (0: the whole sequence so far,
+    the prompt included).  An id v with ``subject[v] != 0`` that occurs c > 0 times in the window loses ``presence + frequency * c``
+    from its logit; an id that would complete an n-gram the row holds already loses ``ban``.  All amounts are finite, so where every
+    other id is masked away (grammar, budget, note rules) a banned id is still drawn: the ban gives way by itself.  Stateless: the
+    history is the decode's own token matrix.  ``subject``: integers [vocab_size], e.g. ``EventSeq.repeat_subject()``"""
+
+    def __init__(self, subject, presence=0.0, frequency=0.0, window=64, ngram=0, span=0, ban=REPEAT_MAX_AMOUNT):
+        self.subject_host, self.presence, self.frequency = subject, presence, frequency
+        self.window, self.ngram, self.span, self.ban = window, ngram, span, ban
+        self.subject = self.pen = None
+
+    @property
+    def counting(self) -> bool:
+        """are the counts on?  With both penalties 0 the kernel is called with window 0 and no tables"""
+        return self.presence != 0 or self.frequency != 0
+
+    @property
+    def inert(self) -> bool:
+        """neither a penalty nor an n-gram rule: the step is the unchanged decode_step"""
+        return not self.counting and self.ngram == 0
+
+    def pen_table(self):
+        """float32 [window + 1]: pen[0] = 0, pen[c] = presence + frequency * c, the sum formed in float64 and rounded once"""
+        c = np.arange(self.window + 1, dtype=np.float64)
+        pen = (np.float64(self.presence) + np.float64(self.frequency) * c).astype(np.float32)
+        pen[0] = 0
+        return pen
+
+    def stage(self, dev) -> "Repetition":
+        """``subject`` and ``pen`` on the device, once per call (nothing with the counts off)"""
+        if self.counting:
+            self.subject = torch.from_numpy(np.ascontiguousarray(np.asarray(self.subject_host).astype(np.int32))).to(dev)
+            self.pen = torch.from_numpy(self.pen_table()).to(dev)
+        return self
+
+    def apply(self, logits, V: int, r: "SubBatch") -> None:
+        ops.repeat_penalty(logits, V, r.out, subject=self.subject, pen=self.pen, window=self.window if self.counting else 0,
+                           ngram=self.ngram, span=self.span, ban=self.ban, **r.step)
+
+
+def check_repeat_args(model, repetition, *, groups=None, masked_groups=False):
+    """every refusal of ``repetition`` (ValueError), on the host before any device work.  Returns a Repetition of its own with the
+    subject as numpy int32 -- the caller's object is not staged, so it serves any number of calls -- or None: no ``repetition``,
+    or an inert one"""
+    if repetition is None:
+        return None
+    if not isinstance(repetition, Repetition):
+        raise ValueError(f"repetition must be a decode.Repetition (or None), got {type(repetition).__name__}")
+    rp, V = repetition, model.vocab_size
+    sub = rp.subject_host
+    arr = np.asarray(sub.detach().cpu() if isinstance(sub, torch.Tensor) else sub)
+    if arr.shape != (V,) or arr.dtype.kind not in "iub":
+        raise ValueError(f"repetition: subject must be integers, one per id, [vocab_size] = [{V}], got {arr.dtype} {tuple(arr.shape)}")
+    if arr[model.pad_token] != 0:
+        raise ValueError(f"repetition: subject[pad_token] must be 0 (an ended row steps on pad tokens), got {arr[model.pad_token]}")
+    for name, v in (("presence", rp.presence), ("frequency", rp.frequency)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+            raise ValueError(f"repetition: {name} must be a finite number >= 0, got {v}")
+
+    def integer(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"repetition: {name} must be an integer, got {v!r}")
+        return int(v)
+    window, ngram, span = integer("window", rp.window), integer("ngram", rp.ngram), integer("span", rp.span)
+    if not 1 <= window <= ops.REPEAT_MAX_WINDOW:
+        raise ValueError(f"repetition: window must lie in 1 .. {ops.REPEAT_MAX_WINDOW}, got {window}")
+    if ngram != 0 and not 2 <= ngram <= ops.REPEAT_MAX_NGRAM:
+        raise ValueError(f"repetition: ngram must be 0 (off) or lie in 2 .. {ops.REPEAT_MAX_NGRAM}, got {ngram}")
+    if span != 0 and span < max(ngram, 1):
+        raise ValueError(f"repetition: span must be 0 (the whole sequence so far) or >= ngram = {ngram}, got {span}")
+    if isinstance(rp.ban, bool) or not isinstance(rp.ban, (int, float, np.integer, np.floating)) or not 0 < rp.ban <= REPEAT_MAX_AMOUNT:
+        raise ValueError(f"repetition: ban must lie in (0, {REPEAT_MAX_AMOUNT:g}], got {rp.ban}")
+    if float(rp.presence) + float(rp.frequency) * window > REPEAT_MAX_AMOUNT:
+        raise ValueError(f"repetition: presence + frequency * window must not exceed {REPEAT_MAX_AMOUNT:g}, got "
+                         f"{float(rp.presence) + float(rp.frequency) * window:g}")
+    if (groups or 1) > 1 or masked_groups:
+        raise ValueError("repetition is not combined with groups / masked_groups (experiment flags: the penalty is tested on the "
+                         "batch as one group)")
+    own = Repetition(np.ascontiguousarray(arr.astype(np.int32)), float(rp.presence), float(rp.frequency), window, ngram, span,
+                     float(rp.ban))
+    return None if own.inert else own
+
+
 def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool, bud: Optional[Budget],
-                            notes: Optional[NoteState]) -> None:
-    """decode_step under the rows' budgets and / or held notes: the logits are masked before the sampler sees them, and the draw
-    is charged to the clock and applied to the notes after it.  With ``notes`` the step draws twice (below)"""
+                            notes: Optional[NoteState], rep: Optional[Repetition] = None) -> None:
+    """decode_step under the rows' budgets, repetition control and / or held notes: the logits are masked and penalised before the
+    sampler sees them, and the draw is charged to the clock and applied to the notes after it (the order: include/mgx.h, ABI 31).
+    With ``notes`` the step draws twice (below); the penalty comes before the first draw, which notes_keep would otherwise let
+    stand unpenalised"""
     logits = step_logits(w, r)
     if bud is not None:
         ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
+    if rep is not None:
+        rep.apply(logits, w.V, r)
     out = r.out if sample_into_out else None
     if notes is not None:
         # the sampler draws by inverse CDF, so a draw from the masked logits is another token even where the unmasked draw of
@@ -682,9 +776,10 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
 
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
                     return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None,
-                    bud: Optional[Budget] = None, note_rules=None, max_polyphony=None):
+                    bud: Optional[Budget] = None, note_rules=None, max_polyphony=None, repetition=None):
     """MusicTransformer.generate_cached (documented there).  ``bud``: generate_timed's budgets, not yet staged -- the steps run
     decode_step_constrained and the loop stops once every row has ended"""
+    rep = check_repeat_args(model, repetition, groups=groups, masked_groups=masked_groups)
     notes = check_note_args(model, note_rules, max_polyphony, grammar=grammar, groups=groups, masked_groups=masked_groups,
                             return_cache=return_cache)
     P, lens, batched, hop = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache, window, hop, groups,
@@ -692,7 +787,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     if samples_per_prompt is not None:
         return generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs,
-                               notes)
+                               notes, rep)
     extra, prior, ragged = prior.shape[1] - P, prior[:, :P], lens is not None      # extra > 0: equal prior_lengths below the width
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -732,10 +827,12 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
             bud.stage(dev)
         if notes is not None:                                 # what every prompt leaves held; the prefill below stays unconstrained
             notes.stage(dev, prior, lens or [P] * B)
+        if rep is not None:
+            rep.stage(dev)
 
         def step_rows(r):                                     # length 0 still runs the last prompt token (its distribution)
-            if bud is not None or notes is not None:
-                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes)
+            if bud is not None or notes is not None or rep is not None:
+                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes, rep)
             else:
                 decode_step(w, r, sampler, length > 0)
         if window is not None:
@@ -766,12 +863,13 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
 
 
 def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, grammar, use_graph: bool, return_probs: bool,
-                    notes: Optional[NoteState] = None):
+                    notes: Optional[NoteState] = None, rep: Optional[Repetition] = None):
     """generate_cached(samples_per_prompt=N), its arguments checked: rows r = b * N + n, sample n of prompt b.  One batched
     prefill of the Bp prompts fills the prompt cache (pre_rows = len_b - 1 rows each); every row then resumes at its prompt's
     last token and runs the ragged step on R = Bp * N rows, whose attention reads the prompt's rows once for the samples of a
     prompt and appends to the row's own cache.  Row r draws with (seed, t, r), as it does in the call on the prompts repeated N
-    times.  ``notes``: a NoteState, not yet staged -- every row starts from its prompt's held notes"""
+    times.  ``notes``: a NoteState, not yet staged -- every row starts from its prompt's held notes.  ``rep``: a checked Repetition, not
+    yet staged -- stateless, so the samples of a prompt need nothing gathered"""
     with decode_session(model) as st:
         (Bp, P), dev = prior.shape, st.param.device
         R, total, d, V = Bp * N, P + length, model.embedding_dim, model.vocab_size
@@ -788,10 +886,12 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
         probs_all, file = probs_filer([r], total, V, pos.long()) if return_probs else (None, None)
         if notes is not None:
             notes.stage(dev, prior, lens, repeat=N)
+        if rep is not None:
+            rep.stage(dev)
 
         def step_rows(r_):                                    # length 0 still runs the last prompt token (its distribution)
-            if notes is not None:
-                decode_step_constrained(w, r_, sampler, length > 0, None, notes)
+            if notes is not None or rep is not None:
+                decode_step_constrained(w, r_, sampler, length > 0, None, notes, rep)
             else:
                 decode_step(w, r_, sampler, length > 0)
         run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=file)
@@ -799,14 +899,15 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
 
 
 def generate_timed(model, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,
-                   prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules=None, max_polyphony=None):
+                   prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules=None, max_polyphony=None, repetition=None):
     """MusicTransformer.generate_timed (documented there): generate_cached's driver with a Budget"""
     B = prior.shape[0]
+    check_repeat_args(model, repetition)
     budgets, cost_i = check_budget_args(model, B, budget, cost, max_length, poll, refused)
     check_args(model, prior, max_length, return_probs, "auto", prior_lengths, kv_cache, window, hop)     # before any device work
     bud = Budget(budgets, cost_i, model.pad_token, bool(inclusive), int(poll))
     res = generate_cached(model, prior, max_length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, "auto",
-                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud, note_rules, max_polyphony)
+                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud, note_rules, max_polyphony, repetition)
     tokens, probs = res if return_probs else (res, None)
     # what every row spent: the cost of the events it kept, columns P_b .. P_b + count_b - 1
     start = torch.tensor(_prompt_lengths(prior, prior_lengths) or [prior.shape[1]] * B, device=tokens.device)[:, None]

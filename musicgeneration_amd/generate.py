@@ -80,6 +80,22 @@ def get_options(argv=None):
     parser.add_option('--release', dest='release', action='store_true', default=False,
                       help='close the notes a sample still holds where it ends: their note_off events are appended before the '
                            'MIDI file is written (--repr midi_like; with --seconds: after the events the sample kept)')
+    parser.add_option('--presence-penalty', dest='presence_penalty', type='float', default=0.0,
+                      help='repetition control (KV-cache decode): subtract X from the logit of every --repeat-ids event that occurs '
+                           'among the last --repeat-window events of the sample, the prompt included.  With --best-of the '
+                           'candidates are ranked by their unpenalised score')
+    parser.add_option('--frequency-penalty', dest='frequency_penalty', type='float', default=0.0,
+                      help='subtract X times the number of its occurrences among the last --repeat-window events')
+    parser.add_option('--repeat-window', dest='repeat_window', type='int', default=64,
+                      help='the events the two penalties look back over (1 .. 4096; default 64)')
+    parser.add_option('--repeat-ids', dest='repeat_ids', type='choice', choices=['pitch', 'all'], default='pitch',
+                      help="the events the two penalties apply to: 'pitch' (default), the note_on events of the --repr -- a penalty "
+                           "on time events would distort the rhythm -- or 'all', every event but the pad")
+    parser.add_option('--no-repeat-ngram', dest='no_repeat_ngram', type='int', default=0,
+                      help='no run of N events (2 .. 64) occurs twice: an event that would complete a run the sample holds already '
+                           'loses 1e4 from its logit (it is still drawn where --grammar, --seconds or --well-formed leave nothing else)')
+    parser.add_option('--ngram-span', dest='ngram_span', type='int', default=0,
+                      help='the events --no-repeat-ngram looks back over (>= N); 0 (default): the whole sequence so far')
     return parser.parse_args(argv)[0]
 
 
@@ -169,6 +185,54 @@ def _check_notes(o):
     return well
 
 
+def _check_repeat(o):
+    """--presence-penalty / --frequency-penalty / --repeat-window / --repeat-ids / --no-repeat-ngram / --ngram-span against the
+    options they do not go with and their own ranges, before any model or device work.  Returns whether any of them is given"""
+    d = get_options([])
+    names = ('presence_penalty', 'frequency_penalty', 'repeat_window', 'repeat_ids', 'no_repeat_ngram', 'ngram_span')
+    given = [n for n in names if getattr(o, n) != getattr(d, n)]
+    if not given:
+        return False
+    flag = '--' + given[0].replace('_', '-')
+    for on, what, why in ((o.beam_size, '-B/--beam-size', 'a search ranks whole beams by likelihood: not built'),
+                          (o.reference_mask, '--reference-mask', 'the KV-cache decode is causal')):
+        if on:
+            raise SystemExit(f'{flag} cannot be combined with {what} ({why})')
+    from .ops import REPEAT_MAX_NGRAM, REPEAT_MAX_WINDOW
+    for name in ('presence_penalty', 'frequency_penalty'):
+        v = getattr(o, name)
+        if not (np.isfinite(v) and v >= 0):
+            raise SystemExit(f"--{name.replace('_', '-')} must be a finite number >= 0, got {v}")
+    if not 1 <= o.repeat_window <= REPEAT_MAX_WINDOW:
+        raise SystemExit(f'--repeat-window must lie in 1 .. {REPEAT_MAX_WINDOW}, got {o.repeat_window}')
+    if o.no_repeat_ngram and not 2 <= o.no_repeat_ngram <= REPEAT_MAX_NGRAM:
+        raise SystemExit(f'--no-repeat-ngram must lie in 2 .. {REPEAT_MAX_NGRAM} (0 = off), got {o.no_repeat_ngram}')
+    if o.ngram_span and o.ngram_span < max(o.no_repeat_ngram, 1):
+        raise SystemExit(f'--ngram-span must be 0 (the whole sequence) or >= --no-repeat-ngram {o.no_repeat_ngram}, got {o.ngram_span}')
+    if o.presence_penalty + o.frequency_penalty * o.repeat_window > 1e4:
+        raise SystemExit('--presence-penalty + --frequency-penalty x --repeat-window must not exceed 1e4, got '
+                         f'{o.presence_penalty + o.frequency_penalty * o.repeat_window:g}')
+    return True
+
+
+def _repeat_args(o, mt):
+    """the keyword argument of generate_cached / generate_timed that the repetition flags set"""
+    from .decode import Repetition
+    if o.repeat_ids == 'all':
+        subject = np.ones(mt.vocab_size, dtype=np.int32)
+        subject[mt.pad_token] = 0
+    else:
+        if o.repr == 'remi':
+            from .REMI import REMI_EventSeq as Codec
+        elif o.repr == 'mumidi':
+            from .MuMIDI import MuMIDI_EventSeq as Codec
+        else:
+            from .sequence import EventSeq as Codec
+        subject = Codec.repeat_subject(mt.vocab_size)
+    return dict(repetition=Repetition(subject, o.presence_penalty, o.frequency_penalty, o.repeat_window, o.no_repeat_ngram,
+                                      o.ngram_span))
+
+
 def _note_args(o, mt):
     """the keyword arguments of generate_cached / generate_timed that --well-formed / --max-polyphony set"""
     from .sequence import EventSeq
@@ -244,11 +308,13 @@ def main(argv=None):
     _check_share_prompt(o)
     timed = _check_timed(o)
     well = _check_notes(o)
+    repeat = _check_repeat(o)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
         raise SystemExit('--reference-mask cannot be combined with --window (the KV-cache decode is causal)')
-    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size or timed or well):
+    if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size or timed or well
+                                     or repeat):
         raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
                          '(or -B K; the default sampler recomputes the window and keeps no cache)')
     # with --window every branch below samples through the KV-cache decode and its re-anchored window
@@ -273,6 +339,8 @@ def main(argv=None):
             print('Test >>>> Loss: {:6.6}, Accuracy: {}'.format(m['loss'], m['accuracy']))
     mt.test()
     notes = _note_args(o, mt) if well else {}             # --well-formed: every sampling call below is the KV-cache decode
+    if repeat:                                            # so it is with the repetition flags; their keyword travels with the notes'
+        notes.update(_repeat_args(o, mt))
 
     def search(prior, **kw):                              # -B: the best beam of every sample
         res, scores = mt.generate_beam(prior, o.max_len, o.beam_size, temperature=o.temperature, stochastic=o.stochastic_beam_search,
@@ -328,10 +396,10 @@ def main(argv=None):
             _write(o, search(prior, grammar=Codec.next_token_table()))
             return
         if timed:
-            _write(o, _timed(o, mt, timed, prior, grammar=Codec.next_token_table()))
+            _write(o, _timed(o, mt, timed, prior, grammar=Codec.next_token_table(), **notes))
             return
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
-                                 grammar=Codec.next_token_table(), **cached).cpu().numpy()
+                                 grammar=Codec.next_token_table(), **cached, **notes).cpu().numpy()
         res = _best_of(o, mt, res, [1] * rows, Codec.next_token_table())
     elif o.beam_size:
         res = search(prior)
@@ -341,7 +409,7 @@ def main(argv=None):
     elif o.share_prompt:                                   # -c FILE: one prompt, -b x --best-of samples
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  samples_per_prompt=rows, **notes).cpu().numpy()
-    elif o.window or well:
+    elif o.window or well or repeat:
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached,
                                  **notes).cpu().numpy()
     else:

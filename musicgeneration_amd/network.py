@@ -339,7 +339,7 @@ class MusicTransformer(torch.nn.Module):
                         grammar=None, prefill: str = "auto", return_cache: bool = False, groups: Optional[int] = None,
                         masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
                         hop: Optional[int] = None, samples_per_prompt: Optional[int] = None, note_rules=None,
-                        max_polyphony: Optional[int] = None):
+                        max_polyphony: Optional[int] = None, repetition=None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq unless ``window`` is given, see below).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -420,17 +420,33 @@ class MusicTransformer(torch.nn.Module):
         Refused (ValueError, before any device work): ``max_polyphony`` without ``note_rules`` or outside 1 .. 128; rules that
         are not integers [vocab_size], exceed +-128, are not 0 at pad_token, or name a key with only one of its two ids (with
         these the mask can never leave a row without an allowed id); ``grammar`` (the two masks together could), ``groups`` > 1,
-        ``masked_groups``, ``return_cache``.  None (default): the call as described above, untouched."""
+        ``masked_groups``, ``return_cache``.  None (default): the call as described above, untouched.
+
+        ``repetition`` (a ``decode.Repetition(subject, presence, frequency, window, ngram, span, ban)``): repetition control.
+        Before the sampler (and before the first draw of ``note_rules``) one stateless launch per step, captured with it
+        (mgx_repeat_penalty, ABI 31), reads the row's own history -- its columns of the token matrix, the prompt included --
+        and subtracts ``presence + frequency * c`` from the logit of every id v with ``subject[v] != 0`` that occurs c > 0 times
+        among the row's last ``window`` tokens, and ``ban`` (default 1e4) from every id that would complete an ``ngram``-gram
+        the row holds already within its last ``span`` tokens (0: the whole sequence so far).  ``EventSeq.repeat_subject()``
+        names the note_on ids, the musical default.  The amounts are finite: the set of finite logits does not change, so it
+        works unchanged with ``grammar``, ``note_rules``, ``generate_timed``'s budgets, ``prior_lengths``, ``kv_cache``,
+        ``window`` / ``hop`` (the history is in absolute columns), ``samples_per_prompt`` and ``return_cache``, and where the
+        other masks leave only a banned id, that id is drawn.  With ``return_probs`` the distributions are those of the
+        PENALISED logits.  Teacher-forced ``prefill="token"`` prompt steps stay unpenalised.  Refused (ValueError, before any
+        device work): a ``subject`` that is not integers [vocab_size] or not 0 at pad_token; ``presence`` / ``frequency``
+        negative or not finite; ``window`` outside 1 .. 4096; ``ngram`` not 0 or 2 .. 64; ``span`` not 0 or >= ``ngram``; ``ban``
+        outside (0, 1e4]; presence + frequency * window > 1e4; ``groups`` > 1, ``masked_groups``.  None (default), or an
+        object with no penalty and no n-gram rule: the call as described above, untouched, with no new launch."""
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
                                       prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop,
-                                      samples_per_prompt, None, note_rules, max_polyphony)
+                                      samples_per_prompt, None, note_rules, max_polyphony, repetition)
 
     @torch.no_grad()
     def generate_timed(self, prior: torch.Tensor, budget, cost, max_length: int, *, inclusive: bool = True, poll: int = 32,
                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, use_graph: bool = True,
                        grammar=None, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
                        hop: Optional[int] = None, return_probs: bool = False, note_rules=None,
-                       max_polyphony: Optional[int] = None, **refused):
+                       max_polyphony: Optional[int] = None, repetition=None, **refused):
         """Generate to a musical length: ``generate_cached`` where every row stops at a budget of its own instead of after a
         number of events.  ``cost`` (int32-representable [vocab_size], >= 0, 0 at pad_token) prices every id --
         ``EventSeq.time_cost`` in centiseconds, ``REMI_EventSeq.bar_cost`` in bars -- and ``budget`` (an int, or one per row;
@@ -451,10 +467,11 @@ class MusicTransformer(torch.nn.Module):
         ``masked_groups``, ``return_cache``, ``beam_size`` (other drivers), a malformed ``cost``, ``poll`` < 1, ``budget`` < 0,
         ``max_length`` < 1, and what ``generate_cached`` refuses.  ``note_rules`` / ``max_polyphony``: as in
         ``generate_cached`` -- the budget's mask and account run first, the notes' second; an ended row steps on pad_token,
-        whose rule is 0, so its held set stays what it was when the row ended."""
+        whose rule is 0, so its held set stays what it was when the row ended.  ``repetition``: as in ``generate_cached`` --
+        after the budget's mask, before the notes' first draw; ``probs`` are then those of the penalised logits."""
         return decode.generate_timed(self, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed,
                                      use_graph, grammar, prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules,
-                                     max_polyphony)
+                                     max_polyphony, repetition)
 
     @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,

@@ -872,6 +872,41 @@ def budget_account(next_tok, out_tokens, pos_dev, cost, remaining, done, count, 
     return next_tok
 
 
+# ---- repetition control on the decode path (ABI 31; contract in include/mgx.h) ---------------------------------------
+REPEAT_MAX_WINDOW = _lib.DEFINES["MGX_REPEAT_MAX_WINDOW"]
+REPEAT_MAX_NGRAM = _lib.DEFINES["MGX_REPEAT_MAX_NGRAM"]
+
+
+def repeat_penalty(logits, V, out_tokens, pos_dev, subject, pen, window, ngram=0, span=0, ban=1e4, *, ragged=False, base=None):
+    """in place, before the sampler: logits bf16 [B, ld] lose pen[cnt] at every id v < V with subject[v] != 0 that occurs cnt > 0
+    times in the last ``window`` columns of its row of out_tokens int32 [B, out_ld] (up to and including column base + pos, the
+    row's last token), and ``ban`` at every id that would complete an ``ngram``-gram the row holds already (inside the last
+    ``span`` columns; 0: the whole row).  subject int32 [V] and pen float32 [window + 1] are None exactly with window == 0.
+    ``ragged`` / ``base`` as in sample_topk_topp"""
+    ld = logits.shape[-1]
+    B = logits.numel() // ld
+    pos = _step_pos("repeat_penalty", pos_dev, B, ragged, base, with_base=True)
+    _need_cuda(logits, out_tokens, pos_dev, base, subject, pen)
+    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
+        raise ValueError(f"repeat_penalty: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or not out_tokens.is_contiguous():
+        raise ValueError(f"repeat_penalty: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
+                         f"{tuple(out_tokens.shape)}")
+    window = int(window)
+    if (window == 0) != (subject is None) or (window == 0) != (pen is None):
+        raise ValueError(f"repeat_penalty: subject and pen are None exactly with window == 0 (window={window})")
+    if window:
+        if subject.dtype != torch.int32 or subject.dim() != 1 or subject.numel() < int(V) or not subject.is_contiguous():
+            raise ValueError(f"repeat_penalty: subject must be a contiguous int32 tensor of at least V = {V} entries, got "
+                             f"{subject.dtype} {tuple(subject.shape)}")
+        if pen.dtype != torch.float32 or pen.dim() != 1 or pen.numel() != window + 1 or not pen.is_contiguous():
+            raise ValueError(f"repeat_penalty: pen must be a contiguous float32 tensor of window + 1 = {window + 1} entries, got "
+                             f"{pen.dtype} {tuple(pen.shape)}")
+    check(_lib.load().mgx_repeat_penalty(ptr(logits), int(V), ld, ptr(out_tokens), out_tokens.shape[1], *pos, ptr(subject), ptr(pen),
+                                         window, int(ngram), int(span), float(ban), B, stream_ptr()), "mgx_repeat_penalty")
+    return logits
+
+
 # ---- held-note state on the decode path (ABI 28; contracts in include/mgx.h) -----------------------------------------
 NOTE_WORDS = _lib.DEFINES["MGX_NOTE_WORDS"]               # int32 words of a row's state
 NOTE_BITS = 32 * NOTE_WORDS                               # the bits a rule may name; max_on = NOTE_BITS is no cap

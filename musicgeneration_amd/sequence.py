@@ -171,6 +171,13 @@ class EventSeq:
         return rule
 
     @staticmethod
+    def repeat_subject(vocab_size=None):
+        """the ids whose repetition ``decode.Repetition`` penalises by default, int32 [vocab_size]: 1 on the note_on ids, 0
+        elsewhere -- also on the ids a model adds beyond dim() (its pad id).  Only pitches: a frequency penalty on time_shift
+        ids would distort the rhythm"""
+        return _vocab.repeat_subject(EventSeq.dim(), EventSeq.feat_ranges()['note_on'], vocab_size)
+
+    @staticmethod
     def transpose_table(offsets, vocab_size=None):
         """what every id becomes under a transposition, int32 [len(offsets), vocab_size]: row s moves the note_on and the
         note_off of key k to key k + offsets[s] (|offset| <= 11), a key that would leave the range coming back by an octave --
