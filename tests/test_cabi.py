@@ -174,6 +174,9 @@ def test_dw_grouped_workspace_says_which_weights_take_the_ring_path():
     block = [(1536, 512), (512, 512), (256, 512), (512, 256)]           # cfg2's encoder block: 20 tiles
     n = need(block, 131072)
     assert n > 0 and n % (20 * 65536 * 4) == 0 and 1 <= n // (20 * 65536 * 4) <= 256 // 20
+    n128 = need(block, 262144)                                           # the benchmark's rows (cfg2 at batch 128): as many M-splits, twice as long
+    assert n128 > 0 and n128 % (20 * 65536 * 4) == 0 and 1 <= n128 // (20 * 65536 * 4) <= 256 // 20
+    assert need([(448, 512)], 262144) > 0 and need(block, 262144 + 8) == 0 and need(block + [(128, 768)], 262144) == n128
     assert need([(448, 512)], 131072) > 0                                # the vocabulary projection: second tile row 192 of 256
     assert need([(384, 768), (768, 384)], 16384) > 0                     # cfg4's FFN weights: 75 % of their tiles
     assert need([(128, 768)], 16384) == 0                                # half a tile row: the 128 x 128 kernel

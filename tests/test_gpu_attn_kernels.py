@@ -67,8 +67,9 @@ seeded non-zero value (the call accumulates; rows < M - L must come back bit-ide
 Shapes: L = 32 one tile | 96 a query block with an idle wave, 32-key dK/dV | 128 the smallest 64-key dK/dV | 160 a forward main-loop
 tile plus tail, L % 128 == 32 | 256 two 128-key blocks | 288 nine tile diagonals: a ragged last de_tiles group; B = 8 at L = 160 for
 the dE groups dealt across XCDs.  Batch groups smaller than B are not reachable at these sizes: the long cases of
-tests/test_gpu_kernels.py (test_rel_attn_bwd_matches_oracle_autograd, test_dkv64_matches_the_32_key_kernel_bitwise) stay the cover
-for that.  The product library only: no experiment build, no environment variable.  Every test prints its largest (error / bound)
+tests/test_gpu_kernels.py (test_rel_attn_bwd_matches_oracle_autograd, test_dkv64_matches_the_32_key_kernel_bitwise) and
+tests/test_gpu_large_offsets.py (L = 2048, d = 512: B = 128 in groups of 8, B = 127 in 127 groups of one) are the cover for that.
+The product library only: no experiment build, no environment variable.  Every test prints its largest (error / bound)
 ratio per output before it asserts (pytest -s; profiles/r18_attn_kernel_tests.txt has the figures).
 """
 import functools

@@ -4,6 +4,7 @@ the full bench batch: causality (bit-exact), linearity in V, row-normalisation, 
 import pytest
 import torch
 
+import large_offsets as LO
 from kernel_checks import cos as _cos, rel as _rel
 
 pytestmark = pytest.mark.gpu
@@ -38,9 +39,10 @@ def test_cfg2_shape_forward_backward_vs_oracle():
     assert _cos(dE.cpu(), Er.grad) > 0.999 and _rel(dE.cpu(), Er.grad) < 2e-2
 
 
-# (64, 2048, 512) is bench.py's default per-GPU shape: the first one whose dS workspace (2.18 GB) has byte offsets beyond 2^31
+# (128, 2048, 512) is bench.py's default per-GPU shape: its dS workspace (4.36 GB) has byte offsets beyond 2^32
+# (64, 2048, 512), the default of rounds 4 and 5 and bench.py's batch64 block, is the first one beyond 2^31 (2.18 GB)
 # (4, 4096, 768) is cfg4's single-GPU share, the shape of bench.py's cfg4 block
-@pytest.mark.parametrize("B,L,d", [(8, 2048, 512), (64, 2048, 512), (2, 4096, 768), (4, 4096, 768)])
+@pytest.mark.parametrize("B,L,d", [(8, 2048, 512), (64, 2048, 512), (128, 2048, 512), (2, 4096, 768), (4, 4096, 768)])
 def test_full_batch_properties(B, L, d):
     from musicgeneration_amd import ops
     dev = torch.device("cuda")
@@ -106,19 +108,21 @@ def test_cfg2_model_step_is_finite_and_learns():
     assert losses[-1] < losses[0] - 0.2, losses
 
 
-@pytest.mark.parametrize("B", [16, 64])
+@pytest.mark.parametrize("B", [16, 64, 128])
 def test_full_size_dE_and_dQ_two_ways(B):
-    """At the bench's per-GPU shape (L=2048, d=512; B=64 is bench.py's default, its dS workspace passes 2^31 bytes): the dE from
-    the dS tiles the dK/dV kernel stores equals the full-recompute dE kernel, dQ from those tiles equals the recompute dQ kernel to
-    bf16 rounding -- independent implementations of the same sums -- and the LAST batch row's dq/dk/dv equal, bit for bit, a
-    batch-of-one call on that row alone (every per-row address, in particular the dS tile offsets, lands where it should)."""
-    from musicgeneration_amd import ops
+    """At the bench's per-GPU shape (L=2048, d=512; B=128 is bench.py's default, its dS workspace passes 2^32 bytes; B=64 passes
+    2^31): the dE from the dS tiles the dK/dV kernel stores equals the full-recompute dE kernel, dQ from those tiles equals the
+    recompute dQ kernel to bf16 rounding -- independent implementations of the same sums -- and EVERY batch row's ctx, lse and
+    dq/dk/dv equal, bit for bit, calls on chunks of batch rows whose workspace stays below 2^31 bytes, the last row also a
+    batch-of-one call on that row alone: every per-row address, in particular the dS tile offsets, lands where it should.  (Were a
+    tile address to wrap, writer and readers alike, the last writer would win: checking the last row alone could pass.)"""
+    from musicgeneration_amd import _lib, ops
     dev = torch.device("cuda")
     L, d = 2048, 512
-    g = torch.Generator().manual_seed(99)
-    qkv = (torch.randn(B, L, 3 * d, generator=g) * 0.6).to(torch.bfloat16).to(dev)
-    E = (torch.randn(L, 64, generator=g) * 0.3).to(torch.bfloat16).to(dev)
-    dctx = torch.randn(B, L, d, generator=g).to(torch.bfloat16).to(dev)
+    g = torch.Generator(device="cuda").manual_seed(99)
+    qkv = LO.fill_normal(torch.empty(B, L, 3 * d, dtype=torch.bfloat16, device=dev), g, 0.6)
+    E = LO.fill_normal(torch.empty(L, 64, dtype=torch.bfloat16, device=dev), g, 0.3)
+    dctx = LO.fill_normal(torch.empty(B, L, d, dtype=torch.bfloat16, device=dev), g)
     ctx, lse = ops.rel_attn_fwd(qkv, E, None)
     dE1, dE2 = torch.zeros(L, 64, device=dev), torch.zeros(L, 64, device=dev)
     dq1 = ops.rel_attn_bwd(qkv, E, None, ctx, dctx, lse, dE1)                     # pre + dK/dV (stores dS) + dQ and dE from the tiles
@@ -129,6 +133,22 @@ def test_full_size_dE_and_dQ_two_ways(B):
     assert torch.equal(dq1[..., d:], dq2[..., d:])                                  # the same dK/dV kernel on the same inputs
     # two derivations of dS (the dK/dV kernel's and the recompute dQ kernel's own): equal up to the bf16 rounding of dS
     assert _rel(dq1[..., :d].float(), dq2[..., :d].float()) < 4e-3
+    # every row, in chunks
+    chunks = LO.row_chunks(B, (_lib.load().mgx_rel_attn_bwd_workspace(1, L, d),))
+    assert len(chunks) == {16: 1, 64: 2, 128: 3}[B]
+    ctx_c, lse_c, dq_c = torch.empty_like(ctx), torch.empty_like(lse), torch.empty_like(dq1)
+    dE_sum = torch.zeros(L, 64, dtype=torch.float64, device=dev)
+    for lo, hi in chunks:
+        ctx_c[lo:hi], lse_c[lo:hi] = ops.rel_attn_fwd(qkv[lo:hi], E, None)
+        dEc = torch.zeros(L, 64, device=dev)
+        dq_c[lo:hi] = ops.rel_attn_bwd(qkv[lo:hi], E, None, ctx[lo:hi], dctx[lo:hi], lse[lo:hi], dEc)
+        dE_sum += dEc.double()
+    torch.cuda.synchronize()
+    LO.compare_rows("fwd", ctx, lambda lo, hi: ctx_c[lo:hi], chunks, f"B={B} ctx")
+    LO.compare_rows("fwd", lse, lambda lo, hi: lse_c[lo:hi], chunks, f"B={B} lse")
+    LO.compare_rows("bwd", dq1, lambda lo, hi: dq_c[lo:hi], chunks, f"B={B} dqkv")
+    assert LO.rel(dE1, dE_sum) < 2e-5
+    del ctx_c, lse_c, dq_c
     # the last row alone
     c1, l1 = ops.rel_attn_fwd(qkv[B - 1:].contiguous(), E, None)
     assert torch.equal(c1[0], ctx[B - 1]) and torch.equal(l1[0], lse[B - 1])
@@ -139,17 +159,24 @@ def test_full_size_dE_and_dQ_two_ways(B):
 
 
 def test_full_size_grouped_dW():
-    """the grouped dW launch equals four separate launches at the B=16 row count (fp32 accumulation order aside)"""
+    """the grouped dW launch equals four separate launches at the row counts of B=16 and of bench.py's default, B=128 (M = 262,144)
+    (fp32 accumulation order aside)"""
+    for B in (16, 128):
+        _grouped_dW_equals_separate_launches(B)
+        torch.cuda.empty_cache()
+
+
+def _grouped_dW_equals_separate_launches(B):
     from musicgeneration_amd import ops
     dev = torch.device("cuda")
-    B, L, d = 16, 2048, 512
-    g = torch.Generator().manual_seed(99)
+    L, d = 2048, 512
+    g = torch.Generator(device="cuda").manual_seed(99)
     M = B * L
     shapes = [(3 * d, d), (d, d), (d // 2, d), (d, d // 2)]
     probs, sep = [], []
     for i, (N, K) in enumerate(shapes):
-        dy = torch.randn(M, N, generator=g).to(torch.bfloat16).to(dev)
-        x = torch.randn(M, K, generator=g).to(torch.bfloat16).to(dev)
+        dy = LO.fill_normal(torch.empty(M, N, dtype=torch.bfloat16, device=dev), g)
+        x = LO.fill_normal(torch.empty(M, K, dtype=torch.bfloat16, device=dev), g)
         gw, gb = torch.zeros(N, K, device=dev), (torch.zeros(N, device=dev) if i % 2 == 0 else None)
         gw2, gb2 = torch.zeros(N, K, device=dev), (torch.zeros(N, device=dev) if i % 2 == 0 else None)
         probs.append((dy, x, gw, gb))
@@ -225,8 +252,8 @@ def test_cfg4_shaped_model_step():
 
 
 def _det_bench_shape_run(scale):
-    """one attention backward + vocabulary-projection dW + embedding gradient + CE statistics at bench.py's per-GPU shape (cfg2,
-    batch 64), gradients multiplied by `scale`"""
+    """one attention backward + vocabulary-projection dW + embedding gradient + CE statistics at the per-GPU shape of bench.py's
+    batch64 block (cfg2, batch 64; its default is batch 128), gradients multiplied by `scale`"""
     from musicgeneration_amd import ops
     dev = torch.device("cuda")
     B, L, d, V = 64, 2048, 512, 337
@@ -253,7 +280,7 @@ def _det_bench_shape_run(scale):
 
 @pytest.mark.parametrize("scale", [1.0, 1e-6])
 def test_deterministic_mode_at_the_bench_shape(scale):
-    """deterministic-reduction mode at cfg2 / batch 64 -- two runs bit-equal, and against the default (fp32
+    """deterministic-reduction mode at cfg2 / batch 64 (bench.py's batch64 block) -- two runs bit-equal, and against the default (fp32
     atomics) within 1e-5.  scale = 1e-6 shows what the FIXED 2^-30 quantum costs on tiny gradients: a partial sum of magnitude m
     keeps m * 2^30 integer steps, so the bound there is absolute (quantum x number of partials), stated below."""
     from musicgeneration_amd import ops

@@ -195,8 +195,9 @@ def test_dw_ring4_matches_the_eight_wave_kernel_bitwise(tmp_path):
 
 
 # (kind, M, N, K, epilogue, expected kernel family): forward C [M,N] = act(A [M,K] . W [N,K]^T + b); dX [M,K] = dY [M,N] . W [N,K]
-# (reduction N) with a ReLU mask / a residual addend.  The shapes are the bench's: cfg2 at batch 32 / 64 (M = 65,536 / 131,072:
-# QKV 1536 x 512, output projection 512 x 512, FFN 256 x 512 and 512 x 256) and cfg4 at batch 8 (M = 32,768: QKV 2304 x 768).
+# (reduction N) with a ReLU mask / a residual addend.  The shapes are the bench's: cfg2 at batch 128, bench.py's default (M = 262,144),
+# and at the batches 32 / 64 of earlier rounds (M = 65,536 / 131,072): QKV 1536 x 512, output projection 512 x 512, FFN 256 x 512 and
+# 512 x 256; and cfg4 at batch 8 (M = 32,768: QKV 2304 x 768).
 _PRODUCT_SHAPES = [
     ("fwd", 65536, 1536, 512, "bias", "RING4"),
     ("fwd", 131072, 512, 512, "bias", "RING4"),
@@ -209,6 +210,12 @@ _PRODUCT_SHAPES = [
     ("dx", 131072, 512, 256, "mask", "RING8"),             # dX of FFN_suf under FFN_pre's ReLU
     ("dx", 131072, 256, 512, "addend", "RING8"),           # dX of FFN_pre + the residual gradient
     ("dx", 32768, 2304, 768, "addend", "RING4"),
+    ("fwd", 262144, 1536, 512, "bias", "RING4"),           # batch 128: 6144 tiles, every workgroup walks 24
+    ("fwd", 262144, 512, 512, "bias", "RING4"),
+    ("dx", 262144, 1536, 512, "addend", "RING4"),
+    ("dx", 262144, 512, 512, "mask", "RING4"),
+    ("dx", 262144, 512, 256, "mask", "RING8"),
+    ("dx", 262144, 256, 512, "addend", "RING8"),
 ]
 
 

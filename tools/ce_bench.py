@@ -1,4 +1,4 @@
-"""Micro-benchmark of the label-smoothed CE kernels at the cfg2 bench shape (rows = 64 x 2048, V = 337 in rows of 384)."""
+"""Micro-benchmark of the label-smoothed CE kernels at cfg2, batch 64 -- the bench default of rounds 3-5, bench.py's batch64 block (rows = 64 x 2048, V = 337 in rows of 384)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

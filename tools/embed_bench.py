@@ -1,4 +1,4 @@
-"""Micro-benchmark of the embedding gradient kernel at the cfg2 bench shape (64 x 2048 tokens, V = 337, d = 512, dropout 0.2)."""
+"""Micro-benchmark of the embedding gradient kernel at cfg2, batch 64 -- the bench default of rounds 3-5, bench.py's batch64 block (64 x 2048 tokens, V = 337, d = 512, dropout 0.2)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
