@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM */
-#define MGX_ABI_VERSION 31
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM; 32: draft-and-verify decode: mgx_lookahead_draft, mgx_rel_attn_decode_multi (with _splits and _workspace), mgx_lookahead_accept, MGX_LOOKAHEAD_MAX_T, MGX_LOOKAHEAD_MAX_NGRAM */
+#define MGX_ABI_VERSION 32
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -582,6 +582,63 @@ int mgx_notes_keep(const int32_t* first_tok, int32_t* next_tok, int32_t* out_tok
 int mgx_repeat_penalty(uint16_t* logits, int V, int ld, const int32_t* out_tokens, int out_ld, const int32_t* pos_dev,
                        const int32_t* base_dev, int per_row, const int32_t* subject, const float* pen, int window, int ngram,
                        int span, float ban, int B, void* stream);
+
+/* ---- Draft and verify (ABI 32): several tokens per step of the KV-cache decode, same sample    (the sampling loop of
+ * network.py:52-77, T positions of it per step).  A step of B rows runs as B * T rows of the ordinary step chain: row b * T + i is
+ * position t_b + i of batch row b on the guessed input draft[b,i].  Every position is then drawn with the draw the one-token step
+ * makes there -- the sampler's draw is a pure function of (seed, absolute step, row) -- and the prefix whose guesses were right is
+ * kept, so the result is the one-token call's sample for that seed up to the rounding difference between two attention kernels.
+ * A step is: mgx_lookahead_draft, the chain on B * T rows with pos_rows as its per-row positions and mgx_rel_attn_decode_multi as
+ * its attention, mgx_lookahead_accept.  2 <= T <= MGX_LOOKAHEAD_MAX_T.
+ * Step positions ("Step positions", K12): pos_dev int32 [B], ALWAYS one position per row (t_b, the position of the step's input
+ * token tok[b]); base_dev of the same shape or NULL, where the call takes one; s = base + t is the column of tok[b] in out_tokens.
+ * No rollback is needed: position t_b + i enters the cache from draft[b,i], and i < n_b (below) means draft[b,0..i] were the tokens
+ * drawn, so after a step every cache row below the new t_b was written from a verified input.  Rejected rows lie at or above the
+ * new t_b and the next step rewrites them -- and reads them from its own qkv_new -- before any query can reach them.
+ *
+ * mgx_lookahead_draft, one launch per step.  out_tokens int32 [B,out_ld] holds the row's history, out_tokens[b,s] == tok[b].
+ *   draft int32 [B,T]: draft[b,0] = tok[b].  pos_rows int32 [B*T]: pos_rows[b*T+i] = min(t_b + i, Lmax - 1) (never below 0).
+ *   guide != NULL (int32 [B,guide_ld]): draft[b,i] = guide[b,s+i] where s + i < guide_ld, else pad_token (i >= 1).
+ *   guide == NULL, history: for n = ngram, ngram-1, .., 1 (an n with s-n+1 < 0 is skipped) find the greatest j < s, j >= n-1, with
+ *     out_tokens[b, j-n+1 .. j] == out_tokens[b, s-n+1 .. s] (raw int32 values); the first n with a match wins.  With
+ *     x~[c] = out_tokens[b,c] for c <= s and x~[c] = x~[c - (s-j)] for c > s (the match extended periodically where it runs into
+ *     the present), draft[b,i] = x~[s+i].  No match at any n (or s outside 1 .. out_ld-1): draft[b,i>=1] = pad_token.
+ *   A draft is only a guess: any id is legal.  1 <= ngram <= MGX_LOOKAHEAD_MAX_NGRAM.  Writes draft and pos_rows only.  One
+ *   workgroup of 256 threads per row, the scan of mgx_repeat_penalty's n-gram rule; LDS atomics only.
+ * mgx_rel_attn_decode_multi: qkv_new bf16 [B*T,3d], row b*T+i the projection of draft[b,i] at position t_b + i.  k and v of every
+ *   i with t_b + i < Lmax are appended to rows t_b + i of kcache / vcache bf16 [B,h,Lmax,64], and
+ *   ctx[b*T+i] = softmax_j((q_i.k_j + q_i.E[M-1-(t_b+i-j)])/8) v_j over j = 0 .. t_b + i  (ctx bf16 [B*T,d]): query i never sees a
+ *   row above t_b + i, and rows t_b .. t_b + T - 1 are read from qkv_new, never from the cache rows this launch writes.  Rows with
+ *   t_b + i >= Lmax append nothing; their ctx is unspecified but finite.  One workgroup per (b, head, key split) with T
+ *   online-softmax states per lane: every K and V row is loaded once for the T queries.  Key splits, partial records (at
+ *   [((b*T+i) * h + head) * splits + split]) and the merge kernel are mgx_rel_attn_decode's; workspace >=
+ *   mgx_rel_attn_decode_multi_workspace() bytes (0 for one split: NULL is accepted then).
+ *   Contract (not checked on the host: t lives on the device): 0 <= t_b < Lmax <= M; a row outside it appends nothing and no
+ *   value turns into an access outside the buffers the shapes describe.
+ * mgx_lookahead_accept in place of the sampler.  logits bf16 [B*T,ld].  y_i is exactly the draw mgx_sample_topk_topp makes from
+ *   row b*T+i with (seed, s+i, row0+b): the same temperature / top_k / top_p thresholds and tie rule, and the same allow_table
+ *   grammar whose previous token is draft[b,i].  a = the largest k <= T-1 with draft[b,i] == y_{i-1} for all 1 <= i <= k.
+ *   limit int32 [B]: the column of every row's last token; n_b = min(a + 1, limit[b] - s).
+ *     n_b <= 0: the row is finished -- nothing is written, its position stays, done[b] = 1 (done int32 [B]).
+ *     else:     out_tokens[b, s+1+i] = y_i for i < n_b, tok[b] = y_{n_b-1}, pos_dev[b] += n_b; probs_all f32 [B,probs_ld,V] (or
+ *               NULL) receives the unfiltered softmax of row b*T+i at column s+i for i < n_b; stats int32 [B,2] (or NULL)
+ *               += (1, n_b).
+ *   Plain loads and stores, no atomics.  One workgroup of T waves per row.  V <= 1024.
+ *   Contract (not checked: the values live on the device): limit[b] < out_ld; a column outside the matrices is not written. */
+#define MGX_LOOKAHEAD_MAX_T 8
+#define MGX_LOOKAHEAD_MAX_NGRAM 8
+int mgx_lookahead_draft(const int32_t* tok, const int32_t* out_tokens, int out_ld, const int32_t* pos_dev,
+                        const int32_t* base_dev, const int32_t* guide, int guide_ld, int ngram, int pad_token, int32_t* draft,
+                        int32_t* pos_rows, int B, int T, int Lmax, void* stream);
+int mgx_rel_attn_decode_multi_splits(int B, int T, int Lmax, int d);
+size_t mgx_rel_attn_decode_multi_workspace(int B, int T, int Lmax, int d);
+int mgx_rel_attn_decode_multi(const uint16_t* qkv_new, uint16_t* kcache, uint16_t* vcache, const uint16_t* E,
+                              const int32_t* pos_dev, uint16_t* ctx, void* workspace, size_t ws_bytes, int B, int T, int Lmax,
+                              int d, int M, void* stream);
+int mgx_lookahead_accept(const uint16_t* logits, int V, int ld, float temperature, int top_k, float top_p, uint64_t seed,
+                         int32_t* pos_dev, const int32_t* base_dev, const int32_t* draft, const int32_t* limit, int32_t* tok,
+                         int32_t* out_tokens, int out_ld, float* probs_all, int probs_ld, int32_t* done, int32_t* stats, int B,
+                         int T, int row0, const uint32_t* allow_table, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

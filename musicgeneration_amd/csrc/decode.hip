@@ -20,11 +20,7 @@
 // get a StepPos without one); mgx_decode_reanchor moves both when the host re-anchors the window.
 // mgx_rel_attn_decode_shared (ABI 26) is the per-row attention for N samples per prompt: the prompt's keys are held once per prompt
 // and loaded once for several of its samples' queries (rel_attn_decode_shared_kernel, below the merge kernel).
-#include "mgx_common.hpp"
-
-namespace {
-constexpr float LOG2E = 1.4426950408889634f;
-}
+#include "decode_common.hpp"                             // key ranges, partials, the merge kernel, the sampler's draw
 
 __global__ __launch_bounds__(256) void decode_embed_kernel(const int32_t* __restrict__ tok, const float* __restrict__ table,
                                                            const float* __restrict__ pe, StepPos stp, uint16_t* __restrict__ out,
@@ -52,14 +48,6 @@ __global__ __launch_bounds__(256) void decode_embed_kernel(const int32_t* __rest
 // contiguous, 64-key aligned share of the keys 0..t (balanced from the device-side position), write an unnormalised
 // partial (m, l, acc[64]) and a tiny second kernel merges them by their maxima.  The new row t is taken from qkv_new by
 // whichever split covers it (another workgroup appends it to the cache in the same launch).
-constexpr int DEC_WAVES = 8;
-constexpr int DEC_PART = 68;                                   // floats per partial: acc[64], m, l, 2 pad (16-byte aligned rows)
-// What the bf16 and the 8-bit kernel share.  DPL = dims per lane (8: bf16, 16: 8-bit codes), so 64 / DPL lanes per key.
-// this split's keys: [lo, hi), shares of ceil((t+1)/nsplit) keys rounded up to the workgroup's 64-key stride
-MGX_DEV void dec_key_range(int t, int nsplit, int sp, int& lo, int& hi) {
-    const int share = ((t + nsplit) / nsplit + 63) & ~63;
-    lo = sp * share, hi = min(t + 1, lo + share);
-}
 // merge the key slots of the wave (lanes with equal dg), then the 8 waves through LDS; 64 threads write ctx (one split) or
 // this split's unnormalised partial
 template <int DPL>
@@ -160,24 +148,6 @@ __global__ __launch_bounds__(64 * DEC_WAVES) void rel_attn_decode_kernel(
         m = mn;
     }
     dec_finish<8>(m, l, acc, ctx, partial, b, hd, d, nsplit, sp, tid, w, ks, dg);
-}
-
-// ctx[b, hd*64 + c] = sum_s acc_s[c] 2^(m_s - m) / sum_s l_s 2^(m_s - m): one wave per (b,h)
-__global__ __launch_bounds__(64) void rel_attn_decode_merge_kernel(const float* __restrict__ partial, uint16_t* __restrict__ ctx,
-                                                                   int nsplit, int d) {
-    const int heads = d >> 6;
-    const int b = blockIdx.x / heads, hd = blockIdx.x % heads, c = threadIdx.x;
-    const float* pp = partial + (size_t)blockIdx.x * nsplit * DEC_PART;
-    float mm = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) mm = fmaxf(mm, pp[s * DEC_PART + 64]);
-    float ll = 0.f, o = 0.f;
-    for (int s = 0; s < nsplit; ++s) {
-        const float ms = pp[s * DEC_PART + 64];
-        const float a = (ms == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(ms - mm);
-        ll += pp[s * DEC_PART + 65] * a;
-        o += pp[s * DEC_PART + c] * a;
-    }
-    ctx[(size_t)b * d + hd * 64 + c] = f32_to_bf16(o / ll);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -477,125 +447,22 @@ __global__ __launch_bounds__(256) void kv_store_fp8_kernel(const uint16_t* __res
 }
 
 // ---------------------------------------------------------------------------------------------------
-// sampling: one wave per row, V <= 64 * 16
+// sampling: one wave per row, V <= 64 * 16 (the draw itself: sample_draw, decode_common.hpp)
 // ---------------------------------------------------------------------------------------------------
-constexpr int SMP_PER_LANE = 16;                         // the uniform: u01 (mgx_common.hpp)
-
 __global__ __launch_bounds__(64) void sample_kernel(const uint16_t* __restrict__ logits, int V, int ld, float inv_temp,
                                                     int top_k, float top_p, uint64_t seed, StepPos stp,
                                                     int32_t* __restrict__ next_tok, int32_t* __restrict__ out_tokens,
                                                     int out_ld, float* __restrict__ probs_out, int row0,
                                                     const uint32_t* __restrict__ allow_table) {
     const int row = blockIdx.x, lane = threadIdx.x;
-    const uint16_t* lp = logits + (size_t)row * ld;
-    float p[SMP_PER_LANE];
-    float mx = -INFINITY;
     // grammar mask: row `prev` of allow_table (bit v = token v may follow token prev); the previous
     // token is what next_tok still holds.  A row that allows nothing is ignored.
-    const uint32_t* arow = nullptr;
-    if (allow_table) {
-        int prev = next_tok[row];
-        prev = prev < 0 ? 0 : (prev >= V ? V - 1 : prev);
-        arow = allow_table + (size_t)prev * ((V + 31) >> 5);
-    }
-#pragma unroll
-    for (int i = 0; i < SMP_PER_LANE; ++i) {
-        const int v = lane + 64 * i;
-        p[i] = (v < V) ? bf16_to_f32(lp[v]) * inv_temp : -INFINITY;
-        if (arow && v < V && !((arow[v >> 5] >> (v & 31)) & 1u)) p[i] = -INFINITY;
-        mx = fmaxf(mx, p[i]);
-    }
-    mx = wave_max(mx);
-    if (arow && mx == -INFINITY) {                       // empty row: fall back to the unmasked distribution
-#pragma unroll
-        for (int i = 0; i < SMP_PER_LANE; ++i) {
-            const int v = lane + 64 * i;
-            p[i] = (v < V) ? bf16_to_f32(lp[v]) * inv_temp : -INFINITY;
-            mx = fmaxf(mx, p[i]);
-        }
-        mx = wave_max(mx);
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < SMP_PER_LANE; ++i) { p[i] = (lane + 64 * i < V) ? __expf(p[i] - mx) : 0.f; sum += p[i]; }
-    sum = wave_sum(sum);
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int i = 0; i < SMP_PER_LANE; ++i) p[i] *= inv;
-    if (probs_out) {
-#pragma unroll
-        for (int i = 0; i < SMP_PER_LANE; ++i)
-            if (lane + 64 * i < V) probs_out[(size_t)row * V + lane + 64 * i] = p[i];
-    }
-    // threshold tau: keep {p_i >= tau}.  top-k: largest tau with count(p >= tau) >= k; top-p: largest tau with
-    // mass(p >= tau) >= top_p.  Positive floats order like their bit patterns -> exact bisection on the bits.
-    uint32_t tau_bits = 0;
-    if (top_k > 0 && top_k < V) {
-        uint32_t lo = 0, hi = 0x3f800001u;          // (p >= lo) holds for all; hi = just above 1.0
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            const float tv = __builtin_bit_cast(float, mid);
-            float c = 0.f;
-#pragma unroll
-            for (int i = 0; i < SMP_PER_LANE; ++i) c += (p[i] >= tv && lane + 64 * i < V) ? 1.f : 0.f;
-            c = wave_sum(c);
-            if (c >= (float)top_k) lo = mid; else hi = mid;
-        }
-        tau_bits = lo;
-    }
-    if (top_p < 1.f) {
-        uint32_t lo = tau_bits, hi = 0x3f800001u;
-        float mass_all = 0.f;
-        {
-            const float tv = __builtin_bit_cast(float, lo);
-#pragma unroll
-            for (int i = 0; i < SMP_PER_LANE; ++i) mass_all += (p[i] >= tv) ? p[i] : 0.f;
-            mass_all = wave_sum(mass_all);
-        }
-        const float need = top_p * mass_all;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            const float tv = __builtin_bit_cast(float, mid);
-            float ms = 0.f;
-#pragma unroll
-            for (int i = 0; i < SMP_PER_LANE; ++i) ms += (p[i] >= tv) ? p[i] : 0.f;
-            ms = wave_sum(ms);
-            if (ms >= need) lo = mid; else hi = mid;
-        }
-        tau_bits = lo;
-    }
-    const float tau = __builtin_bit_cast(float, tau_bits);
-    // categorical draw over the kept set by inverse CDF in index order
-    float kept = 0.f;
-#pragma unroll
-    for (int i = 0; i < SMP_PER_LANE; ++i) { if (!(p[i] >= tau)) p[i] = 0.f; kept += p[i]; }
-    const float total = wave_sum(kept);
+    const uint32_t* arow = allow_table ? grammar_row(allow_table, next_tok[row], V) : nullptr;
     const int step = stp.step(row);                      // the absolute step: the position, plus the window's base if there is one
-    const float target = u01(seed, (uint32_t)step, (uint32_t)(row0 + row)) * total;
-    int choice = -1;
-    float base = 0.f;
-    // index order: v = lane + 64*i  ->  iterate i outer (blocks of 64 consecutive ids), prefix over lanes inner
-#pragma unroll
-    for (int i = 0; i < SMP_PER_LANE; ++i) {
-        float incl = p[i];
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const float up = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += up;
-        }
-        const float blk = __shfl(incl, 63, 64);
-        const bool hit = (choice < 0) && (p[i] > 0.f) && (base + incl >= target);
-        const unsigned long long mask = __ballot(hit);
-        if (choice < 0 && mask) choice = 64 * i + (int)__builtin_ctzll(mask);
-        base += blk;
-    }
-    if (choice < 0) {   // rounding at the top end: take the last kept id
-#pragma unroll
-        for (int i = SMP_PER_LANE - 1; i >= 0; --i) {
-            const unsigned long long mask = __ballot(p[i] > 0.f);
-            if (choice < 0 && mask) choice = 64 * i + 63 - (int)__builtin_clzll(mask);
-        }
-    }
+    float unused[SMP_PER_LANE];
+    const int choice = sample_draw<false>(logits + (size_t)row * ld, V, inv_temp, top_k, top_p, arow,
+                                          u01(seed, (uint32_t)step, (uint32_t)(row0 + row)), lane,
+                                          probs_out ? probs_out + (size_t)row * V : nullptr, unused);
     if (lane == 0) {
         next_tok[row] = choice;
         if (out_tokens) out_tokens[(size_t)row * out_ld + step + 1] = choice;

@@ -15,7 +15,10 @@ ops.budget_mask / ops.budget_account) and a step loop that reads the rows' ``don
 ``NoteState`` (``note_rules=``, ``max_polyphony=``) is the second per-row state bracketing the sampler the same way: the set of
 notes every row holds (ops.notes_mask / ops.notes_account), which keeps a MIDI-like stream well-formed.  ``Repetition``
 (``repetition=``) is not a state: one launch before the sampler (ops.repeat_penalty) reads the row's own columns of the output
-matrix and penalises repeated ids and n-grams by finite amounts."""
+matrix and penalises repeated ids and n-grams by finite amounts.  ``generate_lookahead`` (generate_cached(lookahead=T)) is draft
+and verify: the same step on B * T rows, T consecutive positions of every row on guessed inputs (ops.lookahead_draft), whose
+attention is ops.rel_attn_decode_multi behind a ``LookaheadCache`` and whose sampler is ops.lookahead_accept; a ``DonePoll`` --
+what a ``Budget`` is to the step loop -- stops it once every row holds its last token."""
 from __future__ import annotations
 
 import dataclasses
@@ -402,22 +405,12 @@ def decode_step(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool) -
                          advance=True, row0=r.b0, **r.step, **sampler)
 
 
-class Budget:
-    """the per-row length budgets of generate_timed (include/mgx.h, ABI 27).  On the host: ``budgets``, one int per row
-    (ops.NO_BUDGET: none), ``cost`` int32 [V] (numpy), ``inclusive``, ``poll``.  ``stage`` puts the clock on the device: ``cost``,
-    ``remaining`` [B], ``done`` [B] (set from the start for a budget of 0: the row generates nothing) and ``count`` [B].  The
-    step loop files ``steps_run``"""
+class DonePoll:
+    """what lets the step loop stop early: the rows' ``done`` flags int32 [B] on the device, read every ``poll`` steps (run_steps,
+    replay_graphs).  The loop files ``steps_run``"""
 
-    def __init__(self, budgets, cost, pad_token: int, inclusive: bool, poll: int):
-        self.budgets, self.cost_host, self.pad_token, self.inclusive, self.poll = budgets, cost, pad_token, inclusive, poll
-        self.steps_run = 0
-
-    def stage(self, dev) -> "Budget":
-        self.cost = torch.from_numpy(self.cost_host).to(dev)
-        self.remaining = torch.tensor(self.budgets, dtype=torch.int32, device=dev)
-        self.done = (self.remaining == 0).to(torch.int32)
-        self.count = torch.zeros_like(self.remaining)
-        return self
+    def __init__(self, done, poll: int):
+        self.done, self.poll, self.steps_run = done, poll, 0
 
     def finished(self) -> bool:
         """has every row ended?  One read of ``done``: the loop's only host synchronisation"""
@@ -428,6 +421,24 @@ class Budget:
         return self.poll - made % self.poll
 
 
+class Budget(DonePoll):
+    """the per-row length budgets of generate_timed (include/mgx.h, ABI 27).  On the host: ``budgets``, one int per row
+    (ops.NO_BUDGET: none), ``cost`` int32 [V] (numpy), ``inclusive``, ``poll``.  ``stage`` puts the clock on the device: ``cost``,
+    ``remaining`` [B], ``done`` [B] (set from the start for a budget of 0: the row generates nothing) and ``count`` [B].  The
+    step loop files ``steps_run``"""
+
+    def __init__(self, budgets, cost, pad_token: int, inclusive: bool, poll: int):
+        super().__init__(None, poll)
+        self.budgets, self.cost_host, self.pad_token, self.inclusive = budgets, cost, pad_token, inclusive
+
+    def stage(self, dev) -> "Budget":
+        self.cost = torch.from_numpy(self.cost_host).to(dev)
+        self.remaining = torch.tensor(self.budgets, dtype=torch.int32, device=dev)
+        self.done = (self.remaining == 0).to(torch.int32)
+        self.count = torch.zeros_like(self.remaining)
+        return self
+
+
 def check_budget_args(model, B: int, budget, cost, max_length: int, poll: int, refused: dict):
     """every refusal of generate_timed that generate_cached does not make (ValueError), on the host.  Returns (one int32 budget
     per row, ops.NO_BUDGET for None; cost as a numpy int32 [vocab_size])"""
@@ -435,7 +446,9 @@ def check_budget_args(model, B: int, budget, cost, max_length: int, poll: int, r
            "groups": "the budget clock covers the batch as one group",
            "masked_groups": "the budget clock covers the batch as one group",
            "return_cache": "an ended row's cache rows hold pad-token steps",
-           "beam_size": "beam search is another driver (generate_beam): a beam has no clock of its own"}
+           "beam_size": "beam search is another driver (generate_beam): a beam has no clock of its own",
+           "lookahead": "draft and verify is generate_cached(lookahead=): a budget's state is sequential, a row's next mask "
+                        "depends on the token before it"}
     for name, value in refused.items():
         if name not in why:
             raise TypeError(f"generate_timed() got an unexpected keyword argument {name!r}")
@@ -776,9 +789,19 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
 
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
                     return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None,
-                    bud: Optional[Budget] = None, note_rules=None, max_polyphony=None, repetition=None):
+                    bud: Optional[Budget] = None, note_rules=None, max_polyphony=None, repetition=None, lookahead=None,
+                    draft="history", draft_ngram=3, stats=None):
     """MusicTransformer.generate_cached (documented there).  ``bud``: generate_timed's budgets, not yet staged -- the steps run
     decode_step_constrained and the loop stops once every row has ended"""
+    if lookahead is not None:
+        T, guide = check_lookahead_args(model, prior, lookahead, draft, draft_ngram, window=window, hop=hop, kv_cache=kv_cache,
+                                        samples_per_prompt=samples_per_prompt, groups=groups, masked_groups=masked_groups,
+                                        prefill=prefill, return_cache=return_cache, note_rules=note_rules,
+                                        max_polyphony=max_polyphony, repetition=repetition, bud=bud)
+        P, lens, _, _ = check_args(model, prior, length, False, "batched", prior_lengths, kv_cache)
+        return generate_lookahead(model, prior, P, lens, length, T, guide, int(draft_ngram),
+                                  dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), grammar, use_graph,
+                                  return_probs, stats)
     rep = check_repeat_args(model, repetition, groups=groups, masked_groups=masked_groups)
     notes = check_note_args(model, note_rules, max_polyphony, grammar=grammar, groups=groups, masked_groups=masked_groups,
                             return_cache=return_cache)
@@ -896,6 +919,105 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
                 decode_step(w, r_, sampler, length > 0)
         run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=file)
     return (out, probs_all) if return_probs else out
+
+
+# ---- draft and verify -------------------------------------------------------------------------------------------------------
+LOOKAHEAD_POLL = 32                                       # steps between two reads of the rows' done flags
+
+
+def check_lookahead_args(model, prior, lookahead, draft, draft_ngram, *, window=None, hop=None, kv_cache="bf16",
+                         samples_per_prompt=None, groups=None, masked_groups=False, prefill="auto", return_cache=False,
+                         note_rules=None, max_polyphony=None, repetition=None, bud=None):
+    """every refusal of generate_cached(lookahead=T) (ValueError), on the host before any device work.  Returns (T, the guide as
+    an integer tensor [B, >= Pmax] or None for history drafts)"""
+    def integer(name, v, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
+        return int(v)
+    T = integer("lookahead", lookahead, 2, ops.LOOKAHEAD_MAX_T)
+    integer("draft_ngram", draft_ngram, 1, ops.LOOKAHEAD_MAX_NGRAM)
+    for on, name, why in ((window is not None or hop is not None, "window / hop", "a re-anchor would have to fall between two accepted tokens"),
+                          (kv_cache != "bf16", f"kv_cache={kv_cache!r}", "the T-query attention has no 8-bit form"),
+                          (samples_per_prompt is not None, "samples_per_prompt", "the shared prompt cache is another attention kernel"),
+                          ((groups or 1) > 1 or masked_groups, "groups / masked_groups", "the rows advance by different amounts as one group"),
+                          (prefill == "token", "prefill='token'", "the prompt is prefilled in one batched pass"),
+                          (return_cache, "return_cache", "cache rows above a row's last position hold rejected guesses"),
+                          (note_rules is not None or max_polyphony is not None, "note_rules / max_polyphony",
+                           "the held-note state is sequential: position i + 1 is masked by the token at i"),
+                          (repetition is not None, "repetition", "the penalty of position i + 1 counts the token at i"),
+                          (bud is not None, "generate_timed", "a budget's state is sequential")):
+        if on:
+            raise ValueError(f"lookahead is not combined with {name} ({why}): later work")
+    if isinstance(draft, str):
+        if draft != "history":
+            raise ValueError(f"draft must be 'history' or a guide, integers [B, >= Pmax], got {draft!r}")
+        return T, None
+    guide = torch.as_tensor(draft)
+    B, Pmax = prior.shape
+    if guide.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64) or guide.dim() != 2 \
+            or guide.shape[0] != B or guide.shape[1] < Pmax:
+        raise ValueError(f"draft must be 'history' or a guide, integers [B, >= Pmax] = [{B}, >= {Pmax}], got {guide.dtype} "
+                         f"{tuple(guide.shape)}")
+    return T, guide
+
+
+class LookaheadCache:
+    """a bf16 KVCache behind the attention of T consecutive positions per row (include/mgx.h, ABI 32): the step's SubBatch has
+    B * T rows whose ``at`` is pos_rows, the clamped positions of the row-wise kernels; the attention takes ``pos`` int32 [B],
+    where every batch row stands"""
+
+    def __init__(self, cache: KVCache, pos: torch.Tensor, T: int):
+        self.cache, self.pos, self.T = cache, pos, T
+
+    def attend(self, layer: int, qkv_new, E, at: dict, ctx, workspace):
+        """append k, v of the positions pos_b .. pos_b + T - 1 and attend causally among them and over rows 0 .. pos_b - 1:
+        ctx bf16 [B * T, d]"""
+        return ops.rel_attn_decode_multi(qkv_new, self.cache.k[layer], self.cache.v[layer], E, self.pos, ctx, workspace, self.T)
+
+
+def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, ngram: int, sampling: dict, grammar, use_graph: bool,
+                       return_probs: bool, stats):
+    """generate_cached(lookahead=T), its arguments checked.  A step of the B rows is the ragged step on B * T rows: row b * T + i
+    runs position t_b + i on draft[b, i] (ops.lookahead_draft), the attention is ops.rel_attn_decode_multi, and
+    ops.lookahead_accept draws every position as the one-token call draws it -- (seed, column, b) -- keeps the prefix whose
+    guesses were right and advances row b by it.  Nothing is rolled back: a cache row a rejected guess wrote lies at or above the
+    row's new position and is rewritten by the next step before any query reaches it.  The step is captured once and replayed
+    in runs of LOOKAHEAD_POLL; a row at its last column sets its ``done`` flag and the loop stops when all have, after at most
+    ``length`` steps"""
+    extra, prior = prior.shape[1] - P, prior[:, :P]
+    with decode_session(model) as st:
+        B, total, dev = prior.shape[0], P + length, st.param.device
+        d, V = model.embedding_dim, model.vocab_size
+        prior_i, lens_dev, out, tok, pos = stage_prompt(prior, lens, model.pad_token, total, dev)
+        cache = KVCache("bf16", B, d // 64, total, model.num_layer, dev)
+        w = Weights(model, st, fused=B * T <= 32 and d <= 1024)
+        if P > 1:                                             # positions 0..P-2 in one pass; token P_b-1 takes the first step
+            prefill_batched(w, cache, prior_i[:, :P - 1])
+        draft = torch.zeros(B, T, dtype=torch.int32, device=dev)
+        pos_rows = torch.zeros(B * T, dtype=torch.int32, device=dev)
+        limit = (lens_dev + (length - 1)).contiguous()        # the column of every row's last token
+        poll = DonePoll(torch.zeros(B, dtype=torch.int32, device=dev), LOOKAHEAD_POLL)
+        count = torch.zeros(B, 2, dtype=torch.int32, device=dev)
+        if guide is not None:
+            guide = guide.to(device=dev, dtype=torch.int32).contiguous()
+        probs_all = torch.zeros(B, total, V, dtype=torch.float32, device=dev) if return_probs else None
+        # the step's rows: B * T of them, their tokens the draft and their positions pos_rows; ``out`` stays the B rows' matrix
+        r = SubBatch.alloc(0, B * T, pos_rows, True, draft.view(-1), out, LookaheadCache(cache, pos, T),
+                           ops.rel_attn_decode_multi_workspace(B, T, total, d, dev), d)
+        sampler = dict(sampling, allow_table=ops.grammar_table(grammar, dev))
+
+        def step_rows(r_):
+            ops.lookahead_draft(tok, out, pos, draft, pos_rows, total, model.pad_token, guide=guide, ngram=ngram)
+            ops.lookahead_accept(step_logits(w, r_), V, pos, draft, limit, tok, out, poll.done, probs_all=probs_all, stats=count,
+                                 **sampler)
+        if length > 0:
+            run_steps([r], length, step_rows, graph=use_graph, budget=poll)
+        if stats is not None:
+            steps, tokens = count.cpu().T.tolist()
+            stats.update(steps=steps, tokens=tokens, steps_run=poll.steps_run)
+    pad = torch.nn.functional.pad                         # equal prior_lengths P < Pmax: pad_token / zeros up to Pmax + length
+    toks = pad(out, (0, extra), value=model.pad_token) if extra else out
+    return (toks, pad(probs_all, (0, 0, 0, extra)) if extra else probs_all) if return_probs else toks
 
 
 def generate_timed(model, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,

@@ -96,6 +96,12 @@ def get_options(argv=None):
                            'loses 1e4 from its logit (it is still drawn where --grammar, --seconds or --well-formed leave nothing else)')
     parser.add_option('--ngram-span', dest='ngram_span', type='int', default=0,
                       help='the events --no-repeat-ngram looks back over (>= N); 0 (default): the whole sequence so far')
+    parser.add_option('--lookahead', dest='lookahead', type='int', default=0,
+                      help='draft and verify (KV-cache decode): T positions per step and sample (2 .. 8; 0 = off).  A step guesses '
+                           'the next T - 1 events from the sample\'s own history and keeps the guesses the sampler would have drawn: '
+                           'the same sample for a seed, 1 to T events per step')
+    parser.add_option('--draft-ngram', dest='draft_ngram', type='int', default=3,
+                      help='with --lookahead: the longest run of last events whose earlier occurrence is continued (1 .. 8; default 3)')
     return parser.parse_args(argv)[0]
 
 
@@ -215,6 +221,28 @@ def _check_repeat(o):
     return True
 
 
+def _check_lookahead(o, timed, well, repeat):
+    """--lookahead / --draft-ngram against the options draft and verify does not offer, before any model or device work"""
+    if not o.lookahead:
+        if o.draft_ngram != 3:
+            raise SystemExit('--draft-ngram is the history match of --lookahead: add --lookahead T')
+        return
+    for on, what, why in ((o.beam_size, '-B/--beam-size', 'a search has no single draw per position to verify a guess against'),
+                          (o.share_prompt, '--share-prompt', 'the shared prompt cache is another decode driver'),
+                          (o.window, '--window', 'a re-anchor would have to fall between two accepted events'),
+                          (o.kv_cache != 'bf16', '--kv-cache ' + o.kv_cache, 'the T-query attention has no 8-bit form'),
+                          (timed, '--seconds / --bars', "a budget's state is sequential"),
+                          (well, '--well-formed / --max-polyphony', 'the held-note state is sequential'),
+                          (repeat, 'the repetition flags', 'the penalty of an event counts the event before it'),
+                          (o.reference_mask, '--reference-mask', 'the KV-cache decode is causal')):
+        if on:
+            raise SystemExit(f'--lookahead cannot be combined with {what} ({why})')
+    if not 2 <= o.lookahead <= 8:
+        raise SystemExit(f'--lookahead must lie in 2 .. 8 (0 = off), got {o.lookahead}')
+    if not 1 <= o.draft_ngram <= 8:
+        raise SystemExit(f'--draft-ngram must lie in 1 .. 8, got {o.draft_ngram}')
+
+
 def _repeat_args(o, mt):
     """the keyword argument of generate_cached / generate_timed that the repetition flags set"""
     from .decode import Repetition
@@ -309,6 +337,7 @@ def main(argv=None):
     timed = _check_timed(o)
     well = _check_notes(o)
     repeat = _check_repeat(o)
+    _check_lookahead(o, timed, well, repeat)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
@@ -319,6 +348,9 @@ def main(argv=None):
                          '(or -B K; the default sampler recomputes the window and keeps no cache)')
     # with --window every branch below samples through the KV-cache decode and its re-anchored window
     cached = dict(kv_cache=o.kv_cache, window=o.window or None, hop=o.hop or None)
+    look = {}                                             # --lookahead: what every step accepted, printed when the call is done
+    if o.lookahead:
+        cached.update(lookahead=o.lookahead, draft_ngram=o.draft_ngram, stats=look)
     ragged = _ragged_priors(o) if o.condition_files is not None else None     # checked before any model or device work
     device = torch.device('cuda:0')
     vocab = vocab_of(o.repr)
@@ -367,6 +399,7 @@ def main(argv=None):
                                  prior_lengths=lens, **cached, **notes).cpu().numpy()
         res, lens = _best_of(o, mt, res, lens), lens[::o.best_of]
         res = [row[:n + o.max_len] for row, n in zip(res, lens)]             # without the pad tail
+        _report_lookahead(look)
         _write(o, res)
         return
     rows = o.batch_size * o.best_of                        # --best-of N: N candidates per sample, side by side
@@ -409,7 +442,7 @@ def main(argv=None):
     elif o.share_prompt:                                   # -c FILE: one prompt, -b x --best-of samples
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  samples_per_prompt=rows, **notes).cpu().numpy()
-    elif o.window or well or repeat:
+    elif o.window or well or repeat or o.lookahead:
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached,
                                  **notes).cpu().numpy()
     else:
@@ -417,7 +450,13 @@ def main(argv=None):
                           reference_mask=o.reference_mask).cpu().numpy()
     if not o.grammar:
         res = _best_of(o, mt, res, [prior.shape[1]] * rows)
+    _report_lookahead(look)
     _write(o, res)
+
+
+def _report_lookahead(look):
+    if look:
+        print('Lookahead: {} steps, {:.2f} events per step and sample'.format(look['steps_run'], sum(look['tokens']) / max(1, sum(look['steps']))))
 
 
 def _write(o, res):

@@ -339,7 +339,8 @@ class MusicTransformer(torch.nn.Module):
                         grammar=None, prefill: str = "auto", return_cache: bool = False, groups: Optional[int] = None,
                         masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
                         hop: Optional[int] = None, samples_per_prompt: Optional[int] = None, note_rules=None,
-                        max_polyphony: Optional[int] = None, repetition=None):
+                        max_polyphony: Optional[int] = None, repetition=None, lookahead: Optional[int] = None,
+                        draft="history", draft_ngram: int = 3, stats: Optional[dict] = None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq unless ``window`` is given, see below).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -436,10 +437,36 @@ class MusicTransformer(torch.nn.Module):
         device work): a ``subject`` that is not integers [vocab_size] or not 0 at pad_token; ``presence`` / ``frequency``
         negative or not finite; ``window`` outside 1 .. 4096; ``ngram`` not 0 or 2 .. 64; ``span`` not 0 or >= ``ngram``; ``ban``
         outside (0, 1e4]; presence + frequency * window > 1e4; ``groups`` > 1, ``masked_groups``.  None (default), or an
-        object with no penalty and no n-gram rule: the call as described above, untouched, with no new launch."""
+        object with no penalty and no n-gram rule: the call as described above, untouched, with no new launch.
+
+        ``lookahead`` (T, 2 .. 8), ``draft`` ("history" or a guide) and ``draft_ngram`` (1 .. 8, default 3): draft and verify,
+        several tokens per step with the same sample.  Both bounds of a step -- its ~40 launches and one pass over the row's
+        K/V -- are paid per step, not per token, and music repeats its own figures.  A step guesses the row's next T - 1
+        tokens (mgx_lookahead_draft, ABI 32): with "history" the continuation of the latest earlier occurrence of the row's
+        last ``draft_ngram`` tokens in its own sequence (then of fewer, down to one; extended periodically where the match runs
+        into the present; pad_token without a match), with a guide -- integers [B, >= Pmax], e.g. an earlier result -- its
+        columns.  The T positions t_b .. t_b + T - 1 of every row then run as B * T rows of the ordinary step on the guessed
+        inputs, the attention (mgx_rel_attn_decode_multi) loading every K / V row once for the T queries, and
+        mgx_lookahead_accept draws every position with the draw the one-token call makes there -- the sampler's draw is a
+        pure function of (seed, column, row), so no rejection-sampling arithmetic -- and keeps the prefix whose guesses were
+        right: 1 to T tokens per step and row.  The result is the one-token call's sample for that seed up to the rounding
+        difference between the two chains' kernels (a last-bit difference may flip a draw near a CDF boundary).  Nothing is
+        rolled back: cache rows of rejected guesses lie above the row's new position and are rewritten before they are read.
+        The step is captured once and replayed in runs of 32; between runs the host reads the rows' done flags and stops when
+        every row holds its last token, after at most ``length`` steps.  Returns what the call without it returns, padded as
+        the ragged call pads; with ``return_probs`` row b carries the distributions after columns P_b-1 .. P_b+length-2 and
+        zeros elsewhere (uniform prompts too; the prompt is always prefilled in one batched pass).  ``stats`` (a dict)
+        receives ``steps`` and ``tokens``, one int per row, and ``steps_run``.  Works with ``prior_lengths``, ``grammar`` (the
+        grammar row of position i is that of draft token i), ``return_probs``, ``use_graph`` and ``seed``.  Refused
+        (ValueError, before any device work), all of them later work: T outside 2 .. 8, ``draft_ngram`` outside 1 .. 8, a
+        guide that is not integers [B, >= Pmax]; ``window`` / ``hop``, ``kv_cache="fp8"``, ``samples_per_prompt``, ``groups`` > 1,
+        ``masked_groups``, ``prefill="token"``, ``return_cache``; ``note_rules``, ``max_polyphony`` and ``repetition``, whose
+        state is sequential (position i + 1 depends on the token at i); ``generate_timed`` and ``generate_beam`` refuse the
+        keyword.  None (default): the call as described above, untouched, with no new launch."""
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
                                       prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop,
-                                      samples_per_prompt, None, note_rules, max_polyphony, repetition)
+                                      samples_per_prompt, None, note_rules, max_polyphony, repetition, lookahead, draft,
+                                      draft_ngram, stats)
 
     @torch.no_grad()
     def generate_timed(self, prior: torch.Tensor, budget, cost, max_length: int, *, inclusive: bool = True, poll: int = 32,
@@ -464,7 +491,7 @@ class MusicTransformer(torch.nn.Module):
         row kept;  info: ``steps_run``, ``spent`` int64 [B] (the cost of the kept events), ``remaining`` and ``done`` [B] as the
         device left them, and ``probs`` f32 [B, Pmax+max_length, V] with ``return_probs`` -- the distributions the sampler saw,
         0 at every masked id).  Refused (ValueError, before any device work): ``samples_per_prompt``, ``groups`` > 1,
-        ``masked_groups``, ``return_cache``, ``beam_size`` (other drivers), a malformed ``cost``, ``poll`` < 1, ``budget`` < 0,
+        ``masked_groups``, ``return_cache``, ``beam_size``, ``lookahead`` (other drivers), a malformed ``cost``, ``poll`` < 1, ``budget`` < 0,
         ``max_length`` < 1, and what ``generate_cached`` refuses.  ``note_rules`` / ``max_polyphony``: as in
         ``generate_cached`` -- the budget's mask and account run first, the notes' second; an ended row steps on pad_token,
         whose rule is 0, so its held set stays what it was when the row ended.  ``repetition``: as in ``generate_cached`` --
@@ -476,7 +503,7 @@ class MusicTransformer(torch.nn.Module):
     @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,
                       seed: int = 0, grammar=None, prior_lengths=None, kv_cache: str = "bf16", use_graph: bool = True,
-                      return_beams: bool = False, note_rules=None, max_polyphony: Optional[int] = None):
+                      return_beams: bool = False, note_rules=None, max_polyphony: Optional[int] = None, lookahead=None):
         """Beam search over the KV-cache decode: the ``beam_size`` (K, 1 .. min(16, V)) best continuations of ``length`` events
         of every prompt of ``prior`` [B,P], each prompt searched with its own beam.  A beam's score is the sum of its events'
         log softmax(logits / temperature) (under ``grammar``: over the allowed events, the sampler's rule).  The search starts
@@ -492,7 +519,11 @@ class MusicTransformer(torch.nn.Module):
         rows; scores f32 [B]).  ``return_beams`` appends all beams int32 [B, K, Pmax+length], their scores f32 [B, K] and the
         two history tables int32 [B, K, Pmax+length]: column c of slot j holds the token chosen for that slot at column c and
         the slot (0..K-1) of the previous column that it extends.  ``note_rules`` / ``max_polyphony`` are refused (ValueError): a
-        beam's held notes would have to follow its parent through the reorder, which is not built."""
+        beam's held notes would have to follow its parent through the reorder, which is not built.  ``lookahead`` is refused
+        too: draft and verify keeps one sampled sequence per row, a search ranks K * V expansions per step."""
+        if lookahead is not None:
+            raise ValueError("generate_beam is not combined with lookahead (draft and verify is generate_cached(lookahead=): a "
+                             "search has no single draw per position to verify a guess against)")
         if note_rules is not None or max_polyphony is not None:
             raise ValueError("generate_beam is not combined with note_rules / max_polyphony (a beam's held notes would have to "
                              "follow its parent through the reorder: not built)")

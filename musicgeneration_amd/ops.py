@@ -907,6 +907,117 @@ def repeat_penalty(logits, V, out_tokens, pos_dev, subject, pen, window, ngram=0
     return logits
 
 
+# ---- draft and verify on the decode path (ABI 32; contracts in include/mgx.h) ----------------------------------------
+LOOKAHEAD_MAX_T = _lib.DEFINES["MGX_LOOKAHEAD_MAX_T"]
+LOOKAHEAD_MAX_NGRAM = _lib.DEFINES["MGX_LOOKAHEAD_MAX_NGRAM"]
+
+
+def _check_int32(what, **ts):
+    """name=(tensor, entries): contiguous int32 tensors of that many entries"""
+    for name, (t, n) in ts.items():
+        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of {n} entries, got {t.dtype} {tuple(t.shape)}")
+
+
+def _check_lookahead_T(what, T):
+    if not 2 <= int(T) <= LOOKAHEAD_MAX_T:
+        raise ValueError(f"{what}: T must lie in 2 .. {LOOKAHEAD_MAX_T}, got {T}")
+    return int(T)
+
+
+def lookahead_draft(tok, out_tokens, pos_dev, draft, pos_rows, Lmax, pad_token, *, guide=None, ngram=3, base=None):
+    """the guesses of one draft-and-verify step: draft int32 [B, T] (column 0: tok) and pos_rows int32 [B * T] =
+    min(pos_dev[b] + i, Lmax - 1).  ``guide`` int32 [B, guide_ld]: its columns; else the continuation of the latest earlier
+    occurrence of the row's last ``ngram`` (then fewer) tokens in out_tokens int32 [B, out_ld], extended periodically; pad_token
+    without a match.  pos_dev int32 [B], always one position per row; ``base`` as in sample_topk_topp"""
+    what = "lookahead_draft"
+    B = tok.numel()
+    if draft.dim() != 2 or draft.shape[0] != B:
+        raise ValueError(f"{what}: draft must be int32 [{B}, T], got {tuple(draft.shape)}")
+    T = _check_lookahead_T(what, draft.shape[1])
+    pos = _step_pos(what, pos_dev, B, True, base, with_base=True)
+    _check_int32(what, tok=(tok, B), draft=(draft, B * T), pos_rows=(pos_rows, B * T))
+    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or not out_tokens.is_contiguous():
+        raise ValueError(f"{what}: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} {tuple(out_tokens.shape)}")
+    if guide is not None and (guide.dtype != torch.int32 or guide.dim() != 2 or guide.shape[0] != B or not guide.is_contiguous()):
+        raise ValueError(f"{what}: guide must be contiguous int32 [{B}, guide_ld], got {guide.dtype} {tuple(guide.shape)}")
+    if guide is None and not 1 <= int(ngram) <= LOOKAHEAD_MAX_NGRAM:
+        raise ValueError(f"{what}: ngram must lie in 1 .. {LOOKAHEAD_MAX_NGRAM}, got {ngram}")
+    _need_cuda(tok, out_tokens, pos_dev, base, guide, draft, pos_rows)
+    check(_lib.load().mgx_lookahead_draft(ptr(tok), ptr(out_tokens), out_tokens.shape[1], pos[0], pos[1], ptr(guide),
+                                          0 if guide is None else guide.shape[1], int(ngram), int(pad_token), ptr(draft),
+                                          ptr(pos_rows), B, T, int(Lmax), stream_ptr()), "mgx_lookahead_draft")
+    return draft
+
+
+def rel_attn_decode_multi_splits(B, T, Lmax, d) -> int:
+    return int(_lib.load().mgx_rel_attn_decode_multi_splits(B, T, Lmax, d))
+
+
+def rel_attn_decode_multi_workspace(B, T, Lmax, d, device):
+    """scratch for the split-K partials of mgx_rel_attn_decode_multi (None for one split), as rel_attn_decode_workspace"""
+    n = _lib.load().mgx_rel_attn_decode_multi_workspace(B, T, Lmax, d)
+    return torch.empty(n, dtype=torch.uint8, device=device) if n else None
+
+
+def rel_attn_decode_multi(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace, T):
+    """the decode attention of T consecutive positions of every row: qkv_new bf16 [B * T, 3d], row b * T + i at position
+    pos_dev[b] + i; kcache / vcache bf16 [B, h, Lmax, 64] receive the new rows below Lmax; ctx bf16 [B * T, d]; pos_dev int32 [B]
+    on the device (each < Lmax: checked by the kernel, which then appends nothing)"""
+    what = "rel_attn_decode_multi"
+    T = _check_lookahead_T(what, T)
+    if _check_kv_cache(kcache, vcache, None, None, what):
+        raise ValueError(f"{what}: the caches must be bf16 (the draft-and-verify attention has no 8-bit form)")
+    if not (kcache.is_contiguous() and vcache.is_contiguous()):
+        raise ValueError(f"{what}: the caches must be contiguous")
+    B, heads, Lmax, _ = kcache.shape
+    d = heads * 64
+    for name, t, cols in (("qkv_new", qkv_new, 3 * d), ("ctx", ctx, d)):
+        if t.dtype != torch.bfloat16 or tuple(t.shape) != (B * T, cols) or not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous bf16 [{B * T}, {cols}], got {t.dtype} {tuple(t.shape)}")
+    if E.dtype != torch.bfloat16 or E.dim() != 2 or E.shape[1] != 64 or not E.is_contiguous():
+        raise ValueError(f"{what}: E must be contiguous bf16 [M, 64], got {E.dtype} {tuple(E.shape)}")
+    _step_pos(what, pos_dev, B, True)
+    _need_cuda(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace)
+    check(_lib.load().mgx_rel_attn_decode_multi(ptr(qkv_new), ptr(kcache), ptr(vcache), ptr(E), ptr(pos_dev), ptr(ctx), ptr(workspace),
+                                                0 if workspace is None else workspace.numel(), B, T, Lmax, d, E.shape[0],
+                                                stream_ptr()), "mgx_rel_attn_decode_multi")
+    return ctx
+
+
+def lookahead_accept(logits, V, pos_dev, draft, limit, tok, out_tokens, done, *, probs_all=None, stats=None, temperature=1.0,
+                     top_k=0, top_p=1.0, seed=0, allow_table=None, row0=0, base=None):
+    """in place of the sampler of a draft-and-verify step: logits bf16 [B * T, ld]; position i of row b is drawn as
+    sample_topk_topp draws it with (seed, base + pos + i, row0 + b) and the grammar row of draft[b, i]; the prefix of n draws whose
+    guesses were right (at most up to column limit[b]) goes to out_tokens, the last of them to tok, pos_dev += n, the
+    distributions to probs_all f32 [B, columns, V] and (1, n) to stats int32 [B, 2]; a row already at its limit sets done[b]"""
+    what = "lookahead_accept"
+    B = tok.numel()
+    if draft.dim() != 2 or draft.shape[0] != B:
+        raise ValueError(f"{what}: draft must be int32 [{B}, T], got {tuple(draft.shape)}")
+    T = _check_lookahead_T(what, draft.shape[1])
+    ld = logits.shape[-1]
+    if logits.dtype != torch.bfloat16 or logits.numel() != B * T * ld or not logits.is_contiguous():
+        raise ValueError(f"{what}: logits must be contiguous bf16 [{B * T}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    pos = _step_pos(what, pos_dev, B, True, base, with_base=True)
+    _check_int32(what, draft=(draft, B * T), limit=(limit, B), tok=(tok, B), done=(done, B))
+    if stats is not None:
+        _check_int32(what, stats=(stats, 2 * B))
+    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or not out_tokens.is_contiguous():
+        raise ValueError(f"{what}: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} {tuple(out_tokens.shape)}")
+    if probs_all is not None and (probs_all.dtype != torch.float32 or probs_all.dim() != 3 or probs_all.shape[0] != B
+                                  or probs_all.shape[2] != int(V) or not probs_all.is_contiguous()):
+        raise ValueError(f"{what}: probs_all must be contiguous float32 [{B}, columns, {V}], got {probs_all.dtype} "
+                         f"{tuple(probs_all.shape)}")
+    _check_allow_table(allow_table, V)
+    _need_cuda(logits, pos_dev, base, draft, limit, tok, out_tokens, probs_all, done, stats, allow_table)
+    check(_lib.load().mgx_lookahead_accept(ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed), pos[0],
+                                           pos[1], ptr(draft), ptr(limit), ptr(tok), ptr(out_tokens), out_tokens.shape[1],
+                                           ptr(probs_all), 0 if probs_all is None else probs_all.shape[1], ptr(done), ptr(stats), B, T,
+                                           int(row0), ptr(allow_table), stream_ptr()), "mgx_lookahead_accept")
+    return tok
+
+
 # ---- held-note state on the decode path (ABI 28; contracts in include/mgx.h) -----------------------------------------
 NOTE_WORDS = _lib.DEFINES["MGX_NOTE_WORDS"]               # int32 words of a row's state
 NOTE_BITS = 32 * NOTE_WORDS                               # the bits a rule may name; max_on = NOTE_BITS is no cap
