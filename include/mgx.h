@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM; 32: draft-and-verify decode: mgx_lookahead_draft, mgx_rel_attn_decode_multi (with _splits and _workspace), mgx_lookahead_accept, MGX_LOOKAHEAD_MAX_T, MGX_LOOKAHEAD_MAX_NGRAM */
-#define MGX_ABI_VERSION 32
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM; 32: draft-and-verify decode: mgx_lookahead_draft, mgx_rel_attn_decode_multi (with _splits and _workspace), mgx_lookahead_accept, MGX_LOOKAHEAD_MAX_T, MGX_LOOKAHEAD_MAX_NGRAM; 33: per-class temperature, top-k and top-p on the KV-cache decode: mgx_class_logits, MGX_CLASS_MAX */
+#define MGX_ABI_VERSION 33
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -639,6 +639,41 @@ int mgx_lookahead_accept(const uint16_t* logits, int V, int ld, float temperatur
                          int32_t* pos_dev, const int32_t* base_dev, const int32_t* draft, const int32_t* limit, int32_t* tok,
                          int32_t* out_tokens, int out_ld, float* probs_all, int probs_ld, int32_t* done, int32_t* stats, int B,
                          int T, int row0, const uint32_t* allow_table, void* stream);
+
+/* ---- Per-class sampling (ABI 33): a temperature, a top-k and a top-p of its own for every class of ids (a codec's event types),
+ * in one stateless call, in place on the step's logits bf16 [B,ld] before the sampler.  The row's distribution is sampled in two
+ * stages -- the class at the call's temperature, then the id inside the class at the class's -- and the call writes the logarithm
+ * of the product, so the UNCHANGED sampler, run at temperature 1, draws from it.  No state, nothing gathered; captured with the step.
+ * A step is: logits, (mgx_budget_mask,) (mgx_repeat_penalty,) mgx_class_logits, the sampler or mgx_lookahead_accept at
+ * temperature 1, (mgx_budget_account).  It is not combined with the two draws of the note rules (mgx_notes_mask): an in-place
+ * rewrite cannot serve both.
+ * mgx_class_logits.  cls int32 [V]: the class of every id, 0 <= cls[v] < C.  inv_temp float [C], top_k int32 [C], top_p float [C],
+ *   all on the device.  tok int32 [B] and allow_table uint32 [V, ceil(V/32)] (both or neither): the sampler's grammar, whose
+ *   previous token is tok[b] (clamped to 0 .. V-1); under draft and verify tok is the draft, one entry per logits row.
+ *   For row b, with x_v = f32(logits[b,v]):
+ *   Live ids:  A = {v < V: x_v > -inf, and bit v of the grammar row of tok[b] is set, if there is a table}.  A table under which A
+ *     is empty is ignored for the row (A = {x_v > -inf}): the sampler's own fallback.  If A is still empty the row is left bit for
+ *     bit.  NaN: unspecified.
+ *   Class stage:  P_c = sum_{v in A, cls[v] = c} exp(x_v / temperature) / sum_{v in A} exp(x_v / temperature).
+ *   Inside class c (A_c = {v in A: cls[v] = c} not empty):  q_v = softmax over A_c of x_v * inv_temp[c], then the thresholds and
+ *     the tie rule of mgx_sample_topk_topp on q: with 0 < top_k[c] < |A_c|, tau = the largest value with #{q >= tau} >= top_k[c];
+ *     with top_p[c] < 1, tau rises to the largest value with mass{q >= tau} >= top_p[c] * mass{q >= the top-k tau}.
+ *     K_c = {v in A_c: q_v >= tau} (ties stay together), q'_v = q_v / sum_{K_c} q.
+ *   Result:  p'_v = P_{cls[v]} q'_v on the union of the K_c.  logits[b,v] = bf16(ln p'_v) there and -inf at every other v < V whose
+ *     class lies in 0 .. C-1.  ln p'_v is formed in log space, (lse_c - lse_all) at the call's temperature plus
+ *     (x_v - max_{A_c} x) * inv_temp[c] - ln sum_{K_c} e, so a kept id never becomes -inf through underflow; ONE rounding to bf16,
+ *     nearest-even.  A probability read back from the result is off by at most |ln p'| 2^-8 relative: the order of the bf16 logits
+ *     themselves.  Columns >= V, cls, the parameter arrays, tok and the table are not written.
+ * MGX_ERR_NULL for a NULL logits, cls, inv_temp, top_k or top_p, or exactly one of tok / allow_table NULL.  MGX_ERR_SHAPE unless
+ *   B > 0, 0 < V <= 1024, ld >= V, 1 <= C <= MGX_CLASS_MAX, temperature finite and > 0.
+ * Contract (not checked: the values live on the device): 0 <= cls[v] < C (an id of another class is not written), inv_temp finite
+ *   and > 0, top_k >= 0, 0 < top_p <= 1.
+ * One workgroup of C waves per row, wave c owns class c (the classes' threshold searches run side by side); ids lane + 64 i, 16
+ * per lane, as in the sampler.  Every wave reads the row before the workgroup's one barrier and writes its class's ids after it.
+ * The grid is a function of B only (no host read, no allocation); no LDS, no atomics.                                          */
+#define MGX_CLASS_MAX 16
+int mgx_class_logits(uint16_t* logits, int V, int ld, const int32_t* cls, int C, const float* inv_temp, const int32_t* top_k,
+                     const float* top_p, float temperature, const int32_t* tok, const uint32_t* allow_table, int B, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

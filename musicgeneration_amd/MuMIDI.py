@@ -103,6 +103,12 @@ class MuMIDI_EventSeq:
         return _vocab.repeat_subject(MuMIDI_EventSeq.dim(), MuMIDI_EventSeq.feat_ranges()['note_on'], vocab_size)
 
     @staticmethod
+    def event_classes(vocab_size=None):
+        """the classes of ``decode.ClassSampling``: (names, classes int32 [vocab_size]) -- the features of ``feat_ranges()`` in id
+        order, one class each, and a last class 'other' for the ids a model adds beyond dim() (its pad id)"""
+        return _vocab.event_classes(MuMIDI_EventSeq.feat_ranges(), vocab_size)
+
+    @staticmethod
     def get_track_id(track_name):
         return MuMIDI_EventSeq.feat_ranges()['track'][0] + tracks_idx[track_name]
 

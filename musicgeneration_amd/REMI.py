@@ -170,6 +170,12 @@ class REMI_EventSeq:
         return _vocab.repeat_subject(REMI_EventSeq.dim(), REMI_EventSeq.feat_ranges()['note_on'], vocab_size)
 
     @staticmethod
+    def event_classes(vocab_size=None):
+        """the classes of ``decode.ClassSampling``: (names, classes int32 [vocab_size]) -- the features of ``feat_ranges()`` in id
+        order, one class each, and a last class 'other' for the ids a model adds beyond dim() (its pad id)"""
+        return _vocab.event_classes(REMI_EventSeq.feat_ranges(), vocab_size)
+
+    @staticmethod
     def transpose_table(offsets, vocab_size=None):
         """what every id becomes under a transposition, int32 [len(offsets), vocab_size]: row s moves note_on pitch p to
         p + offsets[s] (|offset| <= 11; a pitch that would leave the range comes back by an octave, as in

@@ -84,3 +84,17 @@ def repeat_subject(dim, note_on, vocab_size=None):
     subject = np.zeros(V, dtype=np.int32)
     subject[note_on.start:note_on.stop] = 1
     return subject
+
+
+def event_classes(ranges, vocab_size=None):
+    """the classes of per-class sampling (``decode.ClassSampling``): (names, classes int32 [vocab_size]).  The layout's features in
+    id order, one class each, then a last class 'other' for the ids a model adds beyond the codec's (its pad id)"""
+    dim = sum(len(r) for r in ranges.values())
+    V = dim if vocab_size is None else int(vocab_size)
+    if V < dim:
+        raise ValueError(f"vocab_size ({V}) is below the codec's {dim} ids")
+    names = list(ranges) + ['other']
+    classes = np.full(V, len(names) - 1, dtype=np.int32)
+    for c, ids in enumerate(ranges.values()):
+        classes[ids.start:ids.stop] = c
+    return names, classes

@@ -15,7 +15,9 @@ ops.budget_mask / ops.budget_account) and a step loop that reads the rows' ``don
 ``NoteState`` (``note_rules=``, ``max_polyphony=``) is the second per-row state bracketing the sampler the same way: the set of
 notes every row holds (ops.notes_mask / ops.notes_account), which keeps a MIDI-like stream well-formed.  ``Repetition``
 (``repetition=``) is not a state: one launch before the sampler (ops.repeat_penalty) reads the row's own columns of the output
-matrix and penalises repeated ids and n-grams by finite amounts.  ``generate_lookahead`` (generate_cached(lookahead=T)) is draft
+matrix and penalises repeated ids and n-grams by finite amounts.  ``ClassSampling`` (``class_sampling=``) is the last launch
+before the sampler (ops.class_logits): a temperature, top-k and top-p per class of ids, written back as ln p' so the sampler,
+at temperature 1, is unchanged.  ``generate_lookahead`` (generate_cached(lookahead=T)) is draft
 and verify: the same step on B * T rows, T consecutive positions of every row on guessed inputs (ops.lookahead_draft), whose
 attention is ops.rel_attn_decode_multi behind a ``LookaheadCache`` and whose sampler is ops.lookahead_accept; a ``DonePoll`` --
 what a ``Budget`` is to the step loop -- stops it once every row holds its last token."""
@@ -632,17 +634,132 @@ def check_repeat_args(model, repetition, *, groups=None, masked_groups=False):
     return None if own.inert else own
 
 
+class ClassSampling:
+    """per-class sampling of generate_cached / generate_timed (include/mgx.h, ABI 33): a temperature, a top-k and a top-p of its
+    own for every class of ids -- a codec's event types, ``EventSeq.event_classes()``.  A class's total probability stays the
+    model's own at the call's temperature; inside class c the ids are drawn from the softmax at ``temperature[c]``, cut by
+    ``top_k[c]`` and ``top_p[c]`` with the sampler's rules.  ``classes``: integers [vocab_size], the class 0 .. 15 of every id.
+    Each of ``temperature``, ``top_k``, ``top_p``: None, one value per class (C = the largest class + 1 of them), or a
+    {class: value} dict; a missing or None entry means the call's temperature and no filter (top_k 0, top_p 1).  Stateless: one
+    launch before the sampler (ops.class_logits), which then runs at temperature 1"""
+
+    def __init__(self, classes, temperature=None, top_k=None, top_p=None):
+        self.classes_host, self.temperature, self.top_k, self.top_p = classes, temperature, top_k, top_p
+        self.call_temperature = None                      # check_class_args's copy knows the call's temperature
+        self.cls = self.inv_temp = self.k = self.p = None
+
+    @staticmethod
+    def entries(spec) -> list:
+        """the values a None / sequence / dict specification names, None entries included"""
+        if spec is None:
+            return []
+        return list(spec.values()) if isinstance(spec, dict) else list(spec)
+
+    @property
+    def inert(self) -> bool:
+        """is every class plain -- no temperature but the call's (where the call's is known: check_class_args's copy), no top-k
+        and no top-p?  The step is then the unchanged decode_step"""
+        def same(t):
+            return self.call_temperature is not None and np.float32(1.0 / t) == np.float32(1.0 / self.call_temperature)
+        return (all(t is None or same(t) for t in self.entries(self.temperature))
+                and all(k is None or k == 0 for k in self.entries(self.top_k))
+                and all(p is None or p == 1 for p in self.entries(self.top_p)))
+
+    def stage(self, dev) -> "ClassSampling":
+        """``classes`` and the three per-class arrays on the device, once per call (a checked copy: lists of C values)"""
+        inv = [1.0 / (self.call_temperature if t is None else t) for t in self.temperature]
+        self.cls = torch.from_numpy(np.ascontiguousarray(np.asarray(self.classes_host).astype(np.int32))).to(dev)
+        self.inv_temp = torch.tensor(inv, dtype=torch.float32, device=dev)
+        self.k = torch.tensor(self.top_k, dtype=torch.int32, device=dev)
+        self.p = torch.tensor(self.top_p, dtype=torch.float32, device=dev)
+        return self
+
+    def apply(self, logits, V: int, r: "SubBatch", temperature: float, allow_table) -> None:
+        ops.class_logits(logits, V, self.cls, self.inv_temp, self.k, self.p, temperature,
+                         tok=None if allow_table is None else r.tok, allow_table=allow_table)
+
+
+def check_class_args(model, class_sampling, temperature, *, groups=None, masked_groups=False, note_rules=None, max_polyphony=None):
+    """every refusal of ``class_sampling`` (ValueError), on the host before any device work.  Returns a ClassSampling of its own --
+    the classes as numpy int32, one value per class in each list, the call's temperature known -- so the caller's object is not
+    staged and serves any number of calls; or None: no ``class_sampling``, or every class plain at this temperature"""
+    if class_sampling is None:
+        return None
+    if not isinstance(class_sampling, ClassSampling):
+        raise ValueError(f"class_sampling must be a decode.ClassSampling (or None), got {type(class_sampling).__name__}")
+
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
+    if not number(temperature) or not np.isfinite(temperature) or temperature <= 0:
+        raise ValueError(f"class_sampling: the call's temperature must be a finite number > 0, got {temperature!r}")
+    cs, V = class_sampling, model.vocab_size
+    raw = cs.classes_host
+    arr = np.asarray(raw.detach().cpu() if isinstance(raw, torch.Tensor) else raw)
+    if arr.shape != (V,) or arr.dtype.kind not in "iu":
+        raise ValueError(f"class_sampling: classes must be integers, one per id, [vocab_size] = [{V}], got {arr.dtype} "
+                         f"{tuple(arr.shape)}")
+    if arr.min() < 0 or arr.max() >= ops.CLASS_MAX:
+        raise ValueError(f"class_sampling: a class must lie in 0 .. {ops.CLASS_MAX - 1}, got {int(arr.min())} .. {int(arr.max())}")
+    specs = (("temperature", cs.temperature), ("top_k", cs.top_k), ("top_p", cs.top_p))
+    for name, spec in specs:
+        if spec is not None and not isinstance(spec, (dict, list, tuple, np.ndarray, torch.Tensor)):
+            raise ValueError(f"class_sampling: {name} must be None, a sequence with one value per class or a {{class: value}} "
+                             f"dict, got {spec!r}")
+    # C: the classes the ids use, or more where a sequence is longer (a class without an id, e.g. 'other' of a model without pad)
+    C = max([int(arr.max()) + 1] + [len(spec) for _, spec in specs if spec is not None and not isinstance(spec, dict)])
+    if C > ops.CLASS_MAX:
+        long = [name for name, spec in specs if spec is not None and not isinstance(spec, dict) and len(spec) == C]
+        raise ValueError(f"class_sampling: at most {ops.CLASS_MAX} classes, got {C} values of {long[0]}")
+
+    def per_class(name, spec, valid, what):
+        vals = [None] * C
+        if spec is None:
+            return vals
+        if isinstance(spec, dict):
+            items = list(spec.items())
+        elif len(spec) == C:
+            items = list(enumerate(spec.tolist() if isinstance(spec, (np.ndarray, torch.Tensor)) else spec))
+        else:
+            raise ValueError(f"class_sampling: {name} has {len(spec)} values for C = {C} classes (one per class, or a "
+                             f"{{class: value}} dict)")
+        for c, v in items:
+            if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < C:
+                raise ValueError(f"class_sampling: {name} names class {c!r}; the classes are 0 .. {C - 1}")
+            if v is not None and not valid(v):
+                raise ValueError(f"class_sampling: {name}[{c}] must be {what}, got {v!r}")
+            vals[int(c)] = v
+        return vals
+    temps = per_class("temperature", cs.temperature, lambda v: number(v) and np.isfinite(v) and v > 0, "a finite number > 0")
+    ks = per_class("top_k", cs.top_k, lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 0 <= v < 2 ** 31,
+                   "an integer >= 0")
+    ps = per_class("top_p", cs.top_p, lambda v: number(v) and 0 < v <= 1, "a number in (0, 1]")
+    if (groups or 1) > 1 or masked_groups:
+        raise ValueError("class_sampling is not combined with groups / masked_groups (experiment flags: the launch is tested on the "
+                         "batch as one group)")
+    if note_rules is not None or max_polyphony is not None:
+        raise ValueError("class_sampling is not combined with note_rules / max_polyphony (that step draws twice, from the logits as "
+                         "they stand and from the masked ones, and an in-place rewrite cannot serve both): later work")
+    own = ClassSampling(np.ascontiguousarray(arr.astype(np.int32)), [None if t is None else float(t) for t in temps],
+                        [0 if k is None else int(k) for k in ks], [1.0 if p is None else float(p) for p in ps])
+    own.call_temperature = float(temperature)
+    return None if own.inert else own
+
+
 def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool, bud: Optional[Budget],
-                            notes: Optional[NoteState], rep: Optional[Repetition] = None) -> None:
-    """decode_step under the rows' budgets, repetition control and / or held notes: the logits are masked and penalised before the
-    sampler sees them, and the draw is charged to the clock and applied to the notes after it (the order: include/mgx.h, ABI 31).
-    With ``notes`` the step draws twice (below); the penalty comes before the first draw, which notes_keep would otherwise let
-    stand unpenalised"""
+                            notes: Optional[NoteState], rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None) -> None:
+    """decode_step under the rows' budgets, repetition control, per-class sampling and / or held notes: the logits are masked,
+    penalised and rewritten before the sampler sees them, and the draw is charged to the clock and applied to the notes after it
+    (the order: include/mgx.h, ABI 31 and 33).  With ``notes`` the step draws twice (below); the penalty comes before the first
+    draw, which notes_keep would otherwise let stand unpenalised.  ``cs`` (never with ``notes``) leaves ln p' in the logits, so
+    the sampler runs at temperature 1"""
     logits = step_logits(w, r)
     if bud is not None:
         ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
     if rep is not None:
         rep.apply(logits, w.V, r)
+    if cs is not None:
+        cs.apply(logits, w.V, r, sampler["temperature"], sampler["allow_table"])
+        sampler = dict(sampler, temperature=1.0)
     out = r.out if sample_into_out else None
     if notes is not None:
         # the sampler draws by inverse CDF, so a draw from the masked logits is another token even where the unmasked draw of
@@ -790,9 +907,11 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
                     return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None,
                     bud: Optional[Budget] = None, note_rules=None, max_polyphony=None, repetition=None, lookahead=None,
-                    draft="history", draft_ngram=3, stats=None):
+                    draft="history", draft_ngram=3, stats=None, class_sampling=None):
     """MusicTransformer.generate_cached (documented there).  ``bud``: generate_timed's budgets, not yet staged -- the steps run
     decode_step_constrained and the loop stops once every row has ended"""
+    cs = check_class_args(model, class_sampling, temperature, groups=groups, masked_groups=masked_groups, note_rules=note_rules,
+                          max_polyphony=max_polyphony)
     if lookahead is not None:
         T, guide = check_lookahead_args(model, prior, lookahead, draft, draft_ngram, window=window, hop=hop, kv_cache=kv_cache,
                                         samples_per_prompt=samples_per_prompt, groups=groups, masked_groups=masked_groups,
@@ -801,7 +920,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
         P, lens, _, _ = check_args(model, prior, length, False, "batched", prior_lengths, kv_cache)
         return generate_lookahead(model, prior, P, lens, length, T, guide, int(draft_ngram),
                                   dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), grammar, use_graph,
-                                  return_probs, stats)
+                                  return_probs, stats, cs)
     rep = check_repeat_args(model, repetition, groups=groups, masked_groups=masked_groups)
     notes = check_note_args(model, note_rules, max_polyphony, grammar=grammar, groups=groups, masked_groups=masked_groups,
                             return_cache=return_cache)
@@ -810,7 +929,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     if samples_per_prompt is not None:
         return generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs,
-                               notes, rep)
+                               notes, rep, cs)
     extra, prior, ragged = prior.shape[1] - P, prior[:, :P], lens is not None      # extra > 0: equal prior_lengths below the width
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -852,10 +971,12 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
             notes.stage(dev, prior, lens or [P] * B)
         if rep is not None:
             rep.stage(dev)
+        if cs is not None:
+            cs.stage(dev)
 
         def step_rows(r):                                     # length 0 still runs the last prompt token (its distribution)
-            if bud is not None or notes is not None or rep is not None:
-                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes, rep)
+            if bud is not None or notes is not None or rep is not None or cs is not None:
+                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes, rep, cs)
             else:
                 decode_step(w, r, sampler, length > 0)
         if window is not None:
@@ -886,13 +1007,13 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
 
 
 def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, grammar, use_graph: bool, return_probs: bool,
-                    notes: Optional[NoteState] = None, rep: Optional[Repetition] = None):
+                    notes: Optional[NoteState] = None, rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None):
     """generate_cached(samples_per_prompt=N), its arguments checked: rows r = b * N + n, sample n of prompt b.  One batched
     prefill of the Bp prompts fills the prompt cache (pre_rows = len_b - 1 rows each); every row then resumes at its prompt's
     last token and runs the ragged step on R = Bp * N rows, whose attention reads the prompt's rows once for the samples of a
     prompt and appends to the row's own cache.  Row r draws with (seed, t, r), as it does in the call on the prompts repeated N
     times.  ``notes``: a NoteState, not yet staged -- every row starts from its prompt's held notes.  ``rep``: a checked Repetition, not
-    yet staged -- stateless, so the samples of a prompt need nothing gathered"""
+    yet staged -- stateless, so the samples of a prompt need nothing gathered.  ``cs``: a checked ClassSampling, likewise"""
     with decode_session(model) as st:
         (Bp, P), dev = prior.shape, st.param.device
         R, total, d, V = Bp * N, P + length, model.embedding_dim, model.vocab_size
@@ -911,10 +1032,12 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
             notes.stage(dev, prior, lens, repeat=N)
         if rep is not None:
             rep.stage(dev)
+        if cs is not None:
+            cs.stage(dev)
 
         def step_rows(r_):                                    # length 0 still runs the last prompt token (its distribution)
-            if notes is not None or rep is not None:
-                decode_step_constrained(w, r_, sampler, length > 0, None, notes, rep)
+            if notes is not None or rep is not None or cs is not None:
+                decode_step_constrained(w, r_, sampler, length > 0, None, notes, rep, cs)
             else:
                 decode_step(w, r_, sampler, length > 0)
         run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=file)
@@ -976,14 +1099,15 @@ class LookaheadCache:
 
 
 def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, ngram: int, sampling: dict, grammar, use_graph: bool,
-                       return_probs: bool, stats):
+                       return_probs: bool, stats, cs: Optional[ClassSampling] = None):
     """generate_cached(lookahead=T), its arguments checked.  A step of the B rows is the ragged step on B * T rows: row b * T + i
     runs position t_b + i on draft[b, i] (ops.lookahead_draft), the attention is ops.rel_attn_decode_multi, and
     ops.lookahead_accept draws every position as the one-token call draws it -- (seed, column, b) -- keeps the prefix whose
     guesses were right and advances row b by it.  Nothing is rolled back: a cache row a rejected guess wrote lies at or above the
     row's new position and is rewritten by the next step before any query reaches it.  The step is captured once and replayed
     in runs of LOOKAHEAD_POLL; a row at its last column sets its ``done`` flag and the loop stops when all have, after at most
-    ``length`` steps"""
+    ``length`` steps.  ``cs``: a checked ClassSampling, not yet staged -- row-wise and stateless, it rewrites the B * T rows' logits
+    (the grammar row of row b * T + i is that of draft[b, i]) and the accept draws at temperature 1"""
     extra, prior = prior.shape[1] - P, prior[:, :P]
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -1006,10 +1130,17 @@ def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, n
                            ops.rel_attn_decode_multi_workspace(B, T, total, d, dev), d)
         sampler = dict(sampling, allow_table=ops.grammar_table(grammar, dev))
 
+        if cs is not None:
+            cs.stage(dev)
+            warped = dict(sampler, temperature=1.0)
+
         def step_rows(r_):
             ops.lookahead_draft(tok, out, pos, draft, pos_rows, total, model.pad_token, guide=guide, ngram=ngram)
-            ops.lookahead_accept(step_logits(w, r_), V, pos, draft, limit, tok, out, poll.done, probs_all=probs_all, stats=count,
-                                 **sampler)
+            logits = step_logits(w, r_)
+            if cs is not None:
+                cs.apply(logits, V, r_, sampler["temperature"], sampler["allow_table"])
+            ops.lookahead_accept(logits, V, pos, draft, limit, tok, out, poll.done, probs_all=probs_all, stats=count,
+                                 **(sampler if cs is None else warped))
         if length > 0:
             run_steps([r], length, step_rows, graph=use_graph, budget=poll)
         if stats is not None:
@@ -1021,15 +1152,18 @@ def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, n
 
 
 def generate_timed(model, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,
-                   prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules=None, max_polyphony=None, repetition=None):
+                   prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules=None, max_polyphony=None, repetition=None,
+                   class_sampling=None):
     """MusicTransformer.generate_timed (documented there): generate_cached's driver with a Budget"""
     B = prior.shape[0]
     check_repeat_args(model, repetition)
+    check_class_args(model, class_sampling, temperature, note_rules=note_rules, max_polyphony=max_polyphony)
     budgets, cost_i = check_budget_args(model, B, budget, cost, max_length, poll, refused)
     check_args(model, prior, max_length, return_probs, "auto", prior_lengths, kv_cache, window, hop)     # before any device work
     bud = Budget(budgets, cost_i, model.pad_token, bool(inclusive), int(poll))
     res = generate_cached(model, prior, max_length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, "auto",
-                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud, note_rules, max_polyphony, repetition)
+                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud, note_rules, max_polyphony, repetition,
+                          class_sampling=class_sampling)
     tokens, probs = res if return_probs else (res, None)
     # what every row spent: the cost of the events it kept, columns P_b .. P_b + count_b - 1
     start = torch.tensor(_prompt_lengths(prior, prior_lengths) or [prior.shape[1]] * B, device=tokens.device)[:, None]

@@ -102,6 +102,14 @@ def get_options(argv=None):
                            'the same sample for a seed, 1 to T events per step')
     parser.add_option('--draft-ngram', dest='draft_ngram', type='int', default=3,
                       help='with --lookahead: the longest run of last events whose earlier occurrence is continued (1 .. 8; default 3)')
+    parser.add_option('--class-temperature', dest='class_temperature', type='string', default=None,
+                      help='per-class sampling (KV-cache decode): NAME=T,NAME=T -- the events of class NAME (the event types of the '
+                           "--repr, e.g. time_shift=0.8,note_on=1.2) are drawn at temperature T inside their class; a class's total "
+                           'probability stays what -t gives it.  With --best-of the candidates are ranked by the model\'s own score')
+    parser.add_option('--class-top-k', dest='class_top_k', type='string', default=None,
+                      help='NAME=K,...: the events of class NAME come from the K most likely of that class (e.g. velocity=4)')
+    parser.add_option('--class-top-p', dest='class_top_p', type='string', default=None,
+                      help='NAME=P,...: the events of class NAME come from the nucleus of mass P of that class (e.g. chord=0.9)')
     return parser.parse_args(argv)[0]
 
 
@@ -243,6 +251,60 @@ def _check_lookahead(o, timed, well, repeat):
         raise SystemExit(f'--draft-ngram must lie in 1 .. 8, got {o.draft_ngram}')
 
 
+def _codec(o):
+    """the codec class of --repr"""
+    if o.repr == 'remi':
+        from .REMI import REMI_EventSeq as Codec
+    elif o.repr == 'mumidi':
+        from .MuMIDI import MuMIDI_EventSeq as Codec
+    else:
+        from .sequence import EventSeq as Codec
+    return Codec
+
+
+def _check_class(o, well):
+    """--class-temperature / --class-top-k / --class-top-p against the options they do not go with, the class names of the --repr
+    and their own ranges, before any model or device work.  Returns the three {class index: value} dicts (None without a flag)"""
+    flags = (('--class-temperature', o.class_temperature, float, lambda v: np.isfinite(v) and v > 0, 'a finite number > 0'),
+             ('--class-top-k', o.class_top_k, int, lambda v: v >= 0, 'an integer >= 0'),
+             ('--class-top-p', o.class_top_p, float, lambda v: 0 < v <= 1, 'a number in (0, 1]'))
+    given = [f for f, text, *_ in flags if text is not None]
+    if not given:
+        return None
+    for on, what, why in ((o.beam_size, '-B/--beam-size', 'a search ranks whole beams by likelihood: not built'),
+                          (o.reference_mask, '--reference-mask', 'the KV-cache decode is causal'),
+                          (well, '--well-formed / --max-polyphony', 'that step draws twice and an in-place rewrite of the logits '
+                                                                    'cannot serve both: later work')):
+        if on:
+            raise SystemExit(f'{given[0]} cannot be combined with {what} ({why})')
+    names = _codec(o).event_classes()[0]
+    out = []
+    for flag, text, conv, valid, what in flags:
+        vals = {}
+        for item in (text or '').split(','):
+            if not item:
+                continue
+            name, eq, v = item.partition('=')
+            if not eq or name not in names:
+                raise SystemExit(f"{flag}: '{item}' is not NAME=VALUE with a class of --repr {o.repr}: the classes are "
+                                 + ', '.join(names))
+            try:
+                val = conv(v)
+            except ValueError:
+                val = None
+            if val is None or not valid(val):
+                raise SystemExit(f'{flag}: {name} must be {what}, got {v!r}')
+            vals[names.index(name)] = val
+        out.append(vals)
+    return tuple(out)
+
+
+def _class_args(o, mt, classes):
+    """the keyword argument of generate_cached / generate_timed that the --class-* flags set"""
+    from .decode import ClassSampling
+    return dict(class_sampling=ClassSampling(_codec(o).event_classes(mt.vocab_size)[1], *classes))
+
+
 def _repeat_args(o, mt):
     """the keyword argument of generate_cached / generate_timed that the repetition flags set"""
     from .decode import Repetition
@@ -250,13 +312,7 @@ def _repeat_args(o, mt):
         subject = np.ones(mt.vocab_size, dtype=np.int32)
         subject[mt.pad_token] = 0
     else:
-        if o.repr == 'remi':
-            from .REMI import REMI_EventSeq as Codec
-        elif o.repr == 'mumidi':
-            from .MuMIDI import MuMIDI_EventSeq as Codec
-        else:
-            from .sequence import EventSeq as Codec
-        subject = Codec.repeat_subject(mt.vocab_size)
+        subject = _codec(o).repeat_subject(mt.vocab_size)
     return dict(repetition=Repetition(subject, o.presence_penalty, o.frequency_penalty, o.repeat_window, o.no_repeat_ngram,
                                       o.ngram_span))
 
@@ -338,12 +394,13 @@ def main(argv=None):
     well = _check_notes(o)
     repeat = _check_repeat(o)
     _check_lookahead(o, timed, well, repeat)
+    classes = _check_class(o, well)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
         raise SystemExit('--reference-mask cannot be combined with --window (the KV-cache decode is causal)')
     if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size or timed or well
-                                     or repeat):
+                                     or repeat or classes):
         raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
                          '(or -B K; the default sampler recomputes the window and keeps no cache)')
     # with --window every branch below samples through the KV-cache decode and its re-anchored window
@@ -373,6 +430,8 @@ def main(argv=None):
     notes = _note_args(o, mt) if well else {}             # --well-formed: every sampling call below is the KV-cache decode
     if repeat:                                            # so it is with the repetition flags; their keyword travels with the notes'
         notes.update(_repeat_args(o, mt))
+    if classes:                                           # and with the --class-* flags
+        notes.update(_class_args(o, mt, classes))
 
     def search(prior, **kw):                              # -B: the best beam of every sample
         res, scores = mt.generate_beam(prior, o.max_len, o.beam_size, temperature=o.temperature, stochastic=o.stochastic_beam_search,
@@ -442,7 +501,7 @@ def main(argv=None):
     elif o.share_prompt:                                   # -c FILE: one prompt, -b x --best-of samples
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  samples_per_prompt=rows, **notes).cpu().numpy()
-    elif o.window or well or repeat or o.lookahead:
+    elif o.window or well or repeat or o.lookahead or classes:
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached,
                                  **notes).cpu().numpy()
     else:

@@ -340,7 +340,7 @@ class MusicTransformer(torch.nn.Module):
                         masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
                         hop: Optional[int] = None, samples_per_prompt: Optional[int] = None, note_rules=None,
                         max_polyphony: Optional[int] = None, repetition=None, lookahead: Optional[int] = None,
-                        draft="history", draft_ngram: int = 3, stats: Optional[dict] = None):
+                        draft="history", draft_ngram: int = 3, stats: Optional[dict] = None, class_sampling=None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq unless ``window`` is given, see below).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -462,18 +462,37 @@ class MusicTransformer(torch.nn.Module):
         guide that is not integers [B, >= Pmax]; ``window`` / ``hop``, ``kv_cache="fp8"``, ``samples_per_prompt``, ``groups`` > 1,
         ``masked_groups``, ``prefill="token"``, ``return_cache``; ``note_rules``, ``max_polyphony`` and ``repetition``, whose
         state is sequential (position i + 1 depends on the token at i); ``generate_timed`` and ``generate_beam`` refuse the
-        keyword.  None (default): the call as described above, untouched, with no new launch."""
+        keyword.  None (default): the call as described above, untouched, with no new launch.
+
+        ``class_sampling`` (a ``decode.ClassSampling(classes, temperature, top_k, top_p)``): a temperature, a top-k and a top-p
+        per class of ids -- steadier rhythm with freer pitches, velocities from the top few, chords from a nucleus.
+        ``classes`` (integers [vocab_size], classes 0 .. 15) comes from the codec: ``EventSeq.event_classes(vocab_size)``
+        gives the names and the array.  Sampling is in two stages: the class is drawn with the model's own probability at the
+        call's ``temperature`` (no mass moves between classes), the id inside class c from the softmax at ``temperature[c]`` cut
+        by ``top_k[c]`` and ``top_p[c]`` with the sampler's rules (ties stay together; the grammar's ids only).  One stateless
+        launch per step, captured with it (mgx_class_logits, ABI 33), writes bf16(ln p') of that distribution over the step's
+        logits -- after the budget's mask and the repetition penalty -- and the unchanged sampler then runs at temperature 1
+        with the call's own ``top_k`` / ``top_p``, which act on p' as a whole.  ``return_probs`` files softmax(bf16(ln p')), what
+        was drawn from: a probability is off by at most |ln p'| 2^-8 relative, the order of the bf16 logits themselves.  Works
+        with ``prior_lengths``, ``kv_cache``, ``window`` / ``hop``, ``samples_per_prompt``, ``grammar``, ``repetition``,
+        ``generate_timed`` and ``lookahead`` (row-wise and stateless); teacher-forced ``prefill="token"`` prompt steps stay
+        unwarped.  Refused (ValueError, before any device work): ``classes`` that are not integers [vocab_size] in 0 .. 15; a
+        temperature that is not finite and > 0 (the call's included); a ``top_k`` that is not an integer >= 0; a ``top_p``
+        outside (0, 1]; a sequence that is not one value per class; ``groups`` > 1, ``masked_groups``; ``note_rules`` /
+        ``max_polyphony`` (that step draws twice and an in-place rewrite cannot serve both: later work).  ``generate_beam``,
+        ``generate`` and ``Event_Melody_RNN`` do not take the keyword.  None (default), or an object whose every class has the
+        call's temperature and no filter: the call as described above, untouched, with no new launch."""
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
                                       prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop,
                                       samples_per_prompt, None, note_rules, max_polyphony, repetition, lookahead, draft,
-                                      draft_ngram, stats)
+                                      draft_ngram, stats, class_sampling)
 
     @torch.no_grad()
     def generate_timed(self, prior: torch.Tensor, budget, cost, max_length: int, *, inclusive: bool = True, poll: int = 32,
                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, use_graph: bool = True,
                        grammar=None, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
                        hop: Optional[int] = None, return_probs: bool = False, note_rules=None,
-                       max_polyphony: Optional[int] = None, repetition=None, **refused):
+                       max_polyphony: Optional[int] = None, repetition=None, class_sampling=None, **refused):
         """Generate to a musical length: ``generate_cached`` where every row stops at a budget of its own instead of after a
         number of events.  ``cost`` (int32-representable [vocab_size], >= 0, 0 at pad_token) prices every id --
         ``EventSeq.time_cost`` in centiseconds, ``REMI_EventSeq.bar_cost`` in bars -- and ``budget`` (an int, or one per row;
@@ -495,10 +514,12 @@ class MusicTransformer(torch.nn.Module):
         ``max_length`` < 1, and what ``generate_cached`` refuses.  ``note_rules`` / ``max_polyphony``: as in
         ``generate_cached`` -- the budget's mask and account run first, the notes' second; an ended row steps on pad_token,
         whose rule is 0, so its held set stays what it was when the row ended.  ``repetition``: as in ``generate_cached`` --
-        after the budget's mask, before the notes' first draw; ``probs`` are then those of the penalised logits."""
+        after the budget's mask, before the notes' first draw; ``probs`` are then those of the penalised logits.
+        ``class_sampling``: as in ``generate_cached`` -- after the budget's mask and the penalty; a masked id stays masked, so
+        no row overshoots; ``probs`` are then softmax(bf16(ln p'))."""
         return decode.generate_timed(self, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed,
                                      use_graph, grammar, prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules,
-                                     max_polyphony, repetition)
+                                     max_polyphony, repetition, class_sampling)
 
     @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,

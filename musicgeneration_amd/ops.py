@@ -907,6 +907,40 @@ def repeat_penalty(logits, V, out_tokens, pos_dev, subject, pen, window, ngram=0
     return logits
 
 
+# ---- per-class sampling on the decode path (ABI 33; contract in include/mgx.h) ---------------------------------------
+CLASS_MAX = _lib.DEFINES["MGX_CLASS_MAX"]
+
+
+def class_logits(logits, V, cls, inv_temp, top_k, top_p, temperature, tok=None, allow_table=None):
+    """in place, before the sampler: every row of logits bf16 [B, ld] becomes bf16(ln p') over its ids v < V, -inf where p' is 0 --
+    p' keeps every class's total probability at ``temperature`` and gives the ids inside class c the softmax at inv_temp[c],
+    filtered by top_k[c] / top_p[c] (the sampler's rules).  cls int32 [>= V], the class of every id; inv_temp float32, top_k
+    int32, top_p float32 [C] each, on the device.  tok int32 [B] and allow_table [V, ceil(V/32)]: the sampler's grammar and
+    the rows' input tokens, both or neither.  The sampler then runs at temperature 1"""
+    ld = logits.shape[-1]
+    B = logits.numel() // ld
+    _need_cuda(logits, cls, inv_temp, top_k, top_p, tok, allow_table)
+    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
+        raise ValueError(f"class_logits: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    if cls.dtype != torch.int32 or cls.dim() != 1 or cls.numel() < int(V) or not cls.is_contiguous():
+        raise ValueError(f"class_logits: cls must be a contiguous int32 tensor of at least V = {V} entries, got {cls.dtype} "
+                         f"{tuple(cls.shape)}")
+    C = inv_temp.numel()
+    for name, t, dt in (("inv_temp", inv_temp, torch.float32), ("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32)):
+        if t.dtype != dt or t.dim() != 1 or t.numel() != C or not t.is_contiguous():
+            raise ValueError(f"class_logits: {name} must be a contiguous {dt} tensor of C = {C} entries, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    if (tok is None) != (allow_table is None):
+        raise ValueError("class_logits: tok and allow_table are given together or not at all")
+    if tok is not None:
+        _check_allow_table(allow_table, V)
+        if tok.dtype != torch.int32 or tok.numel() != B or not tok.is_contiguous():
+            raise ValueError(f"class_logits: tok must be a contiguous int32 tensor of {B} entries, got {tok.dtype} {tuple(tok.shape)}")
+    check(_lib.load().mgx_class_logits(ptr(logits), int(V), ld, ptr(cls), C, ptr(inv_temp), ptr(top_k), ptr(top_p),
+                                       float(temperature), ptr(tok), ptr(allow_table), B, stream_ptr()), "mgx_class_logits")
+    return logits
+
+
 # ---- draft and verify on the decode path (ABI 32; contracts in include/mgx.h) ----------------------------------------
 LOOKAHEAD_MAX_T = _lib.DEFINES["MGX_LOOKAHEAD_MAX_T"]
 LOOKAHEAD_MAX_NGRAM = _lib.DEFINES["MGX_LOOKAHEAD_MAX_NGRAM"]

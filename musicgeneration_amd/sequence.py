@@ -178,6 +178,12 @@ class EventSeq:
         return _vocab.repeat_subject(EventSeq.dim(), EventSeq.feat_ranges()['note_on'], vocab_size)
 
     @staticmethod
+    def event_classes(vocab_size=None):
+        """the classes of ``decode.ClassSampling``: (names, classes int32 [vocab_size]) -- the features of ``feat_ranges()`` in id
+        order, one class each, and a last class 'other' for the ids a model adds beyond dim() (its pad id)"""
+        return _vocab.event_classes(EventSeq.feat_ranges(), vocab_size)
+
+    @staticmethod
     def transpose_table(offsets, vocab_size=None):
         """what every id becomes under a transposition, int32 [len(offsets), vocab_size]: row s moves the note_on and the
         note_off of key k to key k + offsets[s] (|offset| <= 11), a key that would leave the range coming back by an octave --
