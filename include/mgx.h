@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM; 32: draft-and-verify decode: mgx_lookahead_draft, mgx_rel_attn_decode_multi (with _splits and _workspace), mgx_lookahead_accept, MGX_LOOKAHEAD_MAX_T, MGX_LOOKAHEAD_MAX_NGRAM; 33: per-class temperature, top-k and top-p on the KV-cache decode: mgx_class_logits, MGX_CLASS_MAX */
-#define MGX_ABI_VERSION 33
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM; 32: draft-and-verify decode: mgx_lookahead_draft, mgx_rel_attn_decode_multi (with _splits and _workspace), mgx_lookahead_accept, MGX_LOOKAHEAD_MAX_T, MGX_LOOKAHEAD_MAX_NGRAM; 33: per-class temperature, top-k and top-p on the KV-cache decode: mgx_class_logits, MGX_CLASS_MAX; 34: entropy-aware sampling on the KV-cache decode (min-p, typical, Mirostat v2): mgx_entropy_mask, mgx_entropy_account */
+#define MGX_ABI_VERSION 34
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -674,6 +674,55 @@ int mgx_lookahead_accept(const uint16_t* logits, int V, int ld, float temperatur
 #define MGX_CLASS_MAX 16
 int mgx_class_logits(uint16_t* logits, int V, int ld, const int32_t* cls, int C, const float* inv_temp, const int32_t* top_k,
                      const float* top_p, float temperature, const int32_t* tok, const uint32_t* allow_table, int B, void* stream);
+
+/* ---- Entropy-aware sampling (ABI 34): min-p, locally typical sampling and Mirostat v2 on the KV-cache decode (the sampling step of
+ * network.py:52-77, which has a temperature alone) -- three cuts that follow the row's own uncertainty instead of falling at a
+ * fixed place.  Two calls bracket the sampler, as the budget's do; both are captured with the step.
+ * A step is: logits, (mgx_budget_mask,) (mgx_repeat_penalty,) (mgx_class_logits,) mgx_entropy_mask, the sampler or
+ * mgx_lookahead_accept, (mgx_entropy_account,) (mgx_budget_account).  The mask and the account take the SAMPLER's temperature:
+ * 1 after mgx_class_logits.  Not combined with the two draws of the note rules (mgx_notes_mask).
+ * mgx_entropy_mask, in place on the step's logits bf16 [B,ld] before the sampler.  A PURE MASK: it writes -inf (0xFF80) and nothing
+ *   else; every kept id, every column >= V and every id outside the live set stay bit for bit, and the sampler then runs at the
+ *   call's own temperature with its own top-k / top-p.  tok int32 [B] and allow_table uint32 [V, ceil(V/32)] (both or neither):
+ *   the sampler's grammar, whose previous token is tok[b] (clamped to 0 .. V-1); under draft and verify tok is the draft.
+ *   For row b, with z_v = f32(logits[b,v]) * (1 / temperature), the sampler's arithmetic:
+ *   Live ids:  A as in mgx_class_logits -- {v < V: z_v > -inf, and bit v of the grammar row of tok[b] is set, if there is a
+ *     table}; a table under which A is empty is ignored for the row.  If A is still empty the row is left bit for bit and
+ *     lse_out[b] = 0.  NaN: unspecified.
+ *   lse = ln sum_A e^z, ln p_v = z_v - lse.  lse_out f32 [B] (may be NULL) receives lse.
+ *   Three stages, each on the survivors of the one before:
+ *   1. Mirostat cut (mu != NULL; f32 [B], read only):  S1 = {v in A: -ln p_v / ln 2 <= mu[b]}; if that is empty,
+ *      S1 = {v in A: z_v = max_A z}.
+ *   2. min-p (min_p > 0):  S2 = {v in S1: z_v - max_{S1} z >= ln(min_p)}.  A ratio to the maximum does not change under
+ *      renormalisation, so its place in the order does not matter.
+ *   3. Typical (typical_p < 1):  q = p renormalised over S2, H = -sum q ln q, d_v = |-ln q_v - H|, delta = the smallest value with
+ *      mass_q{d <= delta} >= typical_p (of the mass as the kernel sums it), S3 = {v in S2: d_v <= delta}.  delta is found by exact
+ *      bisection on the bit patterns of d, as the sampler finds its thresholds: ids whose d the kernel computes equal -- ids of
+ *      equal logits among them -- stay together.
+ *   The stages are sequential on purpose: computed on one common p, typical and min-p can have an empty intersection
+ *   (p = (0.4, 0.06 x 10), min_p 0.2, typical_p 0.5).  Every v in A \ S3 becomes -inf; S3 is never empty.
+ *   With mu == NULL, min_p == 0 and typical_p == 1 the call is legal and writes only lse_out.
+ * MGX_ERR_NULL for a NULL logits, or exactly one of tok / allow_table NULL.  MGX_ERR_SHAPE unless B > 0, 0 < V <= 1024, ld >= V,
+ *   temperature finite and > 0, 0 <= min_p < 1, 0 < typical_p <= 1.
+ * One wave per row; ids lane + 64 i, 16 per lane, as in the sampler.  The grid is a function of B only (no host read, no
+ * allocation); plain loads and vector stores, no LDS, no atomics.
+ * mgx_entropy_account, after the sampler and its advance and BEFORE mgx_budget_account (which may replace the token by a pad).
+ *   logits bf16 [B,ld] are the step's, as the mask left them; lse f32 [B] is the mask's lse_out.  For row b:
+ *   s = (lse[b] - f32(logits[b,next_tok[b]]) * (1 / temperature)) / ln 2, the surprise in bits of the token that was drawn under
+ *   the row's distribution BEFORE the mask (the kept logits are still there bit for bit).
+ *   mu != NULL (f32 [B]):  mu[b] <- mu[b] - eta * (s - tau), every operation rounded to f32 on its own.
+ *   surprise_out f32 [B,out_ld] (may be NULL) receives s at column col = base + t ("Step positions", K12), t as it stands AFTER the
+ *   advance: the column the sampler has just written, as in mgx_budget_account.
+ *   Nothing is written for a row whose next_tok lies outside 0 .. V-1, whose logit there is not finite, or -- with surprise_out --
+ *   whose column lies outside 0 .. out_ld-1.
+ * MGX_ERR_NULL for a NULL next_tok, logits, lse or pos_dev.  MGX_ERR_SHAPE unless B > 0, V > 0, ld >= V, temperature finite and
+ *   > 0, out_ld > 0 where surprise_out is given, tau and eta finite where mu is given.
+ * One thread per row; no atomics.                                                                                          */
+int mgx_entropy_mask(uint16_t* logits, int V, int ld, float temperature, float min_p, float typical_p, const float* mu,
+                     float* lse_out, const int32_t* tok, const uint32_t* allow_table, int B, void* stream);
+int mgx_entropy_account(const int32_t* next_tok, const uint16_t* logits, int V, int ld, float temperature, const float* lse,
+                        float* mu, float tau, float eta, float* surprise_out, int out_ld, const int32_t* pos_dev,
+                        const int32_t* base_dev, int per_row, int B, void* stream);
 
 /* ---- K13: Event_Melody_RNN step (Event_MelodyRNN/network.py:51-61): the GRU projections run on
  * mgx_linear_fwd; these two kernels are the rest of a step.

@@ -24,7 +24,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libmgx.so")
 SOURCES = ["api.cpp", "rowwise_ops.hip", "rel_attn_fwd.hip", "rel_attn_bwd.hip", "rel_attn_dkv32.hip", "rel_attn_dkv64.hip", "rel_attn_dq_lite.hip",
            "rel_attn_de_tiles.hip", "rel_attn_bwd_recompute.hip", "linear.hip", "linear_tile128.hip", "linear_ring.hip", "linear_skinny.hip",
-           "decode.hip", "lookahead.hip", "beam.hip", "budget.hip", "notes.hip", "repeat.hip", "class_logits.hip", "score.hip", "gru_train.hip", "augment.hip"]
+           "decode.hip", "lookahead.hip", "beam.hip", "budget.hip", "notes.hip", "repeat.hip", "class_logits.hip", "entropy.hip", "score.hip", "gru_train.hip", "augment.hip"]
 EXPERIMENT_DIR = os.path.join(ROOT, "tools", "experiments")
 EXPERIMENT_SOURCES = ["rel_attn_fwd2.hip", "rel_attn_fwd3.hip", "rel_attn_fwd64.hip"]      # --experiments builds only
 # per-file flags.  The 64-rows-per-wave attention kernels run one wave per SIMD with the whole 512-entry register file:

@@ -17,7 +17,9 @@ notes every row holds (ops.notes_mask / ops.notes_account), which keeps a MIDI-l
 (``repetition=``) is not a state: one launch before the sampler (ops.repeat_penalty) reads the row's own columns of the output
 matrix and penalises repeated ids and n-grams by finite amounts.  ``ClassSampling`` (``class_sampling=``) is the last launch
 before the sampler (ops.class_logits): a temperature, top-k and top-p per class of ids, written back as ln p' so the sampler,
-at temperature 1, is unchanged.  ``generate_lookahead`` (generate_cached(lookahead=T)) is draft
+at temperature 1, is unchanged.  ``EntropySampling`` (``entropy_sampling=``) brackets the sampler as a ``Budget`` does: a pure
+mask last before it (ops.entropy_mask: the Mirostat cut, min-p, typical) and, with a threshold to move or a trace to file, an
+account after it (ops.entropy_account); its per-row state is one float.  ``generate_lookahead`` (generate_cached(lookahead=T)) is draft
 and verify: the same step on B * T rows, T consecutive positions of every row on guessed inputs (ops.lookahead_draft), whose
 attention is ops.rel_attn_decode_multi behind a ``LookaheadCache`` and whose sampler is ops.lookahead_accept; a ``DonePoll`` --
 what a ``Budget`` is to the step loop -- stops it once every row holds its last token."""
@@ -745,13 +747,102 @@ def check_class_args(model, class_sampling, temperature, *, groups=None, masked_
     return None if own.inert else own
 
 
+class EntropySampling:
+    """entropy-aware sampling of generate_cached / generate_timed (include/mgx.h, ABI 34): three cuts that follow the row's own
+    uncertainty.  ``min_p`` (0: off) keeps the ids with at least that share of the most likely id's probability; ``typical_p``
+    (1: off) keeps the ids whose surprise lies closest to the row's entropy, up to that mass; ``tau`` (None: off) is Mirostat v2,
+    a feedback loop per row that holds the surprise of what is drawn near ``tau`` bits: ids more surprising than the row's
+    threshold ``mu`` are cut, and after every draw mu -= eta * (surprise - tau).  The stages run in that order -- Mirostat, min-p,
+    typical -- each on the survivors of the one before, as a pure mask ahead of the unchanged sampler (ops.entropy_mask);
+    ops.entropy_account follows it.  ``trace``: keep every drawn token's surprise in bits.
+
+    The per-row state, on the device, after a call: ``mu`` float32 [rows] (started at 2 tau, Mirostat's convention; None without
+    ``tau``), ``lse`` float32 [rows] (the last step's log-sum-exp) and, with ``trace``, ``surprise`` float32 [rows, total], NaN
+    where nothing was generated.  A call works on a checked copy (check_entropy_args) and hands these three back to the
+    caller's object"""
+
+    def __init__(self, min_p=0.0, typical_p=1.0, tau=None, eta=0.1, trace=False):
+        self.min_p, self.typical_p, self.tau, self.eta, self.trace = min_p, typical_p, tau, eta, trace
+        self.mu = self.lse = self.surprise = None
+
+    @property
+    def inert(self) -> bool:
+        """no cut, no loop and no trace: the step is the unchanged decode_step"""
+        return self.min_p == 0 and self.typical_p == 1 and self.tau is None and not self.trace
+
+    @property
+    def accounting(self) -> bool:
+        """does the step need ops.entropy_account -- a threshold to move or a surprise to file?"""
+        return self.tau is not None or bool(self.trace)
+
+    def stage(self, dev, rows: int, total: int) -> "EntropySampling":
+        """the state of ``rows`` rows and ``total`` output columns on the device, once per call"""
+        self.lse = torch.zeros(rows, dtype=torch.float32, device=dev) if self.accounting else None
+        self.mu = None if self.tau is None else torch.full((rows,), 2.0 * self.tau, dtype=torch.float32, device=dev)
+        self.surprise = torch.full((rows, total), float("nan"), dtype=torch.float32, device=dev) if self.trace else None
+        return self
+
+    def mask(self, logits, V: int, r: "SubBatch", temperature: float, allow_table) -> None:
+        ops.entropy_mask(logits, V, temperature, self.min_p, self.typical_p, mu=self.mu, lse_out=self.lse,
+                         tok=None if allow_table is None else r.tok, allow_table=allow_table)
+
+    def account(self, logits, V: int, r: "SubBatch", temperature: float) -> None:
+        ops.entropy_account(r.tok, logits, V, temperature, self.lse, mu=self.mu, tau=self.tau or 0.0, eta=self.eta,
+                            surprise_out=self.surprise, **r.step)
+
+    def hand_back(self, to: "EntropySampling") -> None:
+        """the state after the call, for the caller to read"""
+        to.mu, to.lse, to.surprise = self.mu, self.lse, self.surprise
+
+
+def check_entropy_args(model, entropy_sampling, temperature, *, groups=None, masked_groups=False, note_rules=None,
+                       max_polyphony=None, lookahead=None):
+    """every refusal of ``entropy_sampling`` (ValueError), on the host before any device work.  Returns an EntropySampling of its
+    own -- plain floats, not yet staged -- so the caller's object serves any number of calls and receives the state only once the
+    call is over; or None: no ``entropy_sampling``, or an inert one"""
+    if entropy_sampling is None:
+        return None
+    if not isinstance(entropy_sampling, EntropySampling):
+        raise ValueError(f"entropy_sampling must be a decode.EntropySampling (or None), got {type(entropy_sampling).__name__}")
+
+    def number(v):
+        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
+    if not number(temperature) or temperature <= 0:
+        raise ValueError(f"entropy_sampling: the call's temperature must be a finite number > 0, got {temperature!r}")
+    es = entropy_sampling
+    if not number(es.min_p) or not 0 <= es.min_p < 1:
+        raise ValueError(f"entropy_sampling: min_p must be a number in [0, 1) (0: off), got {es.min_p!r}")
+    if not number(es.typical_p) or not 0 < es.typical_p <= 1:
+        raise ValueError(f"entropy_sampling: typical_p must be a number in (0, 1] (1: off), got {es.typical_p!r}")
+    if es.tau is not None and (not number(es.tau) or es.tau <= 0):
+        raise ValueError(f"entropy_sampling: tau must be a finite number of bits > 0 (None: no Mirostat), got {es.tau!r}")
+    if not number(es.eta) or not 0 < es.eta <= 1:
+        raise ValueError(f"entropy_sampling: eta must be a number in (0, 1] (the loop's learning rate), got {es.eta!r}")
+    if not isinstance(es.trace, (bool, np.bool_)):
+        raise ValueError(f"entropy_sampling: trace must be True or False, got {es.trace!r}")
+    if (groups or 1) > 1 or masked_groups:
+        raise ValueError("entropy_sampling is not combined with groups / masked_groups (experiment flags: the per-row state covers "
+                         "the batch as one group): later work")
+    if note_rules is not None or max_polyphony is not None:
+        raise ValueError("entropy_sampling is not combined with note_rules / max_polyphony (that step draws twice, from the logits "
+                         "as they stand and from the masked ones, and one mask and one account cannot serve both draws): later work")
+    if lookahead is not None and (es.tau is not None or es.trace):
+        raise ValueError("lookahead takes entropy_sampling's min_p and typical_p only, not tau / trace (the Mirostat state is "
+                         "sequential: the cut at position i + 1 depends on the token drawn at i): later work")
+    own = EntropySampling(float(es.min_p), float(es.typical_p), None if es.tau is None else float(es.tau), float(es.eta),
+                          bool(es.trace))
+    return None if own.inert else own
+
+
 def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool, bud: Optional[Budget],
-                            notes: Optional[NoteState], rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None) -> None:
-    """decode_step under the rows' budgets, repetition control, per-class sampling and / or held notes: the logits are masked,
-    penalised and rewritten before the sampler sees them, and the draw is charged to the clock and applied to the notes after it
-    (the order: include/mgx.h, ABI 31 and 33).  With ``notes`` the step draws twice (below); the penalty comes before the first
-    draw, which notes_keep would otherwise let stand unpenalised.  ``cs`` (never with ``notes``) leaves ln p' in the logits, so
-    the sampler runs at temperature 1"""
+                            notes: Optional[NoteState], rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None,
+                            es: Optional[EntropySampling] = None) -> None:
+    """decode_step under the rows' budgets, repetition control, per-class sampling, entropy-aware sampling and / or held notes: the
+    logits are masked, penalised and rewritten before the sampler sees them, and the draw is charged to the clock and applied to
+    the notes after it (the order: include/mgx.h, ABI 31, 33 and 34).  With ``notes`` the step draws twice (below); the penalty
+    comes before the first draw, which notes_keep would otherwise let stand unpenalised.  ``cs`` (never with ``notes``) leaves
+    ln p' in the logits, so the sampler runs at temperature 1.  ``es`` (never with ``notes``) masks last, at the sampler's
+    temperature, and accounts for the draw before the budget can replace it by a pad"""
     logits = step_logits(w, r)
     if bud is not None:
         ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
@@ -760,6 +851,8 @@ def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, sample_into_
     if cs is not None:
         cs.apply(logits, w.V, r, sampler["temperature"], sampler["allow_table"])
         sampler = dict(sampler, temperature=1.0)
+    if es is not None:
+        es.mask(logits, w.V, r, sampler["temperature"], sampler["allow_table"])
     out = r.out if sample_into_out else None
     if notes is not None:
         # the sampler draws by inverse CDF, so a draw from the masked logits is another token even where the unmasked draw of
@@ -772,6 +865,8 @@ def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, sample_into_
     ops.sample_topk_topp(logits, w.V, next_tok=r.tok, out_tokens=out, probs_out=r.probs, advance=True, row0=r.b0, **r.step, **sampler)
     if notes is not None:
         ops.notes_keep(notes.first, r.tok, out, rule=notes.rule, state=notes.state, max_on=notes.max_on, V=w.V, **r.step)
+    if es is not None and es.accounting:
+        es.account(logits, w.V, r, sampler["temperature"])
     if bud is not None:
         ops.budget_account(r.tok, r.out, cost=bud.cost, remaining=bud.remaining, done=bud.done, count=bud.count,
                            pad_token=bud.pad_token, inclusive=bud.inclusive, **r.step)
@@ -907,11 +1002,13 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
 def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
                     return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None,
                     bud: Optional[Budget] = None, note_rules=None, max_polyphony=None, repetition=None, lookahead=None,
-                    draft="history", draft_ngram=3, stats=None, class_sampling=None):
+                    draft="history", draft_ngram=3, stats=None, class_sampling=None, entropy_sampling=None):
     """MusicTransformer.generate_cached (documented there).  ``bud``: generate_timed's budgets, not yet staged -- the steps run
     decode_step_constrained and the loop stops once every row has ended"""
     cs = check_class_args(model, class_sampling, temperature, groups=groups, masked_groups=masked_groups, note_rules=note_rules,
                           max_polyphony=max_polyphony)
+    es = check_entropy_args(model, entropy_sampling, temperature, groups=groups, masked_groups=masked_groups, note_rules=note_rules,
+                            max_polyphony=max_polyphony, lookahead=lookahead)
     if lookahead is not None:
         T, guide = check_lookahead_args(model, prior, lookahead, draft, draft_ngram, window=window, hop=hop, kv_cache=kv_cache,
                                         samples_per_prompt=samples_per_prompt, groups=groups, masked_groups=masked_groups,
@@ -920,7 +1017,7 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
         P, lens, _, _ = check_args(model, prior, length, False, "batched", prior_lengths, kv_cache)
         return generate_lookahead(model, prior, P, lens, length, T, guide, int(draft_ngram),
                                   dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), grammar, use_graph,
-                                  return_probs, stats, cs)
+                                  return_probs, stats, cs, es)
     rep = check_repeat_args(model, repetition, groups=groups, masked_groups=masked_groups)
     notes = check_note_args(model, note_rules, max_polyphony, grammar=grammar, groups=groups, masked_groups=masked_groups,
                             return_cache=return_cache)
@@ -928,8 +1025,11 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
                                        masked_groups, samples_per_prompt, return_cache)
     sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     if samples_per_prompt is not None:
-        return generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs,
-                               notes, rep, cs)
+        res = generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs,
+                              notes, rep, cs, es)
+        if es is not None:
+            es.hand_back(entropy_sampling)
+        return res
     extra, prior, ragged = prior.shape[1] - P, prior[:, :P], lens is not None      # extra > 0: equal prior_lengths below the width
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -973,10 +1073,12 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
             rep.stage(dev)
         if cs is not None:
             cs.stage(dev)
+        if es is not None:
+            es.stage(dev, B, total)
 
         def step_rows(r):                                     # length 0 still runs the last prompt token (its distribution)
-            if bud is not None or notes is not None or rep is not None or cs is not None:
-                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes, rep, cs)
+            if bud is not None or notes is not None or rep is not None or cs is not None or es is not None:
+                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes, rep, cs, es)
             else:
                 decode_step(w, r, sampler, length > 0)
         if window is not None:
@@ -1001,19 +1103,25 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     pad = torch.nn.functional.pad                         # equal prior_lengths P < Pmax: pad_token / zeros up to Pmax + length
     toks = pad(out, (0, extra), value=model.pad_token) if extra else out
     res = (toks, pad(probs_all, (0, 0, 0, extra)) if extra else probs_all) if return_probs else toks
+    if es is not None:
+        if es.surprise is not None and extra:
+            es.surprise = pad(es.surprise, (0, extra), value=float("nan"))
+        es.hand_back(entropy_sampling)
     if window is not None:                                # the cache grows to the rows the full-width call would have
         extra = min(window, total + extra) - cache_rows
     return (res, *(cache.grow(extra) if extra else cache).result()) if return_cache else res
 
 
 def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, grammar, use_graph: bool, return_probs: bool,
-                    notes: Optional[NoteState] = None, rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None):
+                    notes: Optional[NoteState] = None, rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None,
+                    es: Optional[EntropySampling] = None):
     """generate_cached(samples_per_prompt=N), its arguments checked: rows r = b * N + n, sample n of prompt b.  One batched
     prefill of the Bp prompts fills the prompt cache (pre_rows = len_b - 1 rows each); every row then resumes at its prompt's
     last token and runs the ragged step on R = Bp * N rows, whose attention reads the prompt's rows once for the samples of a
     prompt and appends to the row's own cache.  Row r draws with (seed, t, r), as it does in the call on the prompts repeated N
     times.  ``notes``: a NoteState, not yet staged -- every row starts from its prompt's held notes.  ``rep``: a checked Repetition, not
-    yet staged -- stateless, so the samples of a prompt need nothing gathered.  ``cs``: a checked ClassSampling, likewise"""
+    yet staged -- stateless, so the samples of a prompt need nothing gathered.  ``cs``: a checked ClassSampling, likewise.  ``es``: a
+    checked EntropySampling, not yet staged -- every row, sample n of prompt b, carries a Mirostat threshold of its own"""
     with decode_session(model) as st:
         (Bp, P), dev = prior.shape, st.param.device
         R, total, d, V = Bp * N, P + length, model.embedding_dim, model.vocab_size
@@ -1034,10 +1142,12 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
             rep.stage(dev)
         if cs is not None:
             cs.stage(dev)
+        if es is not None:
+            es.stage(dev, R, total)
 
         def step_rows(r_):                                    # length 0 still runs the last prompt token (its distribution)
-            if notes is not None or rep is not None or cs is not None:
-                decode_step_constrained(w, r_, sampler, length > 0, None, notes, rep, cs)
+            if notes is not None or rep is not None or cs is not None or es is not None:
+                decode_step_constrained(w, r_, sampler, length > 0, None, notes, rep, cs, es)
             else:
                 decode_step(w, r_, sampler, length > 0)
         run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=file)
@@ -1099,7 +1209,7 @@ class LookaheadCache:
 
 
 def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, ngram: int, sampling: dict, grammar, use_graph: bool,
-                       return_probs: bool, stats, cs: Optional[ClassSampling] = None):
+                       return_probs: bool, stats, cs: Optional[ClassSampling] = None, es: Optional[EntropySampling] = None):
     """generate_cached(lookahead=T), its arguments checked.  A step of the B rows is the ragged step on B * T rows: row b * T + i
     runs position t_b + i on draft[b, i] (ops.lookahead_draft), the attention is ops.rel_attn_decode_multi, and
     ops.lookahead_accept draws every position as the one-token call draws it -- (seed, column, b) -- keeps the prefix whose
@@ -1107,7 +1217,9 @@ def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, n
     row's new position and is rewritten by the next step before any query reaches it.  The step is captured once and replayed
     in runs of LOOKAHEAD_POLL; a row at its last column sets its ``done`` flag and the loop stops when all have, after at most
     ``length`` steps.  ``cs``: a checked ClassSampling, not yet staged -- row-wise and stateless, it rewrites the B * T rows' logits
-    (the grammar row of row b * T + i is that of draft[b, i]) and the accept draws at temperature 1"""
+    (the grammar row of row b * T + i is that of draft[b, i]) and the accept draws at temperature 1.  ``es``: a checked
+    EntropySampling without tau and trace (check_entropy_args) -- min-p and typical are row-wise and stateless too, a mask on the
+    B * T rows after ``cs`` at the accept's temperature"""
     extra, prior = prior.shape[1] - P, prior[:, :P]
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -1130,17 +1242,21 @@ def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, n
                            ops.rel_attn_decode_multi_workspace(B, T, total, d, dev), d)
         sampler = dict(sampling, allow_table=ops.grammar_table(grammar, dev))
 
+        accept = sampler
         if cs is not None:
             cs.stage(dev)
-            warped = dict(sampler, temperature=1.0)
+            accept = dict(sampler, temperature=1.0)
+        if es is not None:
+            es.stage(dev, B * T, total)
 
         def step_rows(r_):
             ops.lookahead_draft(tok, out, pos, draft, pos_rows, total, model.pad_token, guide=guide, ngram=ngram)
             logits = step_logits(w, r_)
             if cs is not None:
                 cs.apply(logits, V, r_, sampler["temperature"], sampler["allow_table"])
-            ops.lookahead_accept(logits, V, pos, draft, limit, tok, out, poll.done, probs_all=probs_all, stats=count,
-                                 **(sampler if cs is None else warped))
+            if es is not None:
+                es.mask(logits, V, r_, accept["temperature"], sampler["allow_table"])
+            ops.lookahead_accept(logits, V, pos, draft, limit, tok, out, poll.done, probs_all=probs_all, stats=count, **accept)
         if length > 0:
             run_steps([r], length, step_rows, graph=use_graph, budget=poll)
         if stats is not None:
@@ -1153,22 +1269,25 @@ def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, n
 
 def generate_timed(model, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,
                    prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules=None, max_polyphony=None, repetition=None,
-                   class_sampling=None):
+                   class_sampling=None, entropy_sampling=None):
     """MusicTransformer.generate_timed (documented there): generate_cached's driver with a Budget"""
     B = prior.shape[0]
     check_repeat_args(model, repetition)
     check_class_args(model, class_sampling, temperature, note_rules=note_rules, max_polyphony=max_polyphony)
+    es = check_entropy_args(model, entropy_sampling, temperature, note_rules=note_rules, max_polyphony=max_polyphony)
     budgets, cost_i = check_budget_args(model, B, budget, cost, max_length, poll, refused)
     check_args(model, prior, max_length, return_probs, "auto", prior_lengths, kv_cache, window, hop)     # before any device work
     bud = Budget(budgets, cost_i, model.pad_token, bool(inclusive), int(poll))
     res = generate_cached(model, prior, max_length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, "auto",
                           False, None, False, prior_lengths, kv_cache, window, hop, None, bud, note_rules, max_polyphony, repetition,
-                          class_sampling=class_sampling)
+                          class_sampling=class_sampling, entropy_sampling=entropy_sampling)
     tokens, probs = res if return_probs else (res, None)
     # what every row spent: the cost of the events it kept, columns P_b .. P_b + count_b - 1
     start = torch.tensor(_prompt_lengths(prior, prior_lengths) or [prior.shape[1]] * B, device=tokens.device)[:, None]
     cols = torch.arange(tokens.shape[1], device=tokens.device)[None, :]
     kept = (cols >= start) & (cols < start + bud.count[:, None])
+    if es is not None and es.trace:                       # an ended row went on stepping on pads: nothing generated
+        entropy_sampling.surprise.masked_fill_(~kept, float("nan"))
     spent = torch.where(kept, bud.cost[tokens.long()], 0).sum(1)
     info = dict(steps_run=bud.steps_run, spent=spent, remaining=bud.remaining, done=bud.done.bool())
     if return_probs:

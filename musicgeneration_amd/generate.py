@@ -110,6 +110,18 @@ def get_options(argv=None):
                       help='NAME=K,...: the events of class NAME come from the K most likely of that class (e.g. velocity=4)')
     parser.add_option('--class-top-p', dest='class_top_p', type='string', default=None,
                       help='NAME=P,...: the events of class NAME come from the nucleus of mass P of that class (e.g. chord=0.9)')
+    parser.add_option('--min-p', dest='min_p', type='float', default=0.0,
+                      help='entropy-aware sampling (KV-cache decode): keep the events with at least this share of the most likely '
+                           "event's probability (0 .. 1; 0 = off) -- a cut that widens where the model is unsure and narrows where "
+                           'it is certain.  With --best-of the candidates are ranked by the model\'s own score')
+    parser.add_option('--typical-p', dest='typical_p', type='float', default=1.0,
+                      help="locally typical sampling: keep the events whose surprise lies closest to the step's entropy, up to this "
+                           'mass (0 .. 1; 1 = off)')
+    parser.add_option('--mirostat', dest='mirostat', type='float', default=None,
+                      help='Mirostat v2: hold the surprise of the sampled events near TAU bits with a feedback loop per sample '
+                           '(e.g. 3; not with --lookahead)')
+    parser.add_option('--mirostat-eta', dest='mirostat_eta', type='float', default=None,
+                      help="with --mirostat: the loop's learning rate (0 .. 1; default 0.1)")
     return parser.parse_args(argv)[0]
 
 
@@ -305,6 +317,39 @@ def _class_args(o, mt, classes):
     return dict(class_sampling=ClassSampling(_codec(o).event_classes(mt.vocab_size)[1], *classes))
 
 
+def _check_entropy(o, well):
+    """--min-p / --typical-p / --mirostat / --mirostat-eta against the options they do not go with and their own ranges, before
+    any model or device work.  Returns the keyword argument of generate_cached / generate_timed they set ({} without a flag)"""
+    given = [f for f, on in (('--min-p', o.min_p != 0), ('--typical-p', o.typical_p != 1), ('--mirostat', o.mirostat is not None))
+             if on]
+    if not given:
+        if o.mirostat_eta is not None:
+            raise SystemExit("--mirostat-eta is the learning rate of --mirostat's loop: add --mirostat TAU")
+        return {}
+    for on, what, why in ((o.beam_size, '-B/--beam-size', 'a search ranks whole beams by likelihood: not built'),
+                          (o.reference_mask, '--reference-mask', 'the KV-cache decode is causal'),
+                          (well, '--well-formed / --max-polyphony', 'that step draws twice and one mask cannot serve both draws: '
+                                                                    'later work')):
+        if on:
+            raise SystemExit(f'{given[0]} cannot be combined with {what} ({why})')
+    if not (np.isfinite(o.min_p) and 0 <= o.min_p < 1):
+        raise SystemExit(f'--min-p must lie in 0 .. 1 (0 = off, 1 excluded), got {o.min_p}')
+    if not (np.isfinite(o.typical_p) and 0 < o.typical_p <= 1):
+        raise SystemExit(f'--typical-p must lie in 0 .. 1 (1 = off, 0 excluded), got {o.typical_p}')
+    if o.mirostat is None and o.mirostat_eta is not None:
+        raise SystemExit("--mirostat-eta is the learning rate of --mirostat's loop: add --mirostat TAU")
+    if o.mirostat is not None:
+        if not (np.isfinite(o.mirostat) and o.mirostat > 0):
+            raise SystemExit(f'--mirostat must be a number of bits > 0, got {o.mirostat}')
+        if o.mirostat_eta is not None and not (np.isfinite(o.mirostat_eta) and 0 < o.mirostat_eta <= 1):
+            raise SystemExit(f'--mirostat-eta must lie in 0 .. 1 (0 excluded), got {o.mirostat_eta}')
+        if o.lookahead:
+            raise SystemExit('--mirostat cannot be combined with --lookahead (the loop is sequential: the cut of an event depends '
+                             'on the event drawn before it: later work)')
+    from .decode import EntropySampling
+    return dict(entropy_sampling=EntropySampling(o.min_p, o.typical_p, o.mirostat, 0.1 if o.mirostat_eta is None else o.mirostat_eta))
+
+
 def _repeat_args(o, mt):
     """the keyword argument of generate_cached / generate_timed that the repetition flags set"""
     from .decode import Repetition
@@ -395,12 +440,13 @@ def main(argv=None):
     repeat = _check_repeat(o)
     _check_lookahead(o, timed, well, repeat)
     classes = _check_class(o, well)
+    entropy = _check_entropy(o, well)
     if o.hop and not o.window:
         raise SystemExit('--hop is the stride of --window: add --window W')
     if o.window and o.reference_mask:
         raise SystemExit('--reference-mask cannot be combined with --window (the KV-cache decode is causal)')
     if o.kv_cache != 'bf16' and not (o.grammar or o.condition_files is not None or o.window or o.beam_size or timed or well
-                                     or repeat or classes):
+                                     or repeat or classes or entropy):
         raise SystemExit(f'--kv-cache {o.kv_cache} applies to the KV-cache decode only: add --grammar or --condition-files '
                          '(or -B K; the default sampler recomputes the window and keeps no cache)')
     # with --window every branch below samples through the KV-cache decode and its re-anchored window
@@ -432,6 +478,7 @@ def main(argv=None):
         notes.update(_repeat_args(o, mt))
     if classes:                                           # and with the --class-* flags
         notes.update(_class_args(o, mt, classes))
+    notes.update(entropy)                                 # and with --min-p / --typical-p / --mirostat
 
     def search(prior, **kw):                              # -B: the best beam of every sample
         res, scores = mt.generate_beam(prior, o.max_len, o.beam_size, temperature=o.temperature, stochastic=o.stochastic_beam_search,
@@ -501,7 +548,7 @@ def main(argv=None):
     elif o.share_prompt:                                   # -c FILE: one prompt, -b x --best-of samples
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p,
                                  samples_per_prompt=rows, **notes).cpu().numpy()
-    elif o.window or well or repeat or o.lookahead or classes:
+    elif o.window or well or repeat or o.lookahead or classes or entropy:
         res = mt.generate_cached(prior, o.max_len, temperature=o.temperature, top_k=o.top_k, top_p=o.top_p, **cached,
                                  **notes).cpu().numpy()
     else:

@@ -340,7 +340,8 @@ class MusicTransformer(torch.nn.Module):
                         masked_groups: bool = False, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
                         hop: Optional[int] = None, samples_per_prompt: Optional[int] = None, note_rules=None,
                         max_polyphony: Optional[int] = None, repetition=None, lookahead: Optional[int] = None,
-                        draft="history", draft_ngram: int = 3, stats: Optional[dict] = None, class_sampling=None):
+                        draft="history", draft_ngram: int = 3, stats: Optional[dict] = None, class_sampling=None,
+                        entropy_sampling=None):
         """Sample ``length`` events after ``prior`` [B,P] with per-layer K/V caches and absolute positions
         0..P+length-1 (requires P+length <= max_seq unless ``window`` is given, see below).  Every step runs
         embed -> N x (QKV GEMM, cached relative attention, fc, LN, FFN, LN) -> vocabulary GEMM -> fused
@@ -481,18 +482,41 @@ class MusicTransformer(torch.nn.Module):
         outside (0, 1]; a sequence that is not one value per class; ``groups`` > 1, ``masked_groups``; ``note_rules`` /
         ``max_polyphony`` (that step draws twice and an in-place rewrite cannot serve both: later work).  ``generate_beam``,
         ``generate`` and ``Event_Melody_RNN`` do not take the keyword.  None (default), or an object whose every class has the
-        call's temperature and no filter: the call as described above, untouched, with no new launch."""
+        call's temperature and no filter: the call as described above, untouched, with no new launch.
+
+        ``entropy_sampling`` (a ``decode.EntropySampling(min_p, typical_p, tau, eta, trace)``): three cuts that follow the row's
+        own uncertainty, where ``top_k`` / ``top_p`` keep the same share whether the model is certain or lost.  ``min_p`` keeps
+        the ids with at least that share of the most likely id's probability; ``typical_p`` keeps the ids whose surprise lies
+        closest to the row's entropy, up to that mass (locally typical sampling); ``tau`` is Mirostat v2, a feedback loop per row
+        that holds the surprise of what is drawn near ``tau`` bits -- ids more surprising than the row's threshold mu are cut
+        (the most likely ids stand in where that leaves none), mu starts at 2 tau and moves by -eta (surprise - tau) after every
+        draw.  The stages run in that order, each on the survivors of the one before, as a pure mask: one launch per step, the
+        last before the sampler (mgx_entropy_mask, ABI 34; after the budget's mask, the penalty and ``class_sampling``), writes
+        -inf and nothing else, so the unchanged sampler runs at the call's ``temperature`` (1 after ``class_sampling``) with its
+        own ``top_k`` / ``top_p`` and ``return_probs`` files the model's distribution renormalised over what was kept.  With
+        ``tau`` or ``trace=True`` a second launch after the sampler (mgx_entropy_account) computes the drawn token's surprise under
+        the distribution before the mask, moves mu and files the trace.  After the call the object holds the state: ``mu``
+        float32 [rows] and, with ``trace``, ``surprise`` float32 [rows, columns], NaN where nothing was generated.  Works with
+        ``prior_lengths``, ``kv_cache``, ``window`` / ``hop``, ``samples_per_prompt`` (a threshold per sample), ``grammar``,
+        ``repetition``, ``class_sampling`` and ``generate_timed``; under ``lookahead`` only the stateless part works, ``min_p``
+        and ``typical_p`` on the B * T rows.  Refused (ValueError, before any device work): ``min_p`` outside [0, 1),
+        ``typical_p`` outside (0, 1], a ``tau`` that is not finite and > 0, ``eta`` outside (0, 1]; ``tau`` / ``trace`` with
+        ``lookahead`` (the state is sequential: later work); ``note_rules`` / ``max_polyphony`` (that step draws twice: later
+        work); ``groups`` > 1, ``masked_groups`` (later work).  ``generate_beam``, ``generate`` and ``Event_Melody_RNN`` do not
+        take the keyword.  None (default), or an object with min_p 0, typical_p 1, no tau and no trace: the call as described
+        above, untouched, with no new launch."""
         return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
                                       prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop,
                                       samples_per_prompt, None, note_rules, max_polyphony, repetition, lookahead, draft,
-                                      draft_ngram, stats, class_sampling)
+                                      draft_ngram, stats, class_sampling, entropy_sampling)
 
     @torch.no_grad()
     def generate_timed(self, prior: torch.Tensor, budget, cost, max_length: int, *, inclusive: bool = True, poll: int = 32,
                        temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, use_graph: bool = True,
                        grammar=None, prior_lengths=None, kv_cache: str = "bf16", window: Optional[int] = None,
                        hop: Optional[int] = None, return_probs: bool = False, note_rules=None,
-                       max_polyphony: Optional[int] = None, repetition=None, class_sampling=None, **refused):
+                       max_polyphony: Optional[int] = None, repetition=None, class_sampling=None, entropy_sampling=None,
+                       **refused):
         """Generate to a musical length: ``generate_cached`` where every row stops at a budget of its own instead of after a
         number of events.  ``cost`` (int32-representable [vocab_size], >= 0, 0 at pad_token) prices every id --
         ``EventSeq.time_cost`` in centiseconds, ``REMI_EventSeq.bar_cost`` in bars -- and ``budget`` (an int, or one per row;
@@ -516,10 +540,12 @@ class MusicTransformer(torch.nn.Module):
         whose rule is 0, so its held set stays what it was when the row ended.  ``repetition``: as in ``generate_cached`` --
         after the budget's mask, before the notes' first draw; ``probs`` are then those of the penalised logits.
         ``class_sampling``: as in ``generate_cached`` -- after the budget's mask and the penalty; a masked id stays masked, so
-        no row overshoots; ``probs`` are then softmax(bf16(ln p'))."""
+        no row overshoots; ``probs`` are then softmax(bf16(ln p')).
+        ``entropy_sampling``: as in ``generate_cached`` -- the last mask before the sampler, and its account runs before the
+        budget's, which may replace the token by a pad; the trace of an ended row is NaN from its end on."""
         return decode.generate_timed(self, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed,
                                      use_graph, grammar, prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules,
-                                     max_polyphony, repetition, class_sampling)
+                                     max_polyphony, repetition, class_sampling, entropy_sampling)
 
     @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,

@@ -941,6 +941,63 @@ def class_logits(logits, V, cls, inv_temp, top_k, top_p, temperature, tok=None, 
     return logits
 
 
+# ---- entropy-aware sampling on the decode path (ABI 34; contracts in include/mgx.h) ----------------------------------
+def _check_rows_f32(what, B, **ts):
+    """name=tensor: contiguous float32 tensors of B entries (None passes)"""
+    for name, t in ts.items():
+        if t is not None and (t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()):
+            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
+
+
+def entropy_mask(logits, V, temperature, min_p=0.0, typical_p=1.0, mu=None, lse_out=None, tok=None, allow_table=None):
+    """in place, before the sampler: a pure mask on logits bf16 [B, ld] -- the ids v < V that the Mirostat cut (``mu`` float32 [B]:
+    surprise in bits at most mu[b]), min-p and typical sampling drop, in that order and each on the survivors of the one before,
+    become -inf; every other value stays bit for bit.  ``lse_out`` float32 [B] receives the row's log-sum-exp at ``temperature``
+    (what entropy_account reads).  tok int32 [B] and allow_table [V, ceil(V/32)]: the sampler's grammar and the rows' input
+    tokens, both or neither.  The sampler then runs at the same ``temperature``"""
+    ld = logits.shape[-1]
+    B = logits.numel() // ld
+    _need_cuda(logits, mu, lse_out, tok, allow_table)
+    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
+        raise ValueError(f"entropy_mask: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    _check_rows_f32("entropy_mask", B, mu=mu, lse_out=lse_out)
+    if (tok is None) != (allow_table is None):
+        raise ValueError("entropy_mask: tok and allow_table are given together or not at all")
+    if tok is not None:
+        _check_allow_table(allow_table, V)
+        if tok.dtype != torch.int32 or tok.numel() != B or not tok.is_contiguous():
+            raise ValueError(f"entropy_mask: tok must be a contiguous int32 tensor of {B} entries, got {tok.dtype} {tuple(tok.shape)}")
+    check(_lib.load().mgx_entropy_mask(ptr(logits), int(V), ld, float(temperature), float(min_p), float(typical_p), ptr(mu),
+                                       ptr(lse_out), ptr(tok), ptr(allow_table), B, stream_ptr()), "mgx_entropy_mask")
+    return logits
+
+
+def entropy_account(next_tok, logits, V, temperature, lse, pos_dev, mu=None, tau=0.0, eta=0.0, surprise_out=None, *, ragged=False,
+                    base=None):
+    """after the sampler and its advance, before budget_account: s = (lse[b] - logits[b, next_tok[b]] / temperature) / ln 2, the
+    surprise in bits of the token just drawn, moves the Mirostat threshold -- mu[b] -= eta * (s - tau), ``mu`` float32 [B] -- and is
+    filed in ``surprise_out`` float32 [B, out_ld] at the column the sampler has just written.  ``ragged`` / ``base`` as in
+    sample_topk_topp"""
+    ld = logits.shape[-1]
+    B = logits.numel() // ld
+    pos = _step_pos("entropy_account", pos_dev, B, ragged, base, with_base=True)
+    _need_cuda(next_tok, logits, lse, pos_dev, base, mu, surprise_out)
+    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
+        raise ValueError(f"entropy_account: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    if next_tok.dtype != torch.int32 or next_tok.numel() != B or not next_tok.is_contiguous():
+        raise ValueError(f"entropy_account: next_tok must be a contiguous int32 tensor of {B} entries, got {next_tok.dtype} "
+                         f"{tuple(next_tok.shape)}")
+    _check_rows_f32("entropy_account", B, lse=lse, mu=mu)
+    if surprise_out is not None and (surprise_out.dtype != torch.float32 or surprise_out.dim() != 2 or surprise_out.shape[0] != B
+                                     or not surprise_out.is_contiguous()):
+        raise ValueError(f"entropy_account: surprise_out must be contiguous float32 [{B}, out_ld], got {surprise_out.dtype} "
+                         f"{tuple(surprise_out.shape)}")
+    check(_lib.load().mgx_entropy_account(ptr(next_tok), ptr(logits), int(V), ld, float(temperature), ptr(lse), ptr(mu), float(tau),
+                                          float(eta), ptr(surprise_out), 0 if surprise_out is None else surprise_out.shape[1], *pos,
+                                          B, stream_ptr()), "mgx_entropy_account")
+    return mu
+
+
 # ---- draft and verify on the decode path (ABI 32; contracts in include/mgx.h) ----------------------------------------
 LOOKAHEAD_MAX_T = _lib.DEFINES["MGX_LOOKAHEAD_MAX_T"]
 LOOKAHEAD_MAX_NGRAM = _lib.DEFINES["MGX_LOOKAHEAD_MAX_NGRAM"]
