@@ -1,28 +1,14 @@
 """KV-cache decode of ``MusicTransformer`` (cfg5; options documented at ``MusicTransformer.generate_cached``).
-Three drivers -- ``generate_cached``, ``generate_shared`` (generate_cached(samples_per_prompt=N): the ragged step on Bp * N rows
-whose attention reads every prompt's K/V once for the samples of that prompt, ops.rel_attn_decode_shared) and ``generate_beam``
-(beam search over the same step, which ends in ops.beam_select instead of the sampler and hands every surviving beam its
-parent's cache rows, ops.kv_beam_reorder) -- each read: check, stage, build the cache, step, shape the result.  What they share
-has one name each: ``check_args`` (with ``check_shared_args`` / ``check_beam_args``) holds every refusal and runs before any
-device work; ``decode_session`` is the only place that touches ``model.training``; ``stage_prompt`` puts the prompt, the output
-matrix and every row's resume token and position on the device; ``KVCache`` is the only place that knows the two cache formats
-(``SharedKVCache``: two of them, the prompts' and the rows' own); ``SubBatch`` holds the rows of one step with their buffers and
-is where a row's position lives (``pos`` on the device with ``ragged`` and ``base``: one shared counter, or one per row);
-``run_steps`` is the step loop, eager or captured (``replay_graphs``).  ``window_schedule`` is the host-side plan of the
-re-anchored window (``window=``, ``decode_window``), the one way to generate past max_seq with the cache.  ``generate_timed`` is
-``generate_cached`` with a ``Budget``: every row's clock on the device (``decode_step_constrained`` brackets the sampler with
-ops.budget_mask / ops.budget_account) and a step loop that reads the rows' ``done`` flags every ``poll`` steps and stops early.
-``NoteState`` (``note_rules=``, ``max_polyphony=``) is the second per-row state bracketing the sampler the same way: the set of
-notes every row holds (ops.notes_mask / ops.notes_account), which keeps a MIDI-like stream well-formed.  ``Repetition``
-(``repetition=``) is not a state: one launch before the sampler (ops.repeat_penalty) reads the row's own columns of the output
-matrix and penalises repeated ids and n-grams by finite amounts.  ``ClassSampling`` (``class_sampling=``) is the last launch
-before the sampler (ops.class_logits): a temperature, top-k and top-p per class of ids, written back as ln p' so the sampler,
-at temperature 1, is unchanged.  ``EntropySampling`` (``entropy_sampling=``) brackets the sampler as a ``Budget`` does: a pure
-mask last before it (ops.entropy_mask: the Mirostat cut, min-p, typical) and, with a threshold to move or a trace to file, an
-account after it (ops.entropy_account); its per-row state is one float.  ``generate_lookahead`` (generate_cached(lookahead=T)) is draft
-and verify: the same step on B * T rows, T consecutive positions of every row on guessed inputs (ops.lookahead_draft), whose
-attention is ops.rel_attn_decode_multi behind a ``LookaheadCache`` and whose sampler is ops.lookahead_accept; a ``DonePoll`` --
-what a ``Budget`` is to the step loop -- stops it once every row holds its last token."""
+Drivers: ``generate_cached`` -- which hands over to ``generate_shared`` (samples_per_prompt=N: one prompt cache for N rows) or
+``generate_lookahead`` (lookahead=T: draft and verify) -- ``generate_timed`` (generate_cached with a ``Budget`` and a loop that
+stops early) and ``generate_beam``.  Each reads: check, stage, build the cache, step, shape the result.  Below the logits the
+drivers share ``check_args``, ``decode_session``, ``stage_prompt``, ``KVCache``, ``SubBatch``, ``step_logits`` and ``run_steps``
+(eager, then captured and replayed); ``window_schedule`` plans the re-anchored window on the host.
+Above the logits everything that shapes what the sampler sees is a stage -- ``Budget``, ``Repetition``, ``ClassSampling``,
+``EntropySampling``, ``NoteState`` -- and a ``Chain`` holds the stages a call has switched on.  ``check_stages`` builds it on the
+host before any device work (``REFUSED`` is the one table of combinations that do not go together), the drivers stage it once
+(``Chain.stage``), ``decode_step`` runs its launches around the draw in the order of ``BEFORE_DRAW`` and ``AFTER_DRAW``, written
+down there and nowhere else, and ``Chain.finish`` hands the state back to the caller."""
 from __future__ import annotations
 
 import dataclasses
@@ -164,8 +150,7 @@ def check_args(model, prior, length: int, return_probs: bool, prefill: str, prio
     if window is not None:
         if not 2 <= window <= max_seq:
             raise ValueError(f"window must lie in 2 .. max_seq ({max_seq}), got {window}")
-        if (groups or 1) > 1 or masked_groups:
-            raise ValueError("groups / masked_groups are not combined with window (the window decodes the batch as one group)")
+        refuse("window", switched_on(groups=groups, masked_groups=masked_groups))
         if prefill == "token":
             raise ValueError("prefill='token' is not combined with window: the window is always prefilled in one batched pass")
     Pmax = prior.shape[1]
@@ -221,8 +206,7 @@ def check_shared_args(model, prior, length, prefill, prior_lengths, kv_cache, wi
         raise ValueError("samples_per_prompt is not combined with window / hop (a re-anchor would rebuild every sample's own window)")
     if kv_cache != "bf16":
         raise ValueError(f"samples_per_prompt needs kv_cache='bf16' (the shared prompt cache has no 8-bit form), got {kv_cache!r}")
-    if (groups or 1) > 1 or masked_groups:
-        raise ValueError("samples_per_prompt is not combined with groups / masked_groups (the samples of a prompt decode as one group)")
+    refuse("samples_per_prompt", switched_on(groups=groups, masked_groups=masked_groups))
     _check_prefill_name(prefill)
     if prefill == "token":
         raise ValueError("samples_per_prompt needs prefill='batched' or 'auto': the prompt cache is written by one batched pass")
@@ -403,10 +387,87 @@ def step_logits(w: Weights, r: SubBatch) -> torch.Tensor:
     return qkv
 
 
-def decode_step(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool) -> None:
-    """one token for the rows of ``r``; ``sampler``: keyword arguments of ops.sample_topk_topp"""
-    ops.sample_topk_topp(step_logits(w, r), w.V, next_tok=r.tok, out_tokens=r.out if sample_into_out else None, probs_out=r.probs,
-                         advance=True, row0=r.b0, **r.step, **sampler)
+# ---- the stages: what shapes the logits before the draw and follows it after -------------------------------------------------
+def number_in(v, lo, hi, open_lo: bool = False, open_hi: bool = False) -> bool:
+    """is ``v`` a finite number -- no bool, no string -- in [lo, hi], an end left out where it is open?"""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        return False
+    return (lo < v if open_lo else lo <= v) and (v < hi if open_hi else v <= hi)
+
+
+def integer_in(v, lo=-np.inf, hi=np.inf) -> bool:
+    """is ``v`` an integer -- no bool, no float that happens to be whole -- in lo .. hi?"""
+    return isinstance(v, (int, np.integer)) and number_in(v, lo, hi)
+
+
+def id_table(what: str, table, model, kinds: str = "iu", pad_zero: bool = True):
+    """a per-id table -- a tensor or anything array-like -- as a numpy array [vocab_size] of its own dtype (ValueError); the
+    caller checks the range of its values and then narrows them (``int32_table``).  ``kinds``: the numpy dtype kinds allowed;
+    with "f" among them, floats that hold integers.  ``pad_zero``: the entry of pad_token must be 0"""
+    V = model.vocab_size
+    arr = np.asarray(table.detach().cpu() if isinstance(table, torch.Tensor) else table)
+    whole = arr.dtype.kind != "f" or (np.isfinite(arr).all() and (arr == np.rint(arr)).all())
+    if arr.shape != (V,) or arr.dtype.kind not in kinds or not whole:
+        raise ValueError(f"{what} must be integers, one per id, [vocab_size] = [{V}], got {arr.dtype} {tuple(arr.shape)}")
+    if pad_zero and arr[model.pad_token] != 0:
+        raise ValueError(f"{what}[pad_token] must be 0 (an ended row steps on pad tokens), got {arr[model.pad_token]}")
+    return arr
+
+
+def int32_table(arr):
+    return np.ascontiguousarray(arr.astype(np.int32))
+
+
+# The combinations that are refused: (option, what it does not go with, why, is it later work?).  ``refuse`` is the one place that
+# raises them; the first entry of an option that applies is the one reported.
+REFUSED = (
+    ("window", "groups / masked_groups", "the window decodes the batch as one group", False),
+    ("samples_per_prompt", "groups / masked_groups", "the samples of a prompt decode as one group", False),
+    ("class_sampling", "groups / masked_groups", "experiment flags: the launch is tested on the batch as one group", False),
+    ("class_sampling", "note_rules / max_polyphony", "that step draws twice, from the logits as they stand and from the masked ones, "
+     "and an in-place rewrite cannot serve both", True),
+    ("entropy_sampling", "groups / masked_groups", "experiment flags: the per-row state covers the batch as one group", True),
+    ("entropy_sampling", "note_rules / max_polyphony", "that step draws twice, from the logits as they stand and from the masked "
+     "ones, and one mask and one account cannot serve both draws", True),
+    ("entropy_sampling's tau / trace", "lookahead", "the Mirostat state is sequential: the cut at position i + 1 depends on the token "
+     "drawn at i; min_p and typical_p alone are taken", True),
+    ("repetition", "groups / masked_groups", "experiment flags: the penalty is tested on the batch as one group", False),
+    ("note_rules", "grammar", "the two masks together can leave a row no id, and no codec needs both", False),
+    ("note_rules", "groups / masked_groups", "the note state covers the batch as one group", False),
+    ("note_rules", "return_cache", "the caller of return_cache continues a decode whose note state is not returned", False),
+    ("lookahead", "window / hop", "a re-anchor would have to fall between two accepted tokens", True),
+    ("lookahead", "kv_cache='fp8'", "the T-query attention has no 8-bit form", True),
+    ("lookahead", "samples_per_prompt", "the shared prompt cache is another attention kernel", True),
+    ("lookahead", "groups / masked_groups", "the rows advance by different amounts as one group", True),
+    ("lookahead", "prefill='token'", "the prompt is prefilled in one batched pass", True),
+    ("lookahead", "return_cache", "cache rows above a row's last position hold rejected guesses", True),
+    ("lookahead", "note_rules / max_polyphony", "the held-note state is sequential: position i + 1 is masked by the token at i", True),
+    ("lookahead", "repetition", "the penalty of position i + 1 counts the token at i", True),
+    ("generate_timed", "samples_per_prompt", "the shared prompt cache is another driver (generate_cached(samples_per_prompt=))", False),
+    ("generate_timed", "groups", "the budget clock covers the batch as one group", False),
+    ("generate_timed", "masked_groups", "the budget clock covers the batch as one group", False),
+    ("generate_timed", "return_cache", "an ended row's cache rows hold pad-token steps", False),
+    ("generate_timed", "beam_size", "beam search is another driver (generate_beam): a beam has no clock of its own", False),
+    ("generate_timed", "lookahead", "draft and verify is generate_cached(lookahead=): a budget's state is sequential, a row's next "
+     "mask depends on the token before it", False),
+)
+
+
+def switched_on(groups=None, masked_groups=False, note_rules=None, max_polyphony=None, grammar=None, return_cache=False, window=None,
+                hop=None, kv_cache="bf16", samples_per_prompt=None, prefill="auto", repetition=None, lookahead=None) -> dict:
+    """a call's context by the names REFUSED uses for it: is each of them on?"""
+    return {"groups / masked_groups": (groups or 1) > 1 or bool(masked_groups),
+            "note_rules / max_polyphony": note_rules is not None or max_polyphony is not None, "grammar": grammar is not None,
+            "return_cache": bool(return_cache), "window / hop": window is not None or hop is not None,
+            "kv_cache='fp8'": kv_cache == "fp8", "samples_per_prompt": samples_per_prompt is not None,
+            "prefill='token'": prefill == "token", "repetition": repetition is not None, "lookahead": lookahead is not None}
+
+
+def refuse(option: str, on: dict) -> None:
+    """ValueError for the first entry of REFUSED under ``option`` that is ``on``"""
+    for opt, other, why, later in REFUSED:
+        if opt == option and on.get(other):
+            raise ValueError(f"{option} is not combined with {other} ({why})" + (": later work" if later else ""))
 
 
 class DonePoll:
@@ -428,53 +489,42 @@ class DonePoll:
 class Budget(DonePoll):
     """the per-row length budgets of generate_timed (include/mgx.h, ABI 27).  On the host: ``budgets``, one int per row
     (ops.NO_BUDGET: none), ``cost`` int32 [V] (numpy), ``inclusive``, ``poll``.  ``stage`` puts the clock on the device: ``cost``,
-    ``remaining`` [B], ``done`` [B] (set from the start for a budget of 0: the row generates nothing) and ``count`` [B].  The
-    step loop files ``steps_run``"""
+    ``remaining`` [B], ``done`` [B] (set from the start for a budget of 0: the row generates nothing) and ``count`` [B]"""
 
     def __init__(self, budgets, cost, pad_token: int, inclusive: bool, poll: int):
         super().__init__(None, poll)
         self.budgets, self.cost_host, self.pad_token, self.inclusive = budgets, cost, pad_token, inclusive
 
-    def stage(self, dev) -> "Budget":
+    def stage(self, dev, **_) -> None:
         self.cost = torch.from_numpy(self.cost_host).to(dev)
         self.remaining = torch.tensor(self.budgets, dtype=torch.int32, device=dev)
         self.done = (self.remaining == 0).to(torch.int32)
         self.count = torch.zeros_like(self.remaining)
-        return self
+
+    def mask(self, logits, V: int, r: "SubBatch", sampler: dict) -> None:
+        ops.budget_mask(logits, V, self.cost, self.remaining, self.done)
+
+    def account(self, logits, V: int, r: "SubBatch", sampler: dict, out) -> None:
+        ops.budget_account(r.tok, r.out, cost=self.cost, remaining=self.remaining, done=self.done, count=self.count,
+                           pad_token=self.pad_token, inclusive=self.inclusive, **r.step)
 
 
 def check_budget_args(model, B: int, budget, cost, max_length: int, poll: int, refused: dict):
     """every refusal of generate_timed that generate_cached does not make (ValueError), on the host.  Returns (one int32 budget
     per row, ops.NO_BUDGET for None; cost as a numpy int32 [vocab_size])"""
-    why = {"samples_per_prompt": "the shared prompt cache is another driver (generate_cached(samples_per_prompt=))",
-           "groups": "the budget clock covers the batch as one group",
-           "masked_groups": "the budget clock covers the batch as one group",
-           "return_cache": "an ended row's cache rows hold pad-token steps",
-           "beam_size": "beam search is another driver (generate_beam): a beam has no clock of its own",
-           "lookahead": "draft and verify is generate_cached(lookahead=): a budget's state is sequential, a row's next mask "
-                        "depends on the token before it"}
-    for name, value in refused.items():
-        if name not in why:
+    for name in refused:
+        if not any((opt, other) == ("generate_timed", name) for opt, other, _, _ in REFUSED):
             raise TypeError(f"generate_timed() got an unexpected keyword argument {name!r}")
-        if value and not (name == "groups" and int(value) == 1):
-            raise ValueError(f"generate_timed is not combined with {name} ({why[name]})")
+    refuse("generate_timed", {name: value and not (name == "groups" and int(value) == 1) for name, value in refused.items()})
     if int(poll) < 1:
         raise ValueError(f"poll must be >= 1 (the steps between two reads of the rows' done flags), got {poll}")
     if int(max_length) < 1:
         raise ValueError(f"max_length must be >= 1 (the cap on every row's events), got {max_length}")
-    V = model.vocab_size
-    arr = np.asarray(cost.detach().cpu() if isinstance(cost, torch.Tensor) else cost)
-    if arr.shape != (V,):
-        raise ValueError(f"cost must have one entry per id, [vocab_size] = [{V}], got shape {tuple(arr.shape)}")
-    if arr.dtype.kind not in "iu":
-        if arr.dtype.kind != "f" or not np.isfinite(arr).all() or (arr != np.rint(arr)).any():
-            raise ValueError(f"cost must hold integers (int32), got {arr.dtype}")
+    arr = id_table("cost", cost, model, kinds="iuf")
     if (arr < 0).any():
         raise ValueError(f"cost must be >= 0, got {arr.min()} at id {int(arr.argmin())}")
     if (arr > ops.NO_BUDGET).any():
         raise ValueError(f"cost must fit int32, got {arr.max()}")
-    if arr[model.pad_token] != 0:
-        raise ValueError(f"cost[pad_token] must be 0 (an ended row steps on pad tokens), got {arr[model.pad_token]}")
     if isinstance(budget, (torch.Tensor, np.ndarray)):
         budget = budget.tolist()
     rows = list(budget) if isinstance(budget, (list, tuple)) else [budget] * B
@@ -486,7 +536,7 @@ def check_budget_args(model, B: int, budget, cost, max_length: int, poll: int, r
             raise ValueError(f"budget must be an integer >= 0 (or None: no budget), got {v}")
         if int(v) > ops.NO_BUDGET:
             raise ValueError(f"budget must fit int32, got {v}")
-    return [int(v) for v in rows], np.ascontiguousarray(arr.astype(np.int32))
+    return [int(v) for v in rows], int32_table(arr)
 
 
 class NoteState:
@@ -507,7 +557,7 @@ class NoteState:
             words[k >> 5] |= np.uint32(1) << np.uint32(k & 31)
         return words
 
-    def stage(self, dev, prior, lens, repeat: int = 1) -> "NoteState":
+    def stage(self, dev, *, prior, lens, repeat: int = 1, **_) -> None:
         """``prior`` [B, P] with the prompts' lengths ``lens`` (a list): every row starts from what its OWN prompt leaves held,
         folded once on the host -- well-formed or not, above the cap or not; row b * repeat + n belongs to prompt b"""
         rows = np.asarray(prior.detach().cpu())
@@ -515,29 +565,34 @@ class NoteState:
         self.rule = torch.from_numpy(self.rule_host).to(dev)
         self.state = torch.from_numpy(state).to(dev).repeat_interleave(repeat, 0).contiguous()
         self.first = torch.zeros(self.state.shape[0], dtype=torch.int32, device=dev)      # every row's first draw of a step
-        return self
+
+    def mask(self, logits, V: int, r: "SubBatch", sampler: dict) -> dict:
+        # the sampler draws by inverse CDF, so a draw from the masked logits is another token even where the unmasked draw of
+        # the same random number was legal.  Hence two draws: the first from the logits as they stand, with the call's seed and
+        # nothing written but ``first``; the second, the step's own, from the masked logits with a seed of its own; ``keep`` then
+        # puts a legal first draw in the second's place, and the row is the unconstrained row until that one breaks a rule
+        ops.sample_topk_topp(logits, V, next_tok=self.first, advance=False, row0=r.b0, **r.step, **sampler)
+        ops.notes_mask(logits, V, self.rule, self.state, self.max_on)
+        return dict(sampler, seed=(int(sampler["seed"]) + self.SECOND_SEED) % 2 ** 64)
+
+    def keep(self, logits, V: int, r: "SubBatch", sampler: dict, out) -> None:
+        ops.notes_keep(self.first, r.tok, out, rule=self.rule, state=self.state, max_on=self.max_on, V=V, **r.step)
+
+    def account(self, logits, V: int, r: "SubBatch", sampler: dict, out) -> None:
+        ops.notes_account(r.tok, self.rule, self.state, V)
 
 
-def check_note_args(model, note_rules, max_polyphony, *, grammar=None, groups=None, masked_groups=False, return_cache=False):
-    """every refusal of note_rules / max_polyphony (ValueError), on the host.  Returns a NoteState, or None without note_rules"""
+def check_note_args(model, note_rules, max_polyphony, **context):
+    """every refusal of note_rules / max_polyphony (ValueError), on the host; ``context``: what ``switched_on`` takes.  Returns a
+    NoteState, or None without note_rules"""
     if note_rules is None:
         if max_polyphony is not None:
             raise ValueError("max_polyphony caps the notes that note_rules counts: it needs note_rules")
         return None
-    for on, name, why in ((grammar is not None, "grammar", "the two masks together can leave a row no id, and no codec needs both"),
-                          ((groups or 1) > 1 or masked_groups, "groups / masked_groups", "the note state covers the batch as one group"),
-                          (return_cache, "return_cache", "the caller of return_cache continues a decode whose note state is not returned")):
-        if on:
-            raise ValueError(f"note_rules is not combined with {name} ({why})")
+    refuse("note_rules", switched_on(**context))
     if max_polyphony is not None and (max_polyphony != int(max_polyphony) or not 1 <= int(max_polyphony) <= ops.NOTE_BITS):
         raise ValueError(f"max_polyphony must be an integer in 1 .. {ops.NOTE_BITS} (None: no cap), got {max_polyphony}")
-    V = model.vocab_size
-    arr = np.asarray(note_rules.detach().cpu() if isinstance(note_rules, torch.Tensor) else note_rules)
-    if arr.shape != (V,) or arr.dtype.kind not in "iu":
-        raise ValueError(f"note_rules must be integers, one per id, [vocab_size] = [{V}], got {arr.dtype} {tuple(arr.shape)}")
-    arr = arr.astype(np.int64)
-    if arr[model.pad_token] != 0:
-        raise ValueError(f"note_rules[pad_token] must be 0 (an ended row steps on pad tokens), got {arr[model.pad_token]}")
+    arr = id_table("note_rules", note_rules, model).astype(np.int64)
     if (np.abs(arr) > ops.NOTE_BITS).any():
         v = int(np.abs(arr).argmax())
         raise ValueError(f"note_rules must lie in -{ops.NOTE_BITS} .. {ops.NOTE_BITS} (bit k is +-(k + 1)), got {arr[v]} at id {v}")
@@ -545,7 +600,7 @@ def check_note_args(model, note_rules, max_polyphony, *, grammar=None, groups=No
     if sets != clears:
         raise ValueError(f"every bit of note_rules needs an id that sets it and one that clears it (else the mask could leave a "
                          f"row no id): bits {sorted(sets ^ clears)[:8]} have only one of the two")
-    return NoteState(np.ascontiguousarray(arr.astype(np.int32)), max_polyphony)
+    return NoteState(int32_table(arr), max_polyphony)
 
 
 REPEAT_MAX_AMOUNT = 1e4                                   # the largest amount a logit loses: exp(-1e4 / T) is 0 in f32
@@ -581,58 +636,46 @@ class Repetition:
         pen[0] = 0
         return pen
 
-    def stage(self, dev) -> "Repetition":
+    def stage(self, dev, **_) -> None:
         """``subject`` and ``pen`` on the device, once per call (nothing with the counts off)"""
         if self.counting:
-            self.subject = torch.from_numpy(np.ascontiguousarray(np.asarray(self.subject_host).astype(np.int32))).to(dev)
+            self.subject = torch.from_numpy(int32_table(np.asarray(self.subject_host))).to(dev)
             self.pen = torch.from_numpy(self.pen_table()).to(dev)
-        return self
 
-    def apply(self, logits, V: int, r: "SubBatch") -> None:
+    def penalise(self, logits, V: int, r: "SubBatch", sampler: dict) -> None:
         ops.repeat_penalty(logits, V, r.out, subject=self.subject, pen=self.pen, window=self.window if self.counting else 0,
                            ngram=self.ngram, span=self.span, ban=self.ban, **r.step)
 
 
-def check_repeat_args(model, repetition, *, groups=None, masked_groups=False):
-    """every refusal of ``repetition`` (ValueError), on the host before any device work.  Returns a Repetition of its own with the
-    subject as numpy int32 -- the caller's object is not staged, so it serves any number of calls -- or None: no ``repetition``,
-    or an inert one"""
+def check_repeat_args(model, repetition, **context):
+    """every refusal of ``repetition`` (ValueError), on the host before any device work; ``context``: what ``switched_on`` takes.
+    Returns a Repetition of its own, the subject as numpy int32 (Chain says why a copy), or None: no ``repetition``, or an inert one"""
     if repetition is None:
         return None
     if not isinstance(repetition, Repetition):
         raise ValueError(f"repetition must be a decode.Repetition (or None), got {type(repetition).__name__}")
-    rp, V = repetition, model.vocab_size
-    sub = rp.subject_host
-    arr = np.asarray(sub.detach().cpu() if isinstance(sub, torch.Tensor) else sub)
-    if arr.shape != (V,) or arr.dtype.kind not in "iub":
-        raise ValueError(f"repetition: subject must be integers, one per id, [vocab_size] = [{V}], got {arr.dtype} {tuple(arr.shape)}")
-    if arr[model.pad_token] != 0:
-        raise ValueError(f"repetition: subject[pad_token] must be 0 (an ended row steps on pad tokens), got {arr[model.pad_token]}")
+    rp = repetition
+    arr = id_table("repetition: subject", rp.subject_host, model, kinds="iub")
     for name, v in (("presence", rp.presence), ("frequency", rp.frequency)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+        if not number_in(v, 0, np.inf):
             raise ValueError(f"repetition: {name} must be a finite number >= 0, got {v}")
-
-    def integer(name, v):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+    for name, v in (("window", rp.window), ("ngram", rp.ngram), ("span", rp.span)):
+        if not integer_in(v):
             raise ValueError(f"repetition: {name} must be an integer, got {v!r}")
-        return int(v)
-    window, ngram, span = integer("window", rp.window), integer("ngram", rp.ngram), integer("span", rp.span)
+    window, ngram, span = int(rp.window), int(rp.ngram), int(rp.span)
     if not 1 <= window <= ops.REPEAT_MAX_WINDOW:
         raise ValueError(f"repetition: window must lie in 1 .. {ops.REPEAT_MAX_WINDOW}, got {window}")
     if ngram != 0 and not 2 <= ngram <= ops.REPEAT_MAX_NGRAM:
         raise ValueError(f"repetition: ngram must be 0 (off) or lie in 2 .. {ops.REPEAT_MAX_NGRAM}, got {ngram}")
     if span != 0 and span < max(ngram, 1):
         raise ValueError(f"repetition: span must be 0 (the whole sequence so far) or >= ngram = {ngram}, got {span}")
-    if isinstance(rp.ban, bool) or not isinstance(rp.ban, (int, float, np.integer, np.floating)) or not 0 < rp.ban <= REPEAT_MAX_AMOUNT:
+    if not number_in(rp.ban, 0, REPEAT_MAX_AMOUNT, open_lo=True):
         raise ValueError(f"repetition: ban must lie in (0, {REPEAT_MAX_AMOUNT:g}], got {rp.ban}")
     if float(rp.presence) + float(rp.frequency) * window > REPEAT_MAX_AMOUNT:
         raise ValueError(f"repetition: presence + frequency * window must not exceed {REPEAT_MAX_AMOUNT:g}, got "
                          f"{float(rp.presence) + float(rp.frequency) * window:g}")
-    if (groups or 1) > 1 or masked_groups:
-        raise ValueError("repetition is not combined with groups / masked_groups (experiment flags: the penalty is tested on the "
-                         "batch as one group)")
-    own = Repetition(np.ascontiguousarray(arr.astype(np.int32)), float(rp.presence), float(rp.frequency), window, ngram, span,
-                     float(rp.ban))
+    refuse("repetition", switched_on(**context))
+    own = Repetition(int32_table(arr), float(rp.presence), float(rp.frequency), window, ngram, span, float(rp.ban))
     return None if own.inert else own
 
 
@@ -667,39 +710,33 @@ class ClassSampling:
                 and all(k is None or k == 0 for k in self.entries(self.top_k))
                 and all(p is None or p == 1 for p in self.entries(self.top_p)))
 
-    def stage(self, dev) -> "ClassSampling":
+    def stage(self, dev, **_) -> None:
         """``classes`` and the three per-class arrays on the device, once per call (a checked copy: lists of C values)"""
         inv = [1.0 / (self.call_temperature if t is None else t) for t in self.temperature]
-        self.cls = torch.from_numpy(np.ascontiguousarray(np.asarray(self.classes_host).astype(np.int32))).to(dev)
+        self.cls = torch.from_numpy(int32_table(np.asarray(self.classes_host))).to(dev)
         self.inv_temp = torch.tensor(inv, dtype=torch.float32, device=dev)
         self.k = torch.tensor(self.top_k, dtype=torch.int32, device=dev)
         self.p = torch.tensor(self.top_p, dtype=torch.float32, device=dev)
-        return self
 
-    def apply(self, logits, V: int, r: "SubBatch", temperature: float, allow_table) -> None:
-        ops.class_logits(logits, V, self.cls, self.inv_temp, self.k, self.p, temperature,
-                         tok=None if allow_table is None else r.tok, allow_table=allow_table)
+    def rewrite(self, logits, V: int, r: "SubBatch", sampler: dict) -> dict:
+        """ln p' over the logits at the call's temperature: whatever follows runs at temperature 1"""
+        ops.class_logits(logits, V, self.cls, self.inv_temp, self.k, self.p, sampler["temperature"],
+                         tok=None if sampler["allow_table"] is None else r.tok, allow_table=sampler["allow_table"])
+        return dict(sampler, temperature=1.0)
 
 
-def check_class_args(model, class_sampling, temperature, *, groups=None, masked_groups=False, note_rules=None, max_polyphony=None):
-    """every refusal of ``class_sampling`` (ValueError), on the host before any device work.  Returns a ClassSampling of its own --
-    the classes as numpy int32, one value per class in each list, the call's temperature known -- so the caller's object is not
-    staged and serves any number of calls; or None: no ``class_sampling``, or every class plain at this temperature"""
+def check_class_args(model, class_sampling, temperature, **context):
+    """every refusal of ``class_sampling`` (ValueError), on the host before any device work; ``context``: what ``switched_on``
+    takes.  Returns a ClassSampling of its own -- the classes as numpy int32, one value per class in each list, the call's
+    temperature known -- or None: no ``class_sampling``, or every class plain at this temperature"""
     if class_sampling is None:
         return None
     if not isinstance(class_sampling, ClassSampling):
         raise ValueError(f"class_sampling must be a decode.ClassSampling (or None), got {type(class_sampling).__name__}")
-
-    def number(v):
-        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating))
-    if not number(temperature) or not np.isfinite(temperature) or temperature <= 0:
+    if not number_in(temperature, 0, np.inf, open_lo=True):
         raise ValueError(f"class_sampling: the call's temperature must be a finite number > 0, got {temperature!r}")
-    cs, V = class_sampling, model.vocab_size
-    raw = cs.classes_host
-    arr = np.asarray(raw.detach().cpu() if isinstance(raw, torch.Tensor) else raw)
-    if arr.shape != (V,) or arr.dtype.kind not in "iu":
-        raise ValueError(f"class_sampling: classes must be integers, one per id, [vocab_size] = [{V}], got {arr.dtype} "
-                         f"{tuple(arr.shape)}")
+    cs = class_sampling
+    arr = id_table("class_sampling: classes", cs.classes_host, model, pad_zero=False)
     if arr.min() < 0 or arr.max() >= ops.CLASS_MAX:
         raise ValueError(f"class_sampling: a class must lie in 0 .. {ops.CLASS_MAX - 1}, got {int(arr.min())} .. {int(arr.max())}")
     specs = (("temperature", cs.temperature), ("top_k", cs.top_k), ("top_p", cs.top_p))
@@ -731,17 +768,11 @@ def check_class_args(model, class_sampling, temperature, *, groups=None, masked_
                 raise ValueError(f"class_sampling: {name}[{c}] must be {what}, got {v!r}")
             vals[int(c)] = v
         return vals
-    temps = per_class("temperature", cs.temperature, lambda v: number(v) and np.isfinite(v) and v > 0, "a finite number > 0")
-    ks = per_class("top_k", cs.top_k, lambda v: not isinstance(v, bool) and isinstance(v, (int, np.integer)) and 0 <= v < 2 ** 31,
-                   "an integer >= 0")
-    ps = per_class("top_p", cs.top_p, lambda v: number(v) and 0 < v <= 1, "a number in (0, 1]")
-    if (groups or 1) > 1 or masked_groups:
-        raise ValueError("class_sampling is not combined with groups / masked_groups (experiment flags: the launch is tested on the "
-                         "batch as one group)")
-    if note_rules is not None or max_polyphony is not None:
-        raise ValueError("class_sampling is not combined with note_rules / max_polyphony (that step draws twice, from the logits as "
-                         "they stand and from the masked ones, and an in-place rewrite cannot serve both): later work")
-    own = ClassSampling(np.ascontiguousarray(arr.astype(np.int32)), [None if t is None else float(t) for t in temps],
+    temps = per_class("temperature", cs.temperature, lambda v: number_in(v, 0, np.inf, open_lo=True), "a finite number > 0")
+    ks = per_class("top_k", cs.top_k, lambda v: integer_in(v, 0, 2 ** 31 - 1), "an integer >= 0")
+    ps = per_class("top_p", cs.top_p, lambda v: number_in(v, 0, 1, open_lo=True), "a number in (0, 1]")
+    refuse("class_sampling", switched_on(**context))
+    own = ClassSampling(int32_table(arr), [None if t is None else float(t) for t in temps],
                         [0 if k is None else int(k) for k in ks], [1.0 if p is None else float(p) for p in ps])
     own.call_temperature = float(temperature)
     return None if own.inert else own
@@ -775,103 +806,131 @@ class EntropySampling:
         """does the step need ops.entropy_account -- a threshold to move or a surprise to file?"""
         return self.tau is not None or bool(self.trace)
 
-    def stage(self, dev, rows: int, total: int) -> "EntropySampling":
+    def stage(self, dev, *, rows: int, total: int, **_) -> None:
         """the state of ``rows`` rows and ``total`` output columns on the device, once per call"""
         self.lse = torch.zeros(rows, dtype=torch.float32, device=dev) if self.accounting else None
         self.mu = None if self.tau is None else torch.full((rows,), 2.0 * self.tau, dtype=torch.float32, device=dev)
         self.surprise = torch.full((rows, total), float("nan"), dtype=torch.float32, device=dev) if self.trace else None
-        return self
 
-    def mask(self, logits, V: int, r: "SubBatch", temperature: float, allow_table) -> None:
-        ops.entropy_mask(logits, V, temperature, self.min_p, self.typical_p, mu=self.mu, lse_out=self.lse,
-                         tok=None if allow_table is None else r.tok, allow_table=allow_table)
+    def mask(self, logits, V: int, r: "SubBatch", sampler: dict) -> None:
+        ops.entropy_mask(logits, V, sampler["temperature"], self.min_p, self.typical_p, mu=self.mu, lse_out=self.lse,
+                         tok=None if sampler["allow_table"] is None else r.tok, allow_table=sampler["allow_table"])
 
-    def account(self, logits, V: int, r: "SubBatch", temperature: float) -> None:
-        ops.entropy_account(r.tok, logits, V, temperature, self.lse, mu=self.mu, tau=self.tau or 0.0, eta=self.eta,
-                            surprise_out=self.surprise, **r.step)
-
-    def hand_back(self, to: "EntropySampling") -> None:
-        """the state after the call, for the caller to read"""
-        to.mu, to.lse, to.surprise = self.mu, self.lse, self.surprise
+    def account(self, logits, V: int, r: "SubBatch", sampler: dict, out) -> None:
+        if self.accounting:
+            ops.entropy_account(r.tok, logits, V, sampler["temperature"], self.lse, mu=self.mu, tau=self.tau or 0.0, eta=self.eta,
+                                surprise_out=self.surprise, **r.step)
 
 
-def check_entropy_args(model, entropy_sampling, temperature, *, groups=None, masked_groups=False, note_rules=None,
-                       max_polyphony=None, lookahead=None):
-    """every refusal of ``entropy_sampling`` (ValueError), on the host before any device work.  Returns an EntropySampling of its
-    own -- plain floats, not yet staged -- so the caller's object serves any number of calls and receives the state only once the
-    call is over; or None: no ``entropy_sampling``, or an inert one"""
+def check_entropy_args(model, entropy_sampling, temperature, *, lookahead=None, **context):
+    """every refusal of ``entropy_sampling`` (ValueError), on the host before any device work; ``context``: what ``switched_on``
+    takes.  Returns an EntropySampling of its own -- plain floats, not yet staged; ``caller``: the object that receives the state
+    once the call is over (Chain.finish) -- or None: no ``entropy_sampling``, or an inert one"""
     if entropy_sampling is None:
         return None
     if not isinstance(entropy_sampling, EntropySampling):
         raise ValueError(f"entropy_sampling must be a decode.EntropySampling (or None), got {type(entropy_sampling).__name__}")
-
-    def number(v):
-        return not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and np.isfinite(v)
-    if not number(temperature) or temperature <= 0:
+    if not number_in(temperature, 0, np.inf, open_lo=True):
         raise ValueError(f"entropy_sampling: the call's temperature must be a finite number > 0, got {temperature!r}")
     es = entropy_sampling
-    if not number(es.min_p) or not 0 <= es.min_p < 1:
+    if not number_in(es.min_p, 0, 1, open_hi=True):
         raise ValueError(f"entropy_sampling: min_p must be a number in [0, 1) (0: off), got {es.min_p!r}")
-    if not number(es.typical_p) or not 0 < es.typical_p <= 1:
+    if not number_in(es.typical_p, 0, 1, open_lo=True):
         raise ValueError(f"entropy_sampling: typical_p must be a number in (0, 1] (1: off), got {es.typical_p!r}")
-    if es.tau is not None and (not number(es.tau) or es.tau <= 0):
+    if es.tau is not None and not number_in(es.tau, 0, np.inf, open_lo=True):
         raise ValueError(f"entropy_sampling: tau must be a finite number of bits > 0 (None: no Mirostat), got {es.tau!r}")
-    if not number(es.eta) or not 0 < es.eta <= 1:
+    if not number_in(es.eta, 0, 1, open_lo=True):
         raise ValueError(f"entropy_sampling: eta must be a number in (0, 1] (the loop's learning rate), got {es.eta!r}")
     if not isinstance(es.trace, (bool, np.bool_)):
         raise ValueError(f"entropy_sampling: trace must be True or False, got {es.trace!r}")
-    if (groups or 1) > 1 or masked_groups:
-        raise ValueError("entropy_sampling is not combined with groups / masked_groups (experiment flags: the per-row state covers "
-                         "the batch as one group): later work")
-    if note_rules is not None or max_polyphony is not None:
-        raise ValueError("entropy_sampling is not combined with note_rules / max_polyphony (that step draws twice, from the logits "
-                         "as they stand and from the masked ones, and one mask and one account cannot serve both draws): later work")
-    if lookahead is not None and (es.tau is not None or es.trace):
-        raise ValueError("lookahead takes entropy_sampling's min_p and typical_p only, not tau / trace (the Mirostat state is "
-                         "sequential: the cut at position i + 1 depends on the token drawn at i): later work")
+    refuse("entropy_sampling", switched_on(**context))
+    if es.tau is not None or es.trace:
+        refuse("entropy_sampling's tau / trace", switched_on(lookahead=lookahead))
     own = EntropySampling(float(es.min_p), float(es.typical_p), None if es.tau is None else float(es.tau), float(es.eta),
                           bool(es.trace))
+    own.caller = es
     return None if own.inert else own
 
 
-def decode_step_constrained(w: Weights, r: SubBatch, sampler: dict, sample_into_out: bool, bud: Optional[Budget],
-                            notes: Optional[NoteState], rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None,
-                            es: Optional[EntropySampling] = None) -> None:
-    """decode_step under the rows' budgets, repetition control, per-class sampling, entropy-aware sampling and / or held notes: the
-    logits are masked, penalised and rewritten before the sampler sees them, and the draw is charged to the clock and applied to
-    the notes after it (the order: include/mgx.h, ABI 31, 33 and 34).  With ``notes`` the step draws twice (below); the penalty
-    comes before the first draw, which notes_keep would otherwise let stand unpenalised.  ``cs`` (never with ``notes``) leaves
-    ln p' in the logits, so the sampler runs at temperature 1.  ``es`` (never with ``notes``) masks last, at the sampler's
-    temperature, and accounts for the draw before the budget can replace it by a pad"""
+# The order of the launches around the draw (include/mgx.h, ABI 27, 28, 31, 33, 34), written down here and nowhere else: (a stage's
+# class, the method that makes its launch).  A method before the draw may return the sampler's arguments to use from there on.  All
+# run inside graph capture: they launch kernels and rebuild that dict, and neither allocate device memory nor synchronise.
+BEFORE_DRAW = (
+    (Budget, "mask"),                 # first: what a row cannot afford is out before anything is counted or renormalised
+    (Repetition, "penalise"),         # finite amounts; ahead of the notes' first draw, which ``keep`` would else let stand unpenalised
+    (ClassSampling, "rewrite"),       # at the call's temperature, over the masked and penalised logits; temperature 1 from here on
+    (EntropySampling, "mask"),        # the last mask, at the sampler's temperature as it is here
+    (NoteState, "mask"),              # its first draw takes the logits as the others left them; then its mask and the second seed
+)
+AFTER_DRAW = (                        # not the reverse of the above:
+    (NoteState, "keep"),              # may put the first draw back in r.tok: ahead of everything that reads r.tok
+    (EntropySampling, "account"),     # the surprise of the token that was drawn, before the budget can replace it by a pad
+    (Budget, "account"),              # may replace the token by a pad: after the entropy's account, before the notes'
+    (NoteState, "account"),           # last: an ended row's pad has rule 0, so its held set stays what it was
+)
+
+
+class Chain:
+    """the stages a call has switched on (check_stages); an inert or absent one is not in it.  They are checked copies, so the
+    caller's objects are never staged and serve any number of calls.  The drivers stage the chain once, run it around every draw
+    (decode_step; generate_lookahead: the first half only) and finish it once"""
+
+    def __init__(self, stages=()):
+        self.stages = list(stages)
+        self.before, self.after = ([getattr(s, launch) for cls, launch in order for s in self.stages if type(s) is cls]
+                                   for order in (BEFORE_DRAW, AFTER_DRAW))
+
+    def find(self, cls):
+        """the chain's stage of that class, or None"""
+        return next((s for s in self.stages if type(s) is cls), None)
+
+    def stage(self, dev, *, rows: int, total: int, prior, lens, repeat: int = 1) -> None:
+        """once per call, each stage taking what it needs: row b * repeat + n of ``rows`` belongs to prompt b, lens[b] long"""
+        for s in self.stages:
+            s.stage(dev, rows=rows, total=total, prior=prior, lens=lens, repeat=repeat)
+
+    def before_draw(self, logits, V: int, r: SubBatch, sampler: dict) -> dict:
+        """the launches of BEFORE_DRAW on the step's logits; returns the arguments the draw (or the accept) takes"""
+        for launch in self.before:
+            sampler = launch(logits, V, r, sampler) or sampler        # None: the stage leaves the sampler as it is
+        return sampler
+
+    def after_draw(self, logits, V: int, r: SubBatch, sampler: dict, out) -> None:
+        """the launches of AFTER_DRAW; ``sampler``: what before_draw returned; ``out``: where the draw wrote its column, or None"""
+        for launch in self.after:
+            launch(logits, V, r, sampler, out)
+
+    def finish(self, width: int) -> None:
+        """after the last step, the one hand-back: entropy_sampling's state onto the object the caller passed, ``surprise``
+        NaN-padded to the ``width`` of the call's result (equal prior_lengths below the width of prior decode fewer columns)"""
+        es = self.find(EntropySampling)
+        if es is not None:
+            if es.surprise is not None and es.surprise.shape[1] < width:
+                es.surprise = torch.nn.functional.pad(es.surprise, (0, width - es.surprise.shape[1]), value=float("nan"))
+            es.caller.mu, es.caller.lse, es.caller.surprise = es.mu, es.lse, es.surprise
+
+
+def check_stages(model, temperature, *, budget: Optional[Budget] = None, note_rules=None, max_polyphony=None, repetition=None,
+                 class_sampling=None, entropy_sampling=None, lookahead=None, **context) -> Chain:
+    """every refusal of the stages' options (ValueError), on the host before any device work; ``budget``: generate_timed's, checked
+    there; ``context``: the rest of what ``switched_on`` takes.  Returns the call's Chain, of checked copies not yet staged"""
+    noted = dict(context, note_rules=note_rules, max_polyphony=max_polyphony)
+    stages = [budget, check_class_args(model, class_sampling, temperature, **noted),
+              check_entropy_args(model, entropy_sampling, temperature, lookahead=lookahead, **noted)]
+    if lookahead is not None:                             # ahead of the checks of the two options it refuses
+        refuse("lookahead", switched_on(repetition=repetition, **noted))
+    stages += [check_repeat_args(model, repetition, **context), check_note_args(model, note_rules, max_polyphony, **context)]
+    return Chain(s for s in stages if s is not None)
+
+
+def decode_step(w: Weights, r: SubBatch, sampler: dict, into_out: bool, chain: Chain = Chain()) -> None:
+    """one token for the rows of ``r``: the logits, the chain's launches before the draw, the draw, the chain's launches after
+    it.  ``sampler``: keyword arguments of ops.sample_topk_topp; ``into_out``: the draw also writes its column of ``r.out``"""
     logits = step_logits(w, r)
-    if bud is not None:
-        ops.budget_mask(logits, w.V, bud.cost, bud.remaining, bud.done)
-    if rep is not None:
-        rep.apply(logits, w.V, r)
-    if cs is not None:
-        cs.apply(logits, w.V, r, sampler["temperature"], sampler["allow_table"])
-        sampler = dict(sampler, temperature=1.0)
-    if es is not None:
-        es.mask(logits, w.V, r, sampler["temperature"], sampler["allow_table"])
-    out = r.out if sample_into_out else None
-    if notes is not None:
-        # the sampler draws by inverse CDF, so a draw from the masked logits is another token even where the unmasked draw of
-        # the same random number was legal.  Hence two draws: the first from the logits as they stand, with the call's seed and
-        # nothing written but notes.first; the second, below, from the masked logits with a seed of its own; notes_keep then
-        # puts a legal first draw in the second's place, and the row is the unconstrained row until that one breaks a rule
-        ops.sample_topk_topp(logits, w.V, next_tok=notes.first, advance=False, row0=r.b0, **r.step, **sampler)
-        ops.notes_mask(logits, w.V, notes.rule, notes.state, notes.max_on)
-        sampler = dict(sampler, seed=(int(sampler["seed"]) + NoteState.SECOND_SEED) % 2 ** 64)
+    sampler = chain.before_draw(logits, w.V, r, sampler)
+    out = r.out if into_out else None
     ops.sample_topk_topp(logits, w.V, next_tok=r.tok, out_tokens=out, probs_out=r.probs, advance=True, row0=r.b0, **r.step, **sampler)
-    if notes is not None:
-        ops.notes_keep(notes.first, r.tok, out, rule=notes.rule, state=notes.state, max_on=notes.max_on, V=w.V, **r.step)
-    if es is not None and es.accounting:
-        es.account(logits, w.V, r, sampler["temperature"])
-    if bud is not None:
-        ops.budget_account(r.tok, r.out, cost=bud.cost, remaining=bud.remaining, done=bud.done, count=bud.count,
-                           pad_token=bud.pad_token, inclusive=bud.inclusive, **r.step)
-    if notes is not None:
-        ops.notes_account(r.tok, notes.rule, notes.state, w.V)
+    chain.after_draw(logits, w.V, r, sampler, out)
 
 
 def capture_graphs(subs, step_rows) -> None:
@@ -999,37 +1058,35 @@ def decode_window(w: Weights, r: SubBatch, cache: KVCache, prior_i, lens, length
     return ts[-1] if ts else t0
 
 
-def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
+def generate_cached(model, prior, length, *, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, prefill,
                     return_cache, groups, masked_groups, prior_lengths, kv_cache, window=None, hop=None, samples_per_prompt=None,
-                    bud: Optional[Budget] = None, note_rules=None, max_polyphony=None, repetition=None, lookahead=None,
-                    draft="history", draft_ngram=3, stats=None, class_sampling=None, entropy_sampling=None):
-    """MusicTransformer.generate_cached (documented there).  ``bud``: generate_timed's budgets, not yet staged -- the steps run
-    decode_step_constrained and the loop stops once every row has ended"""
-    cs = check_class_args(model, class_sampling, temperature, groups=groups, masked_groups=masked_groups, note_rules=note_rules,
-                          max_polyphony=max_polyphony)
-    es = check_entropy_args(model, entropy_sampling, temperature, groups=groups, masked_groups=masked_groups, note_rules=note_rules,
-                            max_polyphony=max_polyphony, lookahead=lookahead)
+                    lookahead=None, draft="history", draft_ngram=3, stats=None, chain: Optional[Chain] = None, **options):
+    """MusicTransformer.generate_cached (documented there): the checks, the driver that the call selects, the hand-back.
+    ``options``: the stages' options as check_stages takes them; or ``chain``, the one generate_timed has built already"""
+    if chain is None:
+        chain = check_stages(model, temperature, lookahead=lookahead, grammar=grammar, groups=groups, masked_groups=masked_groups,
+                             return_cache=return_cache, window=window, hop=hop, kv_cache=kv_cache, prefill=prefill,
+                             samples_per_prompt=samples_per_prompt, **options)
+    sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     if lookahead is not None:
-        T, guide = check_lookahead_args(model, prior, lookahead, draft, draft_ngram, window=window, hop=hop, kv_cache=kv_cache,
-                                        samples_per_prompt=samples_per_prompt, groups=groups, masked_groups=masked_groups,
-                                        prefill=prefill, return_cache=return_cache, note_rules=note_rules,
-                                        max_polyphony=max_polyphony, repetition=repetition, bud=bud)
+        T, guide = check_lookahead_args(prior, lookahead, draft, draft_ngram)
         P, lens, _, _ = check_args(model, prior, length, False, "batched", prior_lengths, kv_cache)
-        return generate_lookahead(model, prior, P, lens, length, T, guide, int(draft_ngram),
-                                  dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed), grammar, use_graph,
-                                  return_probs, stats, cs, es)
-    rep = check_repeat_args(model, repetition, groups=groups, masked_groups=masked_groups)
-    notes = check_note_args(model, note_rules, max_polyphony, grammar=grammar, groups=groups, masked_groups=masked_groups,
-                            return_cache=return_cache)
+        return generate_lookahead(model, prior, P, lens, length, T, guide, int(draft_ngram), sampling, grammar, use_graph,
+                                  return_probs, stats, chain)
     P, lens, batched, hop = check_args(model, prior, length, return_probs, prefill, prior_lengths, kv_cache, window, hop, groups,
                                        masked_groups, samples_per_prompt, return_cache)
-    sampling = dict(temperature=temperature, top_k=top_k, top_p=top_p, seed=seed)
     if samples_per_prompt is not None:
-        res = generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs,
-                              notes, rep, cs, es)
-        if es is not None:
-            es.hand_back(entropy_sampling)
-        return res
+        res = generate_shared(model, prior, lens, length, int(samples_per_prompt), sampling, grammar, use_graph, return_probs, chain)
+    else:
+        res = generate_rows(model, prior, P, lens, batched, length, sampling, use_graph, return_probs, grammar, return_cache, groups,
+                            masked_groups, kv_cache, window, hop, chain)
+    chain.finish(prior.shape[1] + length)
+    return res
+
+
+def generate_rows(model, prior, P: int, lens, batched: bool, length: int, sampling: dict, use_graph: bool, return_probs: bool,
+                  grammar, return_cache: bool, groups, masked_groups: bool, kv_cache: str, window, hop, chain: Chain):
+    """generate_cached on a cache per row, its arguments checked; with a Budget in the chain the loop stops once every row has ended"""
     extra, prior, ragged = prior.shape[1] - P, prior[:, :P], lens is not None      # extra > 0: equal prior_lengths below the width
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -1065,22 +1122,12 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
         w = Weights(model, st, fused=B <= 32 and d <= 1024)
         probs_all, file = probs_filer(subs, total, V, pos_rows.long()) if return_probs else (None, None)
 
-        if bud is not None:
-            bud.stage(dev)
-        if notes is not None:                                 # what every prompt leaves held; the prefill below stays unconstrained
-            notes.stage(dev, prior, lens or [P] * B)
-        if rep is not None:
-            rep.stage(dev)
-        if cs is not None:
-            cs.stage(dev)
-        if es is not None:
-            es.stage(dev, B, total)
+        # the notes start from what every prompt leaves held; the prefill below stays unconstrained
+        chain.stage(dev, rows=B, total=total, prior=prior, lens=lens or [P] * B)
+        bud = chain.find(Budget)                              # what lets the loop stop early (its max_length >= 1: length > 0)
 
         def step_rows(r):                                     # length 0 still runs the last prompt token (its distribution)
-            if bud is not None or notes is not None or rep is not None or cs is not None or es is not None:
-                decode_step_constrained(w, r, sampler, bud is not None or length > 0, bud, notes, rep, cs, es)
-            else:
-                decode_step(w, r, sampler, length > 0)
+            decode_step(w, r, sampler, length > 0, chain)
         if window is not None:
             final_t = decode_window(w, subs[0], cache, prior_i, lens or [P] * B, length, window, hop, step_rows, use_graph, file,
                                     model.pad_token, bud)
@@ -1103,25 +1150,18 @@ def generate_cached(model, prior, length, temperature, top_k, top_p, seed, use_g
     pad = torch.nn.functional.pad                         # equal prior_lengths P < Pmax: pad_token / zeros up to Pmax + length
     toks = pad(out, (0, extra), value=model.pad_token) if extra else out
     res = (toks, pad(probs_all, (0, 0, 0, extra)) if extra else probs_all) if return_probs else toks
-    if es is not None:
-        if es.surprise is not None and extra:
-            es.surprise = pad(es.surprise, (0, extra), value=float("nan"))
-        es.hand_back(entropy_sampling)
     if window is not None:                                # the cache grows to the rows the full-width call would have
         extra = min(window, total + extra) - cache_rows
     return (res, *(cache.grow(extra) if extra else cache).result()) if return_cache else res
 
 
-def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, grammar, use_graph: bool, return_probs: bool,
-                    notes: Optional[NoteState] = None, rep: Optional[Repetition] = None, cs: Optional[ClassSampling] = None,
-                    es: Optional[EntropySampling] = None):
+def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, grammar, use_graph: bool, return_probs: bool, chain: Chain):
     """generate_cached(samples_per_prompt=N), its arguments checked: rows r = b * N + n, sample n of prompt b.  One batched
     prefill of the Bp prompts fills the prompt cache (pre_rows = len_b - 1 rows each); every row then resumes at its prompt's
     last token and runs the ragged step on R = Bp * N rows, whose attention reads the prompt's rows once for the samples of a
     prompt and appends to the row's own cache.  Row r draws with (seed, t, r), as it does in the call on the prompts repeated N
-    times.  ``notes``: a NoteState, not yet staged -- every row starts from its prompt's held notes.  ``rep``: a checked Repetition, not
-    yet staged -- stateless, so the samples of a prompt need nothing gathered.  ``cs``: a checked ClassSampling, likewise.  ``es``: a
-    checked EntropySampling, not yet staged -- every row, sample n of prompt b, carries a Mirostat threshold of its own"""
+    times.  ``chain`` is staged for the R rows: every row starts from its prompt's held notes and carries a Mirostat threshold of
+    its own; the stateless stages need nothing gathered for the samples of a prompt"""
     with decode_session(model) as st:
         (Bp, P), dev = prior.shape, st.param.device
         R, total, d, V = Bp * N, P + length, model.embedding_dim, model.vocab_size
@@ -1136,20 +1176,10 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
                            V if return_probs else None)
         sampler = dict(sampling, allow_table=ops.grammar_table(grammar, dev))
         probs_all, file = probs_filer([r], total, V, pos.long()) if return_probs else (None, None)
-        if notes is not None:
-            notes.stage(dev, prior, lens, repeat=N)
-        if rep is not None:
-            rep.stage(dev)
-        if cs is not None:
-            cs.stage(dev)
-        if es is not None:
-            es.stage(dev, R, total)
+        chain.stage(dev, rows=R, total=total, prior=prior, lens=lens, repeat=N)
 
         def step_rows(r_):                                    # length 0 still runs the last prompt token (its distribution)
-            if notes is not None or rep is not None or cs is not None or es is not None:
-                decode_step_constrained(w, r_, sampler, length > 0, None, notes, rep, cs, es)
-            else:
-                decode_step(w, r_, sampler, length > 0)
+            decode_step(w, r_, sampler, length > 0, chain)
         run_steps([r], max(length, 1), step_rows, graph=use_graph, on_step=file)
     return (out, probs_all) if return_probs else out
 
@@ -1158,40 +1188,23 @@ def generate_shared(model, prior, lens, length: int, N: int, sampling: dict, gra
 LOOKAHEAD_POLL = 32                                       # steps between two reads of the rows' done flags
 
 
-def check_lookahead_args(model, prior, lookahead, draft, draft_ngram, *, window=None, hop=None, kv_cache="bf16",
-                         samples_per_prompt=None, groups=None, masked_groups=False, prefill="auto", return_cache=False,
-                         note_rules=None, max_polyphony=None, repetition=None, bud=None):
-    """every refusal of generate_cached(lookahead=T) (ValueError), on the host before any device work.  Returns (T, the guide as
-    an integer tensor [B, >= Pmax] or None for history drafts)"""
-    def integer(name, v, lo, hi):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+def check_lookahead_args(prior, lookahead, draft, draft_ngram):
+    """the refusals of generate_cached(lookahead=T)'s own arguments (ValueError), on the host before any device work; what it is
+    not combined with: check_stages.  Returns (T, the guide as an integer tensor [B, >= Pmax] or None for history drafts)"""
+    for name, v, lo, hi in (("lookahead", lookahead, 2, ops.LOOKAHEAD_MAX_T), ("draft_ngram", draft_ngram, 1, ops.LOOKAHEAD_MAX_NGRAM)):
+        if not integer_in(v, lo, hi):
             raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
-        return int(v)
-    T = integer("lookahead", lookahead, 2, ops.LOOKAHEAD_MAX_T)
-    integer("draft_ngram", draft_ngram, 1, ops.LOOKAHEAD_MAX_NGRAM)
-    for on, name, why in ((window is not None or hop is not None, "window / hop", "a re-anchor would have to fall between two accepted tokens"),
-                          (kv_cache != "bf16", f"kv_cache={kv_cache!r}", "the T-query attention has no 8-bit form"),
-                          (samples_per_prompt is not None, "samples_per_prompt", "the shared prompt cache is another attention kernel"),
-                          ((groups or 1) > 1 or masked_groups, "groups / masked_groups", "the rows advance by different amounts as one group"),
-                          (prefill == "token", "prefill='token'", "the prompt is prefilled in one batched pass"),
-                          (return_cache, "return_cache", "cache rows above a row's last position hold rejected guesses"),
-                          (note_rules is not None or max_polyphony is not None, "note_rules / max_polyphony",
-                           "the held-note state is sequential: position i + 1 is masked by the token at i"),
-                          (repetition is not None, "repetition", "the penalty of position i + 1 counts the token at i"),
-                          (bud is not None, "generate_timed", "a budget's state is sequential")):
-        if on:
-            raise ValueError(f"lookahead is not combined with {name} ({why}): later work")
     if isinstance(draft, str):
         if draft != "history":
             raise ValueError(f"draft must be 'history' or a guide, integers [B, >= Pmax], got {draft!r}")
-        return T, None
+        return int(lookahead), None
     guide = torch.as_tensor(draft)
     B, Pmax = prior.shape
     if guide.dtype not in (torch.int8, torch.uint8, torch.int16, torch.int32, torch.int64) or guide.dim() != 2 \
             or guide.shape[0] != B or guide.shape[1] < Pmax:
         raise ValueError(f"draft must be 'history' or a guide, integers [B, >= Pmax] = [{B}, >= {Pmax}], got {guide.dtype} "
                          f"{tuple(guide.shape)}")
-    return T, guide
+    return int(lookahead), guide
 
 
 class LookaheadCache:
@@ -1209,17 +1222,16 @@ class LookaheadCache:
 
 
 def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, ngram: int, sampling: dict, grammar, use_graph: bool,
-                       return_probs: bool, stats, cs: Optional[ClassSampling] = None, es: Optional[EntropySampling] = None):
+                       return_probs: bool, stats, chain: Chain):
     """generate_cached(lookahead=T), its arguments checked.  A step of the B rows is the ragged step on B * T rows: row b * T + i
     runs position t_b + i on draft[b, i] (ops.lookahead_draft), the attention is ops.rel_attn_decode_multi, and
     ops.lookahead_accept draws every position as the one-token call draws it -- (seed, column, b) -- keeps the prefix whose
     guesses were right and advances row b by it.  Nothing is rolled back: a cache row a rejected guess wrote lies at or above the
     row's new position and is rewritten by the next step before any query reaches it.  The step is captured once and replayed
     in runs of LOOKAHEAD_POLL; a row at its last column sets its ``done`` flag and the loop stops when all have, after at most
-    ``length`` steps.  ``cs``: a checked ClassSampling, not yet staged -- row-wise and stateless, it rewrites the B * T rows' logits
-    (the grammar row of row b * T + i is that of draft[b, i]) and the accept draws at temperature 1.  ``es``: a checked
-    EntropySampling without tau and trace (check_entropy_args) -- min-p and typical are row-wise and stateless too, a mask on the
-    B * T rows after ``cs`` at the accept's temperature"""
+    ``length`` steps.  ``chain`` holds row-wise, stateless stages only (check_stages): class sampling and the entropy mask without
+    tau and trace.  Its launches before the draw run on the B * T rows' logits (the grammar row of row b * T + i is that of
+    draft[b, i]), and the accept draws with the arguments they hand on: at temperature 1 after class sampling"""
     extra, prior = prior.shape[1] - P, prior[:, :P]
     with decode_session(model) as st:
         B, total, dev = prior.shape[0], P + length, st.param.device
@@ -1241,21 +1253,12 @@ def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, n
         r = SubBatch.alloc(0, B * T, pos_rows, True, draft.view(-1), out, LookaheadCache(cache, pos, T),
                            ops.rel_attn_decode_multi_workspace(B, T, total, d, dev), d)
         sampler = dict(sampling, allow_table=ops.grammar_table(grammar, dev))
-
-        accept = sampler
-        if cs is not None:
-            cs.stage(dev)
-            accept = dict(sampler, temperature=1.0)
-        if es is not None:
-            es.stage(dev, B * T, total)
+        chain.stage(dev, rows=B * T, total=total, prior=prior, lens=lens or [P] * B, repeat=T)
 
         def step_rows(r_):
             ops.lookahead_draft(tok, out, pos, draft, pos_rows, total, model.pad_token, guide=guide, ngram=ngram)
             logits = step_logits(w, r_)
-            if cs is not None:
-                cs.apply(logits, V, r_, sampler["temperature"], sampler["allow_table"])
-            if es is not None:
-                es.mask(logits, V, r_, accept["temperature"], sampler["allow_table"])
+            accept = chain.before_draw(logits, V, r_, sampler)
             ops.lookahead_accept(logits, V, pos, draft, limit, tok, out, poll.done, probs_all=probs_all, stats=count, **accept)
         if length > 0:
             run_steps([r], length, step_rows, graph=use_graph, budget=poll)
@@ -1267,27 +1270,23 @@ def generate_lookahead(model, prior, P: int, lens, length: int, T: int, guide, n
     return (toks, pad(probs_all, (0, 0, 0, extra)) if extra else probs_all) if return_probs else toks
 
 
-def generate_timed(model, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,
-                   prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules=None, max_polyphony=None, repetition=None,
-                   class_sampling=None, entropy_sampling=None):
-    """MusicTransformer.generate_timed (documented there): generate_cached's driver with a Budget"""
+def generate_timed(model, prior, budget, cost, max_length, *, inclusive, poll, temperature, top_k, top_p, seed, use_graph, grammar,
+                   prior_lengths, kv_cache, window, hop, return_probs, refused, **options):
+    """MusicTransformer.generate_timed (documented there): generate_cached with a Budget in its chain; ``options``: check_stages's"""
     B = prior.shape[0]
-    check_repeat_args(model, repetition)
-    check_class_args(model, class_sampling, temperature, note_rules=note_rules, max_polyphony=max_polyphony)
-    es = check_entropy_args(model, entropy_sampling, temperature, note_rules=note_rules, max_polyphony=max_polyphony)
-    budgets, cost_i = check_budget_args(model, B, budget, cost, max_length, poll, refused)
-    check_args(model, prior, max_length, return_probs, "auto", prior_lengths, kv_cache, window, hop)     # before any device work
-    bud = Budget(budgets, cost_i, model.pad_token, bool(inclusive), int(poll))
-    res = generate_cached(model, prior, max_length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar, "auto",
-                          False, None, False, prior_lengths, kv_cache, window, hop, None, bud, note_rules, max_polyphony, repetition,
-                          class_sampling=class_sampling, entropy_sampling=entropy_sampling)
+    bud = Budget(*check_budget_args(model, B, budget, cost, max_length, poll, refused), model.pad_token, bool(inclusive), int(poll))
+    chain = check_stages(model, temperature, budget=bud, grammar=grammar, **options)
+    res = generate_cached(model, prior, max_length, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, use_graph=use_graph,
+                          return_probs=return_probs, grammar=grammar, prefill="auto", return_cache=False, groups=None,
+                          masked_groups=False, prior_lengths=prior_lengths, kv_cache=kv_cache, window=window, hop=hop, chain=chain)
+    es = chain.find(EntropySampling)
     tokens, probs = res if return_probs else (res, None)
     # what every row spent: the cost of the events it kept, columns P_b .. P_b + count_b - 1
     start = torch.tensor(_prompt_lengths(prior, prior_lengths) or [prior.shape[1]] * B, device=tokens.device)[:, None]
     cols = torch.arange(tokens.shape[1], device=tokens.device)[None, :]
     kept = (cols >= start) & (cols < start + bud.count[:, None])
     if es is not None and es.trace:                       # an ended row went on stepping on pads: nothing generated
-        entropy_sampling.surprise.masked_fill_(~kept, float("nan"))
+        es.surprise.masked_fill_(~kept, float("nan"))     # the tensor the caller's object holds too (EntropySampling.finish)
     spent = torch.where(kept, bud.cost[tokens.long()], 0).sum(1)
     info = dict(steps_run=bud.steps_run, spent=spent, remaining=bud.remaining, done=bud.done.bool())
     if return_probs:

@@ -505,10 +505,13 @@ class MusicTransformer(torch.nn.Module):
         work); ``groups`` > 1, ``masked_groups`` (later work).  ``generate_beam``, ``generate`` and ``Event_Melody_RNN`` do not
         take the keyword.  None (default), or an object with min_p 0, typical_p 1, no tau and no trace: the call as described
         above, untouched, with no new launch."""
-        return decode.generate_cached(self, prior, length, temperature, top_k, top_p, seed, use_graph, return_probs, grammar,
-                                      prefill, return_cache, groups, masked_groups, prior_lengths, kv_cache, window, hop,
-                                      samples_per_prompt, None, note_rules, max_polyphony, repetition, lookahead, draft,
-                                      draft_ngram, stats, class_sampling, entropy_sampling)
+        return decode.generate_cached(self, prior, length, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                                      use_graph=use_graph, return_probs=return_probs, grammar=grammar, prefill=prefill,
+                                      return_cache=return_cache, groups=groups, masked_groups=masked_groups,
+                                      prior_lengths=prior_lengths, kv_cache=kv_cache, window=window, hop=hop,
+                                      samples_per_prompt=samples_per_prompt, lookahead=lookahead, draft=draft,
+                                      draft_ngram=draft_ngram, stats=stats, note_rules=note_rules, max_polyphony=max_polyphony,
+                                      repetition=repetition, class_sampling=class_sampling, entropy_sampling=entropy_sampling)
 
     @torch.no_grad()
     def generate_timed(self, prior: torch.Tensor, budget, cost, max_length: int, *, inclusive: bool = True, poll: int = 32,
@@ -543,9 +546,12 @@ class MusicTransformer(torch.nn.Module):
         no row overshoots; ``probs`` are then softmax(bf16(ln p')).
         ``entropy_sampling``: as in ``generate_cached`` -- the last mask before the sampler, and its account runs before the
         budget's, which may replace the token by a pad; the trace of an ended row is NaN from its end on."""
-        return decode.generate_timed(self, prior, budget, cost, max_length, inclusive, poll, temperature, top_k, top_p, seed,
-                                     use_graph, grammar, prior_lengths, kv_cache, window, hop, return_probs, refused, note_rules,
-                                     max_polyphony, repetition, class_sampling, entropy_sampling)
+        return decode.generate_timed(self, prior, budget, cost, max_length, inclusive=inclusive, poll=poll, temperature=temperature,
+                                     top_k=top_k, top_p=top_p, seed=seed, use_graph=use_graph, grammar=grammar,
+                                     prior_lengths=prior_lengths, kv_cache=kv_cache, window=window, hop=hop,
+                                     return_probs=return_probs, refused=refused, note_rules=note_rules,
+                                     max_polyphony=max_polyphony, repetition=repetition, class_sampling=class_sampling,
+                                     entropy_sampling=entropy_sampling)
 
     @torch.no_grad()
     def generate_beam(self, prior: torch.Tensor, length: int, beam_size: int, temperature: float = 1.0, stochastic: bool = False,
@@ -574,8 +580,9 @@ class MusicTransformer(torch.nn.Module):
         if note_rules is not None or max_polyphony is not None:
             raise ValueError("generate_beam is not combined with note_rules / max_polyphony (a beam's held notes would have to "
                              "follow its parent through the reorder: not built)")
-        return decode.generate_beam(self, prior, length, beam_size, temperature, stochastic, seed, grammar, prior_lengths, kv_cache,
-                                    use_graph, return_beams)
+        return decode.generate_beam(self, prior, length, beam_size, temperature=temperature, stochastic=stochastic, seed=seed,
+                                    grammar=grammar, prior_lengths=prior_lengths, kv_cache=kv_cache, use_graph=use_graph,
+                                    return_beams=return_beams)
 
     @torch.no_grad()
     def score(self, x: torch.Tensor, lengths=None, from_pos=None, temperature: float = 1.0, grammar=None, logits: str = "auto",
