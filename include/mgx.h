@@ -34,8 +34,8 @@ typedef enum {
 /* thread-local, NUL-terminated description of the last failure on this thread */
 const char* mgx_last_error(void);
 /* library/ABI version (bumped on any signature change) */
-int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM; 32: draft-and-verify decode: mgx_lookahead_draft, mgx_rel_attn_decode_multi (with _splits and _workspace), mgx_lookahead_accept, MGX_LOOKAHEAD_MAX_T, MGX_LOOKAHEAD_MAX_NGRAM; 33: per-class temperature, top-k and top-p on the KV-cache decode: mgx_class_logits, MGX_CLASS_MAX; 34: entropy-aware sampling on the KV-cache decode (min-p, typical, Mirostat v2): mgx_entropy_mask, mgx_entropy_account */
-#define MGX_ABI_VERSION 34
+int mgx_abi_version(void);   /* 2: mgx_rel_attn_bwd takes a workspace; 3: mgx_linear_dx takes an addend; 4: mgx_linear_dw_grouped; 5: GRU training ops; 6: sampler grammar mask; 7: mgx_linear_ln_fwd; 8: mgx_rel_attn_fwd/_weights take a workspace; 9: mgx_rel_attn_decode takes a workspace (split-K); 10: mgx_linear_dw_grouped takes a workspace; 11: decode K/V caches are head-major [B,h,Lmax,64]; 12: mgx_decode_embed_linear, mgx_rel_attn_decode_splits; attention partials are 68 floats (acc[64], m, l, 2 pad); 13: mgx_rel_attn_bwd_parts: dK/dV stores the dS tiles, bits 1/3 read them, bit 5 = dQ by recomputation; 14: mgx_gru_step_fwd/bwd, mgx_gru_step_x_fwd, fragment-ordered weights (*_frag), mgx_rel_attn_fwd_nomask; 15: the sampler over rows [row0, row0+B) of a larger batch; 16: mgx_smooth_ce_bwd takes a device-side scale, mgx_pad_bitmap a flag, mgx_set_deterministic; 17: mgx_rel_attn_bwd_parts bit 6; 18: mgx_pad_bitmap's flag records LEADING pads only, mgx_stream_create_cu_mask / mgx_stream_set_cus / mgx_stream_cus / mgx_stream_destroy, mgx_set_deterministic_stream, mgx_linear_kernel_id; 19: per-row decode positions (ragged prompts); 20: 8-bit (fp8 e4m3fn) K/V cache: mgx_kv_store_fp8, mgx_rel_attn_decode_fp8; 21: re-anchored decode window: the sampler's base, mgx_decode_reanchor; 22: beam search on the KV-cache decode: mgx_beam_select, mgx_kv_beam_reorder, mgx_beam_backtrack; 23: scheduled sampling for Event_Melody_RNN: mgx_gru_step_x_fwd_save, mgx_dropout_bf16_at, mgx_gru_next_event; 24: scoring: mgx_token_logprob, mgx_linear_logprob, mgx_score_reduce; 25: global gradient-norm clipping and the non-finite-step guard: mgx_grad_norm, mgx_adam_step_clipped; 26: N samples per prompt over a shared prompt K/V cache: mgx_rel_attn_decode_shared, mgx_rel_attn_decode_shared_splits, mgx_rel_attn_decode_shared_workspace; 27: per-row length budgets on the KV-cache decode: mgx_budget_mask, mgx_budget_account; 28: per-row held-note state on the KV-cache decode: mgx_notes_mask, mgx_notes_account, mgx_notes_keep, MGX_NOTE_WORDS; 29: train-time augmentation on the device: mgx_crop_augment; 30: one step-position convention (pos_dev, base_dev, per_row) and one entry point per decode operation: the _ragged, _rows and _window entry points of ABI 15 / 19 / 20 / 21 are gone, their namesakes take per_row (the sampler also row0 and base_dev; mgx_decode_reanchor takes per_row next to its counters); 31: repetition control on the KV-cache decode: mgx_repeat_penalty, MGX_REPEAT_MAX_WINDOW, MGX_REPEAT_MAX_NGRAM; 32: draft-and-verify decode: mgx_lookahead_draft, mgx_rel_attn_decode_multi (with _splits and _workspace), mgx_lookahead_accept, MGX_LOOKAHEAD_MAX_T, MGX_LOOKAHEAD_MAX_NGRAM; 33: per-class temperature, top-k and top-p on the KV-cache decode: mgx_class_logits, MGX_CLASS_MAX; 34: entropy-aware sampling on the KV-cache decode (min-p, typical, Mirostat v2): mgx_entropy_mask, mgx_entropy_account; 35: AdamW per parameter group, frozen parameters and a weight EMA in the Adam sweep: mgx_adam_step_groups */
+#define MGX_ABI_VERSION 35
 /* number of visible HIP devices, or a negative mgx_status */
 int mgx_device_count(void);
 
@@ -234,6 +234,28 @@ int mgx_grad_norm(const float* g, size_t n, float gscale, float max_norm, double
  * after a skipped one is that of step + 1): a device-side counter would cost the host a read for every state_dict.        */
 int mgx_adam_step_clipped(float* p, const float* g, float* m, float* v, uint16_t* shadow, size_t n, float lr, float beta1,
                           float beta2, float eps, int step, const mgx_clip_state* state, void* stream);
+/* ---- K11c (ABI 35): decoupled weight decay, frozen parameters and a moving average of the weights, in the same sweep
+ * torch.optim.AdamW with param_groups, torch.optim.swa_utils.AveragedModel
+ * The flat buffer is cut into chunks of 64 elements; group_of uint8 [ceil(n / 64)] names the group of each (a caller that places
+ * every parameter at a multiple of 64 elements never has two parameters in a chunk), lr_scale and weight_decay f32 [n_groups],
+ * 1 <= n_groups <= 256, hold the groups' settings; all three are DEVICE arrays.  Per element of a chunk of group k, with
+ * s = lr_scale[k] and w = weight_decay[k], everything in fp32 and in torch.optim.AdamW's order:
+ *   s == 0, or group_of >= n_groups (outside the contract; the byte is then never used as an index):
+ *           the element is FROZEN -- nothing is stored for it, neither p, m, v, shadow nor ema
+ *   else    p <- p * (1 - lr s w);  mgx_adam_step's update with lr s in place of lr;  shadow <- bf16(p) if shadow;
+ *           ema <- ema_decay * ema + (1 - ema_decay) * p (the new p) if ema
+ * The gradient scale is gscale if state == NULL, else state->scale read on the device, and a set state->skipped_last makes the
+ * kernel return before its first store (mgx_adam_step_clipped's rule; ema keeps its bits too).  shadow and ema may be NULL.
+ * With one group (1, 0) and ema == NULL the result is BIT-IDENTICAL to mgx_adam_step (state == NULL) and to
+ * mgx_adam_step_clipped (state given): p * (1 - 0) is exact and the per-element code is shared.
+ * MGX_ERR_NULL: p, g, m, v, group_of, lr_scale or weight_decay is NULL.  MGX_ERR_SHAPE: n == 0, step < 1, n_groups outside
+ * 1 .. 256, ema given and ema_decay outside [0, 1), p / g / m / v / ema not 16-byte aligned, shadow / state not 8-byte aligned,
+ * a table not 4-byte aligned.  Nothing is launched then.  Same grid as mgx_adam_step; no atomics.                         */
+int mgx_adam_step_groups(float* p, const float* g, float* m, float* v, uint16_t* shadow, float* ema, size_t n,
+                         float lr, float beta1, float beta2, float eps, int step, float gscale,
+                         const mgx_clip_state* state,
+                         const uint8_t* group_of, const float* lr_scale, const float* weight_decay, int n_groups,
+                         float ema_decay, void* stream);
 /* shadow bf16 [n] = round(p f32 [n]): nearest even, subnormals kept, +-inf kept, NaN -> a NaN (payload unspecified) */
 int mgx_cast_bf16(const float* p, uint16_t* shadow, size_t n, void* stream);
 

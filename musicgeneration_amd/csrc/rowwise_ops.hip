@@ -710,25 +710,57 @@ extern "C" int mgx_smooth_ce_bwd(const uint16_t* logits, const int32_t* target, 
 // K11  Adam on one flat buffer + bf16 shadow                                train.py:143
 // =================================================================================================
 // One element of torch.optim.Adam on g * gscale: p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps).  Updates m and v, returns the new p.
+// The two sums are written as the fused multiply-adds the compiler made of them when it was free to choose -- and it chose
+// differently for m in the vector loop (VEC: the product b1 m rounded, then one fma) and in the tail (the product (1 - b1) g
+// rounded): pinned here, so that every kernel built on this function gives the same bits whatever else its loop does.
+template <bool VEC>
 MGX_DEV float adam_update(float p, float g, float& m, float& v, float lr, float b1, float b2, float eps, float bc1, float bc2s,
                           float gscale) {
     const float gk = g * gscale;
-    m = b1 * m + (1.f - b1) * gk;
-    v = b2 * v + (1.f - b2) * gk * gk;
+    m = VEC ? __builtin_fmaf(1.f - b1, gk, b1 * m) : __builtin_fmaf(b1, m, (1.f - b1) * gk);
+    v = __builtin_fmaf(b2, v, (1.f - b2) * gk * gk);
     return p - (lr / bc1) * m / (sqrtf(v) / bc2s + eps);
 }
-// The sweep of both Adam kernels: f32x4 groups in a grid-stride loop, then the n % 4 tail by the first threads of the grid.
+// What mgx_adam_step_groups adds to the sweep: the group of every 64-element chunk, the per-group tables, the averaged copy.
+struct AdamGroups {
+    const uint8_t* __restrict__ group_of;
+    const float* __restrict__ lr_scale;
+    const float* __restrict__ weight_decay;
+    float* __restrict__ ema;
+    unsigned n_groups;
+    float ema_decay;
+};
+// lr and the decay factor 1 - lr w of a chunk's group -> false: the chunk is frozen (scale 0, or a byte outside the tables, which
+// is never used as an index) and nothing of it is stored
+MGX_DEV bool adam_group(const AdamGroups& G, size_t chunk, float lr, float& lrk, float& keep) {
+    const unsigned k = G.group_of[chunk];
+    if (k >= G.n_groups) return false;
+    const float s = G.lr_scale[k];
+    if (s == 0.f) return false;
+    lrk = lr * s;
+    keep = 1.f - lrk * G.weight_decay[k];
+    return true;
+}
+// The sweep of all Adam kernels: f32x4 groups in a grid-stride loop, then the n % 4 tail by the first threads of the grid.
+// GROUPS: AdamW per chunk group -- p * (1 - lr s w) first, then the same update with lr s -- and the moving average of the new p.
+// A parameter starts at a multiple of 64 elements, so the 16 f32x4 of a chunk share one group byte (a wave reads 4 of them).
+template <bool GROUPS>
 MGX_DEV void adam_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                         uint16_t* __restrict__ shadow, size_t n, float lr, float b1, float b2, float eps, float bc1, float bc2s,
-                        float gscale) {
+                        float gscale, const AdamGroups& G) {
     const size_t n4 = n >> 2;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+        float lrk = lr, keep = 1.f;
+        if constexpr (GROUPS) {
+            if (!adam_group(G, i >> 4, lr, lrk, keep)) continue;
+        }
         f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float mk = mm[k], vk = vv[k];
-            pp[k] = adam_update(pp[k], gg[k], mk, vk, lr, b1, b2, eps, bc1, bc2s, gscale);
+            if constexpr (GROUPS) pp[k] *= keep;
+            pp[k] = adam_update<true>(pp[k], gg[k], mk, vk, lrk, b1, b2, eps, bc1, bc2s, gscale);
             mm[k] = mk; vv[k] = vk;
         }
         ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
@@ -736,23 +768,39 @@ MGX_DEV void adam_sweep(float* __restrict__ p, const float* __restrict__ g, floa
             u32x2 w = {pack_bf16x2(pp.x, pp.y), pack_bf16x2(pp.z, pp.w)};
             ((u32x2*)shadow)[i] = w;
         }
+        if constexpr (GROUPS) {
+            if (G.ema) {
+                f32x4 ee = ((f32x4*)G.ema)[i];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) ee[k] = G.ema_decay * ee[k] + (1.f - G.ema_decay) * pp[k];
+                ((f32x4*)G.ema)[i] = ee;
+            }
+        }
     }
     // tail (n % 4)
     const size_t t0 = n4 << 2;
     const size_t i = t0 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
-        float mk = m[i], vk = v[i];
-        const float pk = adam_update(p[i], g[i], mk, vk, lr, b1, b2, eps, bc1, bc2s, gscale);
+        float lrk = lr, keep = 1.f;
+        if constexpr (GROUPS) {
+            if (!adam_group(G, i >> 6, lr, lrk, keep)) return;
+        }
+        float mk = m[i], vk = v[i], pk = p[i];
+        if constexpr (GROUPS) pk *= keep;
+        pk = adam_update<false>(pk, g[i], mk, vk, lrk, b1, b2, eps, bc1, bc2s, gscale);
         m[i] = mk; v[i] = vk;
         p[i] = pk;
         if (shadow) shadow[i] = f32_to_bf16(pk);
+        if constexpr (GROUPS) {
+            if (G.ema) G.ema[i] = G.ema_decay * G.ema[i] + (1.f - G.ema_decay) * pk;
+        }
     }
 }
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v,
                                                    uint16_t* __restrict__ shadow, size_t n, float lr, float b1,
                                                    float b2, float eps, float bc1, float bc2s, float gscale) {
-    adam_sweep(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale);
+    adam_sweep<false>(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale, AdamGroups{});
 }
 // The same sweep with the gradient scale of mgx_grad_norm, read from device memory; a skipped step stores nothing.
 __global__ __launch_bounds__(256) void adam_clipped_kernel(float* __restrict__ p, const float* __restrict__ g,
@@ -762,7 +810,19 @@ __global__ __launch_bounds__(256) void adam_clipped_kernel(float* __restrict__ p
                                                            const mgx_clip_state* __restrict__ state) {
     const float gscale = state->scale;                 // uniform: one scalar load for the wave
     if (state->skipped_last) return;
-    adam_sweep(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale);
+    adam_sweep<false>(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale, AdamGroups{});
+}
+// The grouped sweep (K11c); state == NULL: gscale as given, else mgx_adam_step_clipped's rule
+__global__ __launch_bounds__(256) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                          float* __restrict__ m, float* __restrict__ v,
+                                                          uint16_t* __restrict__ shadow, size_t n, float lr, float b1,
+                                                          float b2, float eps, float bc1, float bc2s, float gscale,
+                                                          const mgx_clip_state* __restrict__ state, AdamGroups G) {
+    if (state) {
+        gscale = state->scale;
+        if (state->skipped_last) return;
+    }
+    adam_sweep<true>(p, g, m, v, shadow, n, lr, b1, b2, eps, bc1, bc2s, gscale, G);
 }
 
 // Global gradient norm, launch 1: workspace[block] = sum of g[i]^2 over the block's grid-stride share, in fp64 from the first
@@ -817,7 +877,7 @@ __global__ __launch_bounds__(256) void cast_bf16_kernel(const float* __restrict_
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) s[i] = f32_to_bf16(p[i]);
 }
 
-// the host's part of both Adam entry points: bias corrections of `step` (bc1 = 1 - b1^step, bc2s = sqrt(1 - b2^step)) and the grid
+// the host's part of the Adam entry points: bias corrections of `step` (bc1 = 1 - b1^step, bc2s = sqrt(1 - b2^step)) and the grid
 struct AdamLaunch { float bc1, bc2s; unsigned blocks; };
 static AdamLaunch adam_launch(size_t n, float beta1, float beta2, int step) {
     size_t blocks = (n / 4 + 255) / 256;
@@ -870,6 +930,26 @@ extern "C" int mgx_adam_step_clipped(float* p, const float* g, float* m, float* 
     hipLaunchKernelGGL(adam_clipped_kernel, dim3(a.blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n,
                        lr, beta1, beta2, eps, a.bc1, a.bc2s, state);
     MGX_CHECK_LAUNCH("mgx_adam_step_clipped");
+    return MGX_OK;
+}
+extern "C" int mgx_adam_step_groups(float* p, const float* g, float* m, float* v, uint16_t* shadow, float* ema, size_t n,
+                                    float lr, float beta1, float beta2, float eps, int step, float gscale,
+                                    const mgx_clip_state* state, const uint8_t* group_of, const float* lr_scale,
+                                    const float* weight_decay, int n_groups, float ema_decay, void* stream) {
+    MGX_REQUIRE(p && g && m && v && group_of && lr_scale && weight_decay, MGX_ERR_NULL, "mgx_adam_step_groups: NULL pointer");
+    MGX_REQUIRE(n > 0 && step >= 1, MGX_ERR_SHAPE, "mgx_adam_step_groups: need n>0 and step>=1 (step=%d)", step);
+    MGX_REQUIRE(n_groups >= 1 && n_groups <= 256, MGX_ERR_SHAPE, "mgx_adam_step_groups: n_groups must be 1 .. 256, got %d", n_groups);
+    MGX_REQUIRE(!ema || (ema_decay >= 0.f && ema_decay < 1.f), MGX_ERR_SHAPE,
+                "mgx_adam_step_groups: ema_decay must be in [0, 1), got %g", (double)ema_decay);
+    MGX_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0 &&
+                    (((uintptr_t)shadow | (uintptr_t)state) & 7) == 0 && ((uintptr_t)lr_scale & 3) == 0 &&
+                    ((uintptr_t)weight_decay & 3) == 0,
+                MGX_ERR_SHAPE, "mgx_adam_step_groups: p, g, m, v, ema must be 16-byte aligned (shadow, state: 8; the tables: 4)");
+    const AdamLaunch a = adam_launch(n, beta1, beta2, step);
+    const AdamGroups G = {group_of, lr_scale, weight_decay, ema, (unsigned)n_groups, ema_decay};
+    hipLaunchKernelGGL(adam_groups_kernel, dim3(a.blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, shadow, n,
+                       lr, beta1, beta2, eps, a.bc1, a.bc2s, gscale, state, G);
+    MGX_CHECK_LAUNCH("mgx_adam_step_groups");
     return MGX_OK;
 }
 extern "C" int mgx_cast_bf16(const float* p, uint16_t* shadow, size_t n, void* stream) {

@@ -122,6 +122,8 @@ def get_options(argv=None):
                            '(e.g. 3; not with --lookahead)')
     parser.add_option('--mirostat-eta', dest='mirostat_eta', type='float', default=None,
                       help="with --mirostat: the loop's learning rate (0 .. 1; default 0.1)")
+    parser.add_option('--ema', dest='ema', action='store_true', default=False,
+                      help="sample from the checkpoint's 'net_ema' (train.py --ema-decay), not from 'net'")
     return parser.parse_args(argv)[0]
 
 
@@ -455,12 +457,13 @@ def main(argv=None):
     if o.lookahead:
         cached.update(lookahead=o.lookahead, draft_ngram=o.draft_ngram, stats=look)
     ragged = _ragged_priors(o) if o.condition_files is not None else None     # checked before any model or device work
+    net = utils.load_net(o.load_path, o.ema)
     device = torch.device('cuda:0')
     vocab = vocab_of(o.repr)
     mt = MusicTransformer(embedding_dim=o.d_model, vocab_size=vocab, num_layer=o.num_layers, max_seq=o.max_seq,
                           dropout=0)
-    if o.load_path:
-        mt.load_state_dict(torch.load(o.load_path, map_location='cpu', weights_only=False)['net'])
+    if net is not None:
+        mt.load_state_dict(net)
     mt.to(device).eval()
     if o.data_path and os.path.isdir(o.data_path):
         ds = Data(o.data_path, o.max_seq)

@@ -386,6 +386,51 @@ def adam_step_clipped(p, g, m, v, shadow, lr, beta1, beta2, eps, step, state):
                                             float(beta2), float(eps), int(step), ptr(state), stream_ptr()), "mgx_adam_step_clipped")
 
 
+ADAM_CHUNK = 64                                            # elements per byte of mgx_adam_step_groups' group_of
+ADAM_MAX_GROUPS = 256
+
+
+def adam_group_chunks(offsets, names, group_of_name, numel=None):
+    """the chunk table of mgx_adam_step_groups as a list of ints, one per ADAM_CHUNK elements of a flat buffer: ``offsets[name]``
+    = (start, numel) as in layers.FlatStore, ``names`` in buffer order, ``group_of_name[name]`` the parameter's group.  Every
+    chunk from a parameter's start up to the next parameter's start (the buffer's end, ``numel``, for the last) takes that
+    parameter's group: the zero padding behind a parameter belongs to it.  Pure host code; ValueError for a start that is no
+    multiple of ADAM_CHUNK (a chunk would hold two parameters), overlapping parameters or a group outside 0 .. 255"""
+    starts = [offsets[n][0] for n in names]
+    ends = starts[1:] + [max([numel or 0] + [offsets[n][0] + offsets[n][1] for n in names])]
+    table = [0] * (starts[0] // ADAM_CHUNK if names else 0)               # a gap before the first parameter: nothing lives there
+    for n, lo, hi in zip(names, starts, ends):
+        k = group_of_name[n]
+        if lo % ADAM_CHUNK:
+            raise ValueError(f"parameter {n} starts at element {lo}, not a multiple of {ADAM_CHUNK}")
+        if hi < lo + offsets[n][1]:
+            raise ValueError(f"parameter {n} overlaps the next one")
+        if not (isinstance(k, int) and 0 <= k < ADAM_MAX_GROUPS):
+            raise ValueError(f"group of {n} must be an int in 0 .. {ADAM_MAX_GROUPS - 1}, got {k!r}")
+        table += [k] * ((hi - lo + ADAM_CHUNK - 1) // ADAM_CHUNK)
+    return table
+
+
+def adam_step_groups(p, g, m, v, shadow, ema, lr, beta1, beta2, eps, step, gscale, state, group_of, lr_scale, weight_decay,
+                     ema_decay=0.0):
+    """AdamW per chunk group, frozen chunks and the weight EMA in the one sweep (include/mgx.h: mgx_adam_step_groups).  state None:
+    the gradient scale is gscale; else grad_norm's, and a skipped step writes nothing.  shadow and ema may be None"""
+    _need_cuda(p, g, m, v, shadow, ema, group_of, lr_scale, weight_decay)
+    if state is not None:
+        _check_clip_state(state)
+    n = p.numel()
+    if group_of.dtype != torch.uint8 or group_of.numel() < (n + ADAM_CHUNK - 1) // ADAM_CHUNK:
+        raise ValueError(f"group_of must be uint8 [{(n + ADAM_CHUNK - 1) // ADAM_CHUNK}]")
+    if lr_scale.dtype != torch.float32 or weight_decay.dtype != torch.float32 or lr_scale.numel() != weight_decay.numel():
+        raise ValueError("lr_scale and weight_decay must be float32 arrays of one length, the number of groups")
+    if ema is not None and (ema.dtype != torch.float32 or ema.numel() != n):
+        raise ValueError("ema must be float32 with p's number of elements")
+    check(_lib.load().mgx_adam_step_groups(ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow), ptr(ema), n, float(lr), float(beta1),
+                                           float(beta2), float(eps), int(step), float(gscale), ptr(state), ptr(group_of),
+                                           ptr(lr_scale), ptr(weight_decay), lr_scale.numel(), float(ema_decay), stream_ptr()),
+          "mgx_adam_step_groups")
+
+
 def read_clip_state(state) -> dict:
     """the fields of mgx_clip_state; copies the 32 bytes to the host, so it SYNCHRONISES"""
     s = _ClipState.from_buffer_copy(state.detach().cpu().contiguous().view(torch.uint8)[:CLIP_STATE_BYTES].numpy())

@@ -13,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from . import config, scoring
+from . import config, scoring, utils
 from .data import Data
 from .network import MusicTransformer
 from .train import vocab_of
@@ -37,6 +37,8 @@ def get_options(argv=None):
     parser.add_option('--json', dest='json', type='string', default=None, help='write the figures per file to this file')
     parser.add_option('--midi', dest='midi', type='string', default=None,
                       help='comma-separated MIDI files to score in place of a split (through the MIDI-like codec, as generate.py -c)')
+    parser.add_option('--ema', dest='ema', action='store_true', default=False,
+                      help="score the checkpoint's 'net_ema' (train.py --ema-decay), not its 'net'")
     return parser.parse_args(argv)[0]
 
 
@@ -73,13 +75,14 @@ def main(argv=None):
         raise SystemExit(str(e))
     if o.batch_size < 1:
         raise SystemExit(f'-b must be at least 1, got {o.batch_size}')
+    net = utils.load_net(o.load_path, o.ema)
     pieces = _pieces(o, vocab)
     if not pieces:
         raise SystemExit(f'no file to score in the {o.split} split of {o.data_path}')
     device = torch.device('cuda:0')
     mt = MusicTransformer(embedding_dim=o.d_model, vocab_size=vocab, num_layer=o.num_layers, max_seq=o.max_seq, dropout=0)
-    if o.load_path:
-        mt.load_state_dict(torch.load(o.load_path, map_location='cpu', weights_only=False)['net'])
+    if net is not None:
+        mt.load_state_dict(net)
     mt.to(device).eval()
     per_file, total, count, hits = [], 0.0, 0, 0
     for i in range(0, len(pieces), o.batch_size):

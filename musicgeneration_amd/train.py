@@ -3,7 +3,9 @@ same prints, same checkpoint dict {'net','optimizer','epoch'} and file name, sam
 (train.py:252-329: per-epoch batches, loss/accum_grad, Noam schedule step every accum_grad
 micro-batches, 2-sample eval per epoch, save every 50 epochs and on Ctrl-C) -- running on the MI355X
 kernels.  Extras that do not change the defaults: --num-layers --d-model --repr --dropout --dp, --clip-norm
-(global gradient-norm clipping on the device; a non-finite step is skipped), the device feeder and its
+(global gradient-norm clipping on the device; a non-finite step is skipped), --weight-decay --freeze --lr-scale --ema-decay
+(AdamW on the matrices, frozen / slowed parameters and a moving average of the weights, all inside the one optimiser sweep;
+with --ema-decay the checkpoint gains 'net_ema' and every epoch one more Eval line), the device feeder and its
 train-time augmentation --device-feeder --transpose --stretch (data.DeviceData) and the
 data-parallel co-residency knobs --rccl-cus --nccl-channels --buckets.
 
@@ -27,7 +29,7 @@ from .criterion import CustomSchedule, SmoothCrossEntropyLoss
 from .data import Data
 from .metrics import CategoricalAccuracy, LogitsBucketting, MetricsSet
 from .network import MusicTransformer
-from .optim import FusedAdam, check_clip_args
+from .optim import FusedAdam, check_clip_args, check_ema_decay, check_weight_decay
 
 
 def get_options(argv=None):
@@ -53,6 +55,14 @@ def get_options(argv=None):
     parser.add_option('--max-batches', dest='max_batches', type='int', default=0, help='stop after N micro-batches')
     parser.add_option('--clip-norm', dest='clip_norm', type='float', default=0.0,
                       help='clip the global gradient norm to X and skip non-finite steps; inf = guard only; 0 = off')
+    parser.add_option('--weight-decay', dest='weight_decay', type='float', default=0.0,
+                      help="AdamW's decoupled weight decay on the projection matrices (not on biases, LayerNorm or embeddings); 0 = off")
+    parser.add_option('--freeze', dest='freeze', type='string', default=None,
+                      help='PREFIX[,PREFIX...]: parameters whose name starts with one of these are never updated')
+    parser.add_option('--lr-scale', dest='lr_scale', type='string', default=None,
+                      help='PREFIX=X[,PREFIX=X...]: learning-rate multipliers by name prefix; the longest prefix wins, 0 freezes')
+    parser.add_option('--ema-decay', dest='ema_decay', type='float', default=None,
+                      help="keep an exponential moving average of the weights with this decay, 0 < D < 1; saved as 'net_ema'")
     # the training batches cut, stretched and transposed on the device (data.DeviceData); any of the three selects that feeder
     parser.add_option('--device-feeder', dest='device_feeder', action='store_true', default=False,
                       help='training crops are cut on the device from a corpus uploaded once')
@@ -116,9 +126,48 @@ def augment_args(options):
     return {'transpose': list(range(-n, n + 1)) if n else None, 'stretch': stretch, 'codec': codec_of(options.repr)}
 
 
+def optim_args(options):
+    """--weight-decay / --freeze / --lr-scale / --ema-decay -> the keywords of FusedAdam ({} with none of them given); ValueError
+    naming the flag for what cannot be done.  Host only; a prefix that matches no parameter is refused by FusedAdam itself, which
+    knows the names"""
+    kw = {}
+    try:
+        if check_weight_decay(options.weight_decay) > 0.0:
+            kw['weight_decay'] = options.weight_decay
+    except ValueError as err:
+        raise ValueError(f"--weight-decay: {err}") from None
+    scale = {}
+    if options.lr_scale is not None:
+        for item in options.lr_scale.split(','):
+            prefix, eq, x = item.partition('=')
+            try:
+                value = float(x)
+            except ValueError:
+                value = -1.0
+            if not (prefix and eq) or not 0.0 <= value < float('inf'):
+                raise ValueError(f"--lr-scale takes PREFIX=X[,PREFIX=X...] with X a number >= 0, e.g. Decoder.enc_layers.0=0.1; got {item!r}")
+            scale[prefix] = value
+    if options.freeze is not None:
+        for prefix in options.freeze.split(','):
+            if not prefix:
+                raise ValueError(f"--freeze takes PREFIX[,PREFIX...], e.g. Decoder.embedding; got {options.freeze!r}")
+            if scale.get(prefix, 0.0) != 0.0:
+                raise ValueError(f"--freeze {prefix} contradicts --lr-scale {prefix}={scale[prefix]:g}")
+            scale[prefix] = 0.0
+    if scale:
+        kw['lr_scale'] = scale
+    try:
+        if check_ema_decay(options.ema_decay) is not None:
+            kw['ema_decay'] = options.ema_decay
+    except ValueError as err:
+        raise ValueError(f"--ema-decay: {err}") from None
+    return kw
+
+
 def main(argv=None):
     options = get_options(argv)
     augment_args(options)                                  # refusals first: before the device, the dataset and the model
+    optim_args(options)
     prev = torch.cuda.current_stream() if torch.cuda.is_available() else None
     try:
         return _run(options)
@@ -198,17 +247,19 @@ def _run(options):
     from .dp import DataParallel
     dp = DataParallel(mt, groups=options.buckets or None) if multi_gpu else None
     max_norm = None if options.clip_norm == 0 else check_clip_args(options.clip_norm)
-    opt = FusedAdam(mt, lr=0, betas=(0.9, 0.98), eps=1e-9, grad_scale=dp.grad_scale if dp else 1.0, max_norm=max_norm)
+    opt = FusedAdam(mt, lr=0, betas=(0.9, 0.98), eps=1e-9, grad_scale=dp.grad_scale if dp else 1.0, max_norm=max_norm,
+                    **optim_args(options))
     scheduler = CustomSchedule(config.embedding_dim, optimizer=opt)   # d_model of the schedule = config constant, as in train.py:144
     start_epoch = 0
 
     def to_dev(a):
         return torch.from_numpy(a).contiguous().to(device, non_blocking=True, dtype=torch.int)
 
-    def evaluate():
+    def evaluate(batch=None):
+        """batch: the (x, y) of an earlier call, kept in evaluate.batch -- the EMA is judged on the crops the weights were"""
         mt.eval()
         with torch.no_grad():
-            ex, ey = dataset.slide_seq2seq_batch(2, options.max_seq, 'valid')
+            ex, ey = evaluate.batch = batch or dataset.slide_seq2seq_batch(2, options.max_seq, 'valid')
             try:                                           # the same host-side guard as on the training batches: early, and it names the phase
                 utils.check_no_leading_pads(ex, pad)
             except ValueError as err:
@@ -222,6 +273,12 @@ def _run(options):
         opt.load_state_dict(checkpoint['optimizer'])
         scheduler = CustomSchedule(config.embedding_dim, optimizer=opt)
         scheduler._step = int(checkpoint.get('sched_step', 0))     # extra key; the reference restarts warm-up
+        if opt.ema is not None:
+            if 'net_ema' in checkpoint:
+                opt.load_ema(checkpoint['net_ema'])
+            else:
+                opt.load_ema(checkpoint['net'])
+                log(f"{load_path} has no 'net_ema': the EMA starts from the loaded weights")
         start_epoch = checkpoint['epoch'] + 1
         log(f'Success load {load_path}')
         em = evaluate()
@@ -233,6 +290,8 @@ def _run(options):
             return
         os.makedirs(save_path, exist_ok=True)
         state = {'net': mt.state_dict(), 'optimizer': opt.state_dict(), 'epoch': epoch, 'sched_step': scheduler._step}
+        if opt.ema is not None:
+            state['net_ema'] = opt.ema_state_dict()
         log('Saving to', save_path + 'train-{}-{}.pth'.format(epoch, acc))
         torch.save(state, save_path + 'train-{}-{}.pth'.format(epoch, acc))
         log('Done saving')
@@ -288,6 +347,9 @@ def _run(options):
                 if options.max_batches and idx >= options.max_batches:
                     break
             eval_metrics = evaluate()
+            if opt.ema is not None:
+                with opt.averaged():
+                    ema_metrics = evaluate(evaluate.batch)
             if (e + 1) % options.saving_interval == 0:
                 save_model(e, eval_metrics['accuracy'])
             # the device-side record of the leading-pads guard (this is a synchronisation point anyway).  AFTER the checkpoint: the
@@ -299,6 +361,8 @@ def _run(options):
             if metrics is not None:
                 log('Train >>>> Loss: {:6.6}, Accuracy: {}'.format(metrics['loss'], metrics['accuracy']))
             log('Eval >>>> Loss: {:6.6}, Accuracy: {}'.format(eval_metrics['loss'], eval_metrics['accuracy']))
+            if opt.ema is not None:
+                log('Eval (EMA) >>>> Loss: {:6.6}, Accuracy: {}'.format(ema_metrics['loss'], ema_metrics['accuracy']))
             log('Throughput >>>> {:.0f} events/s'.format(ev_meter / max(dt, 1e-9)))
             if max_norm is not None:
                 cs = opt.clip_stats()                          # reads the device-side state: after the epoch, not per step

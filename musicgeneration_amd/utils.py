@@ -83,3 +83,17 @@ def event_indeces_to_midi_file(event_indeces, midi_file_name, velocity_scale=0.8
         note.velocity = int((note.velocity - 64) * velocity_scale + 64)
     note_seq.to_midi_file(midi_file_name)
     return len(note_seq.notes)
+
+
+def load_net(load_path, ema=False):
+    """the model state_dict of a train.py checkpoint: its 'net', or with ``ema`` (--ema) its 'net_ema', the moving average of the
+    weights that train.py --ema-decay keeps; None without a path.  SystemExit where --ema cannot be honoured (host only)"""
+    import torch
+    if not load_path:
+        if ema:
+            raise SystemExit('--ema samples the averaged weights of a checkpoint: add -s CHECKPOINT')
+        return None
+    checkpoint = torch.load(load_path, map_location='cpu', weights_only=False)
+    if ema and 'net_ema' not in checkpoint:
+        raise SystemExit(f"--ema: {load_path} has no 'net_ema' (it was not trained with train.py --ema-decay)")
+    return checkpoint['net_ema' if ema else 'net']
