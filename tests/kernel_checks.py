@@ -15,6 +15,9 @@ BAND = 512                                          # bytes before and after eve
 PATTERN = b"\x5a"
 C_ADAM = 16.0                                       # noise floors an Adam update may be off by: C["ADAM"] of tests/test_gpu_rowwise_kernels.py
                                                     # (measured there), which the two clip modules check the clipped step with as well
+# noise floors a row-wise kernel may be off by, per family (LayerNorm forward / backward, cross entropy, embedding): measured by
+# tests/test_gpu_rowwise_kernels.py on its edge cases (its docstring has the figures); tests/step_trace.py holds a traced step to them
+C_ROWWISE = {"LNF": 8.0, "LNB": 4.0, "CE": 8.0, "EMB": 4.0}
 
 
 def raw(product_only=False):
@@ -111,6 +114,28 @@ def check_equal(fam, got, want, case):
     assert bad.numel() == 0, (f"{fam} {case}: {bad.shape[0]} elements differ, first {bad[:4].tolist()} got "
                               f"{[got[tuple(i)].item() for i in bad[:4]]} want {[torch.as_tensor(want).expand_as(got)[tuple(i)].item() for i in bad[:4]]}")
     print(f"[{fam}] {case}: exact")
+
+
+# ---- the analytic bounds of the training GEMMs on Gaussian data (tests/test_gpu_gemm_kernels.py derives them) -----------------------
+def gemm_fwd_bound(pre, S, R):
+    """bf16 output of a forward GEMM: 2^-8 |ref| (its rounding) + R 2^-23 S (an fp32 sum of R terms in any order; R = reduction
+    length, + 1 with a bias)"""
+    return 2.0 ** -8 * pre.abs() + R * 2.0 ** -23 * S
+
+
+def gemm_dx_bound(pm, S, N, add=None):
+    """dX of reduction length N, pm the masked product -> (ref, bound): 2^-8 |pm| + N 2^-23 S, and with an addend the two-rounding
+    form on ref = pm + addend: 2^-8 |ref| + (1 + 2^-8) (2^-8 |pm| + N 2^-23 S)"""
+    first = 2.0 ** -8 * pm.abs() + N * 2.0 ** -23 * S
+    if add is None:
+        return pm, first
+    ref = pm + add.to(F64)
+    return ref, 2.0 ** -8 * ref.abs() + (1 + 2.0 ** -8) * first
+
+
+def gemm_dw_bound(S, M):
+    """fp32 gW / gb: M terms and the slot's start value, any order: (M + 1) 2^-23 S, S the sum of |terms|, |start| included"""
+    return (M + 1) * 2.0 ** -23 * S
 
 
 # ---- guard bands ----------------------------------------------------------------------------------------------------------------

@@ -78,8 +78,7 @@ def run_fwd(fam, M, N, K, use_bias, act, kind, cus=0, seed=0):
             rounding_is_exercised(pre, case)
         check_equal(name, C.t, T.bf16_round(pre), case)
     else:
-        R = K + (1 if use_bias else 0)
-        check_bound(name, C.t, pre, 2.0 ** -8 * pre.abs() + R * 2.0 ** -23 * S, case)
+        check_bound(name, C.t, pre, KC.gemm_fwd_bound(pre, S, K + (1 if use_bias else 0)), case)
 
 
 TILE_M = (33, 127, 128, 129, 257)                   # one partial tile; one row short of / exactly / one row past a tile; three tile rows
@@ -166,12 +165,7 @@ def run_dx(fam, M, N, K, epi, kind, cus=0, seed=0):
         check_equal(name, DX.t, final, case)
     else:
         pm = torch.where(keep, p, torch.zeros((), dtype=F64))
-        first = 2.0 ** -8 * pm.abs() + N * 2.0 ** -23 * S
-        if add is None:
-            check_bound(name, DX.t, pm, first, case)
-        else:
-            ref = pm + add.double()
-            check_bound(name, DX.t, ref, 2.0 ** -8 * ref.abs() + (1 + 2.0 ** -8) * first, case)
+        check_bound(name, DX.t, *KC.gemm_dx_bound(pm, S, N, add), case)
 
 
 DX_N_GUARDED, DX_N_EXACT = (8, 72, 200), (64, 192, 512)      # N % 64 != 0: zero-filled reduction tail (linear_dx_kernel<., false>)
@@ -260,9 +254,9 @@ def run_dw(M, shapes, kind, *, path, with_gb=True, det=False, cus=0, calls=1, se
             if GB is not None:
                 check_equal(name, GB.t, gb0.double() + calls * db, c2 + " gb")
         else:
-            check_bound(name, GW.t, gW, (calls * M + 1) * 2.0 ** -23 * SW, c2 + " gW")
+            check_bound(name, GW.t, gW, KC.gemm_dw_bound(SW, calls * M), c2 + " gW")
             if GB is not None:
-                check_bound(name, GB.t, gb0.double() + calls * db, (calls * M + 1) * 2.0 ** -23 * (gb0.double().abs() + calls * Sb), c2 + " gb")
+                check_bound(name, GB.t, gb0.double() + calls * db, KC.gemm_dw_bound(gb0.double().abs() + calls * Sb, calls * M), c2 + " gb")
 
 
 @pytest.mark.parametrize("det", (False, True), ids=("atomics", "deterministic"))
