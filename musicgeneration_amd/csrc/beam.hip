@@ -9,11 +9,10 @@
 //   mgx_beam_backtrack   walks the parent table back from every final beam, one thread per row.
 //
 // Nothing is read back: the positions, parents and scores live on the device, so select and reorder are captured with the step.
-#include "mgx_common.hpp"
+#include "logit_row.hpp"                                  // the sampler-layout row: ids per lane, grammar row, bit test
 
 namespace {
 constexpr int BEAM_MAX = 16;              // beams per prompt
-constexpr int BEAM_PER_LANE = 16;         // V <= 64 * 16 = 1024, as for the sampler
 constexpr int BEAM_WAVES = 4;
 constexpr int NO_INDEX = 0x7fffffff;
 
@@ -53,29 +52,24 @@ __global__ __launch_bounds__(64 * BEAM_WAVES) void beam_select_kernel(
         const int row = row_first + k;
         const float sc = score[row];
         const bool live = sc > -INFINITY;                 // false for a dead beam (and for NaN)
-        float cand[BEAM_PER_LANE], key[BEAM_PER_LANE];
+        float cand[SMP_PER_LANE], key[SMP_PER_LANE];
         if (live) {                                       // wave-uniform
             const uint16_t* lp = logits + (size_t)row * ld;
-            const uint32_t* arow = nullptr;
-            if (allow_table) {
-                int prev = tok[row];
-                prev = prev < 0 ? 0 : (prev >= V ? V - 1 : prev);
-                arow = allow_table + (size_t)prev * ((V + 31) >> 5);
-            }
+            const uint32_t* arow = allow_table ? grammar_row(allow_table, tok[row], V) : nullptr;
             // the logits as they are first; the maximum is taken off BEFORE the division by the temperature, so that the product
             // is rounded at the size of the differences (logits near -200 would lose five bits to it otherwise)
             float mx = -INFINITY;
 #pragma unroll
-            for (int i = 0; i < BEAM_PER_LANE; ++i) {
+            for (int i = 0; i < SMP_PER_LANE; ++i) {
                 const int v = lane + 64 * i;
                 cand[i] = (v < V) ? bf16_to_f32(lp[v]) : -INFINITY;
-                if (arow && v < V && !((arow[v >> 5] >> (v & 31)) & 1u)) cand[i] = -INFINITY;
+                if (arow && v < V && !allowed(arow, v)) cand[i] = -INFINITY;      // arow first, as in sample_draw
                 mx = fmaxf(mx, cand[i]);
             }
             mx = wave_max(mx);
             if (arow && mx == -INFINITY) {                // a grammar row that leaves no finite logit is ignored
 #pragma unroll
-                for (int i = 0; i < BEAM_PER_LANE; ++i) {
+                for (int i = 0; i < SMP_PER_LANE; ++i) {
                     const int v = lane + 64 * i;
                     cand[i] = (v < V) ? bf16_to_f32(lp[v]) : -INFINITY;
                     mx = fmaxf(mx, cand[i]);
@@ -84,13 +78,13 @@ __global__ __launch_bounds__(64 * BEAM_WAVES) void beam_select_kernel(
             }
             float sum = 0.f;
 #pragma unroll
-            for (int i = 0; i < BEAM_PER_LANE; ++i) {
+            for (int i = 0; i < SMP_PER_LANE; ++i) {
                 cand[i] = (cand[i] - mx) * inv_temp;                                // <= 0; -inf for a disallowed id
                 sum += expf(cand[i]);                                               // exp(-inf) = 0
             }
             const float lse = logf(wave_sum(sum));
 #pragma unroll
-            for (int i = 0; i < BEAM_PER_LANE; ++i) {
+            for (int i = 0; i < SMP_PER_LANE; ++i) {
                 const int v = lane + 64 * i;
                 cand[i] = sc + (cand[i] - lse);                                     // -inf for a disallowed id
                 key[i] = cand[i];
@@ -101,13 +95,13 @@ __global__ __launch_bounds__(64 * BEAM_WAVES) void beam_select_kernel(
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < BEAM_PER_LANE; ++i) cand[i] = key[i] = -INFINITY;
+            for (int i = 0; i < SMP_PER_LANE; ++i) cand[i] = key[i] = -INFINITY;
         }
         // the beam's own K best, in order; a key of -inf is never a candidate
         for (int j = 0; j < K; ++j) {
             unsigned long long best = 0;
 #pragma unroll
-            for (int i = 0; i < BEAM_PER_LANE; ++i) {
+            for (int i = 0; i < SMP_PER_LANE; ++i) {
                 const unsigned long long c = key[i] > -INFINITY ? pack_cand(key[i], lane + 64 * i) : 0ull;
                 best = c > best ? c : best;
             }
@@ -115,7 +109,7 @@ __global__ __launch_bounds__(64 * BEAM_WAVES) void beam_select_kernel(
             const int bi = best ? cand_index(best) : NO_INDEX;
             float bk = -INFINITY, bc = -INFINITY;
 #pragma unroll
-            for (int i = 0; i < BEAM_PER_LANE; ++i)
+            for (int i = 0; i < SMP_PER_LANE; ++i)
                 if (lane + 64 * i == bi) { bk = key[i]; bc = cand[i]; key[i] = -INFINITY; }
             bk = wave_max(bk);                                                      // from the one lane that holds them
             bc = wave_max(bc);
@@ -239,10 +233,10 @@ extern "C" int mgx_beam_select(const uint16_t* logits, int V, int ld, float temp
                                int32_t* parent, int32_t* pos_rows, int32_t* hist_tok, int32_t* hist_parent, int out_ld, int B,
                                int K, int advance, const uint32_t* allow_table, int stochastic, uint64_t seed, void* stream) {
     MGX_REQUIRE(logits && score && tok && parent && pos_rows && hist_tok && hist_parent, MGX_ERR_NULL, "mgx_beam_select: NULL pointer");
-    MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * BEAM_PER_LANE && ld >= V && temperature > 0.f && K >= 1 && K <= BEAM_MAX && K <= V &&
+    MGX_REQUIRE(B > 0 && V > 0 && V <= 64 * SMP_PER_LANE && ld >= V && temperature > 0.f && K >= 1 && K <= BEAM_MAX && K <= V &&
                     out_ld > 0 && (size_t)B * K <= 0x7fffffff / 1024,
                 MGX_ERR_SHAPE, "mgx_beam_select: need 0<V<=%d, ld>=V, temperature>0, 1<=K<=min(%d,V), out_ld>0, B*K<2^21 (V=%d ld=%d K=%d B=%d)",
-                64 * BEAM_PER_LANE, BEAM_MAX, V, ld, K, B);
+                64 * SMP_PER_LANE, BEAM_MAX, V, ld, K, B);
     hipLaunchKernelGGL(beam_select_kernel, dim3(B), dim3(64 * BEAM_WAVES), 0, (hipStream_t)stream, logits, V, ld, 1.f / temperature,
                        score, tok, parent, pos_rows, hist_tok, hist_parent, out_ld, K, advance, allow_table, stochastic, seed);
     MGX_CHECK_LAUNCH("mgx_beam_select");

@@ -10,10 +10,9 @@
 //
 // The positions are never touched: an ended row keeps stepping on pad tokens with the others, so the shared counter, the ragged
 // step and the re-anchored window need no new contract.  No atomics: the host reads `done` between runs of replays.
-#include "mgx_common.hpp"
+#include "logit_row.hpp"                                  // BF16_NEG_INF
 
 namespace {
-constexpr uint16_t BF16_NEG_INF = 0xFF80;
 constexpr int MASK_THREADS = 256;
 
 __global__ __launch_bounds__(MASK_THREADS) void budget_mask_kernel(uint16_t* __restrict__ logits, int V, int ld,

@@ -8,15 +8,13 @@
 //                      so no wave reads what another has rewritten.  The row's log-sum-exp costs a wave 16 exponentials and two
 //                      reductions, less than a round trip through LDS and a second barrier would, so every wave forms it itself
 //                      -- from the same values in the same order, hence the same bits -- and nothing is exchanged.  A filtered
-//                      class runs the sampler's bit-pattern bisection (sample_draw, decode_common.hpp) on its own wave: the
+//                      class runs the sampler's bit-pattern bisections (logit_row.hpp) on its own wave: the
 //                      classes' bisections run side by side, not one after the other.
 #include "decode_common.hpp"
 
 #include <cmath>
 
 namespace {
-constexpr uint16_t BF16_NEG_INF = 0xff80u;
-
 __global__ __launch_bounds__(64 * MGX_CLASS_MAX) void class_logits_kernel(uint16_t* __restrict__ logits, int V, int ld,
                                                                           const int32_t* __restrict__ cls,
                                                                           const float* __restrict__ inv_temp,
@@ -27,24 +25,14 @@ __global__ __launch_bounds__(64 * MGX_CLASS_MAX) void class_logits_kernel(uint16
     const int b = blockIdx.x, lane = threadIdx.x & 63, c = threadIdx.x >> 6;     // c: the wave, and the class it owns
     uint16_t* lp = logits + (size_t)b * ld;
     const uint32_t* arow = allow_table ? grammar_row(allow_table, tok[b], V) : nullptr;
-    // bit i of a mask speaks of id lane + 64 i.  fin: the logit is above -inf; live: it is in A; mine: the id belongs to class c
+    // bit i of a mask speaks of id lane + 64 i.  live: the id is in A (load_row, logit_row.hpp); mine: it belongs to class c
     float x[SMP_PER_LANE];
-    uint32_t fin = 0, live = 0, mine = 0;
+    const uint32_t live = load_row(lp, V, arow, lane, x).live;
+    uint32_t mine = 0;
 #pragma unroll
-    for (int i = 0; i < SMP_PER_LANE; ++i) {
-        const int v = lane + 64 * i;
-        x[i] = -INFINITY;
-        if (v < V) {
-            x[i] = bf16_to_f32(lp[v]);
-            if (x[i] > -INFINITY) {
-                fin |= 1u << i;
-                if (!arow || ((arow[v >> 5] >> (v & 31)) & 1u)) live |= 1u << i;
-            }
-            if (cls[v] == c) mine |= 1u << i;
-        }
-    }
+    for (int i = 0; i < SMP_PER_LANE; ++i)
+        if (lane + 64 * i < V && cls[lane + 64 * i] == c) mine |= 1u << i;
     __syncthreads();                                      // every wave holds the row: from here on the waves write their classes
-    if (arow && !__ballot(live != 0)) live = fin;         // a grammar row that leaves nothing is ignored, as the sampler ignores it
     if (!__ballot(live != 0)) return;                     // nothing to draw from: the row stays bit for bit (uniform over the waves)
     const uint32_t mem = live & mine;                     // A_c
     float m_all = -INFINITY, m_c = -INFINITY;
@@ -85,45 +73,13 @@ __global__ __launch_bounds__(64 * MGX_CLASS_MAX) void class_logits_kernel(uint16
     const float n_c = wave_sum((float)__popc(mem));       // |A_c| <= 1024: exact
     uint32_t keep = mem;
     float ln_kept = logf(sum);                            // ln of the kept ids' sum of e
-    if ((k > 0 && (float)k < n_c) || tp < 1.f) {          // sample_draw's thresholds, on q and over A_c
+    if ((k > 0 && (float)k < n_c) || tp < 1.f) {          // the sampler's thresholds, on q and over A_c
         const float inv = 1.f / sum;
 #pragma unroll
         for (int i = 0; i < SMP_PER_LANE; ++i) q[i] *= inv;
         uint32_t tau_bits = 0;
-        if (k > 0 && (float)k < n_c) {
-            uint32_t lo = 0, hi = 0x3f800001u;
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                const float tv = __builtin_bit_cast(float, mid);
-                float cnt = 0.f;
-#pragma unroll
-                for (int i = 0; i < SMP_PER_LANE; ++i) cnt += (q[i] >= tv && ((mem >> i) & 1u)) ? 1.f : 0.f;
-                cnt = wave_sum(cnt);
-                if (cnt >= (float)k) lo = mid; else hi = mid;
-            }
-            tau_bits = lo;
-        }
-        if (tp < 1.f) {
-            uint32_t lo = tau_bits, hi = 0x3f800001u;
-            float mass_all = 0.f;
-            {
-                const float tv = __builtin_bit_cast(float, lo);
-#pragma unroll
-                for (int i = 0; i < SMP_PER_LANE; ++i) mass_all += (q[i] >= tv) ? q[i] : 0.f;
-                mass_all = wave_sum(mass_all);
-            }
-            const float need = tp * mass_all;
-            while (hi - lo > 1) {
-                const uint32_t mid = lo + ((hi - lo) >> 1);
-                const float tv = __builtin_bit_cast(float, mid);
-                float ms = 0.f;
-#pragma unroll
-                for (int i = 0; i < SMP_PER_LANE; ++i) ms += (q[i] >= tv) ? q[i] : 0.f;
-                ms = wave_sum(ms);
-                if (ms >= need) lo = mid; else hi = mid;
-            }
-            tau_bits = lo;
-        }
+        if (k > 0 && (float)k < n_c) tau_bits = topk_threshold(q, [&](int i) { return (mem >> i) & 1u; }, k);
+        if (tp < 1.f) tau_bits = topp_threshold(q, tau_bits, tp);
         const float tau = __builtin_bit_cast(float, tau_bits);
         float kept = 0.f;
         keep = 0;

@@ -1,7 +1,7 @@
 // What the decode kernels of decode.hip and lookahead.hip share: the key ranges, the partial layout and the merge kernel of the
 // split-key attention, and the sampler's draw as a device function (one wave per row).
 #pragma once
-#include "mgx_common.hpp"
+#include "logit_row.hpp"                                // the sampler-layout row: constants, grammar row, masks, thresholds
 
 namespace {
 constexpr float LOG2E = 1.4426950408889634f;
@@ -35,10 +35,8 @@ static __global__ __launch_bounds__(64) void rel_attn_decode_merge_kernel(const 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// sampling: one wave per row, V <= 64 * 16
+// sampling: one wave per row, V <= 64 * SMP_PER_LANE (logit_row.hpp); the uniform: u01 (mgx_common.hpp)
 // ---------------------------------------------------------------------------------------------------
-constexpr int SMP_PER_LANE = 16;                         // the uniform: u01 (mgx_common.hpp)
-
 // The draw of mgx_sample_topk_topp for one row of logits, by one wave: temperature -> (grammar row `arow`, or nullptr) ->
 // softmax -> top-k -> top-p -> inverse CDF at u * (kept mass).  Returns the token in every lane.  The unfiltered softmax goes to
 // probs_row f32 [V] (or nullptr) and, with KEEP, into soft[i] for id lane + 64 i: a caller that learns only later whether the
@@ -53,7 +51,7 @@ MGX_DEV int sample_draw(const uint16_t* __restrict__ lp, int V, float inv_temp, 
     for (int i = 0; i < SMP_PER_LANE; ++i) {
         const int v = lane + 64 * i;
         p[i] = (v < V) ? bf16_to_f32(lp[v]) * inv_temp : -INFINITY;
-        if (arow && v < V && !((arow[v >> 5] >> (v & 31)) & 1u)) p[i] = -INFINITY;
+        if (arow && v < V && !allowed(arow, v)) p[i] = -INFINITY;      // arow first: the wave-uniform test leaves the slots
         mx = fmaxf(mx, p[i]);
     }
     mx = wave_max(mx);
@@ -82,43 +80,10 @@ MGX_DEV int sample_draw(const uint16_t* __restrict__ lp, int V, float inv_temp, 
 #pragma unroll
         for (int i = 0; i < SMP_PER_LANE; ++i) soft[i] = p[i];
     }
-    // threshold tau: keep {p_i >= tau}.  top-k: largest tau with count(p >= tau) >= k; top-p: largest tau with
-    // mass(p >= tau) >= top_p.  Positive floats order like their bit patterns -> exact bisection on the bits.
+    // threshold tau: keep {p_i >= tau}, top-k then top-p over the ids v < V (logit_row.hpp)
     uint32_t tau_bits = 0;
-    if (top_k > 0 && top_k < V) {
-        uint32_t lo = 0, hi = 0x3f800001u;          // (p >= lo) holds for all; hi = just above 1.0
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            const float tv = __builtin_bit_cast(float, mid);
-            float c = 0.f;
-#pragma unroll
-            for (int i = 0; i < SMP_PER_LANE; ++i) c += (p[i] >= tv && lane + 64 * i < V) ? 1.f : 0.f;
-            c = wave_sum(c);
-            if (c >= (float)top_k) lo = mid; else hi = mid;
-        }
-        tau_bits = lo;
-    }
-    if (top_p < 1.f) {
-        uint32_t lo = tau_bits, hi = 0x3f800001u;
-        float mass_all = 0.f;
-        {
-            const float tv = __builtin_bit_cast(float, lo);
-#pragma unroll
-            for (int i = 0; i < SMP_PER_LANE; ++i) mass_all += (p[i] >= tv) ? p[i] : 0.f;
-            mass_all = wave_sum(mass_all);
-        }
-        const float need = top_p * mass_all;
-        while (hi - lo > 1) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            const float tv = __builtin_bit_cast(float, mid);
-            float ms = 0.f;
-#pragma unroll
-            for (int i = 0; i < SMP_PER_LANE; ++i) ms += (p[i] >= tv) ? p[i] : 0.f;
-            ms = wave_sum(ms);
-            if (ms >= need) lo = mid; else hi = mid;
-        }
-        tau_bits = lo;
-    }
+    if (top_k > 0 && top_k < V) tau_bits = topk_threshold(p, [&](int i) { return lane + 64 * i < V; }, top_k);
+    if (top_p < 1.f) tau_bits = topp_threshold(p, tau_bits, top_p);
     const float tau = __builtin_bit_cast(float, tau_bits);
     // categorical draw over the kept set by inverse CDF in index order
     float kept = 0.f;
@@ -151,10 +116,4 @@ MGX_DEV int sample_draw(const uint16_t* __restrict__ lp, int V, float inv_temp, 
         }
     }
     return choice;
-}
-// the grammar row of the previous token `prev` (clamped to 0..V-1), or nullptr without a table
-MGX_DEV const uint32_t* grammar_row(const uint32_t* __restrict__ allow_table, int prev, int V) {
-    if (!allow_table) return nullptr;
-    prev = prev < 0 ? 0 : (prev >= V ? V - 1 : prev);
-    return allow_table + (size_t)prev * ((V + 31) >> 5);
 }

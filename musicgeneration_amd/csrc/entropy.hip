@@ -4,7 +4,7 @@
 //   mgx_entropy_mask      before the sampler, in place on the step's logits: a PURE MASK -- the ids the three stages drop become
 //                         -inf and nothing else is written, so the unchanged sampler draws at the call's own temperature and its
 //                         top-k / top-p act on what is left.  One wave per row in the sampler's layout (ids lane + 64 i, 16 per
-//                         lane; sample_draw, decode_common.hpp).  The Mirostat cut and min-p are comparisons against the row's
+//                         lane; load_row, logit_row.hpp).  The Mirostat cut and min-p are comparisons against the row's
 //                         log-sum-exp and maximum; the typical set's radius is the sampler's exact bisection on float bit
 //                         patterns, here on d = |surprise - entropy|, so ids of equal d -- ids of equal logits among them -- stay
 //                         together by construction.  Also files the row's log-sum-exp for the account.
@@ -18,7 +18,6 @@
 #include <cmath>
 
 namespace {
-constexpr uint16_t BF16_NEG_INF = 0xff80u;
 constexpr float LN2 = 0.6931471805599453f;
 
 __global__ __launch_bounds__(64) void entropy_mask_kernel(uint16_t* __restrict__ logits, int V, int ld, float inv_t, float ln_min_p,
@@ -28,22 +27,9 @@ __global__ __launch_bounds__(64) void entropy_mask_kernel(uint16_t* __restrict__
     const int b = blockIdx.x, lane = threadIdx.x;
     uint16_t* lp = logits + (size_t)b * ld;
     const uint32_t* arow = allow_table ? grammar_row(allow_table, tok[b], V) : nullptr;
-    // bit i of a mask speaks of id lane + 64 i.  fin: the logit is above -inf; live: it is in A
+    // bit i of a mask speaks of id lane + 64 i.  live: the id is in A (load_row, logit_row.hpp)
     float z[SMP_PER_LANE];
-    uint32_t fin = 0, live = 0;
-#pragma unroll
-    for (int i = 0; i < SMP_PER_LANE; ++i) {
-        const int v = lane + 64 * i;
-        z[i] = -INFINITY;
-        if (v < V) {
-            z[i] = bf16_to_f32(lp[v]) * inv_t;            // the sampler's arithmetic
-            if (z[i] > -INFINITY) {
-                fin |= 1u << i;
-                if (!arow || ((arow[v >> 5] >> (v & 31)) & 1u)) live |= 1u << i;
-            }
-        }
-    }
-    if (arow && !__ballot(live != 0)) live = fin;         // a grammar row that leaves nothing is ignored, as the sampler ignores it
+    const uint32_t live = load_row(lp, V, arow, lane, z, inv_t).live;       // logit * inv_t: the sampler's arithmetic
     if (!__ballot(live != 0)) {                           // nothing to draw from: the row stays bit for bit
         if (lse_out && lane == 0) lse_out[b] = 0.f;
         return;

@@ -13,10 +13,9 @@
 //                       So a row is the unconstrained row of the same seed until that one breaks a rule.  One thread per row.
 //
 // mask and account touch no position, no token and no column of the output matrix.  No atomics: one thread owns a row's words in account, mask reads.
-#include "mgx_common.hpp"
+#include "logit_row.hpp"                                  // BF16_NEG_INF
 
 namespace {
-constexpr uint16_t BF16_NEG_INF = 0xFF80;
 constexpr int MASK_THREADS = 256;
 constexpr int NOTE_BITS = 32 * MGX_NOTE_WORDS;
 static_assert(MGX_NOTE_WORDS == 4, "the word select below is written for four words");

@@ -14,6 +14,7 @@
 // and metrics.py:40-52 (the arg-max against the target).
 #include <limits.h>
 #include "rel_attn_common.hpp"
+#include "logit_row.hpp"                                  // the grammar row and its bit test
 
 using namespace relattn;
 
@@ -31,8 +32,6 @@ MGX_DEV int wave_min_i32(int v) {
     return v;
 }
 
-MGX_DEV bool allowed_bit(const uint32_t* arow, int v) { return !arow || ((arow[v >> 5] >> (v & 31)) & 1u); }
-
 __global__ __launch_bounds__(64 * SCORE_WAVES) void token_logprob_kernel(
     const uint16_t* __restrict__ logits, int V, int ld, const int32_t* __restrict__ target, const int32_t* __restrict__ prev,
     const uint32_t* __restrict__ allow_table, float inv_temp, float* __restrict__ logp, float* __restrict__ lse_out,
@@ -43,16 +42,11 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void token_logprob_kernel(
     const int row = blockIdx.x * SCORE_WAVES + (threadIdx.x >> 6);
     if (row >= rows) return;                                  // wave-uniform
     const uint16_t* lp = logits + (size_t)row * ld;
-    const uint32_t* arow = nullptr;
-    if (allow_table) {
-        int p = prev[row];
-        p = p < 0 ? 0 : (p >= V ? V - 1 : p);
-        arow = allow_table + (size_t)p * ((V + 31) >> 5);
-    }
+    const uint32_t* arow = allow_table ? grammar_row(allow_table, prev[row], V) : nullptr;
     // sweep 1: the maximum over the allowed ids (fmaxf: a NaN never is the maximum)
     float mx = -INFINITY;
     for (int v = lane; v < V; v += 64)
-        if (allowed_bit(arow, v)) mx = fmaxf(mx, bf16_to_f32(lp[v]));
+        if (allowed(arow, v)) mx = fmaxf(mx, bf16_to_f32(lp[v]));
     mx = wave_max(mx);
     if (arow && mx == -INFINITY) {                            // a grammar row that leaves no finite logit is ignored
         arow = nullptr;
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void token_logprob_kernel(
     float sum = 0.f, bad = 0.f;
     int first = INT_MAX;
     for (int v = lane; v < V; v += 64) {
-        if (!allowed_bit(arow, v)) continue;
+        if (!allowed(arow, v)) continue;
         const float val = bf16_to_f32(lp[v]);
         if (!(val < INFINITY)) bad = 1.f;
         if (val == mx && v < first) first = v;
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(64 * SCORE_WAVES) void token_logprob_kernel(
         hit[row] = -1;
         return;
     }
-    const bool ok = allowed_bit(arow, t);
+    const bool ok = allowed(arow, t);
     const float xt = ok ? bf16_to_f32(lp[t]) * inv_temp : -INFINITY;
     logp[row] = xt - lse;
     hit[row] = (ok && first == t) ? 1 : 0;

@@ -658,17 +658,46 @@ def linear_dw_grouped(problems):
 
 
 # ---- decode path (no autograd) ----------------------------------------------------------------------
+# Every wrapper below checks its tensors on the host first (ValueError), then asks for device memory (_need_cuda), then calls
+# the library; the tensor contract is stated once, in _tensor_is / _check_tensor.
+def _tensor_is(t, dtypes, entries=None, shape=None, at_least=None):
+    """whether ``t`` is a contiguous tensor of one of ``dtypes`` (a dtype or a tuple of them; None: any) that holds ``entries``
+    entries in any shape, or has ``shape`` -- an int per fixed dimension, a name per free one -- and, with ``at_least``, no
+    fewer entries than that"""
+    if t is None or not (dtypes is None or t.dtype == dtypes or (isinstance(dtypes, tuple) and t.dtype in dtypes)):
+        return False
+    if entries is not None and t.numel() != entries:
+        return False
+    if shape is not None and (t.dim() != len(shape) or any(not isinstance(s, str) and n != s for n, s in zip(t.shape, shape))):
+        return False
+    return (at_least is None or t.numel() >= at_least) and t.is_contiguous()
+
+
+def _check_tensor(what, name, t, dtypes, entries=None, shape=None, at_least=None, optional=False):
+    """the tensor contract of wrapper ``what``'s argument ``name`` (_tensor_is), refused with a ValueError of one form; None
+    passes where the argument is ``optional``"""
+    if (t is None and optional) or _tensor_is(t, dtypes, entries, shape, at_least):
+        return
+    kinds = " / ".join({torch.bfloat16: "bf16"}.get(d, str(d).replace("torch.", ""))
+                       for d in (dtypes if isinstance(dtypes, tuple) else (dtypes,)) if d is not None)
+    form = (f" of {entries} entries" if entries is not None else "") + \
+        (" [" + ", ".join(str(s) for s in shape) + "]" if shape is not None else "") + \
+        (f" of at least {at_least} entries" if at_least is not None else "")
+    got = "None" if t is None else f"{t.dtype} {tuple(t.shape)}" + ("" if t.is_contiguous() else f", strides {t.stride()}")
+    raise ValueError(f"{what}: {name} must be a contiguous {kinds + ' ' if kinds else ''}tensor{form}, got {got}")
+
+
 def _step_pos(what, pos_dev, B, ragged, base=None, with_base=False):
     """the step-position arguments of a decode call (include/mgx.h, "Step positions"), checked on the host (ValueError):
     ``pos_dev`` contiguous int32, one shared counter or -- ``ragged`` -- one position per row, B entries; ``base``, the window's
     base, of the positions' shape or None.  Returns (pos_dev, per_row) as the C arguments, (pos_dev, base_dev, per_row) with
     ``with_base``"""
     n = B if ragged else 1
-    if pos_dev.dtype != torch.int32 or pos_dev.numel() != n or not pos_dev.is_contiguous():
+    if not _tensor_is(pos_dev, torch.int32, entries=n):
         kind = f"ragged decode: the positions must be a contiguous int32 tensor of {B} entries" if ragged else \
             "a shared position is one contiguous int32"
         raise ValueError(f"{what}: {kind} (got {pos_dev.dtype}, {pos_dev.numel()} entries)")
-    if base is not None and (base.dtype != torch.int32 or base.numel() != n or not base.is_contiguous()):
+    if base is not None and not _tensor_is(base, torch.int32, entries=n):
         raise ValueError(f"{what}: base must be a contiguous int32 tensor of the positions' {n} entries "
                          f"(got {base.dtype}, {base.numel()} entries)")
     per_row = 1 if ragged else 0
@@ -716,24 +745,19 @@ _FP8_CACHE = (torch.uint8, torch.float8_e4m3fn)
 
 
 def _check_kv_cache(kcache, vcache, kscale, vscale, what) -> bool:
-    """validates a K/V cache pair, shape first, then dtype: bf16 [B, h, Lmax, 64], or the 8-bit cache (ABI 20) -- codes uint8 /
-    float8_e4m3fn [B, h, Lmax, 64] with scales f32 [B, h, Lmax].  Returns whether it is the 8-bit cache."""
-    if kcache.dim() != 4 or kcache.shape[-1] != 64 or vcache.shape != kcache.shape:
-        raise ValueError(f"{what}: kcache / vcache must be [B, h, Lmax, 64] of one shape, got {tuple(kcache.shape)} / {tuple(vcache.shape)}")
-    if kcache.dtype not in _FP8_CACHE:
-        if kcache.dtype != torch.bfloat16 or vcache.dtype != torch.bfloat16:
-            raise ValueError(f"{what}: caches must be bf16, uint8 or float8_e4m3fn, got {kcache.dtype} / {vcache.dtype}")
+    """validates a K/V cache pair: bf16 [B, h, Lmax, 64], or the 8-bit cache (ABI 20) -- codes uint8 / float8_e4m3fn
+    [B, h, Lmax, 64] with scales f32 [B, h, Lmax] -- all contiguous.  Returns whether it is the 8-bit cache."""
+    _check_tensor(what, "kcache", kcache, (torch.bfloat16,) + _FP8_CACHE, shape=("B", "h", "Lmax", 64))
+    fp8 = kcache.dtype in _FP8_CACHE
+    if fp8 and vcache.dtype not in _FP8_CACHE:
+        raise ValueError(f"{what}: the 8-bit caches must both be uint8 or float8_e4m3fn, got {kcache.dtype} / {vcache.dtype}")
+    _check_tensor(what, "vcache", vcache, _FP8_CACHE if fp8 else torch.bfloat16, shape=tuple(kcache.shape))
+    if not fp8:
         if kscale is not None or vscale is not None:
             raise ValueError(f"{what}: kscale / vscale belong to the 8-bit cache (uint8 or float8_e4m3fn), the caches are bf16")
         return False
-    if vcache.dtype not in _FP8_CACHE:
-        raise ValueError(f"{what}: the 8-bit caches must both be uint8 or float8_e4m3fn, got {kcache.dtype} / {vcache.dtype}")
-    for s in (kscale, vscale):
-        if s is None or s.dtype != torch.float32 or tuple(s.shape) != tuple(kcache.shape[:3]):
-            raise ValueError(f"{what}: kscale / vscale must be float32 [B, h, Lmax] = {tuple(kcache.shape[:3])} beside the 8-bit caches")
-    for t in (kcache, vcache, kscale, vscale):
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: the 8-bit caches and their scales must be contiguous")
+    for s in (kscale, vscale):                            # named together: the message says what stands beside the 8-bit caches
+        _check_tensor(what, "kscale / vscale", s, torch.float32, shape=tuple(kcache.shape[:3]))
     return True
 
 
@@ -744,8 +768,7 @@ def kv_store_fp8(qkv, n, kcache, vcache, kscale, vscale):
         raise ValueError("kv_store_fp8: the caches must be the 8-bit cache (uint8 or float8_e4m3fn), got bf16")
     B, heads, Lmax, _ = kcache.shape
     d = heads * 64
-    if qkv.dtype != torch.bfloat16 or qkv.dim() != 3 or qkv.shape[0] != B or qkv.shape[2] != 3 * d or not qkv.is_contiguous():
-        raise ValueError(f"kv_store_fp8: qkv must be contiguous bf16 [{B}, Lrows, {3 * d}], got {qkv.dtype} {tuple(qkv.shape)}")
+    _check_tensor("kv_store_fp8", "qkv", qkv, torch.bfloat16, shape=(B, "Lrows", 3 * d))
     _need_cuda(qkv, kcache, vcache, kscale, vscale)
     check(_lib.load().mgx_kv_store_fp8(ptr(qkv), qkv.shape[1], int(n), ptr(kcache), ptr(vcache), ptr(kscale), ptr(vscale),
                                        B, Lmax, d, stream_ptr()), "mgx_kv_store_fp8")
@@ -792,25 +815,18 @@ def rel_attn_decode_shared(qkv_new, kpre, vpre, kown, vown, E, pos_rows, pre_row
     N = int(N)
     if not 1 <= N <= SHARED_MAX_N:
         raise ValueError(f"{what}: N must lie in 1 .. {SHARED_MAX_N}, got {N}")
-    for name, (k, v) in (("kpre / vpre", (kpre, vpre)), ("kown / vown", (kown, vown))):
-        if k.dim() != 4 or k.shape[-1] != 64 or v.shape != k.shape:
-            raise ValueError(f"{what}: {name} must be [rows, h, L, 64] of one shape, got {tuple(k.shape)} / {tuple(v.shape)}")
-        if k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16 or not (k.is_contiguous() and v.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be contiguous bf16, got {k.dtype} / {v.dtype}")
+    for kname, k, vname, v in (("kpre", kpre, "vpre", vpre), ("kown", kown, "vown", vown)):
+        _check_tensor(what, kname, k, torch.bfloat16, shape=("rows", "h", "L", 64))
+        _check_tensor(what, vname, v, torch.bfloat16, shape=tuple(k.shape))
     Bp, heads, Lpre, _ = kpre.shape
     R, d = Bp * N, heads * 64
     if kown.shape[0] != R or kown.shape[1] != heads:
         raise ValueError(f"{what}: kown / vown must hold Bp * N = {R} rows of {heads} heads, got {tuple(kown.shape)}")
-    for name, t in (("qkv_new", qkv_new), ("ctx", ctx)):
-        cols = 3 * d if name == "qkv_new" else d
-        if t.dtype != torch.bfloat16 or tuple(t.shape) != (R, cols) or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous bf16 [{R}, {cols}], got {t.dtype} {tuple(t.shape)}")
-    if E.dtype != torch.bfloat16 or E.dim() != 2 or E.shape[1] != 64 or not E.is_contiguous():
-        raise ValueError(f"{what}: E must be contiguous bf16 [M, 64], got {E.dtype} {tuple(E.shape)}")
+    _check_tensor(what, "qkv_new", qkv_new, torch.bfloat16, shape=(R, 3 * d))
+    _check_tensor(what, "ctx", ctx, torch.bfloat16, shape=(R, d))
+    _check_tensor(what, "E", E, torch.bfloat16, shape=("M", 64))
     _step_pos(what, pos_rows, R, True)
-    if pre_rows.dtype != torch.int32 or pre_rows.numel() != Bp or not pre_rows.is_contiguous():
-        raise ValueError(f"{what}: pre_rows must be a contiguous int32 tensor of {Bp} entries "
-                         f"(got {pre_rows.dtype}, {pre_rows.numel()} entries)")
+    _check_tensor(what, "pre_rows", pre_rows, torch.int32, entries=Bp)
     _need_cuda(qkv_new, kpre, vpre, kown, vown, E, pos_rows, pre_rows, ctx, workspace)
     check(_lib.load().mgx_rel_attn_decode_shared(ptr(qkv_new), ptr(kpre), ptr(vpre), ptr(kown), ptr(vown), ptr(E), ptr(pos_rows),
                                                  ptr(pre_rows), ptr(ctx), ptr(workspace),
@@ -828,11 +844,9 @@ def grammar_table(grammar, device):
     return table.to(device=device, dtype=torch.int32).contiguous()
 
 
-def _check_allow_table(allow_table, V):
-    if allow_table is not None and (allow_table.dim() != 2 or allow_table.shape[0] != V
-                                    or allow_table.shape[1] != (V + 31) // 32 or allow_table.element_size() != 4
-                                    or not allow_table.is_contiguous()):
-        raise ValueError("allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
+def _check_allow_table(allow_table, V, what=None):
+    if allow_table is not None and not (_tensor_is(allow_table, None, shape=(V, (V + 31) // 32)) and allow_table.element_size() == 4):
+        raise ValueError((f"{what}: " if what else "") + "allow_table must be a contiguous 32-bit integer tensor of shape [V, ceil(V/32)]")
 
 
 def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=None, temperature=1.0, top_k=0, top_p=1.0,
@@ -845,8 +859,8 @@ def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=No
     ld = logits.shape[-1]
     B = logits.numel() // ld
     pos = _step_pos("sample_topk_topp", pos_dev, B, ragged, base, with_base=True)
+    _check_allow_table(allow_table, V, "sample_topk_topp")
     _need_cuda(logits, pos_dev, next_tok, out_tokens, probs_out, allow_table, base)
-    _check_allow_table(allow_table, V)
     check(_lib.load().mgx_sample_topk_topp(ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed), *pos,
                                            ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[-1],
                                            ptr(probs_out), B, int(row0), 1 if advance else 0, ptr(allow_table), stream_ptr()),
@@ -857,13 +871,11 @@ def sample_topk_topp(logits, V, pos_dev, next_tok, out_tokens=None, probs_out=No
 def decode_reanchor(pos_dev, base, out_tokens, seq, hop, pad_token, *, ragged=False):
     """the re-anchor of the decode window (ABI 21): pos_dev -= hop and base += hop (int32 [1] shared, or [B] with ``ragged``),
     then seq int32 [B, n_pad] = the window's tokens out_tokens[b, base_b : base_b + pos_b], right-padded with pad_token"""
+    _check_tensor("decode_reanchor", "seq", seq, torch.int32, shape=("B", "n_pad"))
     B, n_pad = seq.shape
     pos = _step_pos("decode_reanchor", pos_dev, B, ragged, base, with_base=True)
+    _check_tensor("decode_reanchor", "out_tokens", out_tokens, torch.int32, shape=(B, "out_ld"))
     _need_cuda(pos_dev, base, out_tokens, seq)
-    if (out_tokens.dtype != torch.int32 or seq.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B
-            or not out_tokens.is_contiguous() or not seq.is_contiguous()):
-        raise ValueError(f"decode_reanchor: out_tokens and seq must be contiguous int32 [{B}, ...], got {out_tokens.dtype} "
-                         f"{tuple(out_tokens.shape)} and {seq.dtype} {tuple(seq.shape)}")
     check(_lib.load().mgx_decode_reanchor(*pos, ptr(out_tokens), out_tokens.shape[1], ptr(seq), n_pad, int(hop), int(pad_token), B,
                                           stream_ptr()), "mgx_decode_reanchor")
     return seq
@@ -873,26 +885,18 @@ def decode_reanchor(pos_dev, base, out_tokens, seq, hop, pad_token, *, ragged=Fa
 NO_BUDGET = 2 ** 31 - 1                                   # remaining = INT32_MAX: the row has no budget
 
 
-def _check_budget_state(what, B, cost, **rows):
-    """the budget state: cost int32 [V], remaining / done / count int32 [B], all contiguous"""
-    if cost.dtype != torch.int32 or cost.dim() != 1 or not cost.is_contiguous():
-        raise ValueError(f"{what}: cost must be a contiguous int32 tensor [V], got {cost.dtype} {tuple(cost.shape)}")
-    for name, t in rows.items():
-        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
-
-
 def budget_mask(logits, V, cost, remaining, done):
     """in place, before the sampler: logits bf16 [B, ld] of a live row (done[b] == 0) get -inf at every id v < V with
     cost[v] > remaining[b]; done rows, columns >= V and every other id stay bit for bit"""
-    _need_cuda(logits, cost, remaining, done)
     B = remaining.numel()
     ld = logits.shape[-1]
-    if logits.dtype != torch.bfloat16 or logits.numel() != B * ld:
-        raise ValueError(f"budget_mask: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
-    _check_budget_state("budget_mask", B, cost, remaining=remaining, done=done)
+    _check_tensor("budget_mask", "logits", logits, torch.bfloat16, entries=B * ld)
+    _check_tensor("budget_mask", "cost", cost, torch.int32, shape=("V",))
+    for name, t in (("remaining", remaining), ("done", done)):
+        _check_tensor("budget_mask", name, t, torch.int32, shape=(B,))
     if not 0 < int(V) <= min(ld, cost.numel()):
         raise ValueError(f"budget_mask: V must lie in 1 .. min(ld, the entries of cost) = {min(ld, cost.numel())}, got {V}")
+    _need_cuda(logits, cost, remaining, done)
     check(_lib.load().mgx_budget_mask(ptr(logits), int(V), ld, ptr(cost), ptr(remaining), ptr(done), B, stream_ptr()),
           "mgx_budget_mask")
     return logits
@@ -906,11 +910,11 @@ def budget_account(next_tok, out_tokens, pos_dev, cost, remaining, done, count, 
     sample_topk_topp"""
     B = remaining.numel()
     pos = _step_pos("budget_account", pos_dev, B, ragged, base, with_base=True)
+    _check_tensor("budget_account", "cost", cost, torch.int32, shape=("V",))
+    for name, t in (("next_tok", next_tok), ("remaining", remaining), ("done", done), ("count", count)):
+        _check_tensor("budget_account", name, t, torch.int32, shape=(B,))
+    _check_tensor("budget_account", "out_tokens", out_tokens, torch.int32, shape=(B, "out_ld"))
     _need_cuda(next_tok, out_tokens, pos_dev, base, cost, remaining, done, count)
-    _check_budget_state("budget_account", B, cost, next_tok=next_tok, remaining=remaining, done=done, count=count)
-    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B:
-        raise ValueError(f"budget_account: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
-                         f"{tuple(out_tokens.shape)}")
     check(_lib.load().mgx_budget_account(ptr(next_tok), ptr(out_tokens), out_tokens.shape[1], *pos, ptr(cost), ptr(remaining),
                                          ptr(done), ptr(count), int(pad_token), 1 if inclusive else 0, B, stream_ptr()),
           "mgx_budget_account")
@@ -931,22 +935,15 @@ def repeat_penalty(logits, V, out_tokens, pos_dev, subject, pen, window, ngram=0
     ld = logits.shape[-1]
     B = logits.numel() // ld
     pos = _step_pos("repeat_penalty", pos_dev, B, ragged, base, with_base=True)
-    _need_cuda(logits, out_tokens, pos_dev, base, subject, pen)
-    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
-        raise ValueError(f"repeat_penalty: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
-    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or not out_tokens.is_contiguous():
-        raise ValueError(f"repeat_penalty: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
-                         f"{tuple(out_tokens.shape)}")
+    _check_tensor("repeat_penalty", "logits", logits, torch.bfloat16, entries=B * ld)
+    _check_tensor("repeat_penalty", "out_tokens", out_tokens, torch.int32, shape=(B, "out_ld"))
     window = int(window)
     if (window == 0) != (subject is None) or (window == 0) != (pen is None):
         raise ValueError(f"repeat_penalty: subject and pen are None exactly with window == 0 (window={window})")
     if window:
-        if subject.dtype != torch.int32 or subject.dim() != 1 or subject.numel() < int(V) or not subject.is_contiguous():
-            raise ValueError(f"repeat_penalty: subject must be a contiguous int32 tensor of at least V = {V} entries, got "
-                             f"{subject.dtype} {tuple(subject.shape)}")
-        if pen.dtype != torch.float32 or pen.dim() != 1 or pen.numel() != window + 1 or not pen.is_contiguous():
-            raise ValueError(f"repeat_penalty: pen must be a contiguous float32 tensor of window + 1 = {window + 1} entries, got "
-                             f"{pen.dtype} {tuple(pen.shape)}")
+        _check_tensor("repeat_penalty", "subject", subject, torch.int32, shape=("n",), at_least=int(V))
+        _check_tensor("repeat_penalty", "pen", pen, torch.float32, shape=(window + 1,))
+    _need_cuda(logits, out_tokens, pos_dev, base, subject, pen)
     check(_lib.load().mgx_repeat_penalty(ptr(logits), int(V), ld, ptr(out_tokens), out_tokens.shape[1], *pos, ptr(subject), ptr(pen),
                                          window, int(ngram), int(span), float(ban), B, stream_ptr()), "mgx_repeat_penalty")
     return logits
@@ -964,36 +961,22 @@ def class_logits(logits, V, cls, inv_temp, top_k, top_p, temperature, tok=None, 
     the rows' input tokens, both or neither.  The sampler then runs at temperature 1"""
     ld = logits.shape[-1]
     B = logits.numel() // ld
-    _need_cuda(logits, cls, inv_temp, top_k, top_p, tok, allow_table)
-    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
-        raise ValueError(f"class_logits: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
-    if cls.dtype != torch.int32 or cls.dim() != 1 or cls.numel() < int(V) or not cls.is_contiguous():
-        raise ValueError(f"class_logits: cls must be a contiguous int32 tensor of at least V = {V} entries, got {cls.dtype} "
-                         f"{tuple(cls.shape)}")
+    _check_tensor("class_logits", "logits", logits, torch.bfloat16, entries=B * ld)
+    _check_tensor("class_logits", "cls", cls, torch.int32, shape=("n",), at_least=int(V))
     C = inv_temp.numel()
     for name, t, dt in (("inv_temp", inv_temp, torch.float32), ("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32)):
-        if t.dtype != dt or t.dim() != 1 or t.numel() != C or not t.is_contiguous():
-            raise ValueError(f"class_logits: {name} must be a contiguous {dt} tensor of C = {C} entries, got {t.dtype} "
-                             f"{tuple(t.shape)}")
+        _check_tensor("class_logits", name, t, dt, shape=(C,))
     if (tok is None) != (allow_table is None):
         raise ValueError("class_logits: tok and allow_table are given together or not at all")
-    if tok is not None:
-        _check_allow_table(allow_table, V)
-        if tok.dtype != torch.int32 or tok.numel() != B or not tok.is_contiguous():
-            raise ValueError(f"class_logits: tok must be a contiguous int32 tensor of {B} entries, got {tok.dtype} {tuple(tok.shape)}")
+    _check_allow_table(allow_table, V, "class_logits")
+    _check_tensor("class_logits", "tok", tok, torch.int32, entries=B, optional=True)
+    _need_cuda(logits, cls, inv_temp, top_k, top_p, tok, allow_table)
     check(_lib.load().mgx_class_logits(ptr(logits), int(V), ld, ptr(cls), C, ptr(inv_temp), ptr(top_k), ptr(top_p),
                                        float(temperature), ptr(tok), ptr(allow_table), B, stream_ptr()), "mgx_class_logits")
     return logits
 
 
 # ---- entropy-aware sampling on the decode path (ABI 34; contracts in include/mgx.h) ----------------------------------
-def _check_rows_f32(what, B, **ts):
-    """name=tensor: contiguous float32 tensors of B entries (None passes)"""
-    for name, t in ts.items():
-        if t is not None and (t.dtype != torch.float32 or t.numel() != B or not t.is_contiguous()):
-            raise ValueError(f"{what}: {name} must be a contiguous float32 tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
-
-
 def entropy_mask(logits, V, temperature, min_p=0.0, typical_p=1.0, mu=None, lse_out=None, tok=None, allow_table=None):
     """in place, before the sampler: a pure mask on logits bf16 [B, ld] -- the ids v < V that the Mirostat cut (``mu`` float32 [B]:
     surprise in bits at most mu[b]), min-p and typical sampling drop, in that order and each on the survivors of the one before,
@@ -1002,16 +985,14 @@ def entropy_mask(logits, V, temperature, min_p=0.0, typical_p=1.0, mu=None, lse_
     tokens, both or neither.  The sampler then runs at the same ``temperature``"""
     ld = logits.shape[-1]
     B = logits.numel() // ld
-    _need_cuda(logits, mu, lse_out, tok, allow_table)
-    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
-        raise ValueError(f"entropy_mask: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
-    _check_rows_f32("entropy_mask", B, mu=mu, lse_out=lse_out)
+    _check_tensor("entropy_mask", "logits", logits, torch.bfloat16, entries=B * ld)
+    _check_tensor("entropy_mask", "mu", mu, torch.float32, entries=B, optional=True)
+    _check_tensor("entropy_mask", "lse_out", lse_out, torch.float32, entries=B, optional=True)
     if (tok is None) != (allow_table is None):
         raise ValueError("entropy_mask: tok and allow_table are given together or not at all")
-    if tok is not None:
-        _check_allow_table(allow_table, V)
-        if tok.dtype != torch.int32 or tok.numel() != B or not tok.is_contiguous():
-            raise ValueError(f"entropy_mask: tok must be a contiguous int32 tensor of {B} entries, got {tok.dtype} {tuple(tok.shape)}")
+    _check_allow_table(allow_table, V, "entropy_mask")
+    _check_tensor("entropy_mask", "tok", tok, torch.int32, entries=B, optional=True)
+    _need_cuda(logits, mu, lse_out, tok, allow_table)
     check(_lib.load().mgx_entropy_mask(ptr(logits), int(V), ld, float(temperature), float(min_p), float(typical_p), ptr(mu),
                                        ptr(lse_out), ptr(tok), ptr(allow_table), B, stream_ptr()), "mgx_entropy_mask")
     return logits
@@ -1026,17 +1007,12 @@ def entropy_account(next_tok, logits, V, temperature, lse, pos_dev, mu=None, tau
     ld = logits.shape[-1]
     B = logits.numel() // ld
     pos = _step_pos("entropy_account", pos_dev, B, ragged, base, with_base=True)
+    _check_tensor("entropy_account", "logits", logits, torch.bfloat16, entries=B * ld)
+    _check_tensor("entropy_account", "next_tok", next_tok, torch.int32, entries=B)
+    _check_tensor("entropy_account", "lse", lse, torch.float32, entries=B)
+    _check_tensor("entropy_account", "mu", mu, torch.float32, entries=B, optional=True)
+    _check_tensor("entropy_account", "surprise_out", surprise_out, torch.float32, shape=(B, "out_ld"), optional=True)
     _need_cuda(next_tok, logits, lse, pos_dev, base, mu, surprise_out)
-    if logits.dtype != torch.bfloat16 or not logits.is_contiguous():
-        raise ValueError(f"entropy_account: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
-    if next_tok.dtype != torch.int32 or next_tok.numel() != B or not next_tok.is_contiguous():
-        raise ValueError(f"entropy_account: next_tok must be a contiguous int32 tensor of {B} entries, got {next_tok.dtype} "
-                         f"{tuple(next_tok.shape)}")
-    _check_rows_f32("entropy_account", B, lse=lse, mu=mu)
-    if surprise_out is not None and (surprise_out.dtype != torch.float32 or surprise_out.dim() != 2 or surprise_out.shape[0] != B
-                                     or not surprise_out.is_contiguous()):
-        raise ValueError(f"entropy_account: surprise_out must be contiguous float32 [{B}, out_ld], got {surprise_out.dtype} "
-                         f"{tuple(surprise_out.shape)}")
     check(_lib.load().mgx_entropy_account(ptr(next_tok), ptr(logits), int(V), ld, float(temperature), ptr(lse), ptr(mu), float(tau),
                                           float(eta), ptr(surprise_out), 0 if surprise_out is None else surprise_out.shape[1], *pos,
                                           B, stream_ptr()), "mgx_entropy_account")
@@ -1046,13 +1022,6 @@ def entropy_account(next_tok, logits, V, temperature, lse, pos_dev, mu=None, tau
 # ---- draft and verify on the decode path (ABI 32; contracts in include/mgx.h) ----------------------------------------
 LOOKAHEAD_MAX_T = _lib.DEFINES["MGX_LOOKAHEAD_MAX_T"]
 LOOKAHEAD_MAX_NGRAM = _lib.DEFINES["MGX_LOOKAHEAD_MAX_NGRAM"]
-
-
-def _check_int32(what, **ts):
-    """name=(tensor, entries): contiguous int32 tensors of that many entries"""
-    for name, (t, n) in ts.items():
-        if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of {n} entries, got {t.dtype} {tuple(t.shape)}")
 
 
 def _check_lookahead_T(what, T):
@@ -1068,15 +1037,13 @@ def lookahead_draft(tok, out_tokens, pos_dev, draft, pos_rows, Lmax, pad_token, 
     without a match.  pos_dev int32 [B], always one position per row; ``base`` as in sample_topk_topp"""
     what = "lookahead_draft"
     B = tok.numel()
-    if draft.dim() != 2 or draft.shape[0] != B:
-        raise ValueError(f"{what}: draft must be int32 [{B}, T], got {tuple(draft.shape)}")
+    _check_tensor(what, "draft", draft, torch.int32, shape=(B, "T"))
     T = _check_lookahead_T(what, draft.shape[1])
     pos = _step_pos(what, pos_dev, B, True, base, with_base=True)
-    _check_int32(what, tok=(tok, B), draft=(draft, B * T), pos_rows=(pos_rows, B * T))
-    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or not out_tokens.is_contiguous():
-        raise ValueError(f"{what}: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} {tuple(out_tokens.shape)}")
-    if guide is not None and (guide.dtype != torch.int32 or guide.dim() != 2 or guide.shape[0] != B or not guide.is_contiguous()):
-        raise ValueError(f"{what}: guide must be contiguous int32 [{B}, guide_ld], got {guide.dtype} {tuple(guide.shape)}")
+    _check_tensor(what, "tok", tok, torch.int32, entries=B)
+    _check_tensor(what, "pos_rows", pos_rows, torch.int32, entries=B * T)
+    _check_tensor(what, "out_tokens", out_tokens, torch.int32, shape=(B, "out_ld"))
+    _check_tensor(what, "guide", guide, torch.int32, shape=(B, "guide_ld"), optional=True)
     if guide is None and not 1 <= int(ngram) <= LOOKAHEAD_MAX_NGRAM:
         raise ValueError(f"{what}: ngram must lie in 1 .. {LOOKAHEAD_MAX_NGRAM}, got {ngram}")
     _need_cuda(tok, out_tokens, pos_dev, base, guide, draft, pos_rows)
@@ -1104,15 +1071,11 @@ def rel_attn_decode_multi(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace, T
     T = _check_lookahead_T(what, T)
     if _check_kv_cache(kcache, vcache, None, None, what):
         raise ValueError(f"{what}: the caches must be bf16 (the draft-and-verify attention has no 8-bit form)")
-    if not (kcache.is_contiguous() and vcache.is_contiguous()):
-        raise ValueError(f"{what}: the caches must be contiguous")
     B, heads, Lmax, _ = kcache.shape
     d = heads * 64
-    for name, t, cols in (("qkv_new", qkv_new, 3 * d), ("ctx", ctx, d)):
-        if t.dtype != torch.bfloat16 or tuple(t.shape) != (B * T, cols) or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous bf16 [{B * T}, {cols}], got {t.dtype} {tuple(t.shape)}")
-    if E.dtype != torch.bfloat16 or E.dim() != 2 or E.shape[1] != 64 or not E.is_contiguous():
-        raise ValueError(f"{what}: E must be contiguous bf16 [M, 64], got {E.dtype} {tuple(E.shape)}")
+    _check_tensor(what, "qkv_new", qkv_new, torch.bfloat16, shape=(B * T, 3 * d))
+    _check_tensor(what, "ctx", ctx, torch.bfloat16, shape=(B * T, d))
+    _check_tensor(what, "E", E, torch.bfloat16, shape=("M", 64))
     _step_pos(what, pos_dev, B, True)
     _need_cuda(qkv_new, kcache, vcache, E, pos_dev, ctx, workspace)
     check(_lib.load().mgx_rel_attn_decode_multi(ptr(qkv_new), ptr(kcache), ptr(vcache), ptr(E), ptr(pos_dev), ptr(ctx), ptr(workspace),
@@ -1129,23 +1092,17 @@ def lookahead_accept(logits, V, pos_dev, draft, limit, tok, out_tokens, done, *,
     distributions to probs_all f32 [B, columns, V] and (1, n) to stats int32 [B, 2]; a row already at its limit sets done[b]"""
     what = "lookahead_accept"
     B = tok.numel()
-    if draft.dim() != 2 or draft.shape[0] != B:
-        raise ValueError(f"{what}: draft must be int32 [{B}, T], got {tuple(draft.shape)}")
+    _check_tensor(what, "draft", draft, torch.int32, shape=(B, "T"))
     T = _check_lookahead_T(what, draft.shape[1])
     ld = logits.shape[-1]
-    if logits.dtype != torch.bfloat16 or logits.numel() != B * T * ld or not logits.is_contiguous():
-        raise ValueError(f"{what}: logits must be contiguous bf16 [{B * T}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    _check_tensor(what, "logits", logits, torch.bfloat16, entries=B * T * ld)
     pos = _step_pos(what, pos_dev, B, True, base, with_base=True)
-    _check_int32(what, draft=(draft, B * T), limit=(limit, B), tok=(tok, B), done=(done, B))
-    if stats is not None:
-        _check_int32(what, stats=(stats, 2 * B))
-    if out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B or not out_tokens.is_contiguous():
-        raise ValueError(f"{what}: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} {tuple(out_tokens.shape)}")
-    if probs_all is not None and (probs_all.dtype != torch.float32 or probs_all.dim() != 3 or probs_all.shape[0] != B
-                                  or probs_all.shape[2] != int(V) or not probs_all.is_contiguous()):
-        raise ValueError(f"{what}: probs_all must be contiguous float32 [{B}, columns, {V}], got {probs_all.dtype} "
-                         f"{tuple(probs_all.shape)}")
-    _check_allow_table(allow_table, V)
+    for name, t in (("limit", limit), ("tok", tok), ("done", done)):
+        _check_tensor(what, name, t, torch.int32, entries=B)
+    _check_tensor(what, "stats", stats, torch.int32, entries=2 * B, optional=True)
+    _check_tensor(what, "out_tokens", out_tokens, torch.int32, shape=(B, "out_ld"))
+    _check_tensor(what, "probs_all", probs_all, torch.float32, shape=(B, "columns", int(V)), optional=True)
+    _check_allow_table(allow_table, V, "lookahead_accept")
     _need_cuda(logits, pos_dev, base, draft, limit, tok, out_tokens, probs_all, done, stats, allow_table)
     check(_lib.load().mgx_lookahead_accept(ptr(logits), int(V), ld, float(temperature), int(top_k), float(top_p), int(seed), pos[0],
                                            pos[1], ptr(draft), ptr(limit), ptr(tok), ptr(out_tokens), out_tokens.shape[1],
@@ -1161,10 +1118,8 @@ NOTE_BITS = 32 * NOTE_WORDS                               # the bits a rule may 
 
 def _check_note_state(what, rule, state):
     """the held-note state: rule int32 [V], state int32 [B, NOTE_WORDS], both contiguous.  Returns B"""
-    if rule.dtype != torch.int32 or rule.dim() != 1 or not rule.is_contiguous():
-        raise ValueError(f"{what}: rule must be a contiguous int32 tensor [V], got {rule.dtype} {tuple(rule.shape)}")
-    if state.dtype != torch.int32 or state.dim() != 2 or state.shape[1] != NOTE_WORDS or not state.is_contiguous():
-        raise ValueError(f"{what}: state must be a contiguous int32 tensor [B, {NOTE_WORDS}], got {state.dtype} {tuple(state.shape)}")
+    _check_tensor(what, "rule", rule, torch.int32, shape=("V",))
+    _check_tensor(what, "state", state, torch.int32, shape=("B", NOTE_WORDS))
     return state.shape[0]
 
 
@@ -1172,15 +1127,14 @@ def notes_mask(logits, V, rule, state, max_on=NOTE_BITS):
     """in place, before the sampler: logits bf16 [B, ld] get -inf at every id v < V whose rule sets a bit that state[b] holds
     already -- or any bit, once the row holds ``max_on`` -- and at every id whose rule clears a bit the row does not hold;
     rule-0 ids and columns >= V stay bit for bit"""
-    _need_cuda(logits, rule, state)
     B = _check_note_state("notes_mask", rule, state)
     ld = logits.shape[-1]
-    if logits.dtype != torch.bfloat16 or logits.numel() != B * ld or not logits.is_contiguous():
-        raise ValueError(f"notes_mask: logits must be contiguous bf16 [{B}, ld], got {logits.dtype} {tuple(logits.shape)}")
+    _check_tensor("notes_mask", "logits", logits, torch.bfloat16, entries=B * ld)
     if not 0 < int(V) <= min(ld, rule.numel()):
         raise ValueError(f"notes_mask: V must lie in 1 .. min(ld, the entries of rule) = {min(ld, rule.numel())}, got {V}")
     if not 1 <= int(max_on) <= NOTE_BITS:
         raise ValueError(f"notes_mask: max_on must lie in 1 .. {NOTE_BITS} ({NOTE_BITS}: no cap), got {max_on}")
+    _need_cuda(logits, rule, state)
     check(_lib.load().mgx_notes_mask(ptr(logits), int(V), ld, ptr(rule), ptr(state), int(max_on), B, stream_ptr()), "mgx_notes_mask")
     return logits
 
@@ -1188,14 +1142,12 @@ def notes_mask(logits, V, rule, state, max_on=NOTE_BITS):
 def notes_account(next_tok, rule, state, V=None):
     """after the sampler: applies rule[next_tok[b]] to state[b] -- sets or clears the bit, whatever it was; a token outside
     0 .. V-1 (``V`` None: the entries of rule) and rule 0 leave the row alone"""
-    _need_cuda(next_tok, rule, state)
     B = _check_note_state("notes_account", rule, state)
-    if next_tok.dtype != torch.int32 or next_tok.dim() != 1 or next_tok.numel() != B or not next_tok.is_contiguous():
-        raise ValueError(f"notes_account: next_tok must be a contiguous int32 tensor of {B} entries, got {next_tok.dtype} "
-                         f"{tuple(next_tok.shape)}")
+    _check_tensor("notes_account", "next_tok", next_tok, torch.int32, shape=(B,))
     V = rule.numel() if V is None else int(V)
     if not 0 < V <= rule.numel():
         raise ValueError(f"notes_account: V must lie in 1 .. the entries of rule = {rule.numel()}, got {V}")
+    _need_cuda(next_tok, rule, state)
     check(_lib.load().mgx_notes_account(ptr(next_tok), ptr(rule), ptr(state), V, B, stream_ptr()), "mgx_notes_account")
     return state
 
@@ -1206,31 +1158,21 @@ def notes_keep(first_tok, next_tok, out_tokens, pos_dev, rule, state, max_on=NOT
     to; ``out_tokens`` None: no column) receive it.  ``ragged`` / ``base`` as in sample_topk_topp"""
     B = _check_note_state("notes_keep", rule, state)
     pos = _step_pos("notes_keep", pos_dev, B, ragged, base, with_base=True)
-    _need_cuda(first_tok, next_tok, out_tokens, pos_dev, base, rule, state)
     for name, t in (("first_tok", first_tok), ("next_tok", next_tok)):
-        if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != B or not t.is_contiguous():
-            raise ValueError(f"notes_keep: {name} must be a contiguous int32 tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
-    if out_tokens is not None and (out_tokens.dtype != torch.int32 or out_tokens.dim() != 2 or out_tokens.shape[0] != B
-                                   or out_tokens.stride(1) != 1 or out_tokens.stride(0) != out_tokens.shape[1]):
-        raise ValueError(f"notes_keep: out_tokens must be contiguous int32 [{B}, out_ld], got {out_tokens.dtype} "
-                         f"{tuple(out_tokens.shape)}")
+        _check_tensor("notes_keep", name, t, torch.int32, shape=(B,))
+    _check_tensor("notes_keep", "out_tokens", out_tokens, torch.int32, shape=(B, "out_ld"), optional=True)
     V = rule.numel() if V is None else int(V)
     if not 0 < V <= rule.numel():
         raise ValueError(f"notes_keep: V must lie in 1 .. the entries of rule = {rule.numel()}, got {V}")
     if not 1 <= int(max_on) <= NOTE_BITS:
         raise ValueError(f"notes_keep: max_on must lie in 1 .. {NOTE_BITS} ({NOTE_BITS}: no cap), got {max_on}")
+    _need_cuda(first_tok, next_tok, out_tokens, pos_dev, base, rule, state)
     check(_lib.load().mgx_notes_keep(ptr(first_tok), ptr(next_tok), ptr(out_tokens), 0 if out_tokens is None else out_tokens.shape[1],
                                      *pos, ptr(rule), ptr(state), int(max_on), V, B, stream_ptr()), "mgx_notes_keep")
     return next_tok
 
 
 # ---- train-time augmentation on the device (ABI 29; contract in include/mgx.h) ---------------------------------------
-def _check_crop_rows(B, **rows):
-    for name, (t, dtype) in rows.items():
-        if t is not None and (t.dtype != dtype or t.dim() != 1 or t.numel() != B or not t.is_contiguous()):
-            raise ValueError(f"crop_augment: {name} must be a contiguous {dtype} tensor of {B} entries, got {t.dtype} {tuple(t.shape)}")
-
-
 def crop_augment(corpus, start, avail, x, y, pad_token, *, perm=None, shift_row=None, stretch_q=None, ts0=0, n_ts=0, n_out=None,
                  time_major=False):
     """one crop per row out of ``corpus`` (16-bit ids, 1-D, on the device), stretched in time and transposed, written as the
@@ -1239,29 +1181,28 @@ def crop_augment(corpus, start, avail, x, y, pad_token, *, perm=None, shift_row=
     [B]: where a row's crop begins and how far its piece goes on from there.  perm int32 [S, V] with shift_row int32 [B] (the
     table's row per crop), stretch_q int32 [B] in per-mille with the codec's time run (ts0, n_ts): each optional.  Rows that run
     out of source end in pad_token; n_out int32 [B] (optional) receives the ids written per row.  Returns (x, y)"""
-    _need_cuda(corpus, start, avail, x, y, perm, shift_row, stretch_q, n_out)
-    if corpus.dtype not in (torch.uint16, torch.int16) or corpus.dim() != 1 or corpus.numel() < 1:
-        raise ValueError(f"crop_augment: the corpus must be a non-empty 1-D uint16 tensor, got {corpus.dtype} {tuple(corpus.shape)}")
-    if x.dtype != torch.int32 or x.dim() != 2:
-        raise ValueError(f"crop_augment: x must be a contiguous int32 matrix, got {x.dtype} {tuple(x.shape)}")
-    if y is not None and (y.dtype != torch.int32 or y.shape != x.shape):
-        raise ValueError(f"crop_augment: y must be int32 of x's shape {tuple(x.shape)}, got {y.dtype} {tuple(y.shape)}")
+    what = "crop_augment"
+    _check_tensor(what, "corpus", corpus, (torch.uint16, torch.int16), shape=("n",), at_least=1)
+    _check_tensor(what, "x", x, torch.int32, shape=("rows", "columns"))
+    _check_tensor(what, "y", y, torch.int32, shape=tuple(x.shape), optional=True)
     T, B = (x.shape[0], x.shape[1]) if time_major else (x.shape[1], x.shape[0])
     n = T + (1 if y is not None else 0)
     if B < 1 or T < 1:
         raise ValueError(f"crop_augment: x must hold at least one row and one column, got {tuple(x.shape)}")
-    _check_crop_rows(B, start=(start, torch.int64), avail=(avail, torch.int32), shift_row=(shift_row, torch.int32),
-                     stretch_q=(stretch_q, torch.int32), n_out=(n_out, torch.int32))
+    _check_tensor(what, "start", start, torch.int64, shape=(B,))
+    _check_tensor(what, "avail", avail, torch.int32, shape=(B,))
+    for name, t in (("shift_row", shift_row), ("stretch_q", stretch_q), ("n_out", n_out)):
+        _check_tensor(what, name, t, torch.int32, shape=(B,), optional=True)
     if (perm is None) != (shift_row is None):
         raise ValueError("crop_augment: perm and shift_row go together: give both or neither")
     S, V = 0, 1
     if perm is not None:
-        if perm.dtype != torch.int32 or perm.dim() != 2 or perm.numel() < 1:
-            raise ValueError(f"crop_augment: perm must be a contiguous int32 table [S, V], got {perm.dtype} {tuple(perm.shape)}")
+        _check_tensor(what, "perm", perm, torch.int32, shape=("S", "V"), at_least=1)
         S, V = perm.shape
     if stretch_q is not None and not (int(ts0) >= 0 and int(n_ts) >= 1 and int(ts0) + int(n_ts) <= 65536):
         raise ValueError(f"crop_augment: a stretch needs the codec's time run inside the 16-bit ids, got ts0={ts0}, n_ts={n_ts}")
     stride_b, stride_t = (1, B) if time_major else (T, 1)
+    _need_cuda(corpus, start, avail, x, y, perm, shift_row, stretch_q, n_out)
     check(_lib.load().mgx_crop_augment(ptr(corpus), corpus.numel(), ptr(start), ptr(avail), ptr(perm), S, V, ptr(shift_row),
                                        ptr(stretch_q), int(ts0), int(n_ts), ptr(x), ptr(y), stride_b, stride_t, ptr(n_out),
                                        int(pad_token), B, n, stream_ptr()), "mgx_crop_augment")
@@ -1269,27 +1210,21 @@ def crop_augment(corpus, start, avail, x, y, pad_token, *, perm=None, shift_row=
 
 
 # ---- beam search on the decode path (ABI 22; contracts in include/mgx.h) ---------------------------------------------
-def _check_int32_rows(what, R, **ts):
-    for name, t in ts.items():
-        if t.dtype != torch.int32 or t.shape[0] != R or not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be a contiguous int32 tensor of {R} rows, got {t.dtype} {tuple(t.shape)}")
-
-
 def beam_select(logits, V, score, tok, parent, pos_rows, hist_tok, hist_parent, temperature=1.0, allow_table=None,
                 stochastic=False, seed=0, advance=True):
     """the K best expansions of every prompt's K beams: logits bf16 [B*K, ld], score f32 [B, K] (in/out, -inf = dead beam),
     tok / parent / pos_rows int32 [B*K], hist_tok / hist_parent int32 [B*K, out_ld] (column pos + 1 is written)"""
-    _need_cuda(logits, score, tok, parent, pos_rows, hist_tok, hist_parent, allow_table)
-    if score.dim() != 2 or score.dtype != torch.float32 or not score.is_contiguous():
-        raise ValueError(f"beam_select: score must be contiguous float32 [B, K], got {score.dtype} {tuple(score.shape)}")
+    what = "beam_select"
+    _check_tensor(what, "score", score, torch.float32, shape=("B", "K"))
     B, K = score.shape
     ld = logits.shape[-1]
-    if logits.dtype != torch.bfloat16 or logits.numel() != B * K * ld or not logits.is_contiguous():
-        raise ValueError(f"beam_select: logits must be contiguous bf16 [{B * K}, ld], got {logits.dtype} {tuple(logits.shape)}")
-    _check_int32_rows("beam_select", B * K, tok=tok, parent=parent, pos_rows=pos_rows, hist_tok=hist_tok, hist_parent=hist_parent)
-    if tok.dim() != 1 or parent.dim() != 1 or pos_rows.dim() != 1 or hist_tok.dim() != 2 or hist_parent.shape != hist_tok.shape:
-        raise ValueError("beam_select: tok, parent, pos_rows are [B*K]; hist_tok and hist_parent [B*K, out_ld] of one shape")
-    _check_allow_table(allow_table, V)
+    _check_tensor(what, "logits", logits, torch.bfloat16, entries=B * K * ld)
+    for name, t in (("tok", tok), ("parent", parent), ("pos_rows", pos_rows)):
+        _check_tensor(what, name, t, torch.int32, shape=(B * K,))
+    _check_tensor(what, "hist_tok", hist_tok, torch.int32, shape=(B * K, "out_ld"))
+    _check_tensor(what, "hist_parent", hist_parent, torch.int32, shape=tuple(hist_tok.shape))
+    _check_allow_table(allow_table, V, "beam_select")
+    _need_cuda(logits, score, tok, parent, pos_rows, hist_tok, hist_parent, allow_table)
     check(_lib.load().mgx_beam_select(ptr(logits), int(V), ld, float(temperature), ptr(score), ptr(tok), ptr(parent), ptr(pos_rows),
                                       ptr(hist_tok), ptr(hist_parent), hist_tok.shape[1], B, K, 1 if advance else 0,
                                       ptr(allow_table), 1 if stochastic else 0, int(seed), stream_ptr()), "mgx_beam_select")
@@ -1299,17 +1234,18 @@ def beam_select(logits, V, score, tok, parent, pos_rows, hist_tok, hist_parent, 
 def kv_beam_reorder(dst, src, parent, pos_rows, K):
     """dst[r, h, :n_r] = src[(r // K) * K + parent[r], h, :n_r] with n_r = pos_rows[r], for one cache tensor [R, h, Lmax, 64]
     (bf16, or the 8-bit codes) or [R, h, Lmax] (f32: the 8-bit cache's scales); dst and src are two buffers of one shape"""
-    _need_cuda(dst, src, parent, pos_rows)
-    if dst.shape != src.shape or dst.dtype != src.dtype or dst.dim() not in (3, 4) or not (dst.is_contiguous() and src.is_contiguous()):
-        raise ValueError(f"kv_beam_reorder: dst and src must be contiguous [R, h, Lmax(, 64)] of one shape and dtype, got "
-                         f"{dst.dtype} {tuple(dst.shape)} and {src.dtype} {tuple(src.shape)}")
+    what = "kv_beam_reorder"
+    _check_tensor(what, "dst", dst, None, shape=("R", "h", "Lmax", 64) if dst.dim() == 4 else ("R", "h", "Lmax"))
+    _check_tensor(what, "src", src, dst.dtype, shape=tuple(dst.shape))
     R, heads, Lmax = dst.shape[:3]
     row_bytes = dst.element_size() * (dst.shape[3] if dst.dim() == 4 else 1)
-    if row_bytes not in (128, 64, 4) or (dst.dim() == 4 and dst.shape[3] != 64):
+    if row_bytes not in (128, 64, 4):
         raise ValueError(f"kv_beam_reorder: rows of 64 bf16 values, 64 8-bit codes or one f32 scale, got {dst.dtype} {tuple(dst.shape)}")
-    _check_int32_rows("kv_beam_reorder", R, parent=parent, pos_rows=pos_rows)
+    _check_tensor(what, "parent", parent, torch.int32, shape=(R,))
+    _check_tensor(what, "pos_rows", pos_rows, torch.int32, shape=(R,))
     if R % int(K):
         raise ValueError(f"kv_beam_reorder: {R} rows are no multiple of the beam size {K}")
+    _need_cuda(dst, src, parent, pos_rows)
     check(_lib.load().mgx_kv_beam_reorder(ptr(dst), ptr(src), ptr(parent), ptr(pos_rows), R, int(K), heads, Lmax, row_bytes,
                                           stream_ptr()), "mgx_kv_beam_reorder")
     return dst
@@ -1317,11 +1253,15 @@ def kv_beam_reorder(dst, src, parent, pos_rows, K):
 
 def beam_backtrack(hist_tok, hist_parent, c0_rows, out, K, steps):
     """out[r, c0_r : c0_r + steps] = the tokens of final beam r, walked back through hist_parent (all int32 [R, out_ld])"""
-    _need_cuda(hist_tok, hist_parent, c0_rows, out)
+    what = "beam_backtrack"
+    _check_tensor(what, "out", out, torch.int32, shape=("R", "out_ld"))
     R = out.shape[0]
-    _check_int32_rows("beam_backtrack", R, hist_tok=hist_tok, hist_parent=hist_parent, c0_rows=c0_rows, out=out)
-    if out.dim() != 2 or hist_tok.shape != out.shape or hist_parent.shape != out.shape or c0_rows.dim() != 1 or R % int(K):
-        raise ValueError("beam_backtrack: hist_tok, hist_parent and out are [R, out_ld] of one shape, c0_rows [R], R a multiple of K")
+    _check_tensor(what, "hist_tok", hist_tok, torch.int32, shape=tuple(out.shape))
+    _check_tensor(what, "hist_parent", hist_parent, torch.int32, shape=tuple(out.shape))
+    _check_tensor(what, "c0_rows", c0_rows, torch.int32, shape=(R,))
+    if R % int(K):
+        raise ValueError(f"beam_backtrack: {R} rows are no multiple of the beam size {K}")
+    _need_cuda(hist_tok, hist_parent, c0_rows, out)
     check(_lib.load().mgx_beam_backtrack(ptr(hist_tok), ptr(hist_parent), ptr(c0_rows), ptr(out), out.shape[1], R, int(K), int(steps),
                                          stream_ptr()), "mgx_beam_backtrack")
     return out
@@ -1351,15 +1291,14 @@ def token_logprob(logits, target, temperature=1.0, prev=None, allow_table=None, 
     if (V > 1 and lg.stride(-1) != 1) or ld < V or any(dims[i][1] != dims[i + 1][1] * dims[i + 1][0] for i in range(len(dims) - 1)):
         raise ValueError(f"token_logprob: the rows of logits must be evenly spaced and their columns contiguous "
                          f"(shape {tuple(lg.shape)}, strides {lg.stride()})")
-    if not lg.is_cuda:
-        raise _lib.MgxError("mgx ops need CUDA/HIP tensors (no CPU fallback); got a CPU tensor")
-    _need_cuda(target, prev, allow_table)
-    for name, t in (("target", target), ("prev", prev)):
-        if t is not None and (t.dtype != torch.int32 or t.numel() != rows):
-            raise ValueError(f"token_logprob: {name} must be int32 with one entry per row ({rows}), got {t.dtype} {tuple(t.shape)}")
+    _check_tensor("token_logprob", "target", target, torch.int32, entries=rows)
+    _check_tensor("token_logprob", "prev", prev, torch.int32, entries=rows, optional=True)
     if (prev is None) != (allow_table is None):
         raise ValueError("token_logprob: prev and allow_table are given together or not at all")
-    _check_allow_table(allow_table, V)
+    _check_allow_table(allow_table, V, "token_logprob")
+    if not lg.is_cuda:                                        # a strided view: _need_cuda would ask for a contiguous one
+        raise _lib.MgxError("mgx ops need CUDA/HIP tensors (no CPU fallback); got a CPU tensor")
+    _need_cuda(target, prev, allow_table)
     logp, lse, hit = _score_outputs(rows, lg.device, want_lse)
     check(_lib.load().mgx_token_logprob(ptr(lg), V, int(ld), ptr(target), ptr(prev), ptr(allow_table), float(temperature), ptr(logp),
                                         ptr(lse), ptr(hit), rows, stream_ptr()), "mgx_token_logprob")
@@ -1369,15 +1308,14 @@ def token_logprob(logits, target, temperature=1.0, prev=None, allow_table=None, 
 def linear_logprob(a, w, bias, target, temperature=1.0, want_lse=True):
     """log p(target) under softmax((a w^T + bias) / temperature) without storing the logits: a bf16 [M, K], w bf16 [V, K], bias f32
     [V] or None, target int32 [M].  Returns (logp f32 [M], lse f32 [M] or None, hit int32 [M])"""
-    _need_cuda(a, w, bias, target)
-    if a.dim() != 2 or w.dim() != 2 or a.dtype != BF16 or w.dtype != BF16 or a.shape[1] != w.shape[1]:
-        raise ValueError(f"linear_logprob: a bf16 [M, K] and w bf16 [V, K], got {a.dtype} {tuple(a.shape)} and {w.dtype} {tuple(w.shape)}")
+    what = "linear_logprob"
+    _check_tensor(what, "a", a, BF16, shape=("M", "K"))
     M, K = a.shape
+    _check_tensor(what, "w", w, BF16, shape=("V", K))
     V = w.shape[0]
-    if bias is not None and (bias.dtype != torch.float32 or bias.shape != (V,)):
-        raise ValueError(f"linear_logprob: bias must be float32 [{V}], got {bias.dtype} {tuple(bias.shape)}")
-    if target.dtype != torch.int32 or target.numel() != M:
-        raise ValueError(f"linear_logprob: target must be int32 with one entry per row ({M}), got {target.dtype} {tuple(target.shape)}")
+    _check_tensor(what, "bias", bias, torch.float32, shape=(V,), optional=True)
+    _check_tensor(what, "target", target, torch.int32, entries=M)
+    _need_cuda(a, w, bias, target)
     logp, lse, hit = _score_outputs(M, a.device, want_lse)
     check(_lib.load().mgx_linear_logprob(ptr(a), ptr(w), ptr(bias), ptr(target), float(temperature), ptr(logp), ptr(lse), ptr(hit), M, V,
                                          K, stream_ptr()), "mgx_linear_logprob")
@@ -1387,10 +1325,9 @@ def linear_logprob(a, w, bias, target, temperature=1.0, want_lse=True):
 def score_reduce(logp, hit):
     """per-row totals of logp f32 [B, L] and hit int32 [B, L]: (sum f64 [B] over the entries with hit >= 0, their count int32 [B],
     the count of hit == 1 int32 [B])"""
+    _check_tensor("score_reduce", "logp", logp, torch.float32, shape=("B", "L"))
+    _check_tensor("score_reduce", "hit", hit, torch.int32, shape=tuple(logp.shape))
     _need_cuda(logp, hit)
-    if logp.dim() != 2 or logp.dtype != torch.float32 or hit.dtype != torch.int32 or hit.shape != logp.shape:
-        raise ValueError(f"score_reduce: logp float32 [B, L] and hit int32 [B, L], got {logp.dtype} {tuple(logp.shape)} and "
-                         f"{hit.dtype} {tuple(hit.shape)}")
     B, L = logp.shape
     total = torch.empty(B, dtype=torch.float64, device=logp.device)
     count = torch.empty(B, dtype=torch.int32, device=logp.device)

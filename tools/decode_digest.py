@@ -1,11 +1,14 @@
 """Digests of the KV-cache decode: a fixed, seeded list of small generate_cached calls -- and, for every other driver that passes
-a position, of generate_cached(window= / samples_per_prompt= / note_rules=), generate_timed and generate_beam -- one SHA-256 per
-case over the tokens and, where the case asks for them, the probabilities and every returned tensor (bytes of the contiguous
-CPU copy).  Two checkouts (or two libraries, MGX_LIB_PATH) compute the same thing bit for bit when their lists agree line for line.
-Only the model's public methods are used, so this file copied into an older checkout digests that checkout."""
+a position, of generate_cached(window= / samples_per_prompt= / note_rules=), generate_timed and generate_beam; then of the stages
+that shape a logits row (class_sampling=, entropy_sampling=, lookahead=) and of score -- one SHA-256 per case over the tokens
+and, where the case asks for them, the probabilities and every returned tensor (bytes of the contiguous CPU copy).  Two checkouts
+(or two libraries, MGX_LIB_PATH) compute the same thing bit for bit when their lists agree line for line.
+Only the model's public methods and decode.py's two sampling classes are used, so this file copied into another checkout of the
+same ABI digests that checkout."""
 import hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+from musicgeneration_amd.decode import ClassSampling, EntropySampling
 from musicgeneration_amd.network import MusicTransformer
 
 V = 337
@@ -66,6 +69,17 @@ timed = lambda mt, prior, n, kv, **kw: [(t, c, i["spent"], i["remaining"], i["do
                                         [mt.generate_timed(prior, kw.pop("budget"), cost, n, seed=11, kv_cache=kv, **kw)]]
 beam = lambda mt, prior, n, kv, **kw: mt.generate_beam(prior, n, seed=11, kv_cache=kv, return_beams=True, **kw)
 cached = lambda mt, prior, n, kv, **kw: mt.generate_cached(prior, n, seed=11, kv_cache=kv, **kw)
+score = lambda mt, x, n, kv, **kw: list(mt.score(x, **kw).values())
+
+
+def entropy(mt, prior, n, kv, **kw):
+    """the tokens, then the state the call hands back: the rows' Mirostat thresholds and the trace of surprises"""
+    es = EntropySampling(**kw.pop("entropy"))
+    res = mt.generate_cached(prior, n, seed=11, kv_cache=kv, entropy_sampling=es, **kw)
+    return [res] + [t for t in (es.mu, es.surprise) if t is not None]
+
+
+per_class = ClassSampling(torch.arange(V) % 3, temperature=[0.8, None, 1.3], top_k=[5, 0, 0], top_p=[1.0, 0.9, None])
 # name, call, prior, new tokens, caches, options
 MORE = [
     ("window_ragged", cached, p70, 40, ("bf16", "fp8"), dict(prior_lengths=[70, 40, 33, 30], window=48, hop=8, top_p=0.9,
@@ -79,6 +93,14 @@ MORE = [
     ("notes_samples2", cached, p30, 24, ("bf16",), dict(prior_lengths=lens30, samples_per_prompt=2, note_rules=rules)),
     ("beam4", beam, tokens(3, 12, 12), 20, ("bf16", "fp8"), dict(beam_size=4)),
     ("beam3_ragged_stoch", beam, p30[:2], 21, ("bf16", "fp8"), dict(beam_size=3, prior_lengths=[30, 5], stochastic=True,
+                                                                    temperature=0.9)),
+    ("class_sampling", cached, p30, 40, ("bf16", "fp8"), dict(prior_lengths=lens30, class_sampling=per_class, grammar=grammar,
+                                                              top_p=0.95)),
+    ("entropy_minp_typical", entropy, p30, 40, ("bf16", "fp8"), dict(prior_lengths=lens30, entropy=dict(min_p=0.05, typical_p=0.9),
+                                                                    grammar=grammar, top_k=30)),
+    ("entropy_mirostat", entropy, tokens(3, 12, 13), 40, ("bf16",), dict(entropy=dict(tau=3.0, eta=0.1, trace=True), temperature=0.9)),
+    ("lookahead4", cached, p30, 40, ("bf16",), dict(prior_lengths=lens30, lookahead=4, top_k=20, return_probs=True)),
+    ("score_grammar", score, tokens(3, 50, 14), 0, ("bf16",), dict(lengths=[50, 20, 35], grammar=grammar, logits="bf16",
                                                                     temperature=0.9)),
 ]
 for name, call, prior, n, kvs, kw in MORE:
